@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the per-pixel ray-trace path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|parity]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|parity] [--full] [--dump-outputs DIR]
 
 One process per GPU.  With N > 1 and no WORLD_SIZE in the environment this script LAUNCHES its own ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, fresh child
@@ -15,7 +15,11 @@ tiles, ONE gather brings them to rank 0, rank 0 assembles the RGBA8 frame.  valu
 seconds / 1e6 (whole job, all ranks; total work is fixed as N grows -> "strong" scaling).
 `--config` selects the other BASELINE configurations (same JSON shape; `config.workload` names them).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline fields (`metric`, `value`,
+`unit`, `ms_per_step`, `higher_is_better`, `dtype`, `config`, ...) and nothing more.  N > 1 runs qualify their schedule before it is
+timed (`schedule_check`) in every run.  `--full` adds the objects below, all measured after the clock has stopped:
+  fast_math / texel_tiles / steady_state / parity_schedules
+                N = 1: the opt-in builds and the other schedules on the same workload (never part of `value`).
   roofline      fp32 vector-ALU roofline of the render kernel (north_star: "scalar-ray fp32 FMA, no MFMA"):
                 achieved = ALGORITHMIC flops per launch (work counters of one counting launch x the per-unit
                 figures of SURVEY §8d / DESIGN.md) / the kernel's average duration measured with HIP events on
@@ -33,6 +37,10 @@ Rank 0 prints ONE JSON line.  Extra objects:
                 partition + gather + de-interleave at full size, not kernel parity); N > 1 lines add
                 `verified_whole_frame`, every pixel of the gathered frame against rank 0's render of the whole frame.
   gather_ms     N > 1: one gather + de-interleave on its own (no render), timed after the timed region.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step -- rank 0's RGBA8 frame -- as DIR/frame.npy (float32,
+h x w x 4); a frame larger than 64 MB in float32 is written as a fixed, seeded sample of its rows (DIR/frame.npy) together with the row
+indices (DIR/frame_rows.npy, float64).  The inputs are fixed by the arguments, so two builds can be compared output for output.
 
 `--dry-run` rehearses the N-rank path without a GPU (gloo, CPU tensors, a pattern renderer instead of the HIP
 kernel): it proves that the ranks start, partition, gather and assemble; it measures nothing.
@@ -611,7 +619,13 @@ def parse_args(argv):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="3")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline, verified_rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure: roofline (one counting "
+                         "launch), the opt-in builds and other schedules, cpu_baseline, verified_rows, gather_ms (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write rank 0's frame of the last timed step as DIR/frame.npy (float32; a seeded sample of its rows, with "
+                         "DIR/frame_rows.npy, when the whole frame would exceed 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs (cpu_baseline, verified_rows)")
     ap.add_argument("--tile-rows", type=int, default=4)
     ap.add_argument("--spp", type=int, default=0, help="override the config's samples per pixel (e.g. --config 5 --gpus 8 --spp 4000 = "
                                                         "BASELINE configs[4] in full); the workload string says so")
@@ -630,11 +644,34 @@ def parse_args(argv):
     return ap.parse_args(argv)
 
 
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(directory: str, frame_host) -> None:
+    """`--dump-outputs`: the frame of the last timed step (h x w x 4, RGBA8) as float32 -- whole when it fits DUMP_LIMIT_BYTES, else a
+    fixed, seeded sample of its rows (sorted) with their indices in frame_rows.npy."""
+    import numpy as np
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    frame = np.asarray(frame_host)
+    h, row_bytes = frame.shape[0], frame[0].size * 4
+    if h * row_bytes <= DUMP_LIMIT_BYTES:
+        np.save(out / "frame.npy", frame.astype(np.float32))
+        return
+    keep = (DUMP_LIMIT_BYTES - 2 * 128) // (row_bytes + 8)            # a row and its float64 index; two .npy headers
+    rows = np.sort(np.random.default_rng(0).choice(h, size=keep, replace=False))
+    np.save(out / "frame.npy", frame[rows].astype(np.float32))
+    np.save(out / "frame_rows.npy", rows.astype(np.float64))
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, argv)                       # BEFORE torch / the GPU are touched in this process
@@ -847,9 +884,10 @@ def main(argv=None) -> int:
     total_samples = w * h * spp
 
     # N > 1: one gather + de-interleave on its own, after the clock has stopped (the timed region overlaps it with the next
-    # frame's render, so it cannot be read off the step time): rank 0's wall time of [gather, assemble], ranks released together
+    # frame's render, so it cannot be read off the step time): rank 0's wall time of [gather, assemble], ranks released together.
+    # A --full line only; a dry run, which rehearses every N > 1 branch, always.
     gather_ms = None
-    if multi:
+    if multi and (args.full or dry):
         reps, acc = 5, 0.0
         for _ in range(reps):
             barrier()
@@ -861,6 +899,9 @@ def main(argv=None) -> int:
             sync()
             acc += time.perf_counter() - tg
         gather_ms = round(acc / reps * 1e3, 4)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame.frame.cpu().numpy())
 
     if dry:
         ok = True
@@ -893,34 +934,9 @@ def main(argv=None) -> int:
             dist.destroy_process_group()
         return 0 if ok else 4
 
-    # one counting launch (outside the timed region) gives the exact work of this rank's launch; for grid builds
-    # (many-sphere scenes) it counts the kernel that actually runs, not the flat scan
-    kernel_name = ctx.last_kernel()
-    uses_grid = kernel_uses_grid(kernel_name)
-    pc = m.multi_gpu.part_params(base, rank, world, args.tile_rows)
-    pc.flags |= m.MIRT_FLAG_COUNT_WORK | (m.MIRT_FLAG_COUNT_GRID if uses_grid else 0)
-    scratch = torch.empty((frame.max_rows if multi else frame.frame.shape[0], w, 4), dtype=torch.uint8, device=device)
-    ctx.render_device(pc, scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    work = ctx.stats()
-    counting_kernel = ctx.last_kernel()
-    flops = algorithmic_flops(work, mode=cfg["mode"], grid=uses_grid)      # of THIS rank's share
-    flops_all = flops
-    if multi:
-        t = torch.tensor([flops], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        flops_all = float(t.item())
-
+    result = None
     if rank == 0:
         value = total_samples * args.steps / elapsed / 1e6
-        traffic = profiled_traffic(kernel_name, cfg["workload"]) if not multi else None
-        achieved_tflops = flops / (roof_ms * 1e-3) / 1e12
-        out_bytes = frame.rows * w * 4
-        algo_bytes = algorithmic_bytes(sd, cfg["mode"], out_bytes)
-        lane_slots = 64 * work["wave_iterations"]
-        # MIRT_FLAG_COUNT_WORK can force another schedule than the timed one (the pool's counting build, lane = sample instead
-        # of lane = pixel): the flop counts do not depend on the schedule, lane utilisation does
-        same_schedule = kernel_schedule(counting_kernel) == kernel_schedule(kernel_name)
         result = {
             "metric": "Msamples/sec (pixels x spp) at 1920x1080, 1000 spp" if args.config == "3" else "Msamples/sec (pixels x spp)",
             "value": round(value, 2),
@@ -937,7 +953,40 @@ def main(argv=None) -> int:
             "data": "synthetic",
             "config": {"workload": cfg["workload"], "width": w, "height": h, "spp": spp, "num_bounces": BOUNCES,
                        "mode": cfg["mode"], "partition": partition},
-            "roofline": {
+        }
+        if multi:
+            result["schedule_check"] = schedule_check           # the schedules tried before the timed region, most overlapped first; the last one ran
+
+    # --full: everything beyond the headline figure, after the clock has stopped
+    if args.full:
+        # one counting launch (outside the timed region) gives the exact work of this rank's launch; for grid builds
+        # (many-sphere scenes) it counts the kernel that actually runs, not the flat scan
+        kernel_name = ctx.last_kernel()
+        uses_grid = kernel_uses_grid(kernel_name)
+        pc = m.multi_gpu.part_params(base, rank, world, args.tile_rows)
+        pc.flags |= m.MIRT_FLAG_COUNT_WORK | (m.MIRT_FLAG_COUNT_GRID if uses_grid else 0)
+        scratch = torch.empty((frame.max_rows if multi else frame.frame.shape[0], w, 4), dtype=torch.uint8, device=device)
+        ctx.render_device(pc, scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        work = ctx.stats()
+        counting_kernel = ctx.last_kernel()
+        flops = algorithmic_flops(work, mode=cfg["mode"], grid=uses_grid)      # of THIS rank's share
+        flops_all = flops
+        if multi:
+            t = torch.tensor([flops], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            flops_all = float(t.item())
+
+        if rank == 0:
+            traffic = profiled_traffic(kernel_name, cfg["workload"]) if not multi else None
+            achieved_tflops = flops / (roof_ms * 1e-3) / 1e12
+            out_bytes = frame.rows * w * 4
+            algo_bytes = algorithmic_bytes(sd, cfg["mode"], out_bytes)
+            lane_slots = 64 * work["wave_iterations"]
+            # MIRT_FLAG_COUNT_WORK can force another schedule than the timed one (the pool's counting build, lane = sample instead
+            # of lane = pixel): the flop counts do not depend on the schedule, lane utilisation does
+            same_schedule = kernel_schedule(counting_kernel) == kernel_schedule(kernel_name)
+            result["roofline"] = {
                 "bound": "valu_fp32",
                 "achieved": round(achieved_tflops, 3),
                 "peak": PEAK_FP32_VECTOR_TFLOPS,
@@ -971,37 +1020,37 @@ def main(argv=None) -> int:
                         "peak_gbs": PEAK_HBM_GBS},
                 "note": "fp32 vector-ALU roofline (no MFMA on this path; HBM traffic is the framebuffer + the scene tables once); "
                         "rocprofv3 summaries under profiles/",
-            },
-        }
-        if not multi and cfg["mode"] == "pt":
-            result["fast_math"] = fast_math_line(m, torch, ctx, base, frame.frame, total_samples, flops)
-            if args.config == "4":
-                result["texel_tiles"] = texel_tiles_line(m, torch, ctx, base, frame.frame, total_samples)
-            if args.config == "2" and not args.no_cpu_baseline:   # (not in the profiler passes: since round 4 it runs the timed kernel itself)
-                result["steady_state"] = steady_state_line(m, torch, ctx, base, w, h)
-        if not multi and cfg["mode"] == "parity":
-            result["parity_schedules"] = parity_schedules_line(m, torch, ctx, base, w, h)
-        if multi:
-            result["schedule_check"] = schedule_check           # the schedules tried before the timed region, most overlapped first; the last one ran
-            result["gather_ms"] = gather_ms
-            result["gather_note"] = "one gather + de-interleave alone on rank 0 (no render), after the timed region; the timed steps overlap it with the next frame's render"
-        cpu_rate = None
-        if not multi and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(m, sd, cfg)
-            result["gpu_over_cpu"] = round(value / result["cpu_baseline"]["value"], 1)
-            cpu_rate = result["cpu_baseline"]["value"] if cfg["mode"] == "pt" else None
-            if cfg["mode"] == "pt":                          # the reference's own CPU loop beside it (north_star's last sentence)
-                sys.path.insert(0, str(ROOT / "tests"))
-                import oracle_binding as ob
-                result["cpu_baseline"]["layer_rs"] = layer_rs_baseline(m, ob, build_scene(m, CONFIGS["parity"]), 1920, 1080)
-        if not args.no_cpu_baseline:
-            # the frame the timed region left on rank 0 -- for N > 1 the one gathered over RCCL -- against oracle rows
-            result["verified_rows"] = verify_rows(m, sd, cfg, frame.frame.cpu().numpy(), cpu_msamples_per_s=cpu_rate,
-                                                  self_rows=lambda first, last: self_render_rows(m, torch, ctx, base, first, last),
-                                                  against=VERIFY_CHECKER[args.verify_against])
-            if multi:       # every pixel of the gathered frame against rank 0's own render of the whole frame, when that is a few seconds
-                result["verified_whole_frame"] = verify_whole_frame_self(m, torch, ctx, base, frame.frame, sum(kernel_ms_per_rank))
-            result["verified_frame"] = "whole frame" if not multi else f"gathered from {world} rank{'s' if world > 1 else ' (rehearsal: a one-rank group)'} on rank 0"
+            }
+            if not multi and cfg["mode"] == "pt":
+                result["fast_math"] = fast_math_line(m, torch, ctx, base, frame.frame, total_samples, flops)
+                if args.config == "4":
+                    result["texel_tiles"] = texel_tiles_line(m, torch, ctx, base, frame.frame, total_samples)
+                if args.config == "2" and not args.no_cpu_baseline:   # (not in the profiler passes: since round 4 it runs the timed kernel itself)
+                    result["steady_state"] = steady_state_line(m, torch, ctx, base, w, h)
+            if not multi and cfg["mode"] == "parity":
+                result["parity_schedules"] = parity_schedules_line(m, torch, ctx, base, w, h)
+            if multi:
+                result["gather_ms"] = gather_ms
+                result["gather_note"] = "one gather + de-interleave alone on rank 0 (no render), after the timed region; the timed steps overlap it with the next frame's render"
+            cpu_rate = None
+            if not multi and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(m, sd, cfg)
+                result["gpu_over_cpu"] = round(value / result["cpu_baseline"]["value"], 1)
+                cpu_rate = result["cpu_baseline"]["value"] if cfg["mode"] == "pt" else None
+                if cfg["mode"] == "pt":                          # the reference's own CPU loop beside it (north_star's last sentence)
+                    sys.path.insert(0, str(ROOT / "tests"))
+                    import oracle_binding as ob
+                    result["cpu_baseline"]["layer_rs"] = layer_rs_baseline(m, ob, build_scene(m, CONFIGS["parity"]), 1920, 1080)
+            if not args.no_cpu_baseline:
+                # the frame the timed region left on rank 0 -- for N > 1 the one gathered over RCCL -- against oracle rows
+                result["verified_rows"] = verify_rows(m, sd, cfg, frame.frame.cpu().numpy(), cpu_msamples_per_s=cpu_rate,
+                                                      self_rows=lambda first, last: self_render_rows(m, torch, ctx, base, first, last),
+                                                      against=VERIFY_CHECKER[args.verify_against])
+                if multi:       # every pixel of the gathered frame against rank 0's own render of the whole frame, when that is a few seconds
+                    result["verified_whole_frame"] = verify_whole_frame_self(m, torch, ctx, base, frame.frame, sum(kernel_ms_per_rank))
+                result["verified_frame"] = "whole frame" if not multi else f"gathered from {world} rank{'s' if world > 1 else ' (rehearsal: a one-rank group)'} on rank 0"
+
+    if rank == 0:
         print(json.dumps(result), flush=True)
 
     ctx.close()

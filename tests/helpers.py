@@ -18,6 +18,22 @@ def _flattened(name: str):
     return sc, cam, mats, tex
 
 
+# The reference's two albedo maps (assets/*.jpeg, layer.rs:97,108) are 1024x512 4:4:4 JPEGs with the IJG tables of quality 92
+# (earthmap, baseline) and 90 (moon, progressive).  Their decodes are committed (weekend-raytracer-wgpu_amd/assets/); the tests that
+# need such a FILE encode one of the same kind from that decode (Pillow / libjpeg-turbo).
+ASSET_JPEG_KINDS = {"earthmap": dict(quality=92, subsampling=0, progressive=False),
+                    "moon": dict(quality=90, subsampling=0, progressive=True)}
+
+
+def asset_kind_jpeg(name: str, directory) -> Path:
+    """`directory`/`name`.jpeg: the committed decode of the reference asset `name`, encoded as that asset is."""
+    from PIL import Image
+    rgb = np.load(m.asset_path(f"assets/{name}.jpeg"))["rgb8"]
+    path = Path(directory) / f"{name}.jpeg"
+    Image.fromarray(rgb).save(path, "JPEG", **ASSET_JPEG_KINDS[name])
+    return path
+
+
 def scene_data(name: str, w: int, h: int) -> "m.SceneData":
     """SceneData of a BASELINE config scene with the camera built for a w x h viewport."""
     sc, cam, mats, tex = _flattened(name)

@@ -260,3 +260,45 @@ def test_the_complete_frame_test_never_compares_nothing():
     assert 2 <= len(mid) < 2160 // 16 and mid[0] == (0, 16) and mid[-1] == (2144, 2160)
     assert all(b - a == 16 for a, b in mid) and all(mid[i][1] <= mid[i + 1][0] for i in range(len(mid) - 1))
     assert full_frame_bands(8, 1000.0, 4, 1.0) == [(0, 8)]                              # a frame smaller than a band
+
+
+def test_a_plain_run_is_lean_and_full_is_opt_in():
+    """`--full` (everything beyond the headline figure) is off by default; `--dump-outputs` names a directory; `--steps` is the number of
+    timed steps and must be at least one."""
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs == ""
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+    assert bench.main(["--dry-run", "--steps", "0"]) == 2
+
+
+def test_dump_outputs_writes_the_frame_or_a_seeded_sample_of_its_rows(tmp_path, monkeypatch):
+    import numpy as np
+    frame = bench.pattern_rows(range(40), 24)
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame.astype(np.float32))
+    assert not (tmp_path / "whole" / "frame_rows.npy").exists()
+    # over the limit: a fixed sample of rows (sorted, the same from run to run) and their indices
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 128 + 10 * (24 * 4 * 4 + 8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    rows = np.load(tmp_path / "a" / "frame_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 10 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "frame_rows.npy"))
+    sample = np.load(tmp_path / "a" / "frame.npy")
+    assert sample.dtype == np.float32 and np.array_equal(sample, frame[rows.astype(int)].astype(np.float32))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_the_dry_run_dumps_the_frame_it_assembled(tmp_path):
+    """--dump-outputs after the timed steps, before anything else: in a dry run (no GPU) the pattern frame, exactly."""
+    import subprocess
+    import numpy as np
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--dry-run", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       env=_bare_env(), capture_output=True, text=True, timeout=300, cwd="/tmp")
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["frames_verified"] and d["steps"] == 2
+    frame = np.load(tmp_path / "frame.npy")
+    assert frame.dtype == np.float32 and np.array_equal(frame, bench.pattern_rows(range(108), 192).astype(np.float32))

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import weekend_raytracer_wgpu_amd as m
-from helpers import assert_images_equal, layer_scene_data
+from helpers import asset_kind_jpeg, assert_images_equal, layer_scene_data
 
 ROOT = Path(__file__).resolve().parent.parent
 DEMO = ROOT / "weekend-raytracer-wgpu_amd" / "host" / "layer_demo"
@@ -41,12 +41,18 @@ def test_cpp_layer_tables_and_validation(ppms):
     assert lines[2] == "validate: MIRT_ERR_MAX_SAMPLES_MULTIPLE"
 
 
-@pytest.mark.skipif(not Path("/root/reference/assets/moon.jpeg").exists(), reason="the reference tree is not present on this machine")
-def test_cpp_layer_scene_from_the_reference_jpegs(ppms):
-    """`Layer::scene` as the reference writes it (layer.rs:97,108): straight from assets/*.jpeg through the library's JPEG
-    decoder -- the same texel table, bit for bit, as from the committed decodes."""
-    a = subprocess.run([str(DEMO), "--host-only", ppms["moon"], ppms["earthmap"]], capture_output=True, text=True, timeout=120)
-    b = subprocess.run([str(DEMO), "--host-only", "/root/reference/assets/moon.jpeg", "/root/reference/assets/earthmap.jpeg"],
+def test_cpp_layer_scene_from_the_reference_jpegs(ppms, tmp_path):
+    """`Layer::scene` as the reference writes it (layer.rs:97,108): straight from JPEG files of the kind of its assets/*.jpeg
+    (helpers.asset_kind_jpeg) through the library's JPEG decoder -- the same texel table, bit for bit, as from those files'
+    decodes (libjpeg-turbo) written as PPMs."""
+    from PIL import Image
+    jpegs, decoded = {}, {}
+    for name in ("moon", "earthmap"):
+        jpegs[name] = asset_kind_jpeg(name, tmp_path)
+        decoded[name] = tmp_path / f"{name}.ppm"
+        Image.open(jpegs[name]).convert("RGB").save(decoded[name], "PPM")
+    a = subprocess.run([str(DEMO), "--host-only", str(decoded["moon"]), str(decoded["earthmap"])], capture_output=True, text=True, timeout=120)
+    b = subprocess.run([str(DEMO), "--host-only", str(jpegs["moon"]), str(jpegs["earthmap"])],
                        capture_output=True, text=True, timeout=120)
     assert a.returncode == 0 and b.returncode == 0, (a.stderr, b.stderr)
     assert a.stdout == b.stdout and "texels fnv" in a.stdout

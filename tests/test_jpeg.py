@@ -2,8 +2,8 @@
 
 Pins: (1) bit-identical RGB8 against Pillow (libjpeg-turbo: the IJG slow-integer IDCT, fixed-point YCbCr tables and
 triangle upsampling this decoder restates) on generated files of every supported kind — baseline / progressive, 4:4:4 /
-4:2:2 / 4:2:0, grey, optimised tables, restart intervals, sizes that are not multiples of the MCU; (2) the reference's two
-assets, when the reference tree is present (it is in the build container, not on the GPU box), against the decodes
+4:2:2 / 4:2:0, grey, optimised tables, restart intervals, sizes that are not multiples of the MCU; (2) files of the kind of the
+reference's two assets (helpers.asset_kind_jpeg: 1024x512, 4:4:4, baseline q92 / progressive q90), encoded from the decodes
 committed under weekend-raytracer-wgpu_amd/assets/ — those are what every texture test and bench.py --config 4 use.
 Against the `image` crate the decode stays decoder-unpinned."""
 import ctypes as C
@@ -15,8 +15,9 @@ import pytest
 
 import weekend_raytracer_wgpu_amd as m
 
+from helpers import asset_kind_jpeg
+
 Image = pytest.importorskip("PIL.Image")
-REF_ASSETS = Path("/root/reference/assets")
 
 
 def _gen(w, h, kind, seed=1):
@@ -91,17 +92,21 @@ def test_refused_files_report_an_error():
     assert got.shape == (120, 160, 3) and np.array_equal(got[:32], _pillow(big)[:32])       # the rows before the cut are intact
 
 
-@pytest.mark.skipif(not REF_ASSETS.is_dir(), reason="the reference tree is not present on this machine")
 @pytest.mark.parametrize("name,fixture", [("earthmap.jpeg", "earthmap_1024x512_rgb8.npz"), ("moon.jpeg", "moon_1024x512_rgb8.npz")])
-def test_reference_assets_decode_to_the_committed_texel_fixtures(name, fixture):
-    b = (REF_ASSETS / name).read_bytes()
+def test_reference_assets_decode_to_the_committed_texel_fixtures(name, fixture, tmp_path):
+    """A file of the asset's own kind (size, sampling, baseline / progressive, quantisation tables), encoded from the committed decode:
+    the library decodes it bit for bit as libjpeg-turbo does, and to the committed texels up to the encoding's own loss."""
+    path = asset_kind_jpeg(name[:-len(".jpeg")], tmp_path)
+    b = path.read_bytes()
     got = m.decode_jpeg(b)
-    want = np.load(Path(m.__file__).parent / "assets" / fixture)["rgb8"]
-    assert got.shape == want.shape == (512, 1024, 3)
+    fixed = np.load(Path(m.__file__).parent / "assets" / fixture)["rgb8"]
+    assert got.shape == fixed.shape == (512, 1024, 3)
+    want = _pillow(b)
     assert np.array_equal(got, want)
-    assert np.array_equal(got, _pillow(b))
+    err = np.abs(got.astype(np.int16) - fixed.astype(np.int16))
+    assert err.mean() < 0.5 and err.max() <= 8, (err.mean(), err.max())                                   # the same picture
     # and the Texture the reference's Layer::scene would build from the file
-    t = m.Texture.new_from_image(str(REF_ASSETS / name))
+    t = m.Texture.new_from_image(str(path))
     assert t.dimensions() == (1024, 512)
     assert np.array_equal(t.as_slice(), m.Texture.new_from_rgb8(want).as_slice())
 

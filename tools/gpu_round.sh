@@ -11,7 +11,7 @@ rc=$?
 tail -15 "$OUT/pytest.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest ended with $rc: stopping"; exit $rc; fi
 for c in 3 2 4 5 parity; do
-  timeout -k 10 400 python bench.py --config $c --steps $STEPS --warmup 2 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo "bench $c failed"; tail -5 "$OUT/bench_$c.err"; exit 1; }
+  timeout -k 10 400 python bench.py --config $c --full --steps $STEPS --warmup 2 > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo "bench $c failed"; tail -5 "$OUT/bench_$c.err"; exit 1; }
   python - "$OUT/bench_$c.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
