@@ -61,6 +61,11 @@ void mirt_oracle_math_atan2(const float* y, const float* x, float* r, size_t n);
 void mirt_oracle_math_log2(const float* x, float* y, size_t n);
 void mirt_oracle_math_exp2(const float* x, float* y, size_t n);
 void mirt_oracle_math_pow(const float* x, const float* y, float* r, size_t n);
+void mirt_oracle_math_sin_sign(const float* x, int32_t* sign, size_t n);      /* {-1, 0, +1} */
+void mirt_oracle_math_exp(const float* x, float* y, size_t n);
+/* the path-traced resolve: per-sample fixed point, and one channel sum of n_samples samples -> its 8-bit code */
+void mirt_oracle_to_fixed(const float* x, uint32_t* q, size_t n);
+void mirt_oracle_resolve_channel(const uint64_t* sums, uint8_t* codes, size_t n, uint32_t n_samples, uint32_t flags);
 /* the PT RNG (raytracer.wgsl:493-521): first `n` floats of the stream of (pixel, sample, seed) */
 void mirt_oracle_rng_stream(uint32_t pixel_index, uint32_t sample, uint64_t seed, float* out, size_t n);
 

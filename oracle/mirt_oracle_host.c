@@ -8,6 +8,7 @@
 #define _GNU_SOURCE
 #include "mirt_oracle_internal.h"
 #include "mirt_oracle_math.h"
+#include "mirt_oracle_resolve.h"
 
 #include <math.h>
 #include <omp.h>
@@ -277,4 +278,21 @@ void mirt_oracle_math_exp2(const float* x, float* y, size_t n)
 void mirt_oracle_math_pow(const float* x, const float* y, float* r, size_t n)
 {
     for (size_t i = 0; i < n; ++i) r[i] = om_pow_pos(x[i], y[i]);
+}
+void mirt_oracle_math_sin_sign(const float* x, int32_t* sign, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) sign[i] = om_sin_sign(x[i]);
+}
+void mirt_oracle_math_exp(const float* x, float* y, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) y[i] = om_exp(x[i]);
+}
+void mirt_oracle_to_fixed(const float* x, uint32_t* q, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) q[i] = to_fixed(x[i]);
+}
+void mirt_oracle_resolve_channel(const uint64_t* sums, uint8_t* codes, size_t n, uint32_t n_samples, uint32_t flags)
+{
+#pragma omp parallel for schedule(static) if (n >= 65536)
+    for (size_t i = 0; i < n; ++i) codes[i] = (uint8_t)om_resolve_channel(sums[i], n_samples, flags);
 }

@@ -37,6 +37,7 @@
 
 #include "mirt_oracle_internal.h"
 #include "mirt_oracle_math.h"
+#include "mirt_oracle_resolve.h"
 
 /* ---------------- RNG (wgsl:493-521) ---------------- */
 
@@ -317,14 +318,6 @@ static inline ov3 sky_color(const tctx_t* T, ov3 d)
     return ov(MFMA(t, 0.5f, omt), MFMA(t, 0.7f, omt), MFMA(t, 1.0f, omt));
 }
 
-static inline uint32_t to_fixed(float c)
-{
-    if (!(c > 0.0f)) return 0;                       /* negatives and NaN */
-    float s = c * 1048576.0f;
-    if (s >= 4294967040.0f) s = 4294967040.0f;        /* largest f32 below 2^32 */
-    return (uint32_t)s;
-}
-
 /* samplePixel + rayColor for ONE sample (wgsl:105-172) -> fixed-point rgb */
 /* `rng` = NULL: the sample's own stream (S1).  Otherwise the caller's running stream of the current frame
  * (MirtParams.frame_spp > 0: the reference's samplePixel loop, wgsl:105-122, draws all samples of a frame from one). */
@@ -357,46 +350,11 @@ static void trace_sample(const tctx_t* T, uint32_t x, uint32_t y, uint32_t sampl
     if (rng) *rng = st;              /* the frame's stream continues with the next sample */
 }
 
-/* ---------------- resolve (S5) ---------------- */
-
-static inline float uncharted2_tonemap(float x)
-{
-    const float A = 0.15f, B = 0.50f, CB = 0.05f, DE = 0.004f, DF = 0.06f;
-    const float EF = 0.02f / 0.30f;
-    float num = MFMA(x, MFMA(A, x, CB), DE);
-    float den = MFMA(x, MFMA(A, x, B), DF);
-    return num / den - EF;
-}
-
-static inline float uncharted2(float x)
-{
-    float curr = uncharted2_tonemap(0.246f * x);
-    float white = 1.0f / uncharted2_tonemap(11.2f);
-    return white * curr;
-}
-
-static inline float srgb_oetf(float x)
-{
-    if (!(x > 0.0031308f)) return 12.92f * x;
-    return MFMA(1.055f, om_pow_pos(x, 0.41666666f), -0.055f);
-}
-
-static inline uint8_t quantise(float x)
-{
-    if (!(x > 0.0f)) return 0;
-    if (x > 1.0f) x = 1.0f;
-    return (uint8_t)MFMA(x, 255.0f, 0.5f);
-}
+/* ---------------- resolve (S5, mirt_oracle_resolve.h) ---------------- */
 
 static void resolve_pixel(const uint64_t sum[3], uint32_t n_samples, uint32_t flags, uint8_t px[4])
 {
-    double denom = (double)n_samples * 1048576.0;
-    for (int k = 0; k < 3; ++k) {
-        float m = (float)((double)sum[k] / denom);
-        if (!(flags & MIRT_FLAG_NO_TONEMAP)) m = uncharted2(m);
-        if (!(flags & MIRT_FLAG_NO_SRGB)) m = srgb_oetf(m);
-        px[k] = quantise(m);
-    }
+    for (int k = 0; k < 3; ++k) px[k] = (uint8_t)om_resolve_channel(sum[k], n_samples, flags);
     px[3] = 255;
 }
 

@@ -50,6 +50,10 @@ def _load() -> C.CDLL:
         "mirt_oracle_math_log2": (None, [fp, fp, C.c_size_t]),
         "mirt_oracle_math_exp2": (None, [fp, fp, C.c_size_t]),
         "mirt_oracle_math_pow": (None, [fp, fp, fp, C.c_size_t]),
+        "mirt_oracle_math_sin_sign": (None, [fp, P(C.c_int32), C.c_size_t]),
+        "mirt_oracle_math_exp": (None, [fp, fp, C.c_size_t]),
+        "mirt_oracle_to_fixed": (None, [fp, P(C.c_uint32), C.c_size_t]),
+        "mirt_oracle_resolve_channel": (None, [P(C.c_uint64), P(C.c_uint8), C.c_size_t, C.c_uint32, C.c_uint32]),
         "mirt_oracle_rng_stream": (None, [C.c_uint32, C.c_uint32, C.c_uint64, fp, C.c_size_t]),
         "mirt_params_out_rows_impl": (C.c_uint32, [P(_abi.MirtParams)]),
         "mirt_params_out_row_index_impl": (C.c_uint32, [P(_abi.MirtParams), C.c_uint32]),
@@ -179,6 +183,34 @@ def pow_pos(x, y):
     r = np.empty_like(x)
     LIB.mirt_oracle_math_pow(_fp(x), _fp(y), _fp(r), x.size)
     return r
+
+
+def exp(x): return _unary(LIB.mirt_oracle_math_exp, x)
+
+
+def sin_sign(x):
+    """Sign of sin(x) in {-1, 0, +1} from the argument reduction of sincos (int32)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty(x.shape, dtype=np.int32)
+    LIB.mirt_oracle_math_sin_sign(_fp(x), out.ctypes.data_as(C.POINTER(C.c_int32)), x.size)
+    return out
+
+
+def to_fixed(x):
+    """Per-sample radiance -> fixed point, 2^-20 units clamped to [0, 4096) (uint32)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty(x.shape, dtype=np.uint32)
+    LIB.mirt_oracle_to_fixed(_fp(x), out.ctypes.data_as(C.POINTER(C.c_uint32)), x.size)
+    return out
+
+
+def resolve_channel(sums, n_samples: int, flags: int = 0):
+    """The 8-bit code of each channel sum of `n_samples` fixed-point samples (uint8)."""
+    sums = np.ascontiguousarray(sums, dtype=np.uint64)
+    out = np.empty(sums.shape, dtype=np.uint8)
+    LIB.mirt_oracle_resolve_channel(sums.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    sums.size, n_samples, flags)
+    return out
 
 
 def rng_stream(pixel_index: int, sample: int, seed: int, n: int) -> np.ndarray:
