@@ -425,6 +425,63 @@ int mirt_ctx_deinterleave_device(MirtContext* ctx, const MirtParams* params, con
                                  size_t part_stride, void* d_out_rgba8, size_t out_len,
                                  void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Node: ONE host process renders one frame on several devices (csrc/mirt_node.hip)
+ *
+ * A node drives one member context per entry of a device list.  Member i renders the rows of the 4-row tile interleave with
+ * tile_rows = 4, n_parts = n, part = i; the parts are brought to member 0 and assembled there into the band image.  The result
+ * is byte-identical to mirt_ctx_render of the whole band on one context, for every member count, mode and flag.
+ *   transports: every entry names the SAME device -> loopback: the parts stay in the members' own buffers and the assembly
+ *               reads them in place (no copies, no RCCL; exists to exercise the node on one device, no speed-up);
+ *               all entries DISTINCT -> RCCL: ncclCommInitAll once in mirt_node_create, per frame one ncclGather per member
+ *               (inside ncclGroupStart/End, on the member streams) of its part, padded to the largest part, into a parts
+ *               buffer on member 0.  A mixed list such as {0, 1, 0} is refused.  librccl is loaded with dlopen, and only
+ *               by a node that uses RCCL (an already loaded librccl first, then ROCm's): libmirt.so does not link it.
+ *   params:     the node owns the partition: tile_rows, n_parts and part must be 0 (else MIRT_ERR_BAD_ROWS); every other
+ *               field -- band, sample_begin, frame_spp / frame_begin, mode, flags -- reaches every member unchanged.  A member
+ *               with no rows (a band of fewer than 4 * n rows) is skipped.  With n == 1 and loopback the one member renders
+ *               the band straight into the output.
+ *   ordering:   members render on their own context streams; the assembly waits on their render-done events (loopback)
+ *               or on the gather (RCCL) with stream waits, never a host sync.  A member does not overwrite its part before
+ *               the previous frame's assembly has read it (an event).  Node buffers grow and are never shrunk.
+ *   errors:     MIRT_ERR_NULL_POINTER for null arguments; MIRT_ERR_NO_DEVICE for an empty list, more than
+ *               MIRT_NODE_MAX_MEMBERS entries, a mixed list, MIRT_NODE_RCCL on a repeated device, a bad ordinal, or no GPU
+ *               (no CPU fallback); MIRT_ERR_HIP for an RCCL failure or a missing librccl ("RCCL: ..." in mirt_last_error);
+ *               MIRT_ERR_NO_SCENE for a render before a successful mirt_node_set_scene.
+ *   threading:  a node is used from one host thread at a time, like a context.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct MirtNode MirtNode;                 /* opaque */
+#define MIRT_NODE_MAX_MEMBERS 16
+enum {
+    MIRT_NODE_RCCL = 1u << 0                      /* mirt_node_create flags: force the RCCL transport (even for n = 1) */
+};
+typedef struct MirtNodeStats {
+    uint32_t n_members;
+    uint32_t transport;                           /* 0 = same-device loopback, 1 = RCCL */
+    double   gather_ms;                           /* RCCL: member 0's stream, hipEvents: all member parts ready -> gather done; 0 for loopback */
+    double   assemble_ms;                         /* the assembly kernel of the last render (0 if the last render needed none) */
+} MirtNodeStats;
+
+/* Create a node of `n` members on devices[0..n).  flags: MIRT_NODE_*.  The list's shape is checked before any HIP call. */
+int  mirt_node_create(const int* devices, uint32_t n, uint32_t flags, MirtNode** out);
+/* Waits for everything the node queued, tears the communicators down, destroys the member contexts. */
+void mirt_node_destroy(MirtNode* node);
+/* mirt_ctx_set_scene on every member; if one fails the node has no scene until a later call succeeds. */
+int  mirt_node_set_scene(MirtNode* node, const MirtScene* scene);
+/* mirt_ctx_set_camera on every member (host-side only). */
+int  mirt_node_set_camera(MirtNode* node, const MirtGpuCamera* camera);
+/* Render the band into HOST memory (mirt_params_out_rows(params) * width * 4 bytes); blocking. */
+int  mirt_node_render(MirtNode* node, const MirtParams* params, uint8_t* out_rgba8, size_t out_len);
+/* Render the band into DEVICE memory on member 0's device, asynchronously: the assembly into `d_out_rgba8` is ordered after the
+ * work queued so far on `hip_stream` (a hipStream_t of member 0's device; NULL = the node's own stream) and the result is ordered
+ * on it.  hipStreamLegacy is refused (MIRT_ERR_HIP): pass a stream of your own. */
+int  mirt_node_render_device(MirtNode* node, const MirtParams* params, void* d_out_rgba8, size_t out_len, void* hip_stream);
+/* Member i's context, BORROWED (do not destroy it): per-member statistics, mirt_ctx_last_kernel, mirt_ctx_set_timing.
+ * MIRT_ERR_BAD_ROWS for i >= n. */
+int  mirt_node_context(MirtNode* node, uint32_t i, MirtContext** out);
+/* Members and transport, and the times of the last render (waits for it). */
+int  mirt_node_get_stats(MirtNode* node, MirtNodeStats* out);
+
 #ifdef __cplusplus
 } /* extern "C" */
 

@@ -187,6 +187,24 @@ pub struct MirtContext {
     _private: [u8; 0],
 }
 
+// Node: one process renders one frame on several devices (mirt_node_*, include/mirt.h)
+pub const MIRT_NODE_MAX_MEMBERS: u32 = 16;
+pub const MIRT_NODE_RCCL: u32 = 1 << 0;
+
+#[repr(C)]
+pub struct MirtNode {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtNodeStats {
+    pub n_members: u32,
+    pub transport: u32,
+    pub gather_ms: f64,
+    pub assemble_ms: f64,
+}
+
 extern "C" {
     pub fn mirt_version() -> u32;
     pub fn mirt_last_error() -> *const c_char;
@@ -224,4 +242,12 @@ extern "C" {
     pub fn mirt_rgb8_to_texels(rgb: *const u8, n_pixels: usize, texels: *mut f32) -> c_int;
     pub fn mirt_jpeg_last_error() -> *const c_char;
     pub fn mirt_ctx_deinterleave_device(ctx: *mut MirtContext, params: *const MirtParams, d_parts: *const c_void, part_stride: usize, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_node_create(devices: *const c_int, n: u32, flags: u32, out: *mut *mut MirtNode) -> c_int;
+    pub fn mirt_node_destroy(node: *mut MirtNode);
+    pub fn mirt_node_set_scene(node: *mut MirtNode, scene: *const MirtScene) -> c_int;
+    pub fn mirt_node_set_camera(node: *mut MirtNode, camera: *const MirtGpuCamera) -> c_int;
+    pub fn mirt_node_render(node: *mut MirtNode, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
+    pub fn mirt_node_render_device(node: *mut MirtNode, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_node_context(node: *mut MirtNode, i: u32, out: *mut *mut MirtContext) -> c_int;
+    pub fn mirt_node_get_stats(node: *mut MirtNode, out: *mut MirtNodeStats) -> c_int;
 }

@@ -22,6 +22,10 @@ MIRT_FLAG_COUNT_GRID = 1 << 7
 MIRT_FLAG_FAST_MATH = 1 << 8
 MIRT_FLAG_TEXEL_TILES = 1 << 9
 
+# mirt_node_create: members at most, and its flags
+MIRT_NODE_MAX_MEMBERS = 16
+MIRT_NODE_RCCL = 1 << 0
+
 MIRT_OK = 0
 STATUS = {
     0: "MIRT_OK",
@@ -129,6 +133,14 @@ class MirtStats(C.Structure):
                 "texel_fetches": list(self.texel_fetches), "texel_tile_hits": list(self.texel_tile_hits)}
 
 
+class MirtNodeStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("transport", C.c_uint32), ("gather_ms", C.c_double), ("assemble_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"n_members": self.n_members, "transport": self.transport, "gather_ms": self.gather_ms,
+                "assemble_ms": self.assemble_ms}
+
+
 # every symbol include/mirt.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -169,6 +181,14 @@ SYMBOLS = {
     "mirt_jpeg_last_error": (C.c_char_p, []),
     "mirt_ctx_deinterleave_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t,
                                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mirt_node_create": (C.c_int, [_P(C.c_int), C.c_uint32, C.c_uint32, _P(C.c_void_p)]),
+    "mirt_node_destroy": (None, [C.c_void_p]),
+    "mirt_node_set_scene": (C.c_int, [C.c_void_p, _P(MirtScene)]),
+    "mirt_node_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
+    "mirt_node_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
+    "mirt_node_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mirt_node_context": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_void_p)]),
+    "mirt_node_get_stats": (C.c_int, [C.c_void_p, _P(MirtNodeStats)]),
 }
 
 

@@ -307,6 +307,16 @@ int ensure_capacity(T** ptr, size_t* cap, size_t need)
 
 }  // namespace
 
+// the message of a failing C-ABI call, for the library's other translation units (mirt_node.hip)
+int mirt::set_error(int status, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return status;
+}
+
 struct MirtContext {
     int         device = -1;
     int         cu_count = 0;
@@ -1425,10 +1435,11 @@ int mirt_ctx_deinterleave_device(MirtContext* c, const MirtParams* p, const void
     for (uint32_t i = 0; i < p->n_parts; ++i) { q.part = i; const uint32_t r = out_rows(&q); if (r > max_rows) max_rows = r; }
     if (part_stride < (size_t)max_rows * p->width * 4) return fail(MIRT_ERR_OUT_BUFFER, "part_stride smaller than the largest part");
     HIP_TRY(hipSetDevice(c->device));
-    mirt::DeinterleaveArgs d{};
-    d.parts = (const uint32_t*)d_parts; d.out = (uint32_t*)d_out; d.part_stride_px = part_stride / 4;
+    mirt::AssembleArgs d{};
+    d.parts[0] = (const uint32_t*)d_parts; d.out = (uint32_t*)d_out; d.part_stride_px = part_stride / 4;
     d.width = p->width; d.band_rows = band; d.tile_rows = p->tile_rows; d.n_parts = p->n_parts;
-    HIP_TRY(kx::launch_deinterleave(d, hip_stream ? (hipStream_t)hip_stream : c->stream));
+    d.vec4 = (p->width % 4 == 0 && part_stride % 16 == 0 && (uintptr_t)d_parts % 16 == 0 && (uintptr_t)d_out % 16 == 0) ? 1u : 0u;
+    HIP_TRY(kx::launch_assemble(d, mirt::LaunchOn(hip_stream ? (hipStream_t)hip_stream : c->stream)));
     return MIRT_OK;
 }
 

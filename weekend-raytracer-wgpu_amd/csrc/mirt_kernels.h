@@ -202,11 +202,17 @@ struct RenderArgs {
     float    sph3[12];                     // scenes of exactly three spheres: their {centre, r^2} records as kernel arguments (scalar loads)
 };
 
-struct DeinterleaveArgs {
-    const uint32_t* parts;      // n_parts buffers back-to-back, part_stride_px pixels apart
+// The parts of a tile-interleaved frame and where they go (assemble_parts_kernel).  Two forms:
+//   table  (part_stride_px == 0): parts[i] is part i's compact buffer, n_parts <= kAssembleMaxParts (the node's members);
+//   stride (part_stride_px != 0): part i starts at parts[0] + i * part_stride_px, any n_parts (mirt_ctx_deinterleave_device).
+// vec4 = 1 only if every row start is 16-byte aligned: width % 4 == 0, the part pointers (or base and stride) and out 16-byte aligned.
+constexpr uint32_t kAssembleMaxParts = 16;
+struct AssembleArgs {
+    const uint32_t* parts[kAssembleMaxParts];
     uint32_t*       out;        // band image [band_rows][width]
     uint64_t        part_stride_px;
     uint32_t        width, band_rows, tile_rows, n_parts;
+    uint32_t        vec4;
 };
 
 // Where a render kernel is dispatched: the stream, and optionally the event pair of the launch.  Non-null events ride on the kernel
@@ -242,9 +248,12 @@ uint32_t pool_scatter_queues(uint32_t n_routines, bool count);
 hipError_t launch_resolve(const unsigned long long* accum, uint32_t* out, uint64_t n_pixels, uint32_t n_samples,
                           uint32_t flags, hipStream_t stream);
 hipError_t launch_selftest_math(unsigned long long* d_mismatches, hipStream_t stream);
-hipError_t launch_deinterleave(const DeinterleaveArgs& a, hipStream_t stream);
+hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);
 size_t     scene_lds_bytes(uint32_t n_spheres, uint32_t n_mats, bool pt, bool hosek);
 size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);
 }  // namespace exact_build
+
+// host side (mirt_api.hip): sets the thread's mirt_last_error() message and returns `status`
+int set_error(int status, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 }  // namespace mirt

@@ -1821,7 +1821,7 @@ struct WavePoolLayout {
 #include "mirt_isa_probes.inc"       // tools/isa_mix.py; never part of libmirt.so
 #endif
 
-#ifndef MIRT_FAST_MATH       // self-test, resolve and de-interleave live in the exact build only
+#ifndef MIRT_FAST_MATH       // self-test, resolve and frame assembly live in the exact build only
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns
 // ------------------------------------------------------------------------------------------
@@ -1875,20 +1875,27 @@ hipError_t launch_resolve(const unsigned long long* accum, uint32_t* out, uint64
 }
 
 // ------------------------------------------------------------------------------------------
-// de-interleave: root side of the multi-GPU gather (tile-interleaved parts -> band image)
+// frame assembly: root side of a tile-interleaved render (compact parts -> band image).  One block per output row (grid-stride):
+// (part, local row) are computed once per row, in scalar registers, and the row is copied with 16-byte accesses when every row
+// start is 16-byte aligned (AssembleArgs.vec4), with dwords otherwise.
 // ------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void deinterleave_kernel(DeinterleaveArgs D)
+__global__ __launch_bounds__(256) void assemble_parts_kernel(AssembleArgs A)
 {
-    const uint64_t total = (uint64_t)D.band_rows * D.width;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t row = (uint32_t)(i / D.width);
-        const uint32_t x = (uint32_t)(i - (uint64_t)row * D.width);
-        const uint32_t tile = row / D.tile_rows;
-        const uint32_t part = tile % D.n_parts;
-        const uint32_t local_row = (tile / D.n_parts) * D.tile_rows + row % D.tile_rows;
-        D.out[i] = D.parts[(uint64_t)part * D.part_stride_px + (uint64_t)local_row * D.width + x];
+    for (uint32_t row = blockIdx.x; row < A.band_rows; row += gridDim.x) {
+        const uint32_t tile = row / A.tile_rows;
+        const uint32_t part = tile % A.n_parts;
+        const uint32_t local_row = (tile / A.n_parts) * A.tile_rows + (row - tile * A.tile_rows);
+        const uint32_t* base = A.part_stride_px != 0 ? A.parts[0] + (uint64_t)part * A.part_stride_px : A.parts[part];
+        const uint32_t* __restrict__ src = base + (uint64_t)local_row * A.width;
+        uint32_t* __restrict__ dst = A.out + (uint64_t)row * A.width;
+        if (A.vec4) {
+            const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
+            uint4* __restrict__ d4 = reinterpret_cast<uint4*>(dst);
+            for (uint32_t x = threadIdx.x; x < A.width / 4u; x += blockDim.x) d4[x] = s4[x];
+        } else {
+            for (uint32_t x = threadIdx.x; x < A.width; x += blockDim.x) dst[x] = src[x];
+        }
     }
 }
 
@@ -2198,13 +2205,14 @@ void pool_kernel_name(const RenderArgs& a, uint32_t cfg, bool count, uint32_t nq
 }
 
 #ifndef MIRT_FAST_MATH
-hipError_t launch_deinterleave(const DeinterleaveArgs& a, hipStream_t stream)
+hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on)
 {
-    const uint64_t total = (uint64_t)a.band_rows * a.width;
-    uint32_t blocks = (uint32_t)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(deinterleave_kernel, dim3(blocks), dim3(256), 0, stream, a);
+    const uint32_t blocks = a.band_rows < 4096u ? (a.band_rows ? a.band_rows : 1u) : 4096u;
+    if (on.end != nullptr) {                       // the node's timing events ride on the dispatch
+        hipExtLaunchKernelGGL(assemble_parts_kernel, dim3(blocks), dim3(256), 0, on.stream, on.begin, on.end, 0u, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(assemble_parts_kernel, dim3(blocks), dim3(256), 0, on.stream, a);
     return hipGetLastError();
 }
 #endif

@@ -266,6 +266,56 @@ private:
     std::vector<uint8_t> rgba_;
 };
 
+// Node — one frame on several devices (mirt_node_*): member contexts on `devices`, the parts assembled on member 0.  Same
+// device everywhere -> loopback; all distinct (or rccl = true) -> RCCL gather.  Throws MirtError like the rest of the mirror.
+class Node {
+public:
+    explicit Node(const std::vector<int>& devices, bool rccl = false)
+    {
+        check(mirt_node_create(devices.data(), (uint32_t)devices.size(), rccl ? (uint32_t)MIRT_NODE_RCCL : 0u, &node_));
+    }
+    ~Node() { if (node_) mirt_node_destroy(node_); }
+    Node(const Node&) = delete;
+    Node& operator=(const Node&) = delete;
+    Node(Node&& o) noexcept : node_(o.node_) { o.node_ = nullptr; }
+    Node& operator=(Node&& o) noexcept
+    {
+        if (this != &o) { if (node_) mirt_node_destroy(node_); node_ = o.node_; o.node_ = nullptr; }
+        return *this;
+    }
+
+    void set_scene(const MirtScene& scene) { check(mirt_node_set_scene(node_, &scene)); }
+    void set_camera(const MirtGpuCamera& camera) { check(mirt_node_set_camera(node_, &camera)); }
+    // the band of `p` (tile_rows = n_parts = part = 0) as RGBA8, blocking
+    std::vector<uint8_t> render(const MirtParams& p)
+    {
+        std::vector<uint8_t> out((size_t)mirt_params_out_rows(&p) * p.width * 4);
+        check(mirt_node_render(node_, &p, out.data(), out.size()));
+        return out;
+    }
+    // asynchronous, into device memory on member 0's device, ordered on `hip_stream` (nullptr: the node's own stream)
+    void render_device(const MirtParams& p, void* d_out_rgba8, size_t out_len, void* hip_stream = nullptr)
+    {
+        check(mirt_node_render_device(node_, &p, d_out_rgba8, out_len, hip_stream));
+    }
+    MirtContext* context(uint32_t i) const            // borrowed: the node owns it
+    {
+        MirtContext* c = nullptr;
+        check(mirt_node_context(node_, i, &c));
+        return c;
+    }
+    MirtNodeStats stats() const
+    {
+        MirtNodeStats s{};
+        check(mirt_node_get_stats(node_, &s));
+        return s;
+    }
+    MirtNode* raw() const { return node_; }
+
+private:
+    MirtNode* node_ = nullptr;
+};
+
 // Raytracer — the path-traced mode behind the names of src/raytracer/mod.rs:20-394 (wgpu plumbing
 // omitted).  render_frame() = RenderProgress::next_frame (mod.rs:626-670) + the shader's accumulation.
 class Raytracer {

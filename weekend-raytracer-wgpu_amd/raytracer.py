@@ -18,6 +18,7 @@ import numpy as np
 from . import _abi
 from ._lib import MirtError, check, lib
 from .context import Context, SceneData, make_params
+from .node import Node
 
 f32 = np.float32
 
@@ -389,8 +390,10 @@ def asset_path(name: str) -> str:
 # ------------------------------------------------------------------------------------------------
 
 class Layer:
-    def __init__(self, size, render_params: RenderParams, *, device: int = 0, scene: Optional[Scene] = None):
-        # layer.rs:49-88
+    def __init__(self, size, render_params: RenderParams, *, device: int = 0, scene: Optional[Scene] = None,
+                 devices: Optional[Sequence[int]] = None):
+        # layer.rs:49-88.  `devices`: set_data renders through a Node on those devices (one frame cut across its members)
+        # instead of one Context on `device`; the image is the same.
         self.vp_size = [float(f32(size[0])), float(f32(size[1]))]
         self.camera = GpuCamera.new(render_params.camera, (int(self.vp_size[0]), int(self.vp_size[1])))
         sc = scene if scene is not None else Layer.scene()
@@ -401,6 +404,8 @@ class Layer:
         self.texture_id = 0
         self._device = device
         self._ctx: Optional[Context] = None
+        self._devices = list(devices) if devices is not None else None
+        self._node: Optional[Node] = None
         self._rgba: Optional[np.ndarray] = None
         self.last_stats: Optional[dict] = None
 
@@ -439,10 +444,17 @@ class Layer:
 
     def set_data(self, render_params: RenderParams) -> None:   # layer.rs:264-282 -> ONE FFI call
         w, h = int(self.vp_size[0]), int(self.vp_size[1])
+        params = make_params(w, h, render_params.sampling.num_samples_per_pixel, mode=_abi.MIRT_MODE_PARITY)
+        if self._devices is not None:
+            if self._node is None:
+                self._node = Node(self._devices)
+            self._node.set_scene(self.scene_data())
+            self._rgba = self._node.render(params)
+            self.last_stats = self._node.stats()
+            return
         if self._ctx is None:
             self._ctx = Context(self._device)
         self._ctx.set_scene(self.scene_data())
-        params = make_params(w, h, render_params.sampling.num_samples_per_pixel, mode=_abi.MIRT_MODE_PARITY)
         self._rgba = self._ctx.render(params)
         self.last_stats = self._ctx.stats()
 
@@ -473,6 +485,9 @@ class Layer:
         if self._ctx is not None:
             self._ctx.close()
             self._ctx = None
+        if self._node is not None:
+            self._node.close()
+            self._node = None
 
 
 # ------------------------------------------------------------------------------------------------
