@@ -220,8 +220,8 @@ typedef struct MirtStats {
     uint64_t sky_misses;       /* rays that left the scene */
     uint64_t lane_iterations;  /* PT: active lanes summed over bounce-loop iterations */
     uint64_t wave_iterations;  /* PT: bounce-loop iterations summed over waves (x64 = lane slots) */
-    uint64_t grid_cells;       /* MIRT_FLAG_COUNT_GRID: grid cells visited, summed over lanes */
-    uint64_t grid_wave_cells;  /* MIRT_FLAG_COUNT_GRID: cell-loop iterations summed over waves (x64 = lane slots) */
+    uint64_t grid_cells;       /* MIRT_FLAG_COUNT_GRID: grid cells visited, summed over lanes (MIRT_SCENE_HBM: BVH nodes visited, leaves included) */
+    uint64_t grid_wave_cells;  /* MIRT_FLAG_COUNT_GRID: cell-loop iterations summed over waves (x64 = lane slots; MIRT_SCENE_HBM: BVH loop iterations) */
     uint64_t texel_fetches[2];   /* MIRT_FLAG_TEXEL_TILES: image-texel fetches at [0] camera-ray hits, [1] later bounces */
     uint64_t texel_tile_hits[2]; /* ... of those, served by the wave's LDS tile */
 } MirtStats;
@@ -256,7 +256,9 @@ typedef enum MirtStatus {
      *       2 * (entries beyond the first two of each cell).  A blob that leaves the pooled kernel no
      *       room for its path pools (mirt_grid_plan: pool_slots = 0) runs the strip kernel's grid build.  mirt_grid_plan() answers "which grid would this scene get" without a device.
      * A scene that fits ONLY the grid layout renders in path-traced mode with default flags; a render call in parity mode, or
-     * with MIRT_FLAG_COUNT_WORK without MIRT_FLAG_COUNT_GRID, or with MIRT_FLAG_NO_GRID, returns this code. */
+     * with MIRT_FLAG_COUNT_WORK without MIRT_FLAG_COUNT_GRID, or with MIRT_FLAG_NO_GRID, returns this code.
+     * A world that fits neither layout is set with MIRT_SCENE_HBM (mirt_ctx_set_scene_ex below): its tables stay in device memory
+     * and a BVH replaces the grid, up to MIRT_SCENE_HBM_MAX_SPHERES spheres; above that, set_scene_ex returns this code too. */
     MIRT_ERR_SCENE_TOO_LARGE      = -18,
     MIRT_ERR_FRAME_SPP            = -19, /* frame_spp does not divide spp / sample_begin */
     MIRT_ERR_NO_DEVICE            = -20,
@@ -327,6 +329,45 @@ void mirt_ctx_destroy(MirtContext* ctx);
  * `Layer::new` + `set_global_data` leave in `self`, layer.rs:49-148).  The scene stays
  * resident across render calls until replaced. */
 int mirt_ctx_set_scene(MirtContext* ctx, const MirtScene* scene);
+/* ---- worlds beyond the LDS budget: the scene's tables in device memory, nearest hit through a BVH ----
+ * flags == 0: exactly mirt_ctx_set_scene.  MIRT_SCENE_HBM keeps the spheres, materials and a BVH over the spheres in device memory
+ * whatever the scene's size (small scenes too, so that the path can be compared with the LDS builds); LDS then holds the camera,
+ * the sky and the traversal stacks.  At most MIRT_SCENE_HBM_MAX_SPHERES spheres (512 MiB of 32-byte spheres, the reference's
+ * storage-buffer size, main.rs:448), checked before any sphere is read: MIRT_ERR_SCENE_TOO_LARGE.  Unknown flag bits:
+ * MIRT_ERR_BAD_MODE; a failed allocation: MIRT_ERR_ALLOC.  Failure-atomic like mirt_ctx_set_scene (a refused call leaves the previous
+ * scene in place; a failure after validation leaves no scene).
+ * Render calls on such a scene keep every meaning of MirtParams; the image is byte-identical to the flat scan's:
+ *   default                     lane-per-pixel strip kernel with BVH traversal (render_pt_hbm_kernel<COUNT,HOSEK,true,BY_PIXEL>);
+ *   MIRT_FLAG_FAST_MATH         the fast-math compilation of the same kernel ("fast_build::" + its name);
+ *   MIRT_FLAG_NO_GRID           the flat scan of the sphere table in device memory (render_pt_hbm_kernel<...,false,...>);
+ *   MIRT_FLAG_COUNT_WORK        alone: counts that flat scan (every counter equals the oracle's); with MIRT_FLAG_COUNT_GRID: counts the
+ *                               BVH build (sphere_tests = tests performed, grid_cells / grid_wave_cells = BVH nodes visited);
+ *   MIRT_FLAG_KERNEL_STRIP / _POOL / _TEXEL_TILES: schedule hints, ignored;
+ *   parity mode                 the layer.rs flat scan with the spheres in device memory (render_parity_hbm_kernel).
+ * The BVH: binned SAH over the sphere centres, binary, leaves of at most MIRT_BVH_MAX_LEAF spheres, depth at most MIRT_BVH_MAX_DEPTH by
+ * construction; up to MIRT_BVH_MAX_ALWAYS spheres (those larger than MIRT_BVH_BIG_RADII median radii, and those whose box is not finite)
+ * are tested for every ray instead.  Deterministic, built on at most 16 host threads. */
+enum {
+    MIRT_SCENE_HBM = 1u << 0                      /* mirt_ctx_set_scene_ex / mirt_node_set_scene_ex flags */
+};
+#define MIRT_SCENE_HBM_MAX_SPHERES (1u << 24)
+#define MIRT_BVH_MAX_DEPTH  32                    /* levels below the root; sizes the kernels' traversal stacks */
+#define MIRT_BVH_MAX_LEAF   4
+#define MIRT_BVH_MAX_ALWAYS 64
+#define MIRT_BVH_BIG_RADII  4
+int mirt_ctx_set_scene_ex(MirtContext* ctx, const MirtScene* scene, uint32_t flags);
+/* What the BVH of those spheres would be: HOST-ONLY (no device, no context), the same tree set_scene_ex builds.
+ *   n_nodes          inner nodes (== n_leaves - 1 for a non-empty tree), 64 bytes each (both child boxes in the parent)
+ *   n_leaves         leaves; n_leaf_spheres spheres in them, n_always on the always-tested list (n_leaf_spheres + n_always == n_spheres)
+ *   max_depth        deepest leaf (root = 0), <= MIRT_BVH_MAX_DEPTH;  max_leaf = largest leaf, <= MIRT_BVH_MAX_LEAF
+ *   device_bytes     64 * n_nodes + 20 * n_spheres: nodes, test records {centre, r^2} and original sphere ids (u32), always list first
+ * MIRT_ERR_SCENE_TOO_LARGE above MIRT_SCENE_HBM_MAX_SPHERES. */
+typedef struct MirtBvhPlan {
+    uint32_t n_nodes, n_leaves, n_leaf_spheres, n_always, max_depth, max_leaf;
+    uint64_t device_bytes;
+} MirtBvhPlan;
+int mirt_bvh_plan(const MirtSphere* spheres, uint32_t n_spheres, MirtBvhPlan* out);
+
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by
  * value with each launch, so this neither copies to the device nor synchronises; launches already
@@ -468,6 +509,8 @@ int  mirt_node_create(const int* devices, uint32_t n, uint32_t flags, MirtNode**
 void mirt_node_destroy(MirtNode* node);
 /* mirt_ctx_set_scene on every member; if one fails the node has no scene until a later call succeeds. */
 int  mirt_node_set_scene(MirtNode* node, const MirtScene* scene);
+/* mirt_ctx_set_scene_ex on every member (flags: MIRT_SCENE_*; checked before any member is touched). */
+int  mirt_node_set_scene_ex(MirtNode* node, const MirtScene* scene, uint32_t flags);
 /* mirt_ctx_set_camera on every member (host-side only). */
 int  mirt_node_set_camera(MirtNode* node, const MirtGpuCamera* camera);
 /* Render the band into HOST memory (mirt_params_out_rows(params) * width * 4 bytes); blocking. */

@@ -161,6 +161,28 @@ pub struct MirtGridPlan {
     pub pool_slots: u32,
 }
 
+/// `mirt_bvh_plan`: the BVH `mirt_ctx_set_scene_ex(.., MIRT_SCENE_HBM)` builds (host only).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtBvhPlan {
+    pub n_nodes: u32,
+    pub n_leaves: u32,
+    pub n_leaf_spheres: u32,
+    pub n_always: u32,
+    pub max_depth: u32,
+    pub max_leaf: u32,
+    pub device_bytes: u64,
+}
+
+/// `mirt_ctx_set_scene_ex` / `mirt_node_set_scene_ex` flags: the scene's tables in device memory, nearest hit through a BVH
+/// (worlds beyond the LDS budget, up to `MIRT_SCENE_HBM_MAX_SPHERES`).
+pub const MIRT_SCENE_HBM: u32 = 1 << 0;
+pub const MIRT_SCENE_HBM_MAX_SPHERES: u32 = 1 << 24;
+pub const MIRT_BVH_MAX_DEPTH: u32 = 32;
+pub const MIRT_BVH_MAX_LEAF: u32 = 4;
+pub const MIRT_BVH_MAX_ALWAYS: u32 = 64;
+pub const MIRT_BVH_BIG_RADII: u32 = 4;
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct MirtStats {
@@ -220,6 +242,8 @@ extern "C" {
     pub fn mirt_ctx_create(device: c_int, out: *mut *mut MirtContext) -> c_int;
     pub fn mirt_ctx_destroy(ctx: *mut MirtContext);
     pub fn mirt_ctx_set_scene(ctx: *mut MirtContext, scene: *const MirtScene) -> c_int;
+    pub fn mirt_ctx_set_scene_ex(ctx: *mut MirtContext, scene: *const MirtScene, flags: u32) -> c_int;
+    pub fn mirt_bvh_plan(spheres: *const MirtSphere, n_spheres: u32, out: *mut MirtBvhPlan) -> c_int;
     pub fn mirt_ctx_set_camera(ctx: *mut MirtContext, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_ctx_render(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
@@ -245,6 +269,7 @@ extern "C" {
     pub fn mirt_node_create(devices: *const c_int, n: u32, flags: u32, out: *mut *mut MirtNode) -> c_int;
     pub fn mirt_node_destroy(node: *mut MirtNode);
     pub fn mirt_node_set_scene(node: *mut MirtNode, scene: *const MirtScene) -> c_int;
+    pub fn mirt_node_set_scene_ex(node: *mut MirtNode, scene: *const MirtScene, flags: u32) -> c_int;
     pub fn mirt_node_set_camera(node: *mut MirtNode, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_node_render(node: *mut MirtNode, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_node_render_device(node: *mut MirtNode, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;

@@ -22,6 +22,14 @@ MIRT_FLAG_COUNT_GRID = 1 << 7
 MIRT_FLAG_FAST_MATH = 1 << 8
 MIRT_FLAG_TEXEL_TILES = 1 << 9
 
+# mirt_ctx_set_scene_ex / mirt_node_set_scene_ex flags, and the BVH of such scenes
+MIRT_SCENE_HBM = 1 << 0
+MIRT_SCENE_HBM_MAX_SPHERES = 1 << 24
+MIRT_BVH_MAX_DEPTH = 32
+MIRT_BVH_MAX_LEAF = 4
+MIRT_BVH_MAX_ALWAYS = 64
+MIRT_BVH_BIG_RADII = 4
+
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
 MIRT_NODE_RCCL = 1 << 0
@@ -114,6 +122,14 @@ class MirtGridPlan(C.Structure):
                 ("n_big", C.c_uint32), ("pool_slots", C.c_uint32)]
 
 
+class MirtBvhPlan(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("n_leaf_spheres", C.c_uint32), ("n_always", C.c_uint32),
+                ("max_depth", C.c_uint32), ("max_leaf", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MirtStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("kernel_ms_total", C.c_double), ("launches", C.c_uint64),
                 ("samples", C.c_uint64), ("rays", C.c_uint64),
@@ -159,6 +175,8 @@ SYMBOLS = {
     "mirt_ctx_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "mirt_ctx_destroy": (None, [C.c_void_p]),
     "mirt_ctx_set_scene": (C.c_int, [C.c_void_p, _P(MirtScene)]),
+    "mirt_ctx_set_scene_ex": (C.c_int, [C.c_void_p, _P(MirtScene), C.c_uint32]),
+    "mirt_bvh_plan": (C.c_int, [C.c_void_p, C.c_uint32, _P(MirtBvhPlan)]),
     "mirt_ctx_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_ctx_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -184,6 +202,7 @@ SYMBOLS = {
     "mirt_node_create": (C.c_int, [_P(C.c_int), C.c_uint32, C.c_uint32, _P(C.c_void_p)]),
     "mirt_node_destroy": (None, [C.c_void_p]),
     "mirt_node_set_scene": (C.c_int, [C.c_void_p, _P(MirtScene)]),
+    "mirt_node_set_scene_ex": (C.c_int, [C.c_void_p, _P(MirtScene), C.c_uint32]),
     "mirt_node_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_node_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_node_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),

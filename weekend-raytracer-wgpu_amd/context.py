@@ -9,7 +9,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _abi
-from ._lib import check, lib
+from ._lib import MirtError, check, lib
 
 
 @dataclass
@@ -51,6 +51,27 @@ def make_params(width: int, height: int, spp: int, *, mode: int = _abi.MIRT_MODE
     p.frame_spp = frame_spp
     p.frame_begin = frame_begin
     return p
+
+
+def set_scene_any_size(target, scene: SceneData) -> None:
+    """`target.set_scene(scene)` (a Context or a Node); a world the LDS layouts refuse (MIRT_ERR_SCENE_TOO_LARGE) is set again with
+    MIRT_SCENE_HBM, so that the reference's host objects -- `Layer::set_data` takes any `Vec<Box<Sphere>>` -- take any world."""
+    try:
+        target.set_scene(scene)
+    except MirtError as e:
+        if e.status != _abi.MIRT_ERR_SCENE_TOO_LARGE:
+            raise
+        target.set_scene(scene, hbm=True)
+
+
+def bvh_plan(spheres) -> dict:
+    """mirt_bvh_plan: the BVH mirt_ctx_set_scene_ex(MIRT_SCENE_HBM) would build over `spheres` (a sequence of MirtSphere or a
+    ctypes array of them), host only."""
+    n = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (_abi.MirtSphere * max(1, n))(*spheres)
+    out = _abi.MirtBvhPlan()
+    check(lib().mirt_bvh_plan(C.cast(arr, C.c_void_p), n, C.byref(out)))
+    return out.as_dict()
 
 
 def params_out_rows(params: _abi.MirtParams) -> int:
@@ -103,9 +124,14 @@ class Context:
         except Exception:
             pass
 
-    def set_scene(self, scene: SceneData) -> None:
+    def set_scene(self, scene: SceneData, *, hbm: bool = False) -> None:
+        """mirt_ctx_set_scene; hbm=True: mirt_ctx_set_scene_ex(MIRT_SCENE_HBM) -- the tables stay in device memory and a BVH finds
+        the nearest hit, for worlds beyond the LDS budget (any size up to MIRT_SCENE_HBM_MAX_SPHERES)."""
         c = scene.as_c()
-        check(lib().mirt_ctx_set_scene(self._h, C.byref(c)))
+        if hbm:
+            check(lib().mirt_ctx_set_scene_ex(self._h, C.byref(c), _abi.MIRT_SCENE_HBM))
+        else:
+            check(lib().mirt_ctx_set_scene(self._h, C.byref(c)))
         self._scene = scene
 
     def set_camera(self, camera: _abi.MirtGpuCamera) -> None:

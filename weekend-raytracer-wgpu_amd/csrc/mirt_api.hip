@@ -18,6 +18,7 @@
 
 #include "../../include/mirt.h"
 #include "mirt_kernels.h"
+#include "mirt_bvh.h"
 
 namespace kx = mirt::exact_build;     // the kernels of the bit-exact build (default)
 namespace kf = mirt::fast_build;      // MIRT_FLAG_FAST_MATH: the same kernels with hardware transcendentals
@@ -393,6 +394,14 @@ struct MirtContext {
     MirtStats stats{};
     bool      stats_counted = false;
     char      last_kernel[128] = "";
+
+    // MIRT_SCENE_HBM scene (mirt_ctx_set_scene_ex): the tables stay in device memory, the nearest hit runs through a BVH
+    bool           hbm = false;
+    unsigned char* d_bvh = nullptr;          // one allocation: nodes | test records | original ids (mirt_bvh.h)
+    size_t         cap_bvh = 0;
+    size_t         bvh_off_recs = 0, bvh_off_ids = 0;
+    uint32_t       bvh_root = 0, bvh_n_always = 0;
+    float          bvh_centre[3] = {}, bvh_radius = 0.0f, bvh_rmax = 0.0f;
 };
 
 extern "C" {
@@ -587,7 +596,7 @@ void mirt_ctx_destroy(MirtContext* c)
     if (c->zero_stream) (void)hipStreamSynchronize(c->zero_stream);
     if (c->frame_stream_b) (void)hipStreamSynchronize(c->frame_stream_b);
     if (!c->untimed_streams.empty()) (void)hipDeviceSynchronize();      // launches without an event may still read the tables freed below
-    (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_texels);
+    (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_bvh); (void)hipFree(c->d_texels);
     (void)hipFree(c->d_sky); (void)hipFree(c->d_counters); (void)hipFree(c->d_work_counter); (void)hipFree(c->d_out); (void)hipFree(c->d_accum);
     for (hipEvent_t ev : c->ev_begin) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_end) (void)hipEventDestroy(ev);
@@ -599,31 +608,42 @@ void mirt_ctx_destroy(MirtContext* c)
     delete c;
 }
 
-int mirt_ctx_set_scene(MirtContext* c, const MirtScene* s)
+// mirt_ctx_set_scene (hbm = false) and mirt_ctx_set_scene_ex (hbm = true: MIRT_SCENE_HBM)
+static int set_scene(MirtContext* c, const MirtScene* s, bool hbm)
 {
     if (!c || !s || !s->camera) return fail(MIRT_ERR_NULL_POINTER, "ctx/scene/camera is null");
     if (s->n_spheres && !s->spheres) return fail(MIRT_ERR_NULL_POINTER, "spheres is null");
     if (s->n_materials && !s->materials) return fail(MIRT_ERR_NULL_POINTER, "materials is null");
     if (s->n_texels && !s->texels) return fail(MIRT_ERR_NULL_POINTER, "texels is null");
+    if (hbm && s->n_spheres > MIRT_SCENE_HBM_MAX_SPHERES)            // before any sphere is read
+        return fail(MIRT_ERR_SCENE_TOO_LARGE, "%u spheres exceed MIRT_SCENE_HBM_MAX_SPHERES (%u)", s->n_spheres, (unsigned)MIRT_SCENE_HBM_MAX_SPHERES);
     // The flat kernels stage spheres AND materials in LDS; the grid build (path-traced mode, many spheres)
     // only the spheres + the grid.  A scene is accepted if at least one of the two layouts fits.
-    const bool fits_flat = kx::scene_lds_bytes(s->n_spheres, s->n_materials, true, true) <= mirt::kMaxLdsBytes;
+    const bool fits_flat = !hbm && kx::scene_lds_bytes(s->n_spheres, s->n_materials, true, true) <= mirt::kMaxLdsBytes;
     // The cell size trades sphere tests against cells walked AND against LDS: the blob shares the CU's 160 KB with the path pools,
     // and a pool geometry lost to a large cell table costs more than finer cells bring (RTIOW: cell = 2 median radii drops the
     // pools from 152 to 128 slots per wave and the frame from 13.2 to 19.7 ms): plan_grid.
     double grid_factor = 0.0;
-    std::vector<unsigned char> grid = plan_grid(s->spheres, s->n_spheres, c->tuning.grid_cell, c->tuning.grid_big, c->lds_per_block, &grid_factor);
+    std::vector<unsigned char> grid;
+    if (!hbm) grid = plan_grid(s->spheres, s->n_spheres, c->tuning.grid_cell, c->tuning.grid_big, c->lds_per_block, &grid_factor);
     const bool fits_grid = !grid.empty() && s->n_spheres <= 4095u &&
                            kx::scene_lds_bytes_grid(s->n_spheres, true) + grid.size() <= mirt::kMaxLdsBytes;   // camera (+ sky) + the blob
-    if (!fits_flat && !fits_grid)
+    if (!hbm && !fits_flat && !fits_grid)
         return fail(MIRT_ERR_SCENE_TOO_LARGE, "%u spheres + %u materials exceed the %u-byte LDS budget", s->n_spheres,
                     s->n_materials, mirt::kMaxLdsBytes);
+    // MIRT_SCENE_HBM: the BVH (host, mirt_bvh.cpp), built before the context's scene is touched
+    mirt::BvhBuild bvh;
+    if (hbm) {
+        const int rc = mirt::build_bvh(s->spheres, s->n_spheres, &bvh);
+        if (rc != MIRT_OK) return rc;
+    }
     HIP_TRY(hipSetDevice(c->device));
     // Failure-atomic: from here until the last copy has succeeded the context holds NO scene, so an allocation or
     // copy that fails half-way leaves render calls answering MIRT_ERR_NO_SCENE instead of launching on freed or
     // half-written tables.
     c->have_scene = false;
     c->fits_flat = fits_flat;
+    c->hbm = hbm;
 
     // mode-specific validity is decided here once and reported by the render call that needs it
     c->pt_scene_status = MIRT_OK;
@@ -750,8 +770,30 @@ int mirt_ctx_set_scene(MirtContext* c, const MirtScene* s)
     c->has_image_texture = false;                // ... on a material some sphere uses
     for (uint32_t i = 0; i < s->n_spheres; ++i)
         if (s->spheres[i].material_idx < s->n_materials && mat_has_image[s->spheres[i].material_idx]) c->has_image_texture = true;
+    if (hbm) {                                   // nodes | records | ids, each 16-byte aligned
+        const size_t nb = bvh.nodes.size() * sizeof(mirt::BvhNode), rb = bvh.recs.size() * sizeof(float), ib = bvh.ids.size() * sizeof(uint32_t);
+        c->bvh_off_recs = nb;
+        c->bvh_off_ids = nb + rb;
+        if ((rc = ensure_capacity(&c->d_bvh, &c->cap_bvh, nb + rb + ib + 16)) != MIRT_OK) return rc;
+        if (nb) HIP_TRY(hipMemcpy(c->d_bvh, bvh.nodes.data(), nb, hipMemcpyHostToDevice));
+        if (rb) HIP_TRY(hipMemcpy(c->d_bvh + c->bvh_off_recs, bvh.recs.data(), rb, hipMemcpyHostToDevice));
+        if (ib) HIP_TRY(hipMemcpy(c->d_bvh + c->bvh_off_ids, bvh.ids.data(), ib, hipMemcpyHostToDevice));
+        c->bvh_root = bvh.root;
+        c->bvh_n_always = bvh.n_always;
+        for (int k = 0; k < 3; ++k) c->bvh_centre[k] = bvh.centre[k];
+        c->bvh_radius = bvh.radius;
+        c->bvh_rmax = bvh.r_max;
+    }
     c->have_scene = true;
     return MIRT_OK;
+}
+
+int mirt_ctx_set_scene(MirtContext* c, const MirtScene* s) { return set_scene(c, s, false); }
+
+int mirt_ctx_set_scene_ex(MirtContext* c, const MirtScene* s, uint32_t flags)
+{
+    if (flags & ~(uint32_t)MIRT_SCENE_HBM) return fail(MIRT_ERR_BAD_MODE, "unknown set_scene_ex flags 0x%x", flags);
+    return set_scene(c, s, (flags & MIRT_SCENE_HBM) != 0);
 }
 
 int mirt_ctx_set_camera(MirtContext* c, const MirtGpuCamera* cam)
@@ -1026,7 +1068,21 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     a.grid_flat_y = (use_grid && c->grid_flat_y) ? 1u : 0u;
     // (the strip kernel's grid build keeps a camera-ray candidate list per wave behind the blob: 4 waves x 48 bytes)
     a.lds_bytes = use_grid ? (uint32_t)(scene_lds_g + a.grid_bytes + (pool ? pcu.lds_bytes : 4u * 48u)) : (uint32_t)(scene_lds + (pool ? pcu.lds_bytes : 0));
-    if (!use_grid && !c->fits_flat)
+    // MIRT_SCENE_HBM scene: the strip kernel (parity kernel) with the tables in device memory -- the BVH build unless NO_GRID asks for the
+    // flat scan or a counting launch asks for the flat scan's counters (COUNT_WORK without COUNT_GRID); pool / tile / strip hints do not apply
+    const bool hbm = c->hbm;
+    const bool hbm_bvh = hbm && pt && !(p->flags & MIRT_FLAG_NO_GRID) && (!count || (p->flags & MIRT_FLAG_COUNT_GRID));
+    if (hbm) {
+        a.bvh_nodes = reinterpret_cast<const float4*>(c->d_bvh);
+        a.bvh_recs = reinterpret_cast<const float4*>(c->d_bvh + c->bvh_off_recs);
+        a.bvh_ids = reinterpret_cast<const uint32_t*>(c->d_bvh + c->bvh_off_ids);
+        a.bvh_root = c->bvh_root;
+        a.bvh_n_always = c->bvh_n_always;
+        for (int k = 0; k < 3; ++k) a.bvh_centre[k] = c->bvh_centre[k];
+        a.bvh_radius = c->bvh_radius;
+        a.bvh_rmax = c->bvh_rmax;
+    }
+    if (!use_grid && !c->fits_flat && !hbm)
         return fail(MIRT_ERR_SCENE_TOO_LARGE, "this scene only fits LDS in the grid build of the path-traced mode "
                     "(no parity mode, no MIRT_FLAG_COUNT_WORK / MIRT_FLAG_NO_GRID / MIRT_FLAG_KERNEL_POOL)");
 
@@ -1035,6 +1091,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     //  a tiny frame with many samples per pixel needs the lanes of a wave on the samples)
     bool by_pixel = pt && !pool && !count && (p->spp < mirt::kByPixelMaxSpp || (c->n_shading_routines <= 1 && npix >= 64ull * 4u * c->cu_count));
     if (tune.by_pixel >= 0) by_pixel = pt && !pool && !count && tune.by_pixel == 1;
+    if (hbm_bvh && !count) by_pixel = true;              // the BVH build: lane = pixel at every sample count
     if (frame_stream) by_pixel = true;                    // also for counting launches (flat scan) and any spp
     // parity mode: lane = pixel at EVERY sample count, counting or not (round 3: below 64 spp).  The reference's loop returns at the first
     // terminating sample (layer.rs:320-378), which a lane that walks its own pixel's samples does too, while lane = sample computes 64
@@ -1047,6 +1104,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     // (mirt_kernels.hip: strip_kernel_body<STREAM>; MIRT_STREAM=0/1 for A/B runs)
     a.stream_samples = (pt && by_pixel && !count && !use_grid && p->spp >= 16u) ? 1u : 0u;
     if (tune.stream >= 0 && pt && by_pixel && !count && !use_grid) a.stream_samples = (uint32_t)tune.stream;
+    if (hbm) a.stream_samples = 0u;
     if (by_pixel) {
         // Path-traced lane-per-pixel units: 64 pixels x all samples -- or 32 / 16 pixels with the samples dealt to 2 / 4 groups of lanes:
         // smaller units are more units, and the last unit of a wave is then a smaller part of its life (config 2, 1080p x 100 spp, had 4
@@ -1098,10 +1156,16 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
         if (a.static_units != 0u && tune.static_grid <= 0) a.launch_threads = tune.static_block ? tune.static_block : (use_grid ? 0u : 64u);
         const uint32_t waves_per_block = (a.launch_threads ? a.launch_threads : mirt::kBlockThreads) / 64;
         blocks = (a.n_units + waves_per_block - 1) / waves_per_block;
+        // MIRT_SCENE_HBM: LDS holds the camera (+ sky) and, in the BVH build, every wave's traversal stacks
+        if (hbm) a.lds_bytes = (uint32_t)(scene_lds_g + (hbm_bvh ? waves_per_block * mirt::kBvhStackBytesPerWave : 0u));
         // a persistent grid of exactly the blocks that are resident at once: registers and LDS decide (4-8 per CU for these
         // kernels).  A block beyond that would hold its first unit until the dispenser has run dry and run it alone at the end.
         const bool fast_strip = pt && !count && (p->flags & MIRT_FLAG_FAST_MATH);
-        uint32_t per_cu = !pt ? kx::parity_blocks_per_cu(count, by_pixel, a.lds_bytes)
+        const uint32_t threads = a.launch_threads ? a.launch_threads : mirt::kBlockThreads;
+        uint32_t per_cu = hbm ? (!pt ? kx::parity_hbm_blocks_per_cu(count, by_pixel, threads, a.lds_bytes)
+                                     : fast_strip ? kf::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes)
+                                                  : kx::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes))
+                        : !pt ? kx::parity_blocks_per_cu(count, by_pixel, a.lds_bytes)
                         : fast_strip ? kf::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u)
                                      : kx::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u);
         if (per_cu > 8u) per_cu = 8u;                                 // 2048 threads per CU / 256
@@ -1142,7 +1206,16 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     const bool fast = pt && !count && (p->flags & MIRT_FLAG_FAST_MATH);
     const char* tf[2] = { "false", "true" };
     char kname[112] = "";
-    if (p->mode == MIRT_MODE_PARITY) {
+    if (hbm) {
+        if (p->mode == MIRT_MODE_PARITY) {
+            HIP_TRY(kx::launch_parity_hbm(a, blocks, count, by_pixel, on));
+            snprintf(c->last_kernel, sizeof c->last_kernel, "render_parity_hbm_kernel<%s,%s>", tf[count], tf[by_pixel]);
+        } else {
+            HIP_TRY(fast ? kf::launch_pt_hbm(a, blocks, count, hbm_bvh, by_pixel, on) : kx::launch_pt_hbm(a, blocks, count, hbm_bvh, by_pixel, on));
+            snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_hbm_kernel<%s,%s,%s,%s>", fast ? "fast_build::" : "", tf[count], tf[hosek],
+                     tf[hbm_bvh], tf[by_pixel]);
+        }
+    } else if (p->mode == MIRT_MODE_PARITY) {
         HIP_TRY(kx::launch_parity(a, blocks, count, by_pixel, on));
         snprintf(c->last_kernel, sizeof c->last_kernel, "render_parity_kernel<%s,%s>", tf[count], tf[by_pixel]);
     } else if (pool) {

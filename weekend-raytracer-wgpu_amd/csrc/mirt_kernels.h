@@ -200,7 +200,17 @@ struct RenderArgs {
     uint32_t launch_threads;               // strip-type kernels: threads per block of THIS launch (0: kBlockThreads)
     uint32_t stream_samples;               // lane-per-pixel strip launch in a flat scene: 1 = render_pt_stream_kernel (a lane starts its next sample without waiting for the wave)
     float    sph3[12];                     // scenes of exactly three spheres: their {centre, r^2} records as kernel arguments (scalar loads)
+    // MIRT_SCENE_HBM scenes, BVH build of render_pt_hbm_kernel (mirt_bvh.h; appended so that no older field moves)
+    const float4*   bvh_nodes;             // [n_nodes] BvhNode, four float4 each
+    const float4*   bvh_recs;              // {centre, r^2}: the always-tested list [bvh_n_always], then the leaves' spheres
+    const uint32_t* bvh_ids;               // original sphere index of every record
+    uint32_t        bvh_root;              // reference of the root (BvhNode child encoding)
+    uint32_t        bvh_n_always;
+    float           bvh_centre[3];         // a sphere around every tree sphere's box, and the largest |radius| in the tree:
+    float           bvh_radius, bvh_rmax;  // the traversal's rounding bound (nearest_hit_bvh)
 };
+// MIRT_SCENE_HBM, BVH build: every wave keeps 64 per-lane traversal stacks of MIRT_BVH_MAX_DEPTH node references in LDS
+constexpr uint32_t kBvhStackBytesPerWave = 64u * MIRT_BVH_MAX_DEPTH * 4u;
 
 // The parts of a tile-interleaved frame and where they go (assemble_parts_kernel).  Two forms:
 //   table  (part_stride_px == 0): parts[i] is part i's compact buffer, n_parts <= kAssembleMaxParts (the node's members);
@@ -231,8 +241,16 @@ namespace fast_build {
 hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream);
 uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream);
 hipError_t launch_pt_pool(const RenderArgs& a, uint32_t grid_blocks, uint32_t cfg, bool count, uint32_t nq, LaunchOn stream);
+hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
+uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
 }
 namespace exact_build {
+// MIRT_SCENE_HBM scenes: the strip kernel with the scene in device memory -- a flat scan (bvh = false) or the BVH traversal -- and
+// the parity kernel's flat scan reading the spheres from device memory
+hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
+uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
+hipError_t launch_parity_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);
+uint32_t   parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
 hipError_t launch_parity(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);
 hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream);
 // blocks of the kernel such a launch runs that are resident per CU at once (hipOccupancyMaxActiveBlocksPerMultiprocessor)

@@ -47,7 +47,8 @@ struct SceneLds {
 // Cooperative global -> LDS copy of the scene tables, 16 B per thread per step.
 // PT = false stages the reference-layout material table, PT = true the prepared one.
 // GRID builds (MATS_IN_LDS = false) stage neither the materials nor the spheres: what their sphere tests read lives in
-// the grid blob (stage_grid), and a hit reads its sphere and material from global memory / L2 once.
+// the grid blob (stage_grid), and a hit reads its sphere and material from global memory / L2 once.  The MIRT_SCENE_HBM builds
+// stage neither either: their scans read the tables where they lie, in device memory.
 template <bool PT, bool MATS_IN_LDS = true>
 MIRT_DEV SceneLds stage_scene(const RenderArgs& A, unsigned char* smem, bool hosek)
 {
@@ -82,7 +83,7 @@ MIRT_DEV SceneLds stage_scene(const RenderArgs& A, unsigned char* smem, bool hos
     SceneLds S;
     S.cam = reinterpret_cast<const float*>(smem);
     S.spheres = MATS_IN_LDS ? reinterpret_cast<const PreparedSphere*>(smem + 16 * n_cam) : A.spheres;
-    S.mats = reinterpret_cast<const MirtMaterial*>(smem + 16 * (n_cam + n_sph));
+    S.mats = MATS_IN_LDS ? reinterpret_cast<const MirtMaterial*>(smem + 16 * (n_cam + n_sph)) : A.mats;
     S.pmats = MATS_IN_LDS ? reinterpret_cast<const PreparedMaterial*>(smem + 16 * (n_cam + n_sph)) : A.pmats;
     S.sky = hosek ? reinterpret_cast<const float*>(smem + 16 * (n_cam + n_sph + n_mat)) : nullptr;
     S.end = smem + 16 * total;
@@ -353,11 +354,12 @@ MIRT_DEV bool parity_world_hit(const SceneLds& S, uint32_t n_spheres, const PRay
 // BY_PIXEL = true : a wave owns 64 consecutive pixels, lane = pixel, and every lane runs the reference's sample loop for its pixel
 //                   in order -- the launch shape for the reference's operating point, 2 samples per pixel (mod.rs:605-613), where
 //                   lane = sample would leave 62 of 64 lanes idle.  The host takes it below kByPixelMaxSpp samples per pixel.
-template <bool COUNT, bool BY_PIXEL = false>
-__global__ __launch_bounds__(kBlockThreads) void render_parity_kernel(RenderArgs A)
+// HBM = true (MIRT_SCENE_HBM scenes, render_parity_hbm_kernel): the same scan over the sphere and material tables in device memory.
+template <bool COUNT, bool BY_PIXEL, bool HBM>
+MIRT_DEV void parity_kernel_body(RenderArgs A)             // by value, as the kernel's own argument was: the same registers
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const SceneLds S = stage_scene<false>(A, smem, false);
+    const SceneLds S = stage_scene<false, !HBM>(A, smem, false);
     const uint32_t lane = threadIdx.x & 63u;
     const float wf = (float)A.width, hf = (float)A.height;
     const uint32_t npix = A.out_rows * A.width;
@@ -528,6 +530,18 @@ __global__ __launch_bounds__(kBlockThreads) void render_parity_kernel(RenderArgs
         if (lane < kStripPixels && base + lane < npix) A.out[base + lane] = my_px;
         work.flush(A.counters, lane);
     }
+}
+
+template <bool COUNT, bool BY_PIXEL = false>
+__global__ __launch_bounds__(kBlockThreads) void render_parity_kernel(RenderArgs A)
+{
+    parity_kernel_body<COUNT, BY_PIXEL, false>(A);
+}
+
+template <bool COUNT, bool BY_PIXEL>
+__global__ __launch_bounds__(kBlockThreads) void render_parity_hbm_kernel(RenderArgs A)
+{
+    parity_kernel_body<COUNT, BY_PIXEL, true>(A);
 }
 
 #endif  // !MIRT_FAST_MATH
@@ -1477,17 +1491,149 @@ MIRT_DEV uint32_t strip_candidates(const RenderArgs& AP, const SceneLds& S, uint
     return count;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// nearest hit through a BVH in device memory (MIRT_SCENE_HBM scenes; tree: mirt_bvh.cpp)
+// ------------------------------------------------------------------------------------------
+//
+// The result must be the flat scan's, byte for byte: min f over the spheres (f = the first root above MIN_T that test_sphere
+// computes), on equal f the lower ORIGINAL index.  Every sphere test is test_sphere with its explicit (f, id) tie-break, so the
+// visiting order does not matter; what must hold is that no sphere whose computed f could win is pruned.  Rounding makes the naive
+// rule (visit a box iff the ray meets it before `closest`) wrong: the computed f is not the parameter of a point on the sphere.
+//
+// The bound.  u = 2^-24; for one sphere (c, r) let L = |o - c| + |r|.  test_sphere computes b, cq, disc, sq and f from rounded
+// dot products; with B, CQ, A the exact values for the rounded offset oc (itself within u |o - c| of o - c), the residual of the
+// quadratic at the computed root, g(f) = |oc + f d|^2 - r^2, obeys A g(f^) <= (15 + 2 + 18) u A L^2 for f^ = (-b - sq) / a evaluated
+// exactly (disc's error <= 15 u A L^2, the root's numerator within 9 u sqrt(A) L), so the point P = o + f^ d lies within
+// sqrt(35 u) L = 2^-9.4 L of the sphere's surface: inside the sphere's box grown by E = 2^-8 L on every side (a 2.6x margin).  The
+// computed f differs from f^ by a relative 3 u, a shift ALONG the ray.  L is bounded two ways, both rounded up on the host and with
+// 1 % margins here: L <= |o - C| + R (C, R: a sphere around every tree sphere's box, RenderArgs.bvh_centre / bvh_radius), and, for a
+// sphere that can still win (f <= closest), L <= |P - o| + 2 |r| + E <= closest |d| + 2 r_max (up to the same 2^-8); and for a sphere
+// inside a box, L <= the distance from o to the box's farthest corner.  So every box is grown by
+// E = 2^-8 min(farthest corner, |o - C| + R, closest |d| + 2 r_max) -- closest falls as leaves are tested.
+//   This is LATERAL slack, and it is needed: a ray that passes 0.25 from a sphere of radius 10^-3 at distance 10^3 has a computed
+// disc > 0 (its two products of ~10^6 cancel to within their rounding), and the flat scan counts that hit.
+// The slab test of a grown box: per axis the near plane is picked by the sign of 1/d, t = (plane - o) / d -/+ E |1/d|, each with a
+// relative error of a few u; the visit test is
+//     !(t_near > closest (1 + 2^-9))  &&  !(t_far < 0)  &&  !(t_near > t_far (1 + 2^-9)),
+// so a box that holds P at f^ > MIN_T > 0 with f <= closest passes with a 2^-9 relative margin where a few u are needed.  A component
+// d_k = +-0 gives 1/d = +-inf; (plane - o) * inf - inf and 0 * inf are NaN.  The min / max of the three axes drop a NaN operand
+// (v_min3 / v_max3: IEEE minNum / maxNum), which moves t_near down and t_far up -- towards "visit" -- and three NaN make t_near NaN,
+// which every negated comparison above turns into "visit".  Non-finite boxes (a tree sphere beyond the always-tested list's
+// capacity) are infinite: always visited.  Adversarial cases (tests/test_gpu_hbm_scene.py): 1 000 copies of one sphere, tangent
+// lattices whose boxes share faces, axis-aligned cameras, a camera inside a sphere, grazing rays at r = 10^-3 / distance 10^3,
+// zero-radius and non-finite spheres -- all byte-equal to the flat scan.
+//
+// Traversal: near child first, the far one on a per-lane stack in LDS of MIRT_BVH_MAX_DEPTH entries.  An entry is pushed only at an
+// inner node, at most one per level of the path from the root, and the builder bounds the depth (mirt_bvh.cpp): the stack cannot
+// fill; a push past its end is not written in any case.
+constexpr uint32_t kBvhLeafRef = 0x80000000u;      // mirt_bvh.h: kBvhLeaf -- count in bits 24..30, first record in bits 0..23
+constexpr uint32_t kBvhStack = MIRT_BVH_MAX_DEPTH;
+constexpr float    kBvhSlack = 1.0f + 0x1p-9f;
+
+MIRT_DEV void bvh_slab(float4 lo_hi_a, float4 lo_hi_b, float4 lo_hi_c, int first, f3 ro, f3 inv, float e_cone, bool sx, bool sy, bool sz,
+                       float& tn, float& tf)
+{
+    // the box's six floats start at component `first` of (a, b, c): the left box at 0 (a.xyz | a.w b.x b.y), the right one at 6
+    const float v[12] = { lo_hi_a.x, lo_hi_a.y, lo_hi_a.z, lo_hi_a.w, lo_hi_b.x, lo_hi_b.y, lo_hi_b.z, lo_hi_b.w,
+                          lo_hi_c.x, lo_hi_c.y, lo_hi_c.z, lo_hi_c.w };
+    const float lx = v[first + 0], ly = v[first + 1], lz = v[first + 2], hx = v[first + 3], hy = v[first + 4], hz = v[first + 5];
+    // E for this box: 2^-8 x the distance from o to its farthest corner bounds |o - c| + |r| of every sphere inside (1 % margin),
+    // or the cone bound of the caller, whichever is smaller
+    const float dx = max_(abs_(lx - ro.x), abs_(hx - ro.x)), dy = max_(abs_(ly - ro.y), abs_(hy - ro.y)), dz = max_(abs_(lz - ro.z), abs_(hz - ro.z));
+    const float e_box = (0x1p-8f * 1.01f) * __builtin_sqrtf(dx * dx + dy * dy + dz * dz);
+    const float e = (e_box < e_cone) ? e_box : e_cone;
+    const f3 ev = mk(e * abs_(inv.x), e * abs_(inv.y), e * abs_(inv.z));
+    const float nx = ((sx ? lx : hx) - ro.x) * inv.x - ev.x, fx = ((sx ? hx : lx) - ro.x) * inv.x + ev.x;
+    const float ny = ((sy ? ly : hy) - ro.y) * inv.y - ev.y, fy = ((sy ? hy : ly) - ro.y) * inv.y + ev.y;
+    const float nz = ((sz ? lz : hz) - ro.z) * inv.z - ev.z, fz = ((sz ? hz : lz) - ro.z) * inv.z + ev.z;
+    tn = __builtin_fmaxf(__builtin_fmaxf(nx, ny), nz);
+    tf = __builtin_fminf(__builtin_fminf(fx, fy), fz);
+}
+
+template <bool COUNT>
+MIRT_DEV int nearest_hit_bvh(f3 ro, f3 rd, bool alive, float& closest_out, Work<COUNT>& work, uint32_t lane, uint32_t* stack)
+{
+    const RenderArgs& A = per_strip_args();          // the tree's pointers and bounds: read where they are used, not held across the path
+    const float a = dot(rd, rd);
+    const float inv_a = rcp_(a);
+    float closest = kMaxT;
+    int best = -1;
+    if (alive) work.add(kCntRays);
+    const float4* recs = A.bvh_recs;
+    const uint32_t* ids = A.bvh_ids;
+    const uint32_t n_always = A.bvh_n_always;
+    for (uint32_t j = 0; j < n_always; ++j) test_sphere<COUNT>(recs[j], ids[j], ro, rd, a, inv_a, alive, closest, best, work);
+
+    const f3 inv = mk(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+    const bool sx = inv.x >= 0.0f, sy = inv.y >= 0.0f, sz = inv.z >= 0.0f;
+    const f3 dc = ro - mk(A.bvh_centre[0], A.bvh_centre[1], A.bvh_centre[2]);
+    const float e_world = (0x1p-8f * 1.01f) * (__builtin_sqrtf(dot(dc, dc)) + A.bvh_radius);
+    const float len_d = 1.01f * __builtin_sqrtf(a), two_rmax = 2.0f * A.bvh_rmax;
+    const float4* nodes = A.bvh_nodes;
+    float e_cone;
+    auto grow = [&]() {
+        const float e = (0x1p-8f * 1.01f) * (closest * len_d + two_rmax);
+        e_cone = (e < e_world) ? e : e_world;
+    };
+    grow();
+    uint32_t ref = A.bvh_root, sp = 0;
+    bool go = alive;
+    while (ballot_(go)) {
+        if constexpr (COUNT) { if (go) work.add(kCntCells); if (lane == 0) work.add(kCntWaveCells); }
+        if (go) {
+            bool pop = false;
+            if (ref & kBvhLeafRef) {
+                const uint32_t first = ref & 0xffffffu, cnt = (ref >> 24) & 0x7fu;
+                for (uint32_t k = 0; k < cnt; ++k) test_sphere<COUNT>(recs[first + k], ids[first + k], ro, rd, a, inv_a, true, closest, best, work);
+                grow();
+                pop = true;
+            } else {
+                const float4* nd = nodes + 4ull * ref;
+                const float4 q0 = nd[0], q1 = nd[1], q2 = nd[2], q3 = nd[3];
+                float tnl, tfl, tnr, tfr;
+                bvh_slab(q0, q1, q2, 0, ro, inv, e_cone, sx, sy, sz, tnl, tfl);
+                bvh_slab(q0, q1, q2, 6, ro, inv, e_cone, sx, sy, sz, tnr, tfr);
+                const float lim = closest * kBvhSlack;
+                const bool vl = !(tnl > lim) & !(tfl < 0.0f) & !(tnl > tfl * kBvhSlack);
+                const bool vr = !(tnr > lim) & !(tfr < 0.0f) & !(tnr > tfr * kBvhSlack);
+                const uint32_t lref = bits(q3.x), rref = bits(q3.y);
+                if (vl & vr) {
+                    const bool left_first = !(tnr < tnl);
+                    ref = left_first ? lref : rref;
+                    if (sp < kBvhStack) { stack[sp * 64u + lane] = left_first ? rref : lref; ++sp; }
+                } else if (vl | vr) {
+                    ref = vl ? lref : rref;
+                } else {
+                    pop = true;
+                }
+            }
+            if (pop) {
+                if (sp == 0u) go = false;
+                else { --sp; ref = stack[sp * 64u + lane]; }
+            }
+        }
+    }
+    closest_out = closest;
+    return best;
+}
+
 // ------------------------------------------------------------------------------------------
 // render_pt_strip — one path per lane, per-lane material switch
 // ------------------------------------------------------------------------------------------
 
+// where the strip kernel's scans read the scene: LDS (the default builds), or MIRT_SCENE_HBM's device memory -- the flat sphere table
+// (NO_GRID, counting launches) or the BVH
+constexpr uint32_t kSrcLds = 0, kSrcHbmFlat = 1, kSrcBvh = 2;
+
 // rayColor wgsl:124-172 for the 64 paths of a wave: returns throughput x sky colour (0 if the bounce limit
 // ended the path).  The loop leaves as soon as no lane of the wave has a live path.
-template <bool COUNT, bool HOSEK, bool GRID>
+template <bool COUNT, bool HOSEK, bool GRID, uint32_t SRC = kSrcLds>
 // `cand` / n_cand (GRID builds, lane = pixel): the candidate list of this unit's camera rays (strip_candidates), scanned instead of the
-// grid at bounce 0; n_cand = kNoCand: none.
+// grid at bounce 0; n_cand = kNoCand: none.  `bvh_stack`: this lane's wave's traversal stacks (SRC == kSrcBvh).
 MIRT_DEV f3 path_radiance(const RenderArgs& A, const SceneLds& S, const GridLds& G, bool alive, Rng& rng, f3 ro, f3 rd,
-                          Work<COUNT>& work, uint32_t lane, const unsigned short* cand = nullptr, uint32_t n_cand = kNoCand)
+                          Work<COUNT>& work, uint32_t lane, const unsigned short* cand = nullptr, uint32_t n_cand = kNoCand,
+                          uint32_t* bvh_stack = nullptr)
 {
     f3 thr = mk(1, 1, 1);
     f3 color = mk(0, 0, 0);
@@ -1515,6 +1661,8 @@ MIRT_DEV f3 path_radiance(const RenderArgs& A, const SceneLds& S, const GridLds&
                 best = A.grid_flat_y ? nearest_hit_grid<COUNT, true>(S, G, ro, rd, alive, closest, work, lane)
                                      : nearest_hit_grid<COUNT, false>(S, G, ro, rd, alive, closest, work, lane);
             }
+        } else if constexpr (SRC == kSrcBvh) {
+            best = nearest_hit_bvh<COUNT>(ro, rd, alive, closest, work, lane, bvh_stack);
         } else best = nearest_hit<COUNT>(S, A.n_spheres, ro, rd, alive, closest, work);
         if (alive) {
             if (best >= 0) {
@@ -1522,7 +1670,7 @@ MIRT_DEV f3 path_radiance(const RenderArgs& A, const SceneLds& S, const GridLds&
                 // sphereIntersection wgsl:431-440
                 PreparedSphere sp;
                 if constexpr (GRID) sp = A.spheres[best];           // grid builds keep no sphere table in LDS: one global read per hit
-                else sp = S.spheres[best];
+                else sp = S.spheres[best];                          // (MIRT_SCENE_HBM builds: S.spheres is the table in device memory)
                 const f3 hp = fma3(closest, rd, ro);
                 const f3 hn = sp.inv_r * (hp - mk(sp.cx, sp.cy, sp.cz));
                 const PreparedMaterial* m = &S.pmats[sp.material_idx];
@@ -1557,16 +1705,22 @@ MIRT_DEV f3 path_radiance(const RenderArgs& A, const SceneLds& S, const GridLds&
 // (profiles/r04_lowspp_ab.txt block 9: config 2 -7 %, three spheres 16 / 24 spp -3 / -7 %; below that the fresh camera rays it mixes with old
 // paths make a step run more shading routines than it saves steps: 2 / 8 spp +10 / +4 %).  Same samples, same exact integer sums.
 constexpr uint32_t kStreamRefillMin = 16;
-template <bool COUNT, bool HOSEK, bool GRID, bool BY_PIXEL, bool STREAM>
+// SRC (MIRT_SCENE_HBM scenes, render_pt_hbm_kernel): kSrcHbmFlat scans the sphere table in device memory, kSrcBvh traverses the BVH
+// with the wave's stacks behind the camera (+ sky) in LDS; the scene's tables are not staged.
+template <bool COUNT, bool HOSEK, bool GRID, bool BY_PIXEL, bool STREAM, uint32_t SRC = kSrcLds>
 MIRT_DEV void strip_kernel_body(const RenderArgs& A)
 {
     static_assert(!STREAM || (BY_PIXEL && !GRID && !COUNT), "the streaming schedule exists for lane = pixel in flat scenes");
+    static_assert(SRC == kSrcLds || (!GRID && !STREAM), "MIRT_SCENE_HBM builds have no grid and no streaming schedule");
     extern __shared__ __align__(16) unsigned char smem[];
     // many-sphere scenes (GRID build): the material table (one 48-byte read per hit) stays in global memory / L2
     // so that LDS holds only what every sphere TEST reads, and more waves fit a CU
-    const SceneLds S = stage_scene<true, !GRID>(A, smem, HOSEK);
+    const SceneLds S = stage_scene<true, !GRID && SRC == kSrcLds>(A, smem, HOSEK);
     GridLds G{};
     if constexpr (GRID) G = stage_grid(A, smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, HOSEK, false));
+    uint32_t* bvh_stack = nullptr;
+    if constexpr (SRC == kSrcBvh)
+        bvh_stack = reinterpret_cast<uint32_t*>(smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, HOSEK, false)) + (threadIdx.x >> 6) * (kBvhStackBytesPerWave / 4u);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t npix = A.out_rows * A.width;
 
@@ -1681,7 +1835,7 @@ MIRT_DEV void strip_kernel_body(const RenderArgs& A)
                         generate_primary<false>(A, C, x, y, sample, rng, ro, rd);
                     }
                 }
-                const f3 c = path_radiance<COUNT, HOSEK, GRID>(A, S, G, inside, rng, ro, rd, work, lane, cand, n_cand);
+                const f3 c = path_radiance<COUNT, HOSEK, GRID, SRC>(A, S, G, inside, rng, ro, rd, work, lane, cand, n_cand, bvh_stack);
                 acc_r += to_fixed(c.x);
                 acc_g += to_fixed(c.y);
                 acc_b += to_fixed(c.z);
@@ -1722,7 +1876,7 @@ MIRT_DEV void strip_kernel_body(const RenderArgs& A)
                         const CamRegs C = load_camera(S, A);
                         generate_primary(A, C, x, y, A.sample_begin + s, rng, ro, rd);
                     }
-                    const f3 c = path_radiance<COUNT, HOSEK, GRID>(A, S, G, s < A.spp, rng, ro, rd, work, lane);
+                    const f3 c = path_radiance<COUNT, HOSEK, GRID, SRC>(A, S, G, s < A.spp, rng, ro, rd, work, lane, nullptr, kNoCand, bvh_stack);
                     if (s < A.spp) {
                         acc_r += to_fixed(c.x);
                         acc_g += to_fixed(c.y);
@@ -1750,6 +1904,13 @@ template <bool COUNT, bool HOSEK, bool GRID, bool BY_PIXEL = false>
 __global__ __launch_bounds__(kBlockThreads, (BY_PIXEL && !COUNT && !GRID && !HOSEK) ? 8 : ((BY_PIXEL && !COUNT && GRID) ? 7 : 1)) void render_pt_strip_kernel(RenderArgs A)
 {
     strip_kernel_body<COUNT, HOSEK, GRID, BY_PIXEL, false>(A);
+}
+
+// MIRT_SCENE_HBM scenes: BVH = true traverses the tree (the default), false scans the sphere table in device memory (NO_GRID, counting)
+template <bool COUNT, bool HOSEK, bool BVH, bool BY_PIXEL>
+__global__ __launch_bounds__(kBlockThreads, (BY_PIXEL && !COUNT) ? 6 : 1) void render_pt_hbm_kernel(RenderArgs A)
+{
+    strip_kernel_body<COUNT, HOSEK, false, BY_PIXEL, false, BVH ? kSrcBvh : kSrcHbmFlat>(A);
 }
 
 template <bool HOSEK>
@@ -2010,6 +2171,55 @@ uint32_t strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixe
 uint32_t parity_blocks_per_cu(bool count, bool by_pixel, uint32_t lds_bytes)
 {
     return blocks_per_cu(reinterpret_cast<const void*>(parity_kernel(count, by_pixel)), kBlockThreads, lds_bytes);
+}
+#endif
+
+// ---- MIRT_SCENE_HBM scenes ----
+static StripKernel hbm_kernel(bool count, bool hosek, bool bvh, bool by_pixel)
+{
+#ifdef MIRT_FAST_MATH
+    if (count) return nullptr;                           // the counting builds exist in the exact build only
+#else
+    if (count) {
+        if (bvh) return by_pixel ? (hosek ? render_pt_hbm_kernel<true, true, true, true> : render_pt_hbm_kernel<true, false, true, true>)
+                                 : (hosek ? render_pt_hbm_kernel<true, true, true, false> : render_pt_hbm_kernel<true, false, true, false>);
+        return by_pixel ? (hosek ? render_pt_hbm_kernel<true, true, false, true> : render_pt_hbm_kernel<true, false, false, true>)
+                        : (hosek ? render_pt_hbm_kernel<true, true, false, false> : render_pt_hbm_kernel<true, false, false, false>);
+    }
+#endif
+    if (bvh) return hosek ? render_pt_hbm_kernel<false, true, true, true> : render_pt_hbm_kernel<false, false, true, true>;   // lane = pixel only
+    return by_pixel ? (hosek ? render_pt_hbm_kernel<false, true, false, true> : render_pt_hbm_kernel<false, false, false, true>)
+                    : (hosek ? render_pt_hbm_kernel<false, true, false, false> : render_pt_hbm_kernel<false, false, false, false>);
+}
+
+hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream)
+{
+    const StripKernel k = hbm_kernel(count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, bvh, by_pixel);
+    if (!k) return hipErrorInvalidValue;
+    return launch_with_lds(k, dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
+}
+
+uint32_t hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes)
+{
+    const StripKernel k = hbm_kernel(count, hosek, bvh, by_pixel);
+    return k ? blocks_per_cu(reinterpret_cast<const void*>(k), threads, lds_bytes) : 1u;
+}
+
+#ifndef MIRT_FAST_MATH
+static ParityKernel parity_hbm_kernel(bool count, bool by_pixel)
+{
+    if (by_pixel) return count ? render_parity_hbm_kernel<true, true> : render_parity_hbm_kernel<false, true>;
+    return count ? render_parity_hbm_kernel<true, false> : render_parity_hbm_kernel<false, false>;
+}
+
+hipError_t launch_parity_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream)
+{
+    return launch_with_lds(parity_hbm_kernel(count, by_pixel), dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
+}
+
+uint32_t parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, uint32_t lds_bytes)
+{
+    return blocks_per_cu(reinterpret_cast<const void*>(parity_hbm_kernel(count, by_pixel)), threads, lds_bytes);
 }
 #endif
 

@@ -27,6 +27,16 @@ struct MirtError : std::runtime_error {
 };
 inline void check(int rc) { if (rc != MIRT_OK) throw MirtError(rc, mirt_last_error()); }
 
+// mirt_ctx_set_scene, and a world the LDS layouts refuse (MIRT_ERR_SCENE_TOO_LARGE) set again with MIRT_SCENE_HBM: the reference's
+// `Layer::set_data` takes any `Vec<Box<Sphere>>`
+inline int set_scene_any_size(MirtContext* ctx, const MirtScene& sc)
+{
+    const int rc = mirt_ctx_set_scene(ctx, &sc);
+    return rc == MIRT_ERR_SCENE_TOO_LARGE ? mirt_ctx_set_scene_ex(ctx, &sc, MIRT_SCENE_HBM) : rc;
+}
+// mirt_ctx_set_scene_ex: flags = MIRT_SCENE_*
+inline void set_scene(MirtContext* ctx, const MirtScene& sc, uint32_t flags) { check(mirt_ctx_set_scene_ex(ctx, &sc, flags)); }
+
 // Angle — angle.rs:1-50
 class Angle {
     float radians_;
@@ -231,7 +241,7 @@ public:
         sc.spheres = world.data(); sc.n_spheres = (uint32_t)world.size();
         sc.materials = material_data_.data(); sc.n_materials = (uint32_t)material_data_.size();
         sc.texels = global_texture_data_.data(); sc.n_texels = global_texture_data_.size() / 3;
-        check(mirt_ctx_set_scene(ctx_, &sc));
+        check(set_scene_any_size(ctx_, sc));               // a world beyond the LDS budget: MIRT_SCENE_HBM
         MirtParams p{};
         p.width = w; p.height = h; p.spp = rp.sampling.num_samples_per_pixel; p.mode = MIRT_MODE_PARITY;
         rgba_.assign((size_t)w * h * 4, 0);
@@ -285,6 +295,8 @@ public:
     }
 
     void set_scene(const MirtScene& scene) { check(mirt_node_set_scene(node_, &scene)); }
+    // flags: MIRT_SCENE_* (mirt_node_set_scene_ex)
+    void set_scene(const MirtScene& scene, uint32_t flags) { check(mirt_node_set_scene_ex(node_, &scene, flags)); }
     void set_camera(const MirtGpuCamera& camera) { check(mirt_node_set_camera(node_, &camera)); }
     // the band of `p` (tile_rows = n_parts = part = 0) as RGBA8, blocking
     std::vector<uint8_t> render(const MirtParams& p)
@@ -388,7 +400,7 @@ private:
         sc.materials = material_data_.data(); sc.n_materials = (uint32_t)material_data_.size();
         sc.texels = texels_.data(); sc.n_texels = texels_.size() / 3;
         sc.sky = have_sky_ ? &sky_ : nullptr;
-        check(mirt_ctx_set_scene(ctx_, &sc));
+        check(set_scene_any_size(ctx_, sc));               // a world beyond the LDS budget: MIRT_SCENE_HBM
     }
     RenderParams rp_;
     std::vector<MirtSphere> spheres_;

@@ -56,9 +56,13 @@ class Node:
         except Exception:
             pass
 
-    def set_scene(self, scene: SceneData) -> None:
+    def set_scene(self, scene: SceneData, *, hbm: bool = False) -> None:
+        """mirt_node_set_scene; hbm=True: mirt_node_set_scene_ex(MIRT_SCENE_HBM) on every member (Context.set_scene)."""
         c = scene.as_c()
-        check(lib().mirt_node_set_scene(self._h, C.byref(c)))
+        if hbm:
+            check(lib().mirt_node_set_scene_ex(self._h, C.byref(c), _abi.MIRT_SCENE_HBM))
+        else:
+            check(lib().mirt_node_set_scene(self._h, C.byref(c)))
         self._scene = scene
 
     def set_camera(self, camera: _abi.MirtGpuCamera) -> None:

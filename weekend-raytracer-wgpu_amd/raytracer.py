@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import MirtError, check, lib
-from .context import Context, SceneData, make_params
+from .context import Context, SceneData, make_params, set_scene_any_size
 from .node import Node
 
 f32 = np.float32
@@ -448,13 +448,13 @@ class Layer:
         if self._devices is not None:
             if self._node is None:
                 self._node = Node(self._devices)
-            self._node.set_scene(self.scene_data())
+            set_scene_any_size(self._node, self.scene_data())
             self._rgba = self._node.render(params)
             self.last_stats = self._node.stats()
             return
         if self._ctx is None:
             self._ctx = Context(self._device)
-        self._ctx.set_scene(self.scene_data())
+        set_scene_any_size(self._ctx, self.scene_data())       # worlds beyond the LDS budget: MIRT_SCENE_HBM
         self._rgba = self._ctx.render(params)
         self.last_stats = self._ctx.stats()
 
@@ -515,7 +515,7 @@ class Raytracer:
         self.camera = GpuCamera.new(render_params.camera, render_params.viewport_size)
         self.sky_state = sky_state
         self._ctx = Context(device)
-        self._ctx.set_scene(self.scene_data())
+        set_scene_any_size(self._ctx, self.scene_data())           # worlds beyond the LDS budget: MIRT_SCENE_HBM
         self.last_stats: Optional[dict] = None
         self._accumulated = None        # RenderProgress (mod.rs:615-679): None = reset pending
         self.frame_number = 1           # mod.rs:284; advanced by every render_frame call (mod.rs:350), never reset
