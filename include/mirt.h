@@ -432,6 +432,28 @@ uint32_t mirt_ctx_accum_samples(const MirtContext* ctx);
 int mirt_ctx_accum_resolve(MirtContext* ctx, const MirtParams* params, uint8_t* out_rgba8, size_t out_len);
 /* Copy the raw sums to the host: pixels x 3 uint64 (the fp32-intermediate view used by tests). */
 int mirt_ctx_accum_read(MirtContext* ctx, uint64_t* out_sums, size_t out_len_u64);
+/* ONE progressive frame, the shape of fsMain (wgsl:61-80; `Raytracer::render_frame`, mod.rs:303-351), into DEVICE memory `d_out_rgba8`
+ * (the layout of mirt_ctx_render_device), asynchronously on `hip_stream` (NULL = the context's stream), with no host synchronisation:
+ *   params->spp >= 1   ONE kernel launch: renders spp further samples of every pixel (the rules of mirt_ctx_accum_add: sample_begin is
+ *                      ignored, frame_spp / frame_begin are checked the same way), adds them to the sums and, in the same pass, writes
+ *                      the resolve of the UPDATED sums over all samples accumulated, tone curves per params->flags.  The schedule is
+ *                      the one mirt_ctx_accum_add would take; the kernel is its progressive-frame build (mirt_ctx_last_kernel:
+ *                      "render_pt_strip_frame_kernel<...>", "render_pt_stream_frame_kernel<...>", "render_pt_pool_frame_kernel<...>",
+ *                      "render_pt_pool_tile_frame_kernel<...>", "render_pt_hbm_frame_kernel<...>").  The bytes are those of
+ *                      mirt_ctx_accum_add followed by mirt_ctx_accum_resolve; the sums are those of mirt_ctx_accum_add.
+ *   params->spp == 0   adds nothing: resolve_accum_kernel writes the mean of what is there -- the reference's frame once the accumulation
+ *                      is complete (mod.rs:350).  MIRT_ERR_NO_SCENE if nothing has been accumulated.  Only the frame calls accept spp == 0.
+ * Errors as mirt_ctx_accum_add, plus MIRT_ERR_NULL_POINTER / MIRT_ERR_OUT_BUFFER for the output; a refused call leaves sums and count
+ * untouched.  A frame reads the sums the previous one wrote: consecutive frames on DIFFERENT streams (two frames in flight on
+ * mirt_ctx_frame_stream, into two framebuffers) are ordered by the library with an event wait on the device, whether they add or only
+ * read (spp == 0): the frames form one chain.  (hipStreamLegacy takes no part in event waits: the host waits for it instead.)  Later
+ * mirt_ctx_accum_resolve / _read / _reset calls are ordered after a frame exactly as after a mirt_ctx_accum_add on that stream.
+ * mirt_ctx_accum_add itself waits for nothing: an add that follows a frame on another stream is ordered by the caller, as adds among
+ * themselves are. */
+int mirt_ctx_accum_frame_device(MirtContext* ctx, const MirtParams* params, void* d_out_rgba8, size_t out_len, void* hip_stream);
+/* The same frame into HOST memory: the context's own device buffer, one D2H copy, blocking -- as mirt_ctx_render relates to
+ * mirt_ctx_render_device.  For hosts without HIP. */
+int mirt_ctx_accum_frame(MirtContext* ctx, const MirtParams* params, uint8_t* out_rgba8, size_t out_len);
 
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE
@@ -524,6 +546,31 @@ int  mirt_node_render_device(MirtNode* node, const MirtParams* params, void* d_o
 int  mirt_node_context(MirtNode* node, uint32_t i, MirtContext** out);
 /* Members and transport, and the times of the last render (waits for it). */
 int  mirt_node_get_stats(MirtNode* node, MirtNodeStats* out);
+
+/* ---- progressive accumulation on a node: the reference's render loop on several devices.  Member i owns the exact sums of ITS part
+ * of the tile interleave (mirt_ctx_accum_reset with tile_rows = 4, n_parts = n, part = i); a frame runs mirt_ctx_accum_frame_device on
+ * every member into its part buffer, and the parts then take the path of mirt_node_render_device: in place (loopback) or one ncclGather
+ * per member, then the assembly -- same events, no host sync.  What crosses devices per frame is 4 bytes per pixel of RGBA8, never the
+ * 24 bytes per pixel of sums.  Image, sums and count equal a single context's for every member count.
+ *   params:  the node owns the partition (non-zero tile_rows / n_parts / part: MIRT_ERR_BAD_ROWS); a frame before a successful
+ *            mirt_node_accum_reset, or with another width / height / band than the reset's: MIRT_ERR_OUT_BUFFER.  spp == 0 resolves what
+ *            is there, as on a context.  A member without rows is skipped.
+ *   errors:  every member is asked first, by the context's own rules, whether it would accept the frame: what a member refuses before
+ *            queueing anything (MIRT_ERR_FRAME_SPP, MIRT_ERR_SPP_RANGE, MIRT_ERR_SKY, MIRT_ERR_NO_SCENE for spp == 0 on empty sums, ...)
+ *            is refused up front, with the context's message, and changes nothing.  If a member's call fails after that, the node's
+ *            accumulation is INVALID until the next successful mirt_node_accum_reset: frames return MIRT_ERR_OUT_BUFFER,
+ *            mirt_node_accum_samples 0.
+ *   mirt_node_set_scene* and mirt_node_set_camera do not touch the sums: the host resets, as with a context. ---- */
+int      mirt_node_accum_reset(MirtNode* node, const MirtParams* params);
+/* One progressive frame of the band into DEVICE memory on member 0's device; stream rules of mirt_node_render_device. */
+int      mirt_node_accum_frame_device(MirtNode* node, const MirtParams* params, void* d_out_rgba8, size_t out_len, void* hip_stream);
+/* The same frame into HOST memory; blocking. */
+int      mirt_node_accum_frame(MirtNode* node, const MirtParams* params, uint8_t* out_rgba8, size_t out_len);
+/* Samples per pixel accumulated since the last reset (0 for an invalid accumulation). */
+uint32_t mirt_node_accum_samples(const MirtNode* node);
+/* The sums of the band in band-row order, pixels x 3 uint64: the members' mirt_ctx_accum_read, every compact row placed by
+ * mirt_params_out_row_index.  Blocking; meant for tests. */
+int      mirt_node_accum_read(MirtNode* node, uint64_t* out_sums, size_t out_len_u64);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -257,6 +257,8 @@ extern "C" {
     pub fn mirt_ctx_accum_samples(ctx: *const MirtContext) -> u32;
     pub fn mirt_ctx_accum_resolve(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_accum_read(ctx: *mut MirtContext, out_sums: *mut u64, out_len_u64: usize) -> c_int;
+    pub fn mirt_ctx_accum_frame_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ctx_accum_frame(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_selftest_math(ctx: *mut MirtContext, out_mismatches: *mut u64) -> c_int;
     pub fn mirt_render(scene: *const MirtScene, params: *const MirtParams, device: c_int, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_rgba8_to_rgb8(rgba: *const u8, n_pixels: usize, rgb: *mut u8) -> c_int;
@@ -275,4 +277,9 @@ extern "C" {
     pub fn mirt_node_render_device(node: *mut MirtNode, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_node_context(node: *mut MirtNode, i: u32, out: *mut *mut MirtContext) -> c_int;
     pub fn mirt_node_get_stats(node: *mut MirtNode, out: *mut MirtNodeStats) -> c_int;
+    pub fn mirt_node_accum_reset(node: *mut MirtNode, params: *const MirtParams) -> c_int;
+    pub fn mirt_node_accum_frame_device(node: *mut MirtNode, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_node_accum_frame(node: *mut MirtNode, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
+    pub fn mirt_node_accum_samples(node: *const MirtNode) -> u32;
+    pub fn mirt_node_accum_read(node: *mut MirtNode, out_sums: *mut u64, out_len_u64: usize) -> c_int;
 }

@@ -188,6 +188,8 @@ SYMBOLS = {
     "mirt_ctx_accum_samples": (C.c_uint32, [C.c_void_p]),
     "mirt_ctx_accum_resolve": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_accum_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mirt_ctx_accum_frame_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mirt_ctx_accum_frame": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_selftest_math": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "mirt_ctx_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_frame_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -208,6 +210,11 @@ SYMBOLS = {
     "mirt_node_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),
     "mirt_node_context": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_void_p)]),
     "mirt_node_get_stats": (C.c_int, [C.c_void_p, _P(MirtNodeStats)]),
+    "mirt_node_accum_reset": (C.c_int, [C.c_void_p, _P(MirtParams)]),
+    "mirt_node_accum_frame_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mirt_node_accum_frame": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
+    "mirt_node_accum_samples": (C.c_uint32, [C.c_void_p]),
+    "mirt_node_accum_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
 }
 
 

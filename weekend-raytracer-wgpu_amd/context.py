@@ -174,6 +174,20 @@ class Context:
         check(lib().mirt_ctx_accum_read(self._h, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
+    def accum_frame_device(self, params: _abi.MirtParams, d_out: int, stream: Optional[int] = None, nbytes: Optional[int] = None) -> None:
+        """mirt_ctx_accum_frame_device: ONE progressive frame in one launch -- `params.spp` further samples added to the sums and the
+        resolve of the updated sums written to device memory at address `d_out` (rows x width x 4 bytes unless `nbytes` says more),
+        asynchronously on `stream` (see _stream_arg).  params.spp == 0: the mean of what is there, nothing added."""
+        if nbytes is None:
+            nbytes = params_out_rows(params) * params.width * 4
+        check(lib().mirt_ctx_accum_frame_device(self._h, C.byref(params), C.c_void_p(d_out), nbytes, _stream_arg(stream)))
+
+    def accum_frame(self, params: _abi.MirtParams) -> np.ndarray:
+        """The same frame to host memory (mirt_ctx_accum_frame; blocking) -> uint8 [rows, width, 4]."""
+        out = np.empty((params_out_rows(params), params.width, 4), dtype=np.uint8)
+        check(lib().mirt_ctx_accum_frame(self._h, C.byref(params), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
     def selftest_math(self) -> tuple:
         """(sqrt mismatches, reciprocal mismatches) of the fast sequences vs IEEE over all 2^32 floats."""
         out = (C.c_uint64 * 2)()

@@ -383,6 +383,9 @@ struct MirtContext {
     size_t              last_slot = 0;             // event slot of the last launch (its counters feed MirtStats)
     hipEvent_t          ev_accum = nullptr;        // end of the last launch that adds into d_accum
     bool                accum_pending = false;
+    hipStream_t         accum_stream = nullptr;    // the stream of the last launch that uses d_accum: an add, or a frame -- also one that only reads
+                                                   // the sums, spp == 0 (nullptr: none since the reset).  What order_frame orders the next frame after.
+    hipEvent_t          ev_order = nullptr;        // progressive frames that change streams: the next one waits for the last one (order_frame)
     uint32_t*           d_out = nullptr;     // scratch framebuffer for host-output renders
     size_t              cap_out = 0;
     unsigned long long* d_accum = nullptr;   // progressive accumulation: [pixels][3] exact sums
@@ -570,6 +573,7 @@ int mirt_ctx_create(int device, MirtContext** out)
     c->slot_timed.assign(kEventPool, 0);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->zero_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMalloc(&c->d_sky, sizeof(MirtSkyState));
     if (e == hipSuccess) e = hipMalloc(&c->d_counters, sizeof(unsigned long long) * mirt::kNumCounters * kEventPool);
     if (e == hipSuccess) e = hipMalloc(&c->d_work_counter, sizeof(uint32_t) * kEventPool * kDispenserWords);
@@ -604,6 +608,7 @@ void mirt_ctx_destroy(MirtContext* c)
     if (c->zero_stream) (void)hipStreamDestroy(c->zero_stream);
     if (c->frame_stream_b) (void)hipStreamDestroy(c->frame_stream_b);
     if (c->ev_accum) (void)hipEventDestroy(c->ev_accum);
+    if (c->ev_order) (void)hipEventDestroy(c->ev_order);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -946,6 +951,9 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     const bool hosek = p->mode == MIRT_MODE_PT && (p->flags & MIRT_FLAG_SKY_HOSEK);
 
     const bool pt = p->mode == MIRT_MODE_PT;
+    // a progressive frame (mirt_ctx_accum_frame_device): sums AND image -> the *_frame_kernel build of whatever schedule is chosen below
+    const bool frame = d_out != nullptr && d_accum != nullptr;
+    const char* const kframe = frame ? "_frame" : "";
     const size_t scene_lds = kx::scene_lds_bytes(c->n_spheres, c->n_mats, pt, hosek);
     // kernel choice (path-traced mode): the pooled kernel needs enough samples per tile to keep
     // its path pool full, 8-bit bounce counters and room for the pool beside the scene in LDS
@@ -1163,11 +1171,11 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
         const bool fast_strip = pt && !count && (p->flags & MIRT_FLAG_FAST_MATH);
         const uint32_t threads = a.launch_threads ? a.launch_threads : mirt::kBlockThreads;
         uint32_t per_cu = hbm ? (!pt ? kx::parity_hbm_blocks_per_cu(count, by_pixel, threads, a.lds_bytes)
-                                     : fast_strip ? kf::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes)
-                                                  : kx::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes))
+                                     : fast_strip ? kf::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes, frame)
+                                                  : kx::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes, frame))
                         : !pt ? kx::parity_blocks_per_cu(count, by_pixel, a.lds_bytes)
-                        : fast_strip ? kf::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u)
-                                     : kx::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u);
+                        : fast_strip ? kf::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u, frame)
+                                     : kx::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u, frame);
         if (per_cu > 8u) per_cu = 8u;                                 // 2048 threads per CU / 256
         const uint32_t resident = (uint32_t)c->cu_count * per_cu;
         // ... unless the launch runs one unit per wave (a.static_units): then the grid is the units (MIRT_STATIC_GRID=k, A/B runs: k x the
@@ -1212,7 +1220,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
             snprintf(c->last_kernel, sizeof c->last_kernel, "render_parity_hbm_kernel<%s,%s>", tf[count], tf[by_pixel]);
         } else {
             HIP_TRY(fast ? kf::launch_pt_hbm(a, blocks, count, hbm_bvh, by_pixel, on) : kx::launch_pt_hbm(a, blocks, count, hbm_bvh, by_pixel, on));
-            snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_hbm_kernel<%s,%s,%s,%s>", fast ? "fast_build::" : "", tf[count], tf[hosek],
+            snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_hbm%s_kernel<%s,%s,%s,%s>", fast ? "fast_build::" : "", kframe, tf[count], tf[hosek],
                      tf[hbm_bvh], tf[by_pixel]);
         }
     } else if (p->mode == MIRT_MODE_PARITY) {
@@ -1224,8 +1232,8 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
         snprintf(c->last_kernel, sizeof c->last_kernel, "%s%s", fast ? "fast_build::" : "", kname);
     } else {
         HIP_TRY(fast ? kf::launch_pt_strip(a, blocks, count, use_grid, by_pixel, on) : kx::launch_pt_strip(a, blocks, count, use_grid, by_pixel, on));
-        if (a.stream_samples) snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_stream_kernel<%s>", fast ? "fast_build::" : "", tf[hosek]);
-        else snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_strip_kernel<%s,%s,%s,%s>", fast ? "fast_build::" : "", tf[count], tf[hosek],
+        if (a.stream_samples) snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_stream%s_kernel<%s>", fast ? "fast_build::" : "", kframe, tf[hosek]);
+        else snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_strip%s_kernel<%s,%s,%s,%s>", fast ? "fast_build::" : "", kframe, tf[count], tf[hosek],
                       tf[use_grid], tf[by_pixel]);
     }
     // The kernel is enqueued: from here on the slot is in use, whatever happens below (a failure after this point must not hand the
@@ -1247,6 +1255,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     // context's zero_stream -- never a memset node on the caller's stream, where it costs 3 us between kernels.  Launches whose units are
     // dealt round-robin (the reference's 2-spp frames, parity mode's lane = pixel) never touch the words.
     if (a.static_units == 0u) c->slot_dirty[ev] = 1;
+    if (d_accum) c->accum_stream = stream;
     if (he == hipSuccess && d_accum && stream != c->stream) {   // resolve/read (on the context's stream) must see sums added on a caller stream
         he = hipEventRecord(c->ev_accum, stream);
         if (he == hipSuccess) c->accum_pending = true;
@@ -1395,6 +1404,7 @@ int mirt_ctx_accum_reset(MirtContext* c, const MirtParams* p)
     if ((rc = ensure_capacity(&c->d_accum, &c->cap_accum, (size_t)npix * 3)) != MIRT_OK) return rc;
     HIP_TRY(hipMemsetAsync(c->d_accum, 0, (size_t)npix * 3 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->accum_stream = nullptr;
     c->accum_pixels = npix;
     c->accum_samples = 0;
     c->accum_width = p->width;
@@ -1421,6 +1431,107 @@ int mirt_ctx_accum_add(MirtContext* c, const MirtParams* p, void* hip_stream)
     rc = launch_render(c, &q, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream, c->d_accum);
     if (rc == MIRT_OK) c->accum_samples += p->spp;
     return rc;
+}
+
+// A progressive frame reads -- and, unless spp == 0, rewrites -- the sums the previous one left: frames that alternate between streams (two
+// in flight on mirt_ctx_frame_stream) are ordered here, on the device -- the new stream waits for what the stream of the LAST USER of the
+// sums holds.  Every frame becomes that last user, the spp == 0 frame too: an adding frame that followed it on another stream would
+// otherwise rewrite sums resolve_accum_kernel is still reading.  The frames thus form one chain, whatever streams they are on.
+// hipStreamLegacy takes no part in event waits (see mirt_ctx_accum_resolve): the host waits for it instead.
+static int order_frame(MirtContext* c, hipStream_t st)
+{
+    const hipStream_t prev = c->accum_stream;
+    if (!prev || prev == st) return MIRT_OK;
+    if (prev == hipStreamLegacy || st == hipStreamLegacy) {
+        HIP_TRY(hipStreamSynchronize(prev));
+        return MIRT_OK;
+    }
+    HIP_TRY(hipEventRecord(c->ev_order, prev));
+    HIP_TRY(hipStreamWaitEvent(st, c->ev_order, 0));
+    return MIRT_OK;
+}
+
+// What a progressive frame with these params is refused for before anything is queued, the output apart; *q = the params the launch
+// runs with.  (Also behind mirt::check_accum_frame: the node asks every member before it queues a frame on any.)
+static int check_frame_params(const MirtContext* c, const MirtParams* p, MirtParams* q)
+{
+    if (!c || !p) return fail(MIRT_ERR_NULL_POINTER, "ctx/params is null");
+    *q = *p;
+    if (p->spp == 0) q->spp = (p->mode == MIRT_MODE_PT && p->frame_spp) ? p->frame_spp : 1u;   // the frame after the accumulation is complete: every other field is checked as usual
+    const int rc = check_params(c, q);
+    if (rc != MIRT_OK) return rc;
+    q->spp = p->spp;
+    if (p->mode != MIRT_MODE_PT) return fail(MIRT_ERR_BAD_MODE, "progressive accumulation exists in path-traced mode only");
+    if (p->spp == 0 && (!c->d_accum || c->accum_samples == 0)) return fail(MIRT_ERR_NO_SCENE, "nothing accumulated yet");
+    if (!c->d_accum || c->accum_width != p->width || c->accum_rows != out_rows(p))
+        return fail(MIRT_ERR_OUT_BUFFER, "accumulation buffer does not match these params: call mirt_ctx_accum_reset first");
+    q->sample_begin = c->accum_samples;                 // continue the RNG stream where the last frame stopped (as mirt_ctx_accum_add)
+    if (p->spp != 0) {
+        if ((uint64_t)q->sample_begin + q->spp > 0xffffffffull)
+            return fail(MIRT_ERR_SPP_RANGE, "%u samples accumulated so far + %u would pass 2^32: reset first", q->sample_begin, q->spp);
+        if (q->frame_spp != 0 && q->sample_begin % q->frame_spp != 0)
+            return fail(MIRT_ERR_FRAME_SPP, "frame_spp %u does not divide the %u samples accumulated so far: reset first", q->frame_spp, q->sample_begin);
+    }
+    return MIRT_OK;
+}
+
+// ... and with the output both forms write
+static int check_frame(const MirtContext* c, const MirtParams* p, const void* out, size_t out_len, MirtParams* q)
+{
+    const int rc = check_frame_params(c, p, q);
+    if (rc != MIRT_OK) return rc;
+    if (!out) return fail(MIRT_ERR_NULL_POINTER, "the output buffer is null");
+    const size_t need = (size_t)c->accum_pixels * 4;
+    if (out_len < need) return fail(MIRT_ERR_OUT_BUFFER, "output buffer holds %zu bytes, %zu needed", out_len, need);
+    return MIRT_OK;
+}
+
+// One progressive frame into device memory on `st`: ONE launch -- the frame build of the schedule mirt_ctx_accum_add would run, or,
+// once nothing is to be added (spp == 0), the resolve of what is there.  No host synchronisation.
+static int launch_frame(MirtContext* c, const MirtParams* q, uint32_t* d_out, hipStream_t st)
+{
+    int rc = order_frame(c, st);
+    if (rc != MIRT_OK) return rc;
+    if (q->spp != 0) {
+        rc = launch_render(c, q, d_out, st, c->d_accum);
+        if (rc == MIRT_OK) c->accum_samples += q->spp;
+        return rc;
+    }
+    // the sums are complete: the reference keeps showing their mean (mod.rs:350)
+    HIP_TRY(kx::launch_resolve(c->d_accum, d_out, c->accum_pixels, c->accum_samples, q->flags, st));
+    snprintf(c->last_kernel, sizeof c->last_kernel, "resolve_accum_kernel");
+    c->accum_stream = st;                               // the next frame, on whatever stream, is ordered after this read (order_frame)
+    if (st != c->stream) {                              // mirt_ctx_accum_reset / _resolve / _read (host waits on ev_accum) must not overtake this read.  The frames are
+                                                        // one chain, so the event of the last one covers every earlier one.  (mirt_ctx_accum_add waits for nothing: an
+                                                        // add after a frame on another stream is ordered by the caller, as adds among themselves are.)
+        HIP_TRY(hipEventRecord(c->ev_accum, st));
+        c->accum_pending = true;
+        if (std::find(c->untimed_streams.begin(), c->untimed_streams.end(), st) == c->untimed_streams.end()) c->untimed_streams.push_back(st);
+    }
+    return MIRT_OK;
+}
+
+int mirt_ctx_accum_frame_device(MirtContext* c, const MirtParams* p, void* d_out, size_t out_len, void* hip_stream)
+{
+    MirtParams q;
+    const int rc = check_frame(c, p, d_out, out_len, &q);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return launch_frame(c, &q, (uint32_t*)d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int mirt_ctx_accum_frame(MirtContext* c, const MirtParams* p, uint8_t* out, size_t out_len)
+{
+    MirtParams q;
+    int rc = check_frame(c, p, out, out_len, &q);
+    if (rc != MIRT_OK) return rc;
+    const size_t npix = (size_t)c->accum_pixels;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = ensure_capacity(&c->d_out, &c->cap_out, npix)) != MIRT_OK) return rc;
+    if ((rc = launch_frame(c, &q, c->d_out, c->stream)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
 }
 
 uint32_t mirt_ctx_accum_samples(const MirtContext* c) { return c ? c->accum_samples : 0u; }
@@ -1517,3 +1628,9 @@ int mirt_ctx_deinterleave_device(MirtContext* c, const MirtParams* p, const void
 }
 
 }  // extern "C"
+
+int mirt::check_accum_frame(const MirtContext* ctx, const MirtParams* params)
+{
+    MirtParams q;
+    return check_frame_params(ctx, params, &q);
+}

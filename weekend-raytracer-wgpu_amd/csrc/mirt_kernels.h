@@ -175,7 +175,8 @@ struct RenderArgs {
     uint32_t                strip_cand;        // pool kernel, grid build: 1 = camera rays scan their strip's candidate list (0: A/B runs)
     uint32_t                grid_flat_y;       // grid builds: 1 = the grid is ONE cell high (dims[1] == 1: spheres on a ground plane) -> the 2-D walk
     uint32_t*               work_counter;  // dynamic work dispenser: THIS launch's own word (one per event slot), preset before the launch
-    unsigned long long*     accum;         // nullable: [pixels][3] exact fixed-point sums to ADD into instead of resolving
+    unsigned long long*     accum;         // nullable: [pixels][3] exact fixed-point sums to ADD into instead of resolving; with `out` set too, a
+                                           // progressive frame (the *_frame_kernel builds): add, and write the resolve of the updated sums to `out`
     uint64_t                n_texels;
     uint32_t n_spheres, n_mats;
     uint32_t width, height, spp, num_bounces, flags, seed_mix, sample_begin;
@@ -239,22 +240,22 @@ struct LaunchOn {
 struct PoolConfig { uint32_t threads, slots, lds_bytes; };
 namespace fast_build {
 hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream);
-uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream);
+uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream, bool frame = false);
 hipError_t launch_pt_pool(const RenderArgs& a, uint32_t grid_blocks, uint32_t cfg, bool count, uint32_t nq, LaunchOn stream);
 hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
-uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
+uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame = false);
 }
 namespace exact_build {
 // MIRT_SCENE_HBM scenes: the strip kernel with the scene in device memory -- a flat scan (bvh = false) or the BVH traversal -- and
 // the parity kernel's flat scan reading the spheres from device memory
 hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
-uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
+uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame = false);
 hipError_t launch_parity_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);
 uint32_t   parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
 hipError_t launch_parity(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);
 hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream);
 // blocks of the kernel such a launch runs that are resident per CU at once (hipOccupancyMaxActiveBlocksPerMultiprocessor)
-uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream);
+uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream, bool frame = false);
 uint32_t   parity_blocks_per_cu(bool count, bool by_pixel, uint32_t lds_bytes);
 uint32_t   pool_config_count();
 PoolConfig pool_config(uint32_t i, uint32_t nq);
@@ -273,5 +274,8 @@ size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);
 
 // host side (mirt_api.hip): sets the thread's mirt_last_error() message and returns `status`
 int set_error(int status, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// host side (mirt_api.hip): would mirt_ctx_accum_frame_device accept these params on this context now (the output apart)?  MIRT_OK, or
+// the status and message the frame call would give; queues nothing, changes nothing.
+int check_accum_frame(const MirtContext* ctx, const MirtParams* params);
 
 }  // namespace mirt

@@ -1707,7 +1707,10 @@ MIRT_DEV f3 path_radiance(const RenderArgs& A, const SceneLds& S, const GridLds&
 constexpr uint32_t kStreamRefillMin = 16;
 // SRC (MIRT_SCENE_HBM scenes, render_pt_hbm_kernel): kSrcHbmFlat scans the sphere table in device memory, kSrcBvh traverses the BVH
 // with the wave's stacks behind the camera (+ sky) in LDS; the scene's tables are not staged.
-template <bool COUNT, bool HOSEK, bool GRID, bool BY_PIXEL, bool STREAM, uint32_t SRC = kSrcLds>
+// FRAME = true (the *_frame_kernel builds, mirt_ctx_accum_frame_device): one progressive frame in one launch -- the lane that adds a
+// pixel's sums to A.accum keeps the new sums and stores their resolve over sample_begin + spp samples to A.out (fsMain's shape,
+// wgsl:61-80).  A template parameter and kernels of their own, so that every other launch runs the code object it always ran.
+template <bool COUNT, bool HOSEK, bool GRID, bool BY_PIXEL, bool STREAM, uint32_t SRC = kSrcLds, bool FRAME = false>
 MIRT_DEV void strip_kernel_body(const RenderArgs& A)
 {
     static_assert(!STREAM || (BY_PIXEL && !GRID && !COUNT), "the streaming schedule exists for lane = pixel in flat scenes");
@@ -1847,7 +1850,13 @@ MIRT_DEV void strip_kernel_body(const RenderArgs& A)
             }
             if (inside && grp == 0u) {
                 const RenderArgs& AS = per_strip_args();
-                if (AS.accum) {                  // progressive mode: add the exact sums, resolve later
+                if constexpr (FRAME) {           // progressive frame: add, and resolve the updated sums in the same pass
+                    unsigned long long* const sums = AS.accum + 3ull * pi;
+                    const unsigned long long sum_r = sums[0] + acc_r, sum_g = sums[1] + acc_g, sum_b = sums[2] + acc_b;
+                    sums[0] = sum_r; sums[1] = sum_g; sums[2] = sum_b;
+                    const uint32_t n = AS.sample_begin + AS.spp;
+                    AS.out[pi] = pack_rgba(resolve_channel(sum_r, n, AS.flags), resolve_channel(sum_g, n, AS.flags), resolve_channel(sum_b, n, AS.flags));
+                } else if (AS.accum) {                  // progressive mode: add the exact sums, resolve later
                     AS.accum[3ull * pi + 0] += acc_r; AS.accum[3ull * pi + 1] += acc_g; AS.accum[3ull * pi + 2] += acc_b;
                 } else {
 #ifdef MIRT_PROBE_NOSTORE      // experiment builds only
@@ -1886,7 +1895,14 @@ MIRT_DEV void strip_kernel_body(const RenderArgs& A)
                 acc_r = wave_sum_u64(acc_r);
                 acc_g = wave_sum_u64(acc_g);
                 acc_b = wave_sum_u64(acc_b);
-                if (A.accum) {                   // progressive mode: add the exact sums, resolve later
+                if constexpr (FRAME) {           // progressive frame: every lane reads the old sums (one address), lane 0 stores the new ones
+                    unsigned long long* const sums = A.accum + 3ull * pi;
+                    const unsigned long long sum_r = sums[0] + acc_r, sum_g = sums[1] + acc_g, sum_b = sums[2] + acc_b;
+                    if (lane == 0) { sums[0] = sum_r; sums[1] = sum_g; sums[2] = sum_b; }
+                    const uint32_t n = A.sample_begin + A.spp;
+                    const uint32_t rgba = pack_rgba(resolve_channel(sum_r, n, A.flags), resolve_channel(sum_g, n, A.flags), resolve_channel(sum_b, n, A.flags));
+                    if (lane == p) my_px = rgba;
+                } else if (A.accum) {                   // progressive mode: add the exact sums, resolve later
                     if (lane == 0) { A.accum[3ull * pi + 0] += acc_r; A.accum[3ull * pi + 1] += acc_g; A.accum[3ull * pi + 2] += acc_b; }
                 } else {
                     const uint32_t rgba = pack_rgba(resolve_channel(acc_r, A.spp, A.flags), resolve_channel(acc_g, A.spp, A.flags),
@@ -1894,7 +1910,11 @@ MIRT_DEV void strip_kernel_body(const RenderArgs& A)
                     if (lane == p) my_px = rgba;
                 }
             }
-            if (!A.accum && lane < kStripPixels && base + lane < npix) A.out[base + lane] = my_px;
+            if constexpr (FRAME) {
+                if (lane < kStripPixels && base + lane < npix) A.out[base + lane] = my_px;
+            } else if (!A.accum && lane < kStripPixels && base + lane < npix) {
+                A.out[base + lane] = my_px;
+            }
         }
         work.flush(A.counters, lane);
     }
@@ -1917,6 +1937,25 @@ template <bool HOSEK>
 __global__ __launch_bounds__(kBlockThreads, HOSEK ? 6 : 8) void render_pt_stream_kernel(RenderArgs A)
 {
     strip_kernel_body<false, HOSEK, false, true, true>(A);
+}
+
+// The progressive-frame builds of the three kernels above (strip_kernel_body<FRAME>): same schedules, same launch bounds.
+template <bool COUNT, bool HOSEK, bool GRID, bool BY_PIXEL = false>
+__global__ __launch_bounds__(kBlockThreads, (BY_PIXEL && !COUNT && !GRID && !HOSEK) ? 8 : ((BY_PIXEL && !COUNT && GRID) ? 7 : 1)) void render_pt_strip_frame_kernel(RenderArgs A)
+{
+    strip_kernel_body<COUNT, HOSEK, GRID, BY_PIXEL, false, kSrcLds, true>(A);
+}
+
+template <bool COUNT, bool HOSEK, bool BVH, bool BY_PIXEL>
+__global__ __launch_bounds__(kBlockThreads, (BY_PIXEL && !COUNT) ? 6 : 1) void render_pt_hbm_frame_kernel(RenderArgs A)
+{
+    strip_kernel_body<COUNT, HOSEK, false, BY_PIXEL, false, BVH ? kSrcBvh : kSrcHbmFlat, true>(A);
+}
+
+template <bool HOSEK>
+__global__ __launch_bounds__(kBlockThreads, HOSEK ? 6 : 8) void render_pt_stream_frame_kernel(RenderArgs A)
+{
+    strip_kernel_body<false, HOSEK, false, true, true, kSrcLds, true>(A);
 }
 
 // Shading routines a path can wait for: the five scatter routines of scatterRay (wgsl:174-314), identified by
@@ -1967,6 +2006,7 @@ struct WavePoolLayout {
 // GRID = true (many-sphere scenes): nearest hit through the uniform grid staged behind the spheres; the material
 // table stays in global memory / L2 as in the strip kernel's grid build, and the pools follow the grid in LDS.
 // The kernel's text lives in mirt_pool_kernel.inc and is compiled twice: the default build and the tile build.
+#define MIRT_POOL_KERNEL_FRAME false
 #define MIRT_POOL_KERNEL_NAME render_pt_pool_kernel
 #define MIRT_POOL_KERNEL_TILE false
 #include "mirt_pool_kernel.inc"
@@ -1977,6 +2017,20 @@ struct WavePoolLayout {
 #include "mirt_pool_kernel.inc"
 #undef MIRT_POOL_KERNEL_NAME
 #undef MIRT_POOL_KERNEL_TILE
+#undef MIRT_POOL_KERNEL_FRAME
+// ... and their progressive-frame builds (mirt_ctx_accum_frame_device): the strip's epilogue adds to the sums and resolves them
+#define MIRT_POOL_KERNEL_FRAME true
+#define MIRT_POOL_KERNEL_NAME render_pt_pool_frame_kernel
+#define MIRT_POOL_KERNEL_TILE false
+#include "mirt_pool_kernel.inc"
+#undef MIRT_POOL_KERNEL_NAME
+#undef MIRT_POOL_KERNEL_TILE
+#define MIRT_POOL_KERNEL_NAME render_pt_pool_tile_frame_kernel
+#define MIRT_POOL_KERNEL_TILE true
+#include "mirt_pool_kernel.inc"
+#undef MIRT_POOL_KERNEL_NAME
+#undef MIRT_POOL_KERNEL_TILE
+#undef MIRT_POOL_KERNEL_FRAME
 
 #ifdef MIRT_ISA_PROBES
 #include "mirt_isa_probes.inc"       // tools/isa_mix.py; never part of libmirt.so
@@ -2112,28 +2166,38 @@ hipError_t launch_parity(const RenderArgs& a, uint32_t grid_blocks, bool count, 
 
 using StripKernel = void (*)(RenderArgs);
 
-// the build of the strip kernel a launch runs (nullptr: no such build -- counting launches of the fast-math library)
-static StripKernel strip_kernel(bool count, bool hosek, bool use_grid, bool by_pixel, bool stream = false)
-{
-    if (stream && by_pixel && !count && !use_grid) return hosek ? render_pt_stream_kernel<true> : render_pt_stream_kernel<false>;
+// a progressive frame (mirt_ctx_accum_frame_device): the launch both adds to the sums and writes the image -> the *_frame_kernel builds
+static bool is_frame(const RenderArgs& a) { return a.accum != nullptr && a.out != nullptr; }
+
+// the build of the strip kernel a launch runs (nullptr: no such build -- counting launches of the fast-math library); frame = the
+// progressive-frame build of the same schedule.  One text for both families:
 #ifdef MIRT_FAST_MATH
-    if (count) return nullptr;                           // the counting builds exist in the exact build only
+#define MIRT_STRIP_COUNT_TREE(K) if (count) return nullptr;                  /* the counting builds exist in the exact build only */
 #else
-    if (count && use_grid) return hosek ? render_pt_strip_kernel<true, true, true> : render_pt_strip_kernel<true, false, true>;
-    if (count && by_pixel) return hosek ? render_pt_strip_kernel<true, true, false, true> : render_pt_strip_kernel<true, false, false, true>;
-    if (count) return hosek ? render_pt_strip_kernel<true, true, false> : render_pt_strip_kernel<true, false, false>;
+#define MIRT_STRIP_COUNT_TREE(K)                                                                                                   \
+    if (count && use_grid) return hosek ? K<true, true, true> : K<true, false, true>;                                             \
+    if (count && by_pixel) return hosek ? K<true, true, false, true> : K<true, false, false, true>;                               \
+    if (count) return hosek ? K<true, true, false> : K<true, false, false>;
 #endif
-    if (by_pixel) {
-        if (use_grid) return hosek ? render_pt_strip_kernel<false, true, true, true> : render_pt_strip_kernel<false, false, true, true>;
-        return hosek ? render_pt_strip_kernel<false, true, false, true> : render_pt_strip_kernel<false, false, false, true>;
-    }
-    if (use_grid) return hosek ? render_pt_strip_kernel<false, true, true> : render_pt_strip_kernel<false, false, true>;
-    return hosek ? render_pt_strip_kernel<false, true, false> : render_pt_strip_kernel<false, false, false>;
+#define MIRT_STRIP_TREE(K, KSTREAM)                                                                                                \
+    if (stream && by_pixel && !count && !use_grid) return hosek ? KSTREAM<true> : KSTREAM<false>;                                  \
+    MIRT_STRIP_COUNT_TREE(K)                                                                                                       \
+    if (by_pixel) {                                                                                                                \
+        if (use_grid) return hosek ? K<false, true, true, true> : K<false, false, true, true>;                                     \
+        return hosek ? K<false, true, false, true> : K<false, false, false, true>;                                                 \
+    }                                                                                                                              \
+    if (use_grid) return hosek ? K<false, true, true> : K<false, false, true>;                                                     \
+    return hosek ? K<false, true, false> : K<false, false, false>;
+
+static StripKernel strip_kernel(bool count, bool hosek, bool use_grid, bool by_pixel, bool stream = false, bool frame = false)
+{
+    if (frame) { MIRT_STRIP_TREE(render_pt_strip_frame_kernel, render_pt_stream_frame_kernel) }
+    MIRT_STRIP_TREE(render_pt_strip_kernel, render_pt_stream_kernel)
 }
 
 hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream)
 {
-    const StripKernel k = strip_kernel(count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, use_grid, by_pixel, a.stream_samples != 0u);
+    const StripKernel k = strip_kernel(count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, use_grid, by_pixel, a.stream_samples != 0u, is_frame(a));
     if (!k) return hipErrorInvalidValue;
     return launch_with_lds(k, dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
 }
@@ -2161,9 +2225,9 @@ static uint32_t blocks_per_cu(const void* kernel, uint32_t threads, uint32_t lds
     return blocks;
 }
 
-uint32_t strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream)
+uint32_t strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream, bool frame)
 {
-    const StripKernel k = strip_kernel(count, hosek, use_grid, by_pixel, stream);
+    const StripKernel k = strip_kernel(count, hosek, use_grid, by_pixel, stream, frame);
     return k ? blocks_per_cu(reinterpret_cast<const void*>(k), kBlockThreads, lds_bytes) : 1u;
 }
 
@@ -2175,33 +2239,39 @@ uint32_t parity_blocks_per_cu(bool count, bool by_pixel, uint32_t lds_bytes)
 #endif
 
 // ---- MIRT_SCENE_HBM scenes ----
-static StripKernel hbm_kernel(bool count, bool hosek, bool bvh, bool by_pixel)
-{
 #ifdef MIRT_FAST_MATH
-    if (count) return nullptr;                           // the counting builds exist in the exact build only
+#define MIRT_HBM_COUNT_TREE(K) if (count) return nullptr;                    /* the counting builds exist in the exact build only */
 #else
-    if (count) {
-        if (bvh) return by_pixel ? (hosek ? render_pt_hbm_kernel<true, true, true, true> : render_pt_hbm_kernel<true, false, true, true>)
-                                 : (hosek ? render_pt_hbm_kernel<true, true, true, false> : render_pt_hbm_kernel<true, false, true, false>);
-        return by_pixel ? (hosek ? render_pt_hbm_kernel<true, true, false, true> : render_pt_hbm_kernel<true, false, false, true>)
-                        : (hosek ? render_pt_hbm_kernel<true, true, false, false> : render_pt_hbm_kernel<true, false, false, false>);
+#define MIRT_HBM_COUNT_TREE(K)                                                                                                     \
+    if (count) {                                                                                                                   \
+        if (bvh) return by_pixel ? (hosek ? K<true, true, true, true> : K<true, false, true, true>)                                \
+                                 : (hosek ? K<true, true, true, false> : K<true, false, true, false>);                             \
+        return by_pixel ? (hosek ? K<true, true, false, true> : K<true, false, false, true>)                                       \
+                        : (hosek ? K<true, true, false, false> : K<true, false, false, false>);                                    \
     }
 #endif
-    if (bvh) return hosek ? render_pt_hbm_kernel<false, true, true, true> : render_pt_hbm_kernel<false, false, true, true>;   // lane = pixel only
-    return by_pixel ? (hosek ? render_pt_hbm_kernel<false, true, false, true> : render_pt_hbm_kernel<false, false, false, true>)
-                    : (hosek ? render_pt_hbm_kernel<false, true, false, false> : render_pt_hbm_kernel<false, false, false, false>);
+#define MIRT_HBM_TREE(K)                                                                                                           \
+    MIRT_HBM_COUNT_TREE(K)                                                                                                         \
+    if (bvh) return hosek ? K<false, true, true, true> : K<false, false, true, true>;   /* lane = pixel only */                    \
+    return by_pixel ? (hosek ? K<false, true, false, true> : K<false, false, false, true>)                                         \
+                    : (hosek ? K<false, true, false, false> : K<false, false, false, false>);
+
+static StripKernel hbm_kernel(bool count, bool hosek, bool bvh, bool by_pixel, bool frame = false)
+{
+    if (frame) { MIRT_HBM_TREE(render_pt_hbm_frame_kernel) }
+    MIRT_HBM_TREE(render_pt_hbm_kernel)
 }
 
 hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream)
 {
-    const StripKernel k = hbm_kernel(count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, bvh, by_pixel);
+    const StripKernel k = hbm_kernel(count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, bvh, by_pixel, is_frame(a));
     if (!k) return hipErrorInvalidValue;
     return launch_with_lds(k, dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
 }
 
-uint32_t hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes)
+uint32_t hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame)
 {
-    const StripKernel k = hbm_kernel(count, hosek, bvh, by_pixel);
+    const StripKernel k = hbm_kernel(count, hosek, bvh, by_pixel, frame);
     return k ? blocks_per_cu(reinterpret_cast<const void*>(k), threads, lds_bytes) : 1u;
 }
 
@@ -2226,28 +2296,32 @@ uint32_t parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, u
 // builds of the pool kernel by scatter queues: 3 and 5 for every geometry; 1, 2 and 4 as well (FEW = true) for the default and the
 // tile geometry -- a scene with fewer shading routines than queues would carry empty queues through every pick and push
 // (two routines, config 4: -1.2 %)
+// the pool kernel a launcher below starts: the progressive-frame build of the same geometry when the launch is a frame (`frame`)
+#define MIRT_POOL_K(...)      (frame ? render_pt_pool_frame_kernel<__VA_ARGS__> : render_pt_pool_kernel<__VA_ARGS__>)
+#define MIRT_POOL_TILE_K(...) (frame ? render_pt_pool_tile_frame_kernel<__VA_ARGS__> : render_pt_pool_tile_kernel<__VA_ARGS__>)
 template <uint32_t T, uint32_t SL, uint32_t MW = 1, bool FEW = false>
 static hipError_t launch_pool_cfg(const RenderArgs& a, uint32_t grid_blocks, bool count, bool hosek, uint32_t nq, LaunchOn stream)
 {
     const dim3 g(grid_blocks), b(T);
+    const bool frame = is_frame(a);
 #ifdef MIRT_FAST_MATH
     if (count) return hipErrorInvalidValue;
 #else
-    if (count) return hosek ? launch_with_lds(render_pt_pool_kernel<T, SL, 1, true, true>, g, b, a, stream)
-                            : launch_with_lds(render_pt_pool_kernel<T, SL, 1, true, false>, g, b, a, stream);
+    if (count) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, 1, true, true), g, b, a, stream)
+                            : launch_with_lds(MIRT_POOL_K(T, SL, 1, true, false), g, b, a, stream);
 #endif
     if constexpr (FEW) {
-        if (nq == 1) return hosek ? launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, true, 1>, g, b, a, stream)
-                                  : launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, false, 1>, g, b, a, stream);
-        if (nq == 2) return hosek ? launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, true, 2>, g, b, a, stream)
-                                  : launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, false, 2>, g, b, a, stream);
-        if (nq == 4) return hosek ? launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, true, 4>, g, b, a, stream)
-                                  : launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, false, 4>, g, b, a, stream);
+        if (nq == 1) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 1), g, b, a, stream)
+                                  : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 1), g, b, a, stream);
+        if (nq == 2) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 2), g, b, a, stream)
+                                  : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 2), g, b, a, stream);
+        if (nq == 4) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 4), g, b, a, stream)
+                                  : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 4), g, b, a, stream);
     }
-    if (nq <= 3) return hosek ? launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, true, 3>, g, b, a, stream)
-                              : launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, false, 3>, g, b, a, stream);
-    return hosek ? launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, true>, g, b, a, stream)
-                 : launch_with_lds(render_pt_pool_kernel<T, SL, MW, false, false>, g, b, a, stream);
+    if (nq <= 3) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 3), g, b, a, stream)
+                              : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 3), g, b, a, stream);
+    return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true), g, b, a, stream)
+                 : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false), g, b, a, stream);
 }
 
 // the tile build (MIRT_FLAG_TEXEL_TILES): fewer slots, a texel window per wave
@@ -2255,22 +2329,23 @@ template <uint32_t T, uint32_t SL, uint32_t MW>
 static hipError_t launch_pool_tile(const RenderArgs& a, uint32_t grid_blocks, bool count, bool hosek, uint32_t nq, LaunchOn stream)
 {
     const dim3 g(grid_blocks), b(T);
+    const bool frame = is_frame(a);
 #ifdef MIRT_FAST_MATH
     if (count) return hipErrorInvalidValue;
 #else
-    if (count) return hosek ? launch_with_lds(render_pt_pool_tile_kernel<T, SL, 1, true, true>, g, b, a, stream)
-                            : launch_with_lds(render_pt_pool_tile_kernel<T, SL, 1, true, false>, g, b, a, stream);
+    if (count) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, 1, true, true), g, b, a, stream)
+                            : launch_with_lds(MIRT_POOL_TILE_K(T, SL, 1, true, false), g, b, a, stream);
 #endif
-    if (nq == 1) return hosek ? launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, true, 1>, g, b, a, stream)
-                              : launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, false, 1>, g, b, a, stream);
-    if (nq == 2) return hosek ? launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, true, 2>, g, b, a, stream)
-                              : launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, false, 2>, g, b, a, stream);
-    if (nq == 4) return hosek ? launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, true, 4>, g, b, a, stream)
-                              : launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, false, 4>, g, b, a, stream);
-    if (nq <= 3) return hosek ? launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, true, 3>, g, b, a, stream)
-                              : launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, false, 3>, g, b, a, stream);
-    return hosek ? launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, true>, g, b, a, stream)
-                 : launch_with_lds(render_pt_pool_tile_kernel<T, SL, MW, false, false>, g, b, a, stream);
+    if (nq == 1) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 1), g, b, a, stream)
+                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 1), g, b, a, stream);
+    if (nq == 2) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 2), g, b, a, stream)
+                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 2), g, b, a, stream);
+    if (nq == 4) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 4), g, b, a, stream)
+                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 4), g, b, a, stream);
+    if (nq <= 3) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 3), g, b, a, stream)
+                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 3), g, b, a, stream);
+    return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true), g, b, a, stream)
+                 : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false), g, b, a, stream);
 }
 
 // grid build of the default pool geometry: LDS (scene + grid + pools) bounds it to a few blocks per CU, so the
@@ -2279,31 +2354,32 @@ template <bool FLATY>
 static hipError_t launch_pool_grid_(const RenderArgs& a, uint32_t grid_blocks, bool count, bool hosek, LaunchOn stream)
 {
     const dim3 g(grid_blocks), b(kGridPoolThreads);
+    const bool frame = is_frame(a);
     const uint32_t slots = a.grid_pool_slots;
 #ifdef MIRT_FAST_MATH
     if (count) return hipErrorInvalidValue;
 #else
     if (count) {                                // counting builds exist for the two largest geometries
         if (slots == kGridPoolSlotChoices[0])
-            return hosek ? launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[0], 1, true, true, 1, true, FLATY>, g, b, a, stream)
-                         : launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[0], 1, true, false, 1, true, FLATY>, g, b, a, stream);
+            return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], 1, true, true, 1, true, FLATY), g, b, a, stream)
+                         : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], 1, true, false, 1, true, FLATY), g, b, a, stream);
         if (slots == kGridPoolSlotChoices[1])
-            return hosek ? launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[1], 1, true, true, 1, true, FLATY>, g, b, a, stream)
-                         : launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[1], 1, true, false, 1, true, FLATY>, g, b, a, stream);
+            return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], 1, true, true, 1, true, FLATY), g, b, a, stream)
+                         : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], 1, true, false, 1, true, FLATY), g, b, a, stream);
         return hipErrorInvalidValue;
     }
 #endif
     if (slots == kGridPoolSlotChoices[0])
-        return hosek ? launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[0], kGridPoolMinWaves, false, true, 1, true, FLATY>, g, b, a, stream)
-                     : launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[0], kGridPoolMinWaves, false, false, 1, true, FLATY>, g, b, a, stream);
+        return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
+                     : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
     if (slots == kGridPoolSlotChoices[1])
-        return hosek ? launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[1], kGridPoolMinWaves, false, true, 1, true, FLATY>, g, b, a, stream)
-                     : launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[1], kGridPoolMinWaves, false, false, 1, true, FLATY>, g, b, a, stream);
+        return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
+                     : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
     if (slots == kGridPoolSlotChoices[2])
-        return hosek ? launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[2], kGridPoolMinWaves, false, true, 1, true, FLATY>, g, b, a, stream)
-                     : launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[2], kGridPoolMinWaves, false, false, 1, true, FLATY>, g, b, a, stream);
-    return hosek ? launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[3], kGridPoolMinWaves, false, true, 1, true, FLATY>, g, b, a, stream)
-                 : launch_with_lds(render_pt_pool_kernel<kGridPoolThreads, kGridPoolSlotChoices[3], kGridPoolMinWaves, false, false, 1, true, FLATY>, g, b, a, stream);
+        return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[2], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
+                     : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[2], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
+    return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[3], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
+                 : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[3], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
 }
 
 // grid builds have ONE scatter queue (per-lane material switch); FLATY = the grid is one cell high (RenderArgs.grid_flat_y)
@@ -2393,6 +2469,7 @@ void pool_kernel_name(const RenderArgs& a, uint32_t cfg, bool count, uint32_t nq
 {
     const bool hosek = (a.flags & MIRT_FLAG_SKY_HOSEK) != 0;
     const char* tf[2] = { "false", "true" };
+    const char* frame = is_frame(a) ? "_frame" : "";
     uint32_t slots = 112, minw = 6, threads = 256;
     if (a.grid) { threads = kGridPoolThreads; slots = a.grid_pool_slots; minw = count ? 1 : kGridPoolMinWaves; nq = 1; }
     else {
@@ -2406,11 +2483,11 @@ void pool_kernel_name(const RenderArgs& a, uint32_t cfg, bool count, uint32_t nq
         }
         if (count) { minw = 1; nq = 5; } else nq = built_queues(cfg, nq);
         if (cfg == kTilePoolConfig) {
-            snprintf(out, out_len, "render_pt_pool_tile_kernel<%u,%u,%u,%s,%s,%u,false>", threads, slots, minw, tf[count], tf[hosek], nq);
+            snprintf(out, out_len, "render_pt_pool_tile%s_kernel<%u,%u,%u,%s,%s,%u,false>", frame, threads, slots, minw, tf[count], tf[hosek], nq);
             return;
         }
     }
-    snprintf(out, out_len, "render_pt_pool_kernel<%u,%u,%u,%s,%s,%u,%s,%s>", threads, slots, minw, tf[count], tf[hosek], nq, tf[a.grid != nullptr],
+    snprintf(out, out_len, "render_pt_pool%s_kernel<%u,%u,%u,%s,%s,%u,%s,%s>", frame, threads, slots, minw, tf[count], tf[hosek], nq, tf[a.grid != nullptr],
              tf[a.grid != nullptr && a.grid_flat_y != 0u]);
 }
 

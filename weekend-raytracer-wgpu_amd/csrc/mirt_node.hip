@@ -8,7 +8,8 @@
 //        into a parts buffer on member 0 (every part padded to the largest).  librccl is loaded with dlopen by such a node only.
 //
 // Ordering (no host sync on the frame path)
-//   member i:  [wait ev_consumed] render part i on its context stream -> ev_done[i]
+//   member i:  [wait ev_consumed] fill part i on its context stream -> ev_done[i]
+//              (fill = mirt_ctx_render_device, or mirt_ctx_accum_frame_device for a progressive frame: the ONLY difference between the two)
 //   loopback:  tail stream waits ev_done[i] of every member with rows
 //   RCCL:      member 0's stream waits ev_done[i > 0] -> ev_gather_begin -> group of gathers -> ev_gather_end; tail waits ev_gather_end
 //   tail:      assemble_parts_kernel (events ev_asm_begin / ev_asm_end on its dispatch) -> ev_consumed [-> D2H copy]
@@ -19,11 +20,13 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <mutex>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/mirt.h"
 #include "mirt_kernels.h"
@@ -126,27 +129,48 @@ struct MirtNode {
     uint32_t*    d_out = nullptr;                               // mirt_node_render: the band before its D2H copy
     size_t       cap_out = 0;
     bool         have_scene = false;
+    // progressive accumulation: member i owns the exact sums of its part (mirt_ctx_accum_reset with q[i]); what crosses devices per frame
+    // is the members' RGBA8 parts, never the sums
+    bool         accum_valid = false;                           // a reset succeeded and no member's frame has failed since
+    MirtParams   accum_params = {};                             // the reset's params (geometry of the sums)
+    uint32_t     accum_samples = 0;
 };
 
 namespace {
 
-// The tail of a frame on `tail` (a stream of member 0's device): members render, the parts reach member 0, the assembly writes
-// `d_out`.  Params are checked by the caller (mirt_node_render / _device) except what the member contexts check themselves.
-int node_frame(MirtNode* nd, const MirtParams* p, uint32_t* d_out, hipStream_t tail)
+// What fills member i's part: a one-shot render, or one progressive frame on the member's own sums.
+enum Fill { kFillRender, kFillAccumFrame };
+
+int fill_part(Fill fill, MirtContext* ctx, const MirtParams* q, void* d_part, size_t len, void* stream)
+{
+    return fill == kFillRender ? mirt_ctx_render_device(ctx, q, d_part, len, stream) : mirt_ctx_accum_frame_device(ctx, q, d_part, len, stream);
+}
+
+// Member i's share of the band: the 4-row tile interleave.  Returns the largest number of rows a member has.
+uint32_t member_params(const MirtNode* nd, const MirtParams* p, MirtParams* q, uint32_t* rows)
+{
+    uint32_t max_rows = 0;
+    for (uint32_t i = 0; i < nd->n; ++i) {
+        q[i] = *p;
+        q[i].tile_rows = kNodeTileRows;
+        q[i].n_parts = nd->n;
+        q[i].part = i;
+        rows[i] = mirt_params_out_rows(&q[i]);
+        if (rows[i] > max_rows) max_rows = rows[i];
+    }
+    return max_rows;
+}
+
+// The tail of a frame on `tail` (a stream of member 0's device): members fill their parts, the parts reach member 0, the assembly
+// writes `d_out`.  Params are checked by the caller (mirt_node_render / _accum_frame / _device) except what the member contexts check
+// themselves.
+int node_frame(MirtNode* nd, const MirtParams* p, uint32_t* d_out, hipStream_t tail, Fill fill)
 {
     const uint32_t n = nd->n;
     const uint32_t w = p->width;
     MirtParams q[MIRT_NODE_MAX_MEMBERS];
     uint32_t rows[MIRT_NODE_MAX_MEMBERS];
-    uint32_t max_rows = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        q[i] = *p;
-        q[i].tile_rows = kNodeTileRows;
-        q[i].n_parts = n;
-        q[i].part = i;
-        rows[i] = mirt_params_out_rows(&q[i]);
-        if (rows[i] > max_rows) max_rows = rows[i];
-    }
+    const uint32_t max_rows = member_params(nd, p, q, rows);
     const bool rccl = nd->transport == 1;
     const size_t slot_px = (size_t)max_rows * w;
 
@@ -176,7 +200,7 @@ int node_frame(MirtNode* nd, const MirtParams* p, uint32_t* d_out, hipStream_t t
         NODE_HIP_TRY(hipSetDevice(nd->device[i]));
         if (nd->consumed_pending) NODE_HIP_TRY(hipStreamWaitEvent(nd->stream[i], nd->ev_consumed, 0));
         if (rows[i]) {
-            const int rc = mirt_ctx_render_device(nd->ctx[i], &q[i], nd->d_part[i], (size_t)rows[i] * w * 4, nd->stream[i]);
+            const int rc = fill_part(fill, nd->ctx[i], &q[i], nd->d_part[i], (size_t)rows[i] * w * 4, nd->stream[i]);
             if (rc != MIRT_OK) return rc;
         }
         NODE_HIP_TRY(hipEventRecord(nd->ev_done[i], nd->stream[i]));
@@ -380,18 +404,43 @@ int mirt_node_set_camera(MirtNode* nd, const MirtGpuCamera* camera)
     return MIRT_OK;
 }
 
+static int refuse_legacy_stream(const void* hip_stream)
+{
+    if ((hipStream_t)hip_stream == hipStreamLegacy)
+        return mirt::set_error(MIRT_ERR_HIP, "the node does not order work on hipStreamLegacy: pass a stream of your own, or NULL");
+    return MIRT_OK;
+}
+
+// Both device forms: the band into `d_out`, asynchronously.
+static int node_frame_device(MirtNode* nd, const MirtParams* p, void* d_out, size_t out_len, void* hip_stream, Fill fill)
+{
+    if (nd->n == 1 && nd->transport == 0) {                        // one member on one device: the band straight into the output
+        nd->asm_timed = nd->gather_timed = false;
+        return fill_part(fill, nd->ctx[0], p, d_out, out_len, hip_stream ? hip_stream : (void*)nd->root_stream);
+    }
+    return node_frame(nd, p, (uint32_t*)d_out, hip_stream ? (hipStream_t)hip_stream : nd->root_stream, fill);
+}
+
+// Both host forms: the band into the node's own buffer, one D2H copy, blocking.
+static int node_frame_host(MirtNode* nd, const MirtParams* p, uint8_t* out, size_t need, Fill fill)
+{
+    int rc;
+    NODE_HIP_TRY(hipSetDevice(nd->device[0]));
+    if ((rc = grow(&nd->d_out, &nd->cap_out, need / 4)) != MIRT_OK) return rc;
+    if ((rc = node_frame_device(nd, p, nd->d_out, need, nullptr, fill)) != MIRT_OK) return rc;
+    NODE_HIP_TRY(hipSetDevice(nd->device[0]));
+    NODE_HIP_TRY(hipMemcpyAsync(out, nd->d_out, need, hipMemcpyDeviceToHost, nd->root_stream));
+    NODE_HIP_TRY(hipStreamSynchronize(nd->root_stream));
+    return MIRT_OK;
+}
+
 int mirt_node_render_device(MirtNode* nd, const MirtParams* p, void* d_out, size_t out_len, void* hip_stream)
 {
     size_t need = 0;
-    const int rc = check_node_params(nd, p, d_out, out_len, &need);
+    int rc = check_node_params(nd, p, d_out, out_len, &need);
+    if (rc == MIRT_OK) rc = refuse_legacy_stream(hip_stream);
     if (rc != MIRT_OK) return rc;
-    if ((hipStream_t)hip_stream == hipStreamLegacy)
-        return mirt::set_error(MIRT_ERR_HIP, "the node does not order work on hipStreamLegacy: pass a stream of your own, or NULL");
-    if (nd->n == 1 && nd->transport == 0) {                        // one member on one device: the band straight into the output
-        nd->asm_timed = nd->gather_timed = false;
-        return mirt_ctx_render_device(nd->ctx[0], p, d_out, out_len, hip_stream ? hip_stream : (void*)nd->root_stream);
-    }
-    return node_frame(nd, p, (uint32_t*)d_out, hip_stream ? (hipStream_t)hip_stream : nd->root_stream);
+    return node_frame_device(nd, p, d_out, out_len, hip_stream, kFillRender);
 }
 
 int mirt_node_render(MirtNode* nd, const MirtParams* p, uint8_t* out, size_t out_len)
@@ -403,12 +452,111 @@ int mirt_node_render(MirtNode* nd, const MirtParams* p, uint8_t* out, size_t out
         nd->asm_timed = nd->gather_timed = false;
         return mirt_ctx_render(nd->ctx[0], p, out, out_len);
     }
-    NODE_HIP_TRY(hipSetDevice(nd->device[0]));
-    if ((rc = grow(&nd->d_out, &nd->cap_out, need / 4)) != MIRT_OK) return rc;
-    if ((rc = node_frame(nd, p, nd->d_out, nd->root_stream)) != MIRT_OK) return rc;
-    NODE_HIP_TRY(hipSetDevice(nd->device[0]));
-    NODE_HIP_TRY(hipMemcpyAsync(out, nd->d_out, need, hipMemcpyDeviceToHost, nd->root_stream));
-    NODE_HIP_TRY(hipStreamSynchronize(nd->root_stream));
+    return node_frame_host(nd, p, out, need, kFillRender);
+}
+
+// ---- progressive accumulation on a node ----
+
+int mirt_node_accum_reset(MirtNode* nd, const MirtParams* p)
+{
+    if (!nd || !p) return mirt::set_error(MIRT_ERR_NULL_POINTER, "node/params is null");
+    size_t need = 0;
+    int rc = check_node_params(nd, p, p, SIZE_MAX, &need);         // (no output here: scene, partition, viewport and rows)
+    if (rc != MIRT_OK) return rc;
+    nd->accum_valid = false;
+    nd->accum_samples = 0;
+    MirtParams q[MIRT_NODE_MAX_MEMBERS];
+    uint32_t rows[MIRT_NODE_MAX_MEMBERS];
+    (void)member_params(nd, p, q, rows);
+    for (uint32_t i = 0; i < nd->n; ++i) {
+        if (!rows[i]) continue;                                    // a member without rows owns no sums
+        if ((rc = mirt_ctx_accum_reset(nd->ctx[i], &q[i])) != MIRT_OK) return rc;
+    }
+    nd->accum_params = *p;
+    nd->accum_valid = true;
+    return MIRT_OK;
+}
+
+// What both frame calls check after check_node_params: the sums exist and have this geometry.
+static int check_node_accum(const MirtNode* nd, const MirtParams* p)
+{
+    const MirtParams& r = nd->accum_params;
+    if (!nd->accum_valid || r.width != p->width || r.height != p->height || r.row_begin != p->row_begin ||
+        (r.row_end == 0 ? r.height : r.row_end) != (p->row_end == 0 ? p->height : p->row_end))
+        return mirt::set_error(MIRT_ERR_OUT_BUFFER, "accumulation buffer does not match these params: call mirt_node_accum_reset first");
+    return MIRT_OK;
+}
+
+// After the members' calls: the count follows the members' (they advance together), a failure invalidates the accumulation.
+static int node_accum_done(MirtNode* nd, const MirtParams* p, int rc)
+{
+    if (rc != MIRT_OK) {
+        nd->accum_valid = false;
+        nd->accum_samples = 0;
+        return rc;
+    }
+    nd->accum_samples += p->spp;
+    return MIRT_OK;
+}
+
+// A refusal a member would give before it queues anything leaves the accumulation as it is: every member with rows is asked first,
+// with the context's own rules (mirt::check_accum_frame), before a frame is queued on any.
+static int precheck_node_frame(MirtNode* nd, const MirtParams* p)
+{
+    MirtParams q[MIRT_NODE_MAX_MEMBERS];
+    uint32_t rows[MIRT_NODE_MAX_MEMBERS];
+    (void)member_params(nd, p, q, rows);
+    for (uint32_t i = 0; i < nd->n; ++i) {
+        if (!rows[i]) continue;
+        const int rc = mirt::check_accum_frame(nd->ctx[i], &q[i]);
+        if (rc != MIRT_OK) return rc;
+    }
+    return MIRT_OK;
+}
+
+int mirt_node_accum_frame_device(MirtNode* nd, const MirtParams* p, void* d_out, size_t out_len, void* hip_stream)
+{
+    size_t need = 0;
+    int rc = check_node_params(nd, p, d_out, out_len, &need);
+    if (rc == MIRT_OK) rc = check_node_accum(nd, p);
+    if (rc == MIRT_OK) rc = precheck_node_frame(nd, p);
+    if (rc == MIRT_OK) rc = refuse_legacy_stream(hip_stream);
+    if (rc != MIRT_OK) return rc;
+    return node_accum_done(nd, p, node_frame_device(nd, p, d_out, out_len, hip_stream, kFillAccumFrame));
+}
+
+int mirt_node_accum_frame(MirtNode* nd, const MirtParams* p, uint8_t* out, size_t out_len)
+{
+    size_t need = 0;
+    int rc = check_node_params(nd, p, out, out_len, &need);
+    if (rc == MIRT_OK) rc = check_node_accum(nd, p);
+    if (rc == MIRT_OK) rc = precheck_node_frame(nd, p);
+    if (rc != MIRT_OK) return rc;
+    return node_accum_done(nd, p, node_frame_host(nd, p, out, need, kFillAccumFrame));
+}
+
+uint32_t mirt_node_accum_samples(const MirtNode* nd) { return (nd && nd->accum_valid) ? nd->accum_samples : 0u; }
+
+int mirt_node_accum_read(MirtNode* nd, uint64_t* out_sums, size_t out_len_u64)
+{
+    if (!nd || !out_sums) return mirt::set_error(MIRT_ERR_NULL_POINTER, "node/out is null");
+    if (!nd->accum_valid) return mirt::set_error(MIRT_ERR_NO_SCENE, "nothing accumulated yet");
+    const MirtParams* p = &nd->accum_params;
+    const size_t w = p->width;
+    if (out_len_u64 < (size_t)mirt_params_out_rows(p) * w * 3) return mirt::set_error(MIRT_ERR_OUT_BUFFER, "output buffer too small");
+    MirtParams q[MIRT_NODE_MAX_MEMBERS];
+    uint32_t rows[MIRT_NODE_MAX_MEMBERS];
+    const uint32_t max_rows = member_params(nd, p, q, rows);
+    std::vector<uint64_t> part((size_t)max_rows * w * 3);
+    for (uint32_t i = 0; i < nd->n; ++i) {
+        if (!rows[i]) continue;
+        const int rc = mirt_ctx_accum_read(nd->ctx[i], part.data(), part.size());
+        if (rc != MIRT_OK) return rc;
+        for (uint32_t r = 0; r < rows[i]; ++r) {                   // compact row r of part i -> its row of the band
+            const uint32_t band_row = mirt_params_out_row_index(&q[i], r) - p->row_begin;
+            std::copy(part.begin() + (size_t)r * w * 3, part.begin() + (size_t)(r + 1) * w * 3, out_sums + (size_t)band_row * w * 3);
+        }
+    }
     return MIRT_OK;
 }
 

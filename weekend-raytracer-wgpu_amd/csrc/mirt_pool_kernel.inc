@@ -1,4 +1,5 @@
-// mirt_pool_kernel.inc -- the text of the pooled path-traced kernel.  mirt_kernels.hip includes it twice:
+// mirt_pool_kernel.inc -- the text of the pooled path-traced kernel.  mirt_kernels.hip includes it twice, and twice more with
+// MIRT_POOL_KERNEL_FRAME = true for the progressive-frame builds (render_pt_pool_frame_kernel, render_pt_pool_tile_frame_kernel):
 //   MIRT_POOL_KERNEL_NAME = render_pt_pool_kernel,      MIRT_POOL_KERNEL_TILE = false   (the default build)
 //   MIRT_POOL_KERNEL_NAME = render_pt_pool_tile_kernel, MIRT_POOL_KERNEL_TILE = true    (MIRT_FLAG_TEXEL_TILES: flat scenes with an
 //       image texture; a texel window per wave behind its pool)
@@ -9,6 +10,7 @@ template <uint32_t THREADS, uint32_t SLOTS, uint32_t MINW, bool COUNT, bool HOSE
 __global__ __launch_bounds__(THREADS, MINW) void MIRT_POOL_KERNEL_NAME(RenderArgs A)
 {
     constexpr bool TILE = MIRT_POOL_KERNEL_TILE;
+    constexpr bool FRAME = MIRT_POOL_KERNEL_FRAME;         // the progressive-frame build: see the strip's epilogue
     using Lay = WavePoolLayout<SLOTS, NQ, GRID, TILE>;
     static_assert(!(GRID && TILE), "the tile build exists for flat scenes");
     static_assert(GRID || !FLATY, "FLATY: a grid one cell high");
@@ -340,7 +342,20 @@ __global__ __launch_bounds__(THREADS, MINW) void MIRT_POOL_KERNEL_NAME(RenderArg
         stamps.flush(A.counters, lane);
         {
             const RenderArgs& AS = per_strip_args();
-            if (AS.accum) {                      // progressive mode: add the exact sums, resolve later
+            if constexpr (FRAME) {               // progressive frame: add, and resolve the updated sums in the same pass.  Lane l owns ONE sum --
+                // channel l % 3 of pixel l / 3 -- so it resolves that one channel (48 lanes busy with one channel each instead of 16
+                // with three); the pixel's lane then collects its three codes from its neighbours.
+                uint32_t code = 0u;
+                if (lane < strip_pixels * 3) {
+                    const unsigned long long sum = AS.accum[3ull * base_pix + lane] + L_acc[lane];
+                    AS.accum[3ull * base_pix + lane] = sum;
+                    code = resolve_channel(sum, AS.sample_begin + AS.spp, AS.flags);
+                }
+                const uint32_t src = (lane < kStripPixels ? lane : 0u) * 3u;
+                const uint32_t r = (uint32_t)__shfl((int)code, (int)src, 64), g = (uint32_t)__shfl((int)code, (int)src + 1, 64),
+                               b = (uint32_t)__shfl((int)code, (int)src + 2, 64);
+                if (lane < strip_pixels) AS.out[base_pix + lane] = pack_rgba(r, g, b);
+            } else if (AS.accum) {                      // progressive mode: add the exact sums, resolve later
                 if (lane < strip_pixels * 3) AS.accum[3ull * base_pix + lane] += L_acc[lane];
             } else if (lane < strip_pixels) {
                 const uint32_t rgba = pack_rgba(resolve_channel(L_acc[lane * 3 + 0], AS.spp, AS.flags),

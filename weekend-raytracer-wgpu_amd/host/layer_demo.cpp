@@ -5,10 +5,13 @@
 //   layer_demo MOON.ppm EARTH.ppm W H SPP OUT.rgba       renders Layer::scene on device 0, writes raw RGBA8
 //   layer_demo --pt MOON.ppm EARTH.ppm W H NUM MAX OUT   path-traced main.rs scene: MAX/NUM progressive frames of
 //                                                        NUM spp (Raytracer::render_frame), writes the final RGBA8
+//   layer_demo --pt ... OUT DEVICES                      the same loop through a node: DEVICES = a comma-separated device list, e.g. 0,0,0
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <vector>
 
 #include "mirt_host.hpp"
 
@@ -29,7 +32,10 @@ int main(int argc, char** argv)
             sc.spheres = { sphere_new({ 0.0f, -500.0f, -1.0f }, 500.0f, 0), sphere_new({ 0.0f, 1.0f, 0.0f }, 1.0f, 3),
                            sphere_new({ -5.0f, 1.0f, 0.0f }, 1.0f, 2),     sphere_new({ 5.0f, 0.8f, 1.5f }, 0.8f, 1),
                            sphere_new({ 5.0f, 1.2f, -1.5f }, 1.2f, 4) };
-            Raytracer rt(sc, rp);
+            std::vector<int> devices;                                   // optional: run the loop on a node of these devices
+            if (argc > 9) for (const char* s = argv[9]; *s; ) { devices.push_back(std::atoi(s)); while (*s && *s != ',') ++s; if (*s) ++s; }
+            const std::unique_ptr<Raytracer> owner(devices.empty() ? new Raytracer(sc, rp) : new Raytracer(sc, rp, devices));
+            Raytracer& rt = *owner;
             std::vector<uint8_t> img;
             int frames = 0;
             while (rt.progress() < 1.0f) { img = rt.render_frame(); ++frames; }

@@ -310,6 +310,26 @@ public:
     {
         check(mirt_node_render_device(node_, &p, d_out_rgba8, out_len, hip_stream));
     }
+    // ---- progressive accumulation: every member owns the exact sums of its part; a frame moves RGBA8 parts only ----
+    void accum_reset(const MirtParams& p) { check(mirt_node_accum_reset(node_, &p)); }
+    // one progressive frame of the band (p.spp further samples; 0 = the mean of what is there), blocking
+    std::vector<uint8_t> accum_frame(const MirtParams& p)
+    {
+        std::vector<uint8_t> out((size_t)mirt_params_out_rows(&p) * p.width * 4);
+        check(mirt_node_accum_frame(node_, &p, out.data(), out.size()));
+        return out;
+    }
+    void accum_frame_device(const MirtParams& p, void* d_out_rgba8, size_t out_len, void* hip_stream = nullptr)
+    {
+        check(mirt_node_accum_frame_device(node_, &p, d_out_rgba8, out_len, hip_stream));
+    }
+    uint32_t accum_samples() const { return mirt_node_accum_samples(node_); }
+    std::vector<uint64_t> accum_read(const MirtParams& p)          // band-row order, pixels x 3
+    {
+        std::vector<uint64_t> out((size_t)mirt_params_out_rows(&p) * p.width * 3);
+        check(mirt_node_accum_read(node_, out.data(), out.size()));
+        return out;
+    }
     MirtContext* context(uint32_t i) const            // borrowed: the node owns it
     {
         MirtContext* c = nullptr;
@@ -329,12 +349,83 @@ private:
 };
 
 // Raytracer — the path-traced mode behind the names of src/raytracer/mod.rs:20-394 (wgpu plumbing
-// omitted).  render_frame() = RenderProgress::next_frame (mod.rs:626-670) + the shader's accumulation.
+// omitted).  render_frame() = RenderProgress::next_frame (mod.rs:626-670) + the shader's accumulation: ONE frame call.
+// With a device LIST the loop runs through a node (mirt_node_accum_*): every frame cut across the members; the images are the same.
 class Raytracer {
 public:
     Raytracer(const Scene& scene, const RenderParams& rp, int device = 0, const MirtSkyState* sky = nullptr)
         : rp_(rp), spheres_(scene.spheres)
     {
+        init(scene, sky);
+        check(mirt_ctx_create(device, &ctx_));
+        upload();
+    }
+    Raytracer(const Scene& scene, const RenderParams& rp, const std::vector<int>& devices, const MirtSkyState* sky = nullptr)
+        : rp_(rp), spheres_(scene.spheres)
+    {
+        init(scene, sky);
+        check(mirt_node_create(devices.data(), (uint32_t)devices.size(), 0u, &node_));
+        upload();
+    }
+    ~Raytracer() { if (ctx_) mirt_ctx_destroy(ctx_); if (node_) mirt_node_destroy(node_); }
+    Raytracer(const Raytracer&) = delete;
+    Raytracer& operator=(const Raytracer&) = delete;
+
+    void set_render_params(const RenderParams& rp)                         // mod.rs:353-388
+    {
+        rp.validate();
+        rp_ = rp;
+        camera_ = gpu_camera_new(rp.camera, rp.viewport_w, rp.viewport_h);
+        check(node_ ? mirt_node_set_camera(node_, &camera_) : mirt_ctx_set_camera(ctx_, &camera_));
+        accumulated_ = -1;                                                 // render_progress.reset()
+    }
+
+    // all max_samples_per_pixel samples in one launch
+    std::vector<uint8_t> render(uint64_t seed = 0, uint32_t flags = 0)
+    {
+        MirtParams p = params(rp_.sampling.max_samples_per_pixel, seed, flags);
+        std::vector<uint8_t> out((size_t)p.width * p.height * 4);
+        check(node_ ? mirt_node_render(node_, &p, out.data(), out.size()) : mirt_ctx_render(ctx_, &p, out.data(), out.size()));
+        return out;
+    }
+
+    // one progressive frame, one call: add num_samples_per_pixel until max_samples_per_pixel (then spp = 0: the mean of what is
+    // there, mod.rs:350), return the estimate
+    std::vector<uint8_t> render_frame(uint64_t seed = 0, uint32_t flags = 0)
+    {
+        MirtParams p = next_frame(seed, flags);
+        std::vector<uint8_t> out((size_t)p.width * p.height * 4);
+        check(node_ ? mirt_node_accum_frame(node_, &p, out.data(), out.size()) : mirt_ctx_accum_frame(ctx_, &p, out.data(), out.size()));
+        accumulated_ += (int)p.spp;
+        return out;
+    }
+    // the same frame into device memory (height x width x 4 bytes), asynchronously on `hip_stream` (nullptr: the context's / node's
+    // own stream): for hosts that draw from device memory.  Two frames in flight: alternate the streams of mirt_ctx_frame_stream
+    // and two framebuffers.
+    void render_frame_device(void* d_out_rgba8, void* hip_stream = nullptr, uint64_t seed = 0, uint32_t flags = 0)
+    {
+        MirtParams p = next_frame(seed, flags);
+        const size_t len = (size_t)p.width * p.height * 4;
+        check(node_ ? mirt_node_accum_frame_device(node_, &p, d_out_rgba8, len, hip_stream)
+                    : mirt_ctx_accum_frame_device(ctx_, &p, d_out_rgba8, len, hip_stream));
+        accumulated_ += (int)p.spp;
+    }
+    float progress() const { return (accumulated_ < 0 ? 0.0f : (float)accumulated_) / (float)rp_.sampling.max_samples_per_pixel; }   // mod.rs:390-393
+    MirtContext* context() const { return ctx_; }      // nullptr when the loop runs on a node
+    MirtNode* node() const { return node_; }
+
+private:
+    // RenderProgress::next_frame: clears after a reset; the params of the frame call to issue now
+    MirtParams next_frame(uint64_t seed, uint32_t flags)
+    {
+        MirtParams p = params(rp_.sampling.num_samples_per_pixel, seed, flags);
+        if (accumulated_ < 0) { check(node_ ? mirt_node_accum_reset(node_, &p) : mirt_ctx_accum_reset(ctx_, &p)); accumulated_ = 0; }
+        if ((uint32_t)accumulated_ + p.spp > rp_.sampling.max_samples_per_pixel) p.spp = 0;
+        return p;
+    }
+    void init(const Scene& scene, const MirtSkyState* sky)
+    {
+        const RenderParams& rp = rp_;
         rp.validate();                                                     // mod.rs:44-47
         for (const Material& m : scene.materials) {                        // mod.rs:160-183 (same (odd, even) swap)
             if (auto* l = std::get_if<Lambertian>(&m)) material_data_.push_back(gpu_material::lambertian(l->albedo, texels_));
@@ -344,47 +435,7 @@ public:
         }
         if (sky) { sky_ = *sky; have_sky_ = true; }
         camera_ = gpu_camera_new(rp.camera, rp.viewport_w, rp.viewport_h);
-        check(mirt_ctx_create(device, &ctx_));
-        upload();
     }
-    ~Raytracer() { if (ctx_) mirt_ctx_destroy(ctx_); }
-    Raytracer(const Raytracer&) = delete;
-    Raytracer& operator=(const Raytracer&) = delete;
-
-    void set_render_params(const RenderParams& rp)                         // mod.rs:353-388
-    {
-        rp.validate();
-        rp_ = rp;
-        camera_ = gpu_camera_new(rp.camera, rp.viewport_w, rp.viewport_h);
-        check(mirt_ctx_set_camera(ctx_, &camera_));
-        accumulated_ = -1;                                                 // render_progress.reset()
-    }
-
-    // all max_samples_per_pixel samples in one launch
-    std::vector<uint8_t> render(uint64_t seed = 0, uint32_t flags = 0)
-    {
-        MirtParams p = params(rp_.sampling.max_samples_per_pixel, seed, flags);
-        std::vector<uint8_t> out((size_t)p.width * p.height * 4);
-        check(mirt_ctx_render(ctx_, &p, out.data(), out.size()));
-        return out;
-    }
-
-    // one progressive frame: add num_samples_per_pixel until max_samples_per_pixel, return the estimate
-    std::vector<uint8_t> render_frame(uint64_t seed = 0, uint32_t flags = 0)
-    {
-        MirtParams p = params(rp_.sampling.num_samples_per_pixel, seed, flags);
-        if (accumulated_ < 0) { check(mirt_ctx_accum_reset(ctx_, &p)); accumulated_ = 0; }
-        if ((uint32_t)accumulated_ + p.spp <= rp_.sampling.max_samples_per_pixel) {
-            check(mirt_ctx_accum_add(ctx_, &p, nullptr));
-            accumulated_ += (int)p.spp;
-        }
-        std::vector<uint8_t> out((size_t)p.width * p.height * 4);
-        check(mirt_ctx_accum_resolve(ctx_, &p, out.data(), out.size()));
-        return out;
-    }
-    float progress() const { return (accumulated_ < 0 ? 0.0f : (float)accumulated_) / (float)rp_.sampling.max_samples_per_pixel; }   // mod.rs:390-393
-
-private:
     MirtParams params(uint32_t spp, uint64_t seed, uint32_t flags) const
     {
         MirtParams p{};
@@ -400,7 +451,13 @@ private:
         sc.materials = material_data_.data(); sc.n_materials = (uint32_t)material_data_.size();
         sc.texels = texels_.data(); sc.n_texels = texels_.size() / 3;
         sc.sky = have_sky_ ? &sky_ : nullptr;
-        check(set_scene_any_size(ctx_, sc));               // a world beyond the LDS budget: MIRT_SCENE_HBM
+        if (node_) {                                       // a world beyond the LDS budget: MIRT_SCENE_HBM
+            int rc = mirt_node_set_scene(node_, &sc);
+            if (rc == MIRT_ERR_SCENE_TOO_LARGE) rc = mirt_node_set_scene_ex(node_, &sc, MIRT_SCENE_HBM);
+            check(rc);
+        } else {
+            check(set_scene_any_size(ctx_, sc));
+        }
     }
     RenderParams rp_;
     std::vector<MirtSphere> spheres_;
@@ -410,6 +467,7 @@ private:
     MirtSkyState sky_{};
     bool have_sky_ = false;
     MirtContext* ctx_ = nullptr;
+    MirtNode* node_ = nullptr;
     int accumulated_ = -1;
 };
 

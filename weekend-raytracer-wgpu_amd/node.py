@@ -80,6 +80,32 @@ class Node:
         default stream, 0, is refused by the library: pass a stream of your own)."""
         check(lib().mirt_node_render_device(self._h, C.byref(params), C.c_void_p(d_ptr), nbytes, _stream_arg(stream)))
 
+    # ---- progressive accumulation: every member owns the exact sums of its part; a frame moves RGBA8 parts only ----
+    def accum_reset(self, params: _abi.MirtParams) -> None:
+        check(lib().mirt_node_accum_reset(self._h, C.byref(params)))
+
+    def accum_frame_device(self, params: _abi.MirtParams, d_out: int, stream: Optional[int] = None, nbytes: Optional[int] = None) -> None:
+        """mirt_node_accum_frame_device: one progressive frame of the band (Context.accum_frame_device on every member, then the
+        node's gather and assembly) into device memory at address `d_out` on member 0's device, ordered on `stream`."""
+        if nbytes is None:
+            nbytes = params_out_rows(params) * params.width * 4
+        check(lib().mirt_node_accum_frame_device(self._h, C.byref(params), C.c_void_p(d_out), nbytes, _stream_arg(stream)))
+
+    def accum_frame(self, params: _abi.MirtParams) -> np.ndarray:
+        """The same frame to host memory (blocking) -> uint8 [rows, width, 4]."""
+        out = np.empty((params_out_rows(params), params.width, 4), dtype=np.uint8)
+        check(lib().mirt_node_accum_frame(self._h, C.byref(params), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def accum_samples(self) -> int:
+        return int(lib().mirt_node_accum_samples(self._h))
+
+    def accum_read(self, params: _abi.MirtParams) -> np.ndarray:
+        """The band's sums in band-row order -> uint64 [rows, width, 3]."""
+        out = np.empty((params_out_rows(params), params.width, 3), dtype=np.uint64)
+        check(lib().mirt_node_accum_read(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
     def context(self, i: int) -> Context:
         """Member i's context (borrowed): stats(), last_kernel(), set_timing()."""
         h = C.c_void_p()

@@ -497,8 +497,12 @@ class Layer:
 
 class Raytracer:
     def __init__(self, scene: Scene, render_params: RenderParams, *, device: int = 0,
-                 sky_state: Optional[_abi.MirtSkyState] = None, reference_stream: bool = False):
-        """`reference_stream=True` makes `render_frame` (and `render`) draw the samples of one frame from ONE RNG
+                 sky_state: Optional[_abi.MirtSkyState] = None, reference_stream: bool = False,
+                 devices: Optional[Sequence[int]] = None):
+        """`devices`: the render loop runs through a Node on those devices (every frame cut across its members, each member keeping
+        the exact sums of its part) instead of one Context on `device`; the images are the same.
+
+        `reference_stream=True` makes `render_frame` (and `render`) draw the samples of one frame from ONE RNG
         stream per pixel, seeded with the frame number -- the reference's initRng / samplePixel (wgsl:498-502,
         105-122) for `num_samples_per_pixel` samples per frame (MirtParams.frame_spp).  The default keeps one stream
         per sample (frame_number = sample + 1), which does not depend on how samples are grouped into frames.
@@ -514,8 +518,10 @@ class Raytracer:
         self.spheres = list(scene.spheres)
         self.camera = GpuCamera.new(render_params.camera, render_params.viewport_size)
         self.sky_state = sky_state
-        self._ctx = Context(device)
+        self._ctx = Node(list(devices)) if devices is not None else Context(device)    # the same calls on either
+        self._on_node = devices is not None
         set_scene_any_size(self._ctx, self.scene_data())           # worlds beyond the LDS budget: MIRT_SCENE_HBM
+        self._frames_queued = 0         # render_frame_device: frame k goes to frame stream k & 1
         self.last_stats: Optional[dict] = None
         self._accumulated = None        # RenderProgress (mod.rs:615-679): None = reset pending
         self.frame_number = 1           # mod.rs:284; advanced by every render_frame call (mod.rs:350), never reset
@@ -536,20 +542,48 @@ class Raytracer:
                            frame_spp=rp.sampling.num_samples_per_pixel if self.reference_stream else 0,
                            frame_begin=frame_begin if self.reference_stream else 0)
 
-    def render_frame(self, *, seed: int = 0, flags: int = 0) -> np.ndarray:
-        """`Raytracer::render_frame` (mod.rs:303-351) without the wgpu draw: add
-        `num_samples_per_pixel` samples per call until `max_samples_per_pixel` is reached
-        (`RenderProgress::next_frame`, mod.rs:626-670), return the current estimate as RGBA8."""
+    def _next_frame(self, seed: int, flags: int) -> _abi.MirtParams:
+        """`RenderProgress::next_frame` (mod.rs:626-670): the params of the frame call to issue now -- `num_samples_per_pixel` samples
+        until `max_samples_per_pixel` is reached, then spp = 0 (show the mean, add nothing: mod.rs:350).  Clears the sums first
+        after a reset."""
         smp = self.render_params.sampling
         if self._accumulated is None:                          # first frame after a reset: clear
             self._frame_begin = self.frame_number - 1          # this accumulation's frames are frame_number, frame_number + 1, ...
             self._ctx.accum_reset(self._params(smp.num_samples_per_pixel, seed, flags))
             self._accumulated = 0
-        if self._accumulated + smp.num_samples_per_pixel <= smp.max_samples_per_pixel:
-            self._ctx.accum_add(self._params(smp.num_samples_per_pixel, seed, flags))
-            self._accumulated += smp.num_samples_per_pixel
+        spp = smp.num_samples_per_pixel if self._accumulated + smp.num_samples_per_pixel <= smp.max_samples_per_pixel else 0
+        return self._params(spp, seed, flags)
+
+    def _frame_issued(self, params: _abi.MirtParams) -> None:
+        self._accumulated += params.spp
         self.frame_number += 1                                 # mod.rs:350: also when the accumulation was complete already
-        return self._ctx.accum_resolve(self._params(smp.num_samples_per_pixel, seed, flags))
+
+    def render_frame(self, *, seed: int = 0, flags: int = 0) -> np.ndarray:
+        """`Raytracer::render_frame` (mod.rs:303-351) without the wgpu draw: ONE frame call (one kernel launch) adds
+        `num_samples_per_pixel` samples and returns the current estimate as RGBA8; once `max_samples_per_pixel` is reached the
+        call adds nothing and returns the mean."""
+        params = self._next_frame(seed, flags)
+        img = self._ctx.accum_frame(params)
+        self._frame_issued(params)
+        return img
+
+    def render_frame_device(self, d_out: int, stream: Optional[int] = None, *, seed: int = 0, flags: int = 0) -> int:
+        """The same frame into device memory at address `d_out` (height x width x 4 bytes), asynchronously: for hosts that draw
+        from device memory.  Returns the stream handle the frame is ordered on: wait on it before reading `d_out`.
+        On a context `stream=None` alternates between its two frame streams (mirt_ctx_frame_stream), so that a host with two
+        framebuffers keeps two frames in flight: pass framebuffer k & 1 for call k.  On a node the caller passes a stream of its
+        own on member 0's device (the node's own stream has no handle to wait on): `stream=None` raises ValueError."""
+        if self._on_node:
+            if stream is None:
+                raise ValueError("render_frame_device on a node needs a stream of the caller's (on member 0's device) to wait on")
+        elif stream is None:
+            stream = self._ctx.frame_stream(self._frames_queued & 1)
+        params = self._next_frame(seed, flags)
+        self._ctx.accum_frame_device(params, d_out, stream)
+        if not self._on_node:
+            self._frames_queued += 1
+        self._frame_issued(params)
+        return stream
 
     def progress(self) -> float:                               # mod.rs:390-393
         return (self._accumulated or 0) / float(self.render_params.sampling.max_samples_per_pixel)
@@ -571,7 +605,7 @@ class Raytracer:
         `reference_stream` (one stream per sample)."""
         params = self._params(self.render_params.sampling.max_samples_per_pixel, seed, flags, frame_begin=frame_begin)
         img = self._ctx.render(params)
-        self.last_stats = self._ctx.stats()
+        self.last_stats = self._ctx.stats()                        # (a node: its MirtNodeStats)
         return img
 
     def close(self) -> None:
