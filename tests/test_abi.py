@@ -94,18 +94,10 @@ from helpers import bimodal_soup  # noqa: E402
 
 
 def _entries_at(cs, rs, factor):
-    """Cell entries the binning of csrc/mirt_api.hip::build_grid produces at `factor` median radii (same arithmetic, in numpy)."""
-    import numpy as np
-    cs, rs = cs.astype(np.float64), rs.astype(np.float64)
-    cell = factor * np.sort(rs)[len(rs) // 2]
-    lo, hi = (cs - rs[:, None]).min(0), (cs + rs[:, None]).max(0)
-    while np.prod(np.maximum(1, np.ceil((hi - lo) / cell + 1e-6))) > 4096:
-        cell *= 1.26
-    dims = np.maximum(1, np.ceil((hi - lo) / cell + 1e-6)).astype(int)
-    eps = 1e-3 * cell
-    c0 = np.clip(np.floor((cs - rs[:, None] - eps - lo) / cell), 0, dims - 1)
-    c1 = np.clip(np.floor((cs + rs[:, None] + eps - lo) / cell), 0, dims - 1)
-    return int(np.prod(c1 - c0 + 1, axis=1).sum())
+    """Cell entries the binning of csrc/mirt_api.hip::build_grid produces at `factor` median radii (the same arithmetic in numpy:
+    tests/grid_rounding.py, with the enlargement that covers the rounding of the sphere test and of the walk)."""
+    from grid_rounding import binning
+    return binning(cs, rs, factor)["n_entries"]
 
 
 def test_grid_plan_of_the_rtiow_scene():

@@ -130,33 +130,13 @@ def test_bvh_against_device_flat_scan(hctx, n, w, h, spp, band):
 
 # 4. adversarial geometry, against the flat scan and the oracle
 def _adversarial():
+    """The worlds of tests/grid_rounding.py::adversarial_worlds at their HBM size: 1 000 copies of one sphere (the lowest index must
+    win), a tangent 13^3 lattice seen along an axis and obliquely, a camera inside a big sphere, and rays grazing r = 1e-3 spheres at
+    distance 1e3 with zero-radius and non-finite spheres among them.  The LDS grid builds are held to the same definitions
+    (test_gpu_grid_rounding.py)."""
+    from grid_rounding import adversarial_worlds
     mats, tex = field_materials()
-    out = []
-    # 1 000 copies of one sphere with different materials: the lowest index must win
-    k = 1000
-    out.append(("copies", sphere_array(np.tile([[0.0, 0.0, -3.0]], (k, 1)), np.full(k, 0.7), np.arange(k) % len(mats)),
-                (0, 0, 1), (0, 0, -3), 60))
-    # a tangent lattice: spheres of radius 0.5 on a unit grid, boxes sharing faces, seen along an axis (zero ray components)
-    g = np.arange(-6, 7, dtype=np.float64)
-    X, Y, Z = np.meshgrid(g, g, g - 10, indexing="ij")
-    lat = np.stack([X.ravel(), Y.ravel(), Z.ravel()], 1)
-    out.append(("lattice axis", sphere_array(lat, np.full(len(lat), 0.5), np.arange(len(lat)) % len(mats)), (0, 0, 8), (0, 0, -10), 40))
-    out.append(("lattice oblique", sphere_array(lat, np.full(len(lat), 0.5), np.arange(len(lat)) % len(mats)), (9, 7, 5), (0, 0, -10), 40))
-    # a camera inside a big sphere, small ones around it
-    rng = np.random.default_rng(9)
-    cen = np.concatenate([[[0, 0, 0]], rng.uniform(-3, 3, (300, 3))])
-    rad = np.concatenate([[5.0], rng.uniform(0.05, 0.3, 300)])
-    out.append(("inside", sphere_array(cen, rad, rng.integers(0, len(mats), 301)), (0.1, 0.2, 0.3), (1, 0, -2), 70))
-    # rays grazing r = 1e-3 spheres at distance ~1e3, zero-radius and non-finite spheres among them
-    cen = np.concatenate([rng.uniform(-40, 40, (2000, 2)), np.full((2000, 1), -1000.0)], 1)[:, [0, 1, 2]]
-    rad = np.full(2000, 1e-3)
-    rad[::7] = 0.0
-    cen[5] = [np.inf, 0, -1000]
-    cen[11] = [np.nan, 1, -1000]
-    rad[17] = np.inf
-    rad[23] = np.nan
-    out.append(("grazing", sphere_array(cen, rad, rng.integers(0, len(mats), 2000)), (0, 0, 0), (0, 0, -1000), 4.5))
-    return out, mats, tex
+    return [(name, sphere_array(cen, rad, mat), eye, at, vfov) for name, cen, rad, mat, eye, at, vfov in adversarial_worlds(lattice_half=6)], mats, tex
 
 
 @pytest.mark.parametrize("case", range(5))

@@ -130,14 +130,49 @@ std::vector<unsigned char> build_grid(const MirtSphere* sph, uint32_t n, double 
     // table outgrows LDS: 128-slot pools); fewer tests per ray against more cells per ray (profiles/r03_c5_ab.txt blocks 4 and 7)
     const double cell_factor = cell_factor_knob > 0.0 ? cell_factor_knob : 2.5;   // mirt_ctx_set_scene passes the factor it settles on
     double cell = cell_factor * r_med;
+    // What the enlargement `eps` of the binning must absorb (the argument is written out above GridLds in mirt_kernels.hip):
+    //   e_disc  the rounding of the SPHERE TEST: the flat scan reports a hit at a point up to sqrt(r^2 + K u L^2) from the centre of a
+    //           sphere (c, r), L = |o - c| + |r|, K u = 35 * 2^-24.  sqrt(r^2 + x) - r falls as r grows, so the smallest binned |r|
+    //           bounds it for every binned sphere, for every ray with L <= L_safe.  L_safe = kGridSafeReach x R_g covers the scene's
+    //           own extent and an eye next to it (R_g: radius of a sphere around all binned spheres); rays from farther away are
+    //           recognised by their origin and do not rely on the binning (GridHeader.guard).  e_disc is held to a quarter cell --
+    //           tiny spheres in coarse cells -- by shrinking L_safe instead.
+    //   e_walk  the rounding of the WALK: cell faces fma(i, cell, org) and entry points are rounded at the size M of the scene's
+    //           coordinates (2 u M each), a crossing parameter carries a few u, and `tx += ddx` adds one u per step, all relative to
+    //           a parameter whose point lies within L of the origin: 2^-22 M + 2^-23 (steps + 16) L_safe, plus the 1e-3 cell of old.
+    // The grid's box is grown by eps as well, so a reported hit point always lies INSIDE the box the walk is clipped to.
+    constexpr double kDiscErr = 35.0 * 0x1p-24, kGridSafeReach = 2.5;
+    double r_min = 1e300, cg[3], rg2 = 0.0, coord_max = 0.0;
+    for (uint16_t i : small) r_min = std::min(r_min, (double)radii[i]);
+    for (int k = 0; k < 3; ++k) {
+        cg[k] = 0.5 * (lo[k] + hi[k]);
+        rg2 += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]);
+        coord_max = std::max(coord_max, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+    }
+    const double rg = std::sqrt(rg2);
     uint32_t dims[3];
+    double eps = 0.0, l_safe = 0.0, glo[3], ghi[3];
     for (;;) {
+        l_safe = kGridSafeReach * rg;
+        double e_disc = std::sqrt(r_min * r_min + kDiscErr * l_safe * l_safe) - r_min;
+        if (e_disc > 0.25 * cell) {
+            e_disc = 0.25 * cell;
+            l_safe = std::sqrt(((r_min + e_disc) * (r_min + e_disc) - r_min * r_min) / kDiscErr);
+        }
         uint64_t total = 1;
-        for (int k = 0; k < 3; ++k) { dims[k] = (uint32_t)std::max(1.0, std::ceil((hi[k] - lo[k]) / cell + 1e-6)); total *= dims[k]; }
+        for (int pass = 0; pass < 2; ++pass) {                    // the step count of e_walk comes from the dims: settle them in two passes
+            const double steps = pass ? (double)dims[0] + dims[1] + dims[2] : 3.0 * 16.0;
+            eps = 1e-3 * cell + 0x1p-22 * coord_max + 0x1p-23 * (steps + 16.0) * l_safe + e_disc;
+            total = 1;
+            for (int k = 0; k < 3; ++k) {
+                glo[k] = lo[k] - eps; ghi[k] = hi[k] + eps;
+                dims[k] = (uint32_t)std::max(1.0, std::ceil((ghi[k] - glo[k]) / cell + 1e-6)); total *= dims[k];
+            }
+        }
         if (total <= mirt::kGridMaxCells) break;
         cell *= 1.26;
     }
-    const double eps = 1e-3 * cell;                               // enlargement that makes the binning conservative
+    for (int k = 0; k < 3; ++k) lo[k] = glo[k];                   // the grid's lower corner: the spheres' box grown by eps
     const uint32_t ncells = dims[0] * dims[1] * dims[2];
     std::vector<std::vector<uint16_t>> lists(ncells);
     for (uint16_t i : small) {
@@ -175,6 +210,11 @@ std::vector<unsigned char> build_grid(const MirtSphere* sph, uint32_t n, double 
     h.off_cells = (uint32_t)bytes;                                // two u32 per cell: first further item | count << 16, id0 | id1 << 16
     bytes = (bytes + 8 * (size_t)ncells + 15) & ~size_t(15);
     h.n_entries = (uint32_t)n_entries;
+    h.n_spheres = n;
+    const double far_d = l_safe / 1.02 - rg;                      // 2 %: the kernels' float arithmetic on |o - C_g|^2, R_g rounded below
+    for (int k = 0; k < 3; ++k) h.guard[k] = (float)cg[k];
+    h.guard[3] = far_d > 0.0 ? (float)(far_d * far_d) : -1.0f;
+    h.bound_r = (float)(rg * 1.0001);
     h.inv_dim_x = 1.0f / (float)dims[0];
     h.inv_dim_xy = 1.0f / (float)(dims[0] * dims[1]);
     h.off_big_recs = (uint32_t)bytes;

@@ -50,7 +50,8 @@ static_assert(sizeof(ShadeRec) == 64, "ShadeRec is one 64-byte line");
 
 // Uniform grid over the small spheres of a many-sphere scene (>= kGridMinSpheres): the nearest-hit scan
 // visits only the cells a ray crosses (3D-DDA) plus a short list of "big" spheres.  The grid is
-// CONSERVATIVE (every sphere is listed in all cells its slightly enlarged bounding box touches) and the
+// CONSERVATIVE (every sphere is listed in all cells its enlarged bounding box touches; the enlargement covers the rounding of
+// the walk and, for ray origins within GridHeader.guard, of the sphere test -- mirt_kernels.hip above GridLds) and the
 // hit rule breaks ties by sphere index, so the result is identical to the reference's flat scan.
 // Layout of the blob (all of it is staged into LDS; the kernels of a grid build read NO other sphere data from LDS):
 //   GridHeader | big ids [n_big] u16 | FURTHER item ids [n_items] u16 (a cell's third, fourth ... sphere, ascending)
@@ -79,7 +80,14 @@ struct GridHeader {
     uint32_t n_entries;     // cell entries in total (a sphere counts once per cell that lists it)
     float    inv_dim_x;     // 1 / dims[0] and 1 / (dims[0] * dims[1]), IEEE quotients from the host: a parked walk's linear cell index is
     float    inv_dim_xy;    // taken apart with them (floor((n + 0.5) * inv) == n / d exactly for n, d <= 8192: tests/test_abi.py)
-    uint32_t pad_;
+    uint32_t n_spheres;     // records behind off_recs (the far-origin scan of the strip kernels, see `guard`)
+    // The far-origin guard (mirt_kernels.hip: "what the binning absorbs").  The binning enlargement covers the rounding of the sphere
+    // test only for rays whose origin lies within `L_safe - R_g` of the centre C_g of a sphere (C_g, R_g) around every binned sphere:
+    // guard = {C_g, (L_safe / 1.02 - R_g)^2, or -1 when that difference is not positive}; a ray with |o - C_g|^2 above guard[3]
+    // (or NaN) does not trust the walk.  bound_r = R_g.
+    float    guard[4];
+    float    bound_r;
+    uint32_t pad_[3];
 };
 static_assert(sizeof(GridHeader) % 16 == 0, "GridHeader is staged with 16-byte copies");
 #ifndef MIRT_DISPENSER_STRIDE

@@ -782,7 +782,25 @@ struct Stamps {
 // possibly several times, so the update rule carries the tie-break explicitly.  A cell walk may
 // stop as soon as closest <= the parameter at which the ray leaves the current cell: any sphere
 // with a smaller f is intersected inside a cell already visited, and is listed there because every
-// sphere is registered in all cells its (slightly enlarged) bounding box overlaps.
+// sphere is registered in all cells its enlarged bounding box overlaps.
+//
+// What the binning absorbs, and what it does not.  "Intersected" above means: by the ARITHMETIC of test_sphere, not by geometry.
+// With u = 2^-24 and L = |o - c| + |r|, the computed disc carries an error of up to 15 u A L^2 and the computed root f^ a residual
+// A g(f^) <= 35 u A L^2 (the derivation stands next to kBvhSlack below), so the flat scan reports hits at points P = o + f^ d up to
+// sqrt(r^2 + 35 u L^2) from the centre: a ray that passes 0.25 beside a sphere of radius 1e-3 at distance 1e3 "hits" it, and the
+// exact 64-bit sums count that hit.  The builder (mirt_api.hip: build_grid) therefore enlarges every binned box, and the grid's own
+// box, by eps = e_disc + e_walk:
+//   e_disc = sqrt(r_min^2 + 35 u L_safe^2) - r_min covers P for every binned sphere and every ray with L <= L_safe;
+//   e_walk covers the rounding of the walk itself (cell faces and entry points rounded at the size of the coordinates, crossing
+//          parameters a few u off, one more u per `tx += ddx`), which only steers the walk.
+// P then lies in a cell that lists the sphere, inside the box the walk is clipped to, and the walk reaches that cell unless a
+// nearer hit ended it -- the flat scan's result.  A ray whose origin is farther from the binned spheres than L_safe allows (a
+// telephoto eye, a bounce off a distant part of a ground sphere) is NOT covered by eps.  Such a ray is recognised by its origin
+// alone (GridHeader.guard: |o - C_g|^2 above (L_safe / 1.02 - R_g)^2, hence a pure function of the ray) and does not walk: if it
+// can reach the box grown by E = 2^-8 L at all (far_ray_reaches, the BVH's lateral slack: 2.6 x sqrt(35 u) L) it tests EVERY
+// binned sphere -- the strip kernels scan the records, the pooled kernel sweeps the cells by linear index in the instalments of
+// its walk -- and otherwise no binned sphere: P would lie in that grown box.  Repeated tests of one sphere are harmless
+// (test_sphere's explicit (f, id) tie-break).  The always-tested list needs none of this.
 struct GridLds {
     const GridHeader*     h;
     const unsigned short* big;        // ids of the big spheres
@@ -881,6 +899,30 @@ MIRT_DEV void test_big_spheres(const GridLds& G, f3 ro, f3 rd, float a, float in
     for (; j < n_big; ++j) test_sphere<COUNT>(G.big_recs[j], G.big[j], ro, rd, a, inv_a, alive, closest, best, work);
 }
 
+// Far-origin rays (GridHeader.guard; the argument stands above GridLds): can the ray produce a computed hit on a binned sphere at all?
+// Such a hit's point lies within E of the grid's box [lo, hi], E = 2^-8 x 1.01 x (|o - C_g| + R_g).  Slab test of the grown box with a
+// relative 2^-9 where a few u are needed; every comparison is written so that a NaN answers "yes".
+constexpr float kFarSlack = 0x1p-8f * 1.01f;
+MIRT_DEV bool far_ray_reaches(f3 ro, f3 rd, f3 lo, f3 hi, float dist2, float bound_r)
+{
+    const float E = kFarSlack * (__builtin_sqrtf(dist2) + bound_r);
+    const float o[3] = { ro.x, ro.y, ro.z }, d[3] = { rd.x, rd.y, rd.z };
+    const float lo3[3] = { lo.x - E, lo.y - E, lo.z - E }, hi3[3] = { hi.x + E, hi.y + E, hi.z + E };
+    float tn = 0.0f, tf = 3.0e38f;
+    bool miss = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const bool nz = d[k] != 0.0f;
+        const float inv = __builtin_amdgcn_rcpf(nz ? d[k] : 1.0f);
+        const float ta = (lo3[k] - o[k]) * inv, tb = (hi3[k] - o[k]) * inv;
+        const float t_lo = (ta < tb) ? ta : tb, t_hi = (ta < tb) ? tb : ta;
+        tn = (nz & (t_lo > tn)) ? t_lo : tn;
+        tf = (nz & (t_hi < tf)) ? t_hi : tf;
+        miss = miss | (!nz & ((o[k] < lo3[k]) | (o[k] > hi3[k])));
+    }
+    return !miss & !(tf < 0.0f) & !(tn > fma_(tf, 0x1p-9f, tf));
+}
+
 // A cell's items from its table entry `cw` (count = 0 for lanes that are not walking): the first two ids came with the entry, so their
 // records are ONE round trip away (entry -> records) instead of two (entry -> ids -> records) -- and most cells list at most two
 // spheres (RTIOW: 0.84 tests per visited cell).  Further items as before: ids, then records, two per round trip.
@@ -958,6 +1000,18 @@ MIRT_DEV int nearest_hit_grid(const SceneLds& S, const GridLds& G, f3 ro, f3 rd,
     }
     // a little slack on both ends: the walk below is clamped to the grid anyway
     bool walking = inside && (tmin <= tmax) && (tmin < closest);
+    // far-origin rays do not trust the walk (see above GridLds): they scan every record, if they can reach the grid at all
+    const float4 gd = *reinterpret_cast<const float4*>(H.guard);
+    const f3 qc = ro - mk(gd.x, gd.y, gd.z);
+    const float dist2 = dot(qc, qc);
+    const bool far = alive & !(dist2 <= gd.w);
+    if (ballot_(far)) {
+        const bool scan = far && far_ray_reaches(ro, rd, org, hi, dist2, H.bound_r);
+        walking = walking & !far;
+        const uint32_t n_rec = __builtin_amdgcn_readfirstlane(H.n_spheres);
+        if (ballot_(scan))
+            for (uint32_t i = 0; i < n_rec; ++i) test_sphere<COUNT>(G.recs[i], i, ro, rd, a, inv_a, scan, closest, best, work);
+    }
     const f3 p0 = fma3(tmin, rd, ro);
     int cx = (int)((p0.x - org.x) * inv_cell.x), cy = 0, cz = (int)((p0.z - org.z) * inv_cell.z);
     cx = cx < 0 ? 0 : (cx >= dx ? dx - 1 : cx);
@@ -1016,7 +1070,10 @@ MIRT_DEV int nearest_hit_grid(const SceneLds& S, const GridLds& G, f3 ro, f3 rd,
 // the unfinished paths instead of idling the finished lanes (36 % lane use in the un-cut walk of nearest_hit_grid).
 // A resumed instalment recomputes the per-axis crossing parameters from the cell index with the formula the fresh
 // walk starts from; the cells visited may differ from the uncut walk's in the last bit of a crossing parameter,
-// which the conservative binning absorbs exactly as it absorbs the rounding of `tx += ddx` (see GridLds above).
+// which the conservative binning absorbs exactly as it absorbs the rounding of `tx += ddx` (e_walk, see GridLds above).
+// Far-origin rays (GridHeader.guard, same place) SWEEP the cells 0, 1, 2 ... by linear index instead of walking: the parked state
+// is the same 16-bit index, the guard is a function of the ray's origin alone and is recomputed by every instalment, and the
+// other lanes' walks do not wait for the sweep -- it is cut and re-queued like any long walk.
 
 template <bool COUNT, bool FLATY>
 MIRT_DEV void grid_walk(const SceneLds& S, const GridLds& G, f3 ro, f3 rd, bool active, bool resume /* wave-uniform */, uint32_t budget,
@@ -1028,10 +1085,11 @@ MIRT_DEV void grid_walk(const SceneLds& S, const GridLds& G, f3 ro, f3 rd, bool 
     const f3 org = GC.org, cell = GC.cell;                 // the header's fields: registers (GridConsts), not LDS reads per step
     const int dx = GC.dx, dy = GC.dy, dz = GC.dz;
     const float kHuge = 3.0e38f;
-    // The crossing parameters only STEER the walk (which cells, when to stop); the hit itself is decided by the exact
-    // sphere tests.  An error of a few ulp in them is absorbed by the conservative binning (cells are enlarged by
-    // 1e-3 cell, GridLds above) exactly like the rounding of `tx += ddx`, so the hardware reciprocal (1 ulp, one
-    // instruction, no range guard) is enough here; every build and the resumed instalments use the same one.
+    // The crossing parameters only STEER the walk (which cells, when to stop); the hit itself is decided by the
+    // sphere tests.  An error of a few ulp in them is absorbed by the conservative binning (the e_walk part of the
+    // enlargement, GridLds above) exactly like the rounding of `tx += ddx`, so the hardware reciprocal (1 ulp, one
+    // instruction, no range guard) is enough here; every build and the resumed instalments use the same one.  The rounding
+    // of the sphere tests themselves is the e_disc part, which holds for the rays the guard below lets walk.
     const f3 inv_d = mk(rd.x != 0.0f ? __builtin_amdgcn_rcpf(rd.x) : kHuge, rd.y != 0.0f ? __builtin_amdgcn_rcpf(rd.y) : kHuge,
                         rd.z != 0.0f ? __builtin_amdgcn_rcpf(rd.z) : kHuge);
     const f3 hi = GC.hi;
@@ -1051,6 +1109,10 @@ MIRT_DEV void grid_walk(const SceneLds& S, const GridLds& G, f3 ro, f3 rd, bool 
             inside = inside & (nz | ((o[k] >= lo3[k]) & (o[k] <= hi3[k])));
         }
     }
+    const float4 gd = *reinterpret_cast<const float4*>(G.h->guard);       // one broadcast LDS read per instalment
+    const f3 qc = ro - mk(gd.x, gd.y, gd.z);
+    const float dist2 = dot(qc, qc);
+    const bool far = active & !(dist2 <= gd.w);                             // the same answer in every instalment of one ray
     int cx, cy, cz;
     if (!resume) {
         closest = kMaxT;
@@ -1072,6 +1134,11 @@ MIRT_DEV void grid_walk(const SceneLds& S, const GridLds& G, f3 ro, f3 rd, bool 
         cz = cz < 0 ? 0 : (cz >= dz ? dz - 1 : cz);
         if constexpr (FLATY) cy = 0;
         else { cy = (int)((p0.y - org.y) * inv_cell.y); cy = cy < 0 ? 0 : (cy >= dy ? dy - 1 : cy); }
+        if (ballot_(far)) {                                                  // rare: the sweep starts at cell 0, if the ray can reach the grid at all
+            const bool reach = far_ray_reaches(ro, rd, org, hi, dist2, G.h->bound_r);
+            walking = far ? reach : walking;
+            cx = far ? 0 : cx; cy = far ? 0 : cy; cz = far ? 0 : cz;
+        }
     } else {
         walking = active;
         // the parked LINEAR index taken apart: floor((n + 0.5) * (1 / d)) == n / d exactly for n, d <= 8192
@@ -1096,6 +1163,9 @@ MIRT_DEV void grid_walk(const SceneLds& S, const GridLds& G, f3 ro, f3 rd, bool 
     // linear cell index, advanced with the walk (one multiply-add pair per WALK instead of per cell; the strides are selects)
     uint32_t cidx = FLATY ? (uint32_t)(cz * dx + cx) : (uint32_t)((cz * dy + cy) * dx + cx);
     const int nxy_ = FLATY ? dx : dx * dy;
+    const uint32_t ncells = (uint32_t)(nxy_ * dz);
+    cidx = (far & resume) ? cellp : cidx;
+    tmax = far ? kMaxT : tmax;
     const int stride_y = sy > 0 ? dx : -dx, stride_z = sz > 0 ? nxy_ : -nxy_;
     if (resume) stamps.mark(7); else stamps.mark(4);
     // (Letting an instalment run past its budget while most lanes are still walking was measured: the fuller instalments gain 1-2 %,
@@ -1112,6 +1182,7 @@ MIRT_DEV void grid_walk(const SceneLds& S, const GridLds& G, f3 ro, f3 rd, bool 
         const uint2 cw_now = cw;
         float t_exit;
         bool inside_grid;
+        const uint32_t cidx_sweep = cidx + 1u;
         if constexpr (FLATY) {
             // A grid ONE cell high (spheres on a ground plane: RTIOW): the walk is two-dimensional.  The y slab ends the walk through
             // tmax -- the clip's far parameter on y is the very expression the 3-D walk's `ty` starts from (cy = 0, dims[1] = 1), so
@@ -1133,6 +1204,10 @@ MIRT_DEV void grid_walk(const SceneLds& S, const GridLds& G, f3 ro, f3 rd, bool 
             tx = ax ? tx + ddx : tx; ty = ay ? ty + ddy : ty; tz = az ? tz + ddz : tz;
             inside_grid = ((uint32_t)cx < (uint32_t)dx) & ((uint32_t)cy < (uint32_t)dy) & ((uint32_t)cz < (uint32_t)dz);
         }
+        // far-origin lanes sweep: the next linear index, to the last cell, whatever the hits so far
+        cidx = far ? cidx_sweep : cidx;
+        inside_grid = far ? (cidx_sweep < ncells) : inside_grid;
+        t_exit = far ? -1.0f : t_exit;
         const bool may_go_on = walking & inside_grid & !(t_exit > tmax);
         if (it + 1 < budget) cw = G.cells[may_go_on ? cidx : 0u];                // in flight while the tests below run
         test_cell_entry<COUNT>(G, cw_now, count, ro, rd, a, inv_a, closest, best, work);
@@ -1443,9 +1518,13 @@ constexpr uint32_t kCandBytes = 48;       // u16 ids [kMaxCand] | u32 count (kNo
 // focal plane, |F - Fc| <= delta (Fc its centre): P(t) = O + t (F - O) = eye + t (Fc - eye) + w with |w| <= t (delta + R) + R.
 // With a = Fc - eye, D = |a|, and for a sphere (c, r): s = (c - eye) . a / D, d = distance of c from the axis.  A hit needs
 // |c - P(t)| <= r for some t >= 0, hence |s - t D| <= r + R + t g and d <= r + R + t g with g = delta + R; the first gives
-// t <= tmax = (s + r + R) / (D - g) (and s + r + R >= 0), the second then d <= r + R + tmax g.  Everything is evaluated with slack
-// (2 % on g, 5 % + 0.01 + 0.001 |c - eye| on the bound) that dwarfs the rounding of these few float operations, and every
-// comparison is written so that a NaN keeps the sphere: the list is a superset by construction.
+// t <= tmax = (s + r + R) / (D - g) (and s + r + R >= 0), the second then d <= r + R + tmax g.  That is geometry; the hits the flat
+// scan COUNTS are those test_sphere computes, at points up to sqrt(r^2 + 35 u L^2) <= r + 2^-9.4 L from the centre, L = |O - c| + r
+// <= |c - eye| + R + r (the bound next to kBvhSlack).  With r' = r + 2^-9.4 L in place of r both conditions grow by at most
+// 2^-9.4 L (1 + g / (D - g)) <= 1.34 x 2^-9.4 L (g < D / 4).  Everything is evaluated with slack (2 % on g, 5 % + 0.01 +
+// 2^-8 (|c - eye| + r + R) on the bound: twice that growth, and the cancellation in d = sqrt(|q|^2 - s^2), up to 2^-11 |q|, on
+// top) that also dwarfs the rounding of these few float operations, and every comparison is written so that a NaN keeps the
+// sphere: the list is a superset by construction.
 MIRT_DEV uint32_t strip_candidates(const RenderArgs& AP, const SceneLds& S, uint32_t x0, uint32_t n, uint32_t y, unsigned short* ids, uint32_t lane)
 {
     const f3 eye = mk(S.cam[0], S.cam[1], S.cam[2]), hor = mk(S.cam[4], S.cam[5], S.cam[6]), ver = mk(S.cam[8], S.cam[9], S.cam[10]);
@@ -1475,7 +1554,7 @@ MIRT_DEV uint32_t strip_candidates(const RenderArgs& AP, const SceneLds& S, uint
         const float d2 = qq - s * s;
         const float dperp = __builtin_sqrtf(d2 > 0.0f ? d2 : 0.0f);
         const float len_q = __builtin_sqrtf(qq);
-        const float margin = 0.01f + 1.0e-3f * len_q;
+        const float margin = 0.01f + kFarSlack * (len_q + r + R);                 // the hits test_sphere COMPUTES (see the comment above)
         const float reach = s + r + R;
         const float tmax = (reach > 0.0f ? reach : 0.0f) * inv_den;
         const float bound = 1.05f * (r + R + tmax * g) + margin;
