@@ -346,9 +346,15 @@ int mirt_ctx_set_scene(MirtContext* ctx, const MirtScene* scene);
  *   parity mode                 the layer.rs flat scan with the spheres in device memory (render_parity_hbm_kernel).
  * The BVH: binned SAH over the sphere centres, binary, leaves of at most MIRT_BVH_MAX_LEAF spheres, depth at most MIRT_BVH_MAX_DEPTH by
  * construction; up to MIRT_BVH_MAX_ALWAYS spheres (those larger than MIRT_BVH_BIG_RADII median radii, and those whose box is not finite)
- * are tested for every ray instead.  Deterministic, built on at most 16 host threads. */
+ * are tested for every ray instead.  Deterministic, built on at most 16 host threads.
+ * MIRT_SCENE_HBM | MIRT_SCENE_BVH_DEVICE builds the tree on the device instead (the flag alone: MIRT_ERR_BAD_MODE): the same
+ * always-tested list (host, O(n)), the other spheres sorted by the Morton code of their centre and split top-down, level by level, where
+ * the code's highest differing bit flips -- at the object median where the codes are equal or the split would break the depth limit.
+ * Same node layout, leaf size and depth limit, the host formula's boxes, so the image is byte-identical to the host tree's; the
+ * tree is a different one and culls somewhat less.  Deterministic; synchronous like every set_scene. */
 enum {
-    MIRT_SCENE_HBM = 1u << 0                      /* mirt_ctx_set_scene_ex / mirt_node_set_scene_ex flags */
+    MIRT_SCENE_HBM        = 1u << 0,              /* mirt_ctx_set_scene_ex / mirt_node_set_scene_ex flags */
+    MIRT_SCENE_BVH_DEVICE = 1u << 1               /* only together with MIRT_SCENE_HBM: build the BVH on the device */
 };
 #define MIRT_SCENE_HBM_MAX_SPHERES (1u << 24)
 #define MIRT_BVH_MAX_DEPTH  32                    /* levels below the root; sizes the kernels' traversal stacks */
@@ -367,6 +373,20 @@ typedef struct MirtBvhPlan {
     uint64_t device_bytes;
 } MirtBvhPlan;
 int mirt_bvh_plan(const MirtSphere* spheres, uint32_t n_spheres, MirtBvhPlan* out);
+/* The tree a context holds (either builder): its counts as mirt_bvh_plan reports them (for a host-built tree: equal to mirt_bvh_plan of
+ * the same spheres), the root reference, and the traversal bounds.  MIRT_ERR_NO_SCENE without a MIRT_SCENE_HBM scene. */
+typedef struct MirtBvhInfo {
+    MirtBvhPlan plan;            /* of the tree in the context (either builder) */
+    uint32_t    root;
+    uint32_t    built_on_device;
+    float       centre[3], radius, r_max;
+} MirtBvhInfo;
+int mirt_ctx_bvh_info(MirtContext* ctx, MirtBvhInfo* out);
+/* Copies the tree to the host: plan.n_nodes nodes of 64 bytes {left box min[3] max[3], right box min[3] max[3], left, right, 2 x u32 pad}
+ * (a reference with bit 31 set is a leaf: bits 24..30 = sphere count, bits 0..23 = first record), 4 floats {centre, r * r} per sphere and
+ * the original index of every record (always-tested list first).  Blocking; meant for tests, like mirt_ctx_accum_read.
+ * MIRT_ERR_OUT_BUFFER if a buffer is too small (nodes_bytes in bytes, recs_len in floats, ids_len in entries). */
+int mirt_ctx_bvh_read(MirtContext* ctx, void* nodes, size_t nodes_bytes, float* recs, size_t recs_len, uint32_t* ids, size_t ids_len);
 
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by

@@ -174,9 +174,23 @@ pub struct MirtBvhPlan {
     pub device_bytes: u64,
 }
 
+/// `mirt_ctx_bvh_info`: the tree a context holds (either builder), its root reference and the traversal bounds.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtBvhInfo {
+    pub plan: MirtBvhPlan,
+    pub root: u32,
+    pub built_on_device: u32,
+    pub centre: [f32; 3],
+    pub radius: f32,
+    pub r_max: f32,
+}
+
 /// `mirt_ctx_set_scene_ex` / `mirt_node_set_scene_ex` flags: the scene's tables in device memory, nearest hit through a BVH
 /// (worlds beyond the LDS budget, up to `MIRT_SCENE_HBM_MAX_SPHERES`).
 pub const MIRT_SCENE_HBM: u32 = 1 << 0;
+/// Only together with `MIRT_SCENE_HBM`: build the BVH on the device.
+pub const MIRT_SCENE_BVH_DEVICE: u32 = 1 << 1;
 pub const MIRT_SCENE_HBM_MAX_SPHERES: u32 = 1 << 24;
 pub const MIRT_BVH_MAX_DEPTH: u32 = 32;
 pub const MIRT_BVH_MAX_LEAF: u32 = 4;
@@ -244,6 +258,8 @@ extern "C" {
     pub fn mirt_ctx_set_scene(ctx: *mut MirtContext, scene: *const MirtScene) -> c_int;
     pub fn mirt_ctx_set_scene_ex(ctx: *mut MirtContext, scene: *const MirtScene, flags: u32) -> c_int;
     pub fn mirt_bvh_plan(spheres: *const MirtSphere, n_spheres: u32, out: *mut MirtBvhPlan) -> c_int;
+    pub fn mirt_ctx_bvh_info(ctx: *mut MirtContext, out: *mut MirtBvhInfo) -> c_int;
+    pub fn mirt_ctx_bvh_read(ctx: *mut MirtContext, nodes: *mut c_void, nodes_bytes: usize, recs: *mut f32, recs_len: usize, ids: *mut u32, ids_len: usize) -> c_int;
     pub fn mirt_ctx_set_camera(ctx: *mut MirtContext, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_ctx_render(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;

@@ -24,6 +24,7 @@ MIRT_FLAG_TEXEL_TILES = 1 << 9
 
 # mirt_ctx_set_scene_ex / mirt_node_set_scene_ex flags, and the BVH of such scenes
 MIRT_SCENE_HBM = 1 << 0
+MIRT_SCENE_BVH_DEVICE = 1 << 1       # only together with MIRT_SCENE_HBM: build the BVH on the device
 MIRT_SCENE_HBM_MAX_SPHERES = 1 << 24
 MIRT_BVH_MAX_DEPTH = 32
 MIRT_BVH_MAX_LEAF = 4
@@ -130,6 +131,15 @@ class MirtBvhPlan(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MirtBvhInfo(C.Structure):
+    _fields_ = [("plan", MirtBvhPlan), ("root", C.c_uint32), ("built_on_device", C.c_uint32),
+                ("centre", C.c_float * 3), ("radius", C.c_float), ("r_max", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {"plan": self.plan.as_dict(), "root": int(self.root), "built_on_device": int(self.built_on_device),
+                "centre": [float(v) for v in self.centre], "radius": float(self.radius), "r_max": float(self.r_max)}
+
+
 class MirtStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("kernel_ms_total", C.c_double), ("launches", C.c_uint64),
                 ("samples", C.c_uint64), ("rays", C.c_uint64),
@@ -177,6 +187,8 @@ SYMBOLS = {
     "mirt_ctx_set_scene": (C.c_int, [C.c_void_p, _P(MirtScene)]),
     "mirt_ctx_set_scene_ex": (C.c_int, [C.c_void_p, _P(MirtScene), C.c_uint32]),
     "mirt_bvh_plan": (C.c_int, [C.c_void_p, C.c_uint32, _P(MirtBvhPlan)]),
+    "mirt_ctx_bvh_info": (C.c_int, [C.c_void_p, _P(MirtBvhInfo)]),
+    "mirt_ctx_bvh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "mirt_ctx_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_ctx_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -74,6 +74,22 @@ def bvh_plan(spheres) -> dict:
     return out.as_dict()
 
 
+# one inner node as mirt_ctx_bvh_read returns it (csrc/mirt_bvh.h: BvhNode, 64 bytes)
+BVH_NODE_DTYPE = np.dtype([("lmin", "<f4", (3,)), ("lmax", "<f4", (3,)), ("rmin", "<f4", (3,)), ("rmax", "<f4", (3,)),
+                           ("left", "<u4"), ("right", "<u4"), ("pad", "<u4", (2,))])
+BVH_LEAF = 0x80000000      # a child reference with this bit is a leaf: bits 24..30 = sphere count, bits 0..23 = first record
+
+
+def scene_flags(hbm: bool, bvh: str) -> int:
+    """The mirt_*_set_scene_ex flags of `set_scene(scene, hbm=..., bvh=...)`: bvh = "host" (default) or "device"
+    (MIRT_SCENE_BVH_DEVICE, only with hbm=True)."""
+    if bvh not in ("host", "device"):
+        raise ValueError(f"bvh must be 'host' or 'device', not {bvh!r}")
+    if bvh == "device" and not hbm:
+        raise ValueError("bvh='device' needs hbm=True (MIRT_SCENE_BVH_DEVICE only together with MIRT_SCENE_HBM)")
+    return (_abi.MIRT_SCENE_HBM if hbm else 0) | (_abi.MIRT_SCENE_BVH_DEVICE if bvh == "device" else 0)
+
+
 def params_out_rows(params: _abi.MirtParams) -> int:
     return int(lib().mirt_params_out_rows(C.byref(params)))
 
@@ -124,15 +140,36 @@ class Context:
         except Exception:
             pass
 
-    def set_scene(self, scene: SceneData, *, hbm: bool = False) -> None:
+    def set_scene(self, scene: SceneData, *, hbm: bool = False, bvh: str = "host") -> None:
         """mirt_ctx_set_scene; hbm=True: mirt_ctx_set_scene_ex(MIRT_SCENE_HBM) -- the tables stay in device memory and a BVH finds
-        the nearest hit, for worlds beyond the LDS budget (any size up to MIRT_SCENE_HBM_MAX_SPHERES)."""
+        the nearest hit, for worlds beyond the LDS budget (any size up to MIRT_SCENE_HBM_MAX_SPHERES).  bvh="device" (with
+        hbm=True): MIRT_SCENE_BVH_DEVICE, the tree is built on the device -- the same image, a much shorter call on large worlds."""
+        flags = scene_flags(hbm, bvh)
         c = scene.as_c()
-        if hbm:
-            check(lib().mirt_ctx_set_scene_ex(self._h, C.byref(c), _abi.MIRT_SCENE_HBM))
+        if flags:
+            check(lib().mirt_ctx_set_scene_ex(self._h, C.byref(c), flags))
         else:
             check(lib().mirt_ctx_set_scene(self._h, C.byref(c)))
         self._scene = scene
+
+    def bvh_info(self) -> dict:
+        """mirt_ctx_bvh_info: the tree this context holds -- {"plan": counts as bvh_plan() reports them, "root", "built_on_device",
+        "centre", "radius", "r_max"}."""
+        out = _abi.MirtBvhInfo()
+        check(lib().mirt_ctx_bvh_info(self._h, C.byref(out)))
+        return out.as_dict()
+
+    def bvh_read(self) -> tuple:
+        """mirt_ctx_bvh_read: (nodes [n_nodes] of BVH_NODE_DTYPE, recs float32 [n, 4] = {centre, r * r}, ids uint32 [n]) of the tree
+        this context holds; blocking, meant for tests."""
+        plan = self.bvh_info()["plan"]
+        n = plan["n_leaf_spheres"] + plan["n_always"]
+        nodes = np.zeros(plan["n_nodes"], BVH_NODE_DTYPE)
+        recs = np.zeros((n, 4), np.float32)
+        ids = np.zeros(n, np.uint32)
+        check(lib().mirt_ctx_bvh_read(self._h, nodes.ctypes.data_as(C.c_void_p), nodes.nbytes, recs.ctypes.data_as(C.c_void_p), recs.size,
+                                      ids.ctypes.data_as(C.c_void_p), ids.size))
+        return nodes, recs, ids
 
     def set_camera(self, camera: _abi.MirtGpuCamera) -> None:
         check(lib().mirt_ctx_set_camera(self._h, C.byref(camera)))

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -445,6 +446,9 @@ struct MirtContext {
     size_t         bvh_off_recs = 0, bvh_off_ids = 0;
     uint32_t       bvh_root = 0, bvh_n_always = 0;
     float          bvh_centre[3] = {}, bvh_radius = 0.0f, bvh_rmax = 0.0f;
+    MirtBvhPlan    bvh_plan{};               // of the tree in d_bvh, whichever builder made it (mirt_ctx_bvh_info)
+    bool           bvh_on_device = false;    // MIRT_SCENE_BVH_DEVICE built it
+    mirt::BvhDeviceScratch bvh_scratch;      // the device builder's temporary storage: grows, never shrinks
 };
 
 extern "C" {
@@ -640,7 +644,7 @@ void mirt_ctx_destroy(MirtContext* c)
     if (c->zero_stream) (void)hipStreamSynchronize(c->zero_stream);
     if (c->frame_stream_b) (void)hipStreamSynchronize(c->frame_stream_b);
     if (!c->untimed_streams.empty()) (void)hipDeviceSynchronize();      // launches without an event may still read the tables freed below
-    (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_bvh); (void)hipFree(c->d_texels);
+    (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_bvh); (void)hipFree(c->bvh_scratch.d); (void)hipFree(c->d_texels);
     (void)hipFree(c->d_sky); (void)hipFree(c->d_counters); (void)hipFree(c->d_work_counter); (void)hipFree(c->d_out); (void)hipFree(c->d_accum);
     for (hipEvent_t ev : c->ev_begin) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_end) (void)hipEventDestroy(ev);
@@ -653,8 +657,8 @@ void mirt_ctx_destroy(MirtContext* c)
     delete c;
 }
 
-// mirt_ctx_set_scene (hbm = false) and mirt_ctx_set_scene_ex (hbm = true: MIRT_SCENE_HBM)
-static int set_scene(MirtContext* c, const MirtScene* s, bool hbm)
+// mirt_ctx_set_scene (hbm = false) and mirt_ctx_set_scene_ex (hbm = true: MIRT_SCENE_HBM; bvh_device: | MIRT_SCENE_BVH_DEVICE)
+static int set_scene(MirtContext* c, const MirtScene* s, bool hbm, bool bvh_device = false)
 {
     if (!c || !s || !s->camera) return fail(MIRT_ERR_NULL_POINTER, "ctx/scene/camera is null");
     if (s->n_spheres && !s->spheres) return fail(MIRT_ERR_NULL_POINTER, "spheres is null");
@@ -677,10 +681,21 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm)
         return fail(MIRT_ERR_SCENE_TOO_LARGE, "%u spheres + %u materials exceed the %u-byte LDS budget", s->n_spheres,
                     s->n_materials, mirt::kMaxLdsBytes);
     // MIRT_SCENE_HBM: the BVH (host, mirt_bvh.cpp), built before the context's scene is touched
+    // (MIRT_SCENE_BVH_DEVICE: only the always-tested list here; the tree is built on the device once the spheres are there)
     mirt::BvhBuild bvh;
-    if (hbm) {
+    std::vector<uint32_t> bvh_always;
+    mirt::BvhDeviceResult dev_bvh;
+    if (hbm && !bvh_device) {
         const int rc = mirt::build_bvh(s->spheres, s->n_spheres, &bvh);
         if (rc != MIRT_OK) return rc;
+    } else if (hbm) {
+        const auto t0 = std::chrono::steady_clock::now();
+        try {
+            bvh_always = mirt::bvh_always_list(s->spheres, s->n_spheres);
+        } catch (const std::bad_alloc&) {
+            return fail(MIRT_ERR_ALLOC, "out of host memory listing the always-tested spheres of %u", s->n_spheres);
+        }
+        dev_bvh.always_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     HIP_TRY(hipSetDevice(c->device));
     // Failure-atomic: from here until the last copy has succeeded the context holds NO scene, so an allocation or
@@ -784,6 +799,7 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm)
     if ((rc = ensure_capacity(&c->d_mats, &c->cap_mats, (size_t)s->n_materials)) != MIRT_OK) return rc;
     if ((rc = ensure_capacity(&c->d_texels, &c->cap_texels, (size_t)s->n_texels * 3)) != MIRT_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());      // renders may be in flight on caller streams (mirt_ctx_render_device)
+    const auto t_upload = std::chrono::steady_clock::now();
     c->cam = *s->camera;
     if (s->n_spheres) HIP_TRY(hipMemcpy(c->d_spheres, prep.data(), prep.size() * sizeof(mirt::PreparedSphere), hipMemcpyHostToDevice));
     if (s->n_materials) HIP_TRY(hipMemcpy(c->d_mats, s->materials, (size_t)s->n_materials * sizeof(MirtMaterial), hipMemcpyHostToDevice));
@@ -815,7 +831,22 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm)
     c->has_image_texture = false;                // ... on a material some sphere uses
     for (uint32_t i = 0; i < s->n_spheres; ++i)
         if (s->spheres[i].material_idx < s->n_materials && mat_has_image[s->spheres[i].material_idx]) c->has_image_texture = true;
-    if (hbm) {                                   // nodes | records | ids, each 16-byte aligned
+    if (hbm && bvh_device) {                     // the tree from the prepared spheres just uploaded, on the context's stream; synchronous
+        const double upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_upload).count();
+        if ((rc = mirt::build_bvh_device(bvh_always, s->n_spheres, c->d_spheres, c->stream, &c->bvh_scratch, &c->d_bvh, &c->cap_bvh, &dev_bvh)) != MIRT_OK) return rc;
+        c->bvh_off_recs = dev_bvh.off_recs;
+        c->bvh_off_ids = dev_bvh.off_ids;
+        c->bvh_root = dev_bvh.root;
+        c->bvh_n_always = dev_bvh.plan.n_always;
+        for (int k = 0; k < 3; ++k) c->bvh_centre[k] = dev_bvh.centre[k];
+        c->bvh_radius = dev_bvh.radius;
+        c->bvh_rmax = dev_bvh.r_max;
+        c->bvh_plan = dev_bvh.plan;
+        c->bvh_on_device = true;
+        if (std::getenv("MIRT_BVH_TIMING"))       // tools/hbm_scene_rates.py: the parts of a device build
+            std::fprintf(stderr, "mirt_bvh_device: n=%u always_ms=%.3f upload_ms=%.3f kernels_ms=%.3f levels=%u\n", s->n_spheres, dev_bvh.always_ms,
+                         upload_ms, dev_bvh.kernels_ms, dev_bvh.levels);
+    } else if (hbm) {                            // nodes | records | ids, each 16-byte aligned
         const size_t nb = bvh.nodes.size() * sizeof(mirt::BvhNode), rb = bvh.recs.size() * sizeof(float), ib = bvh.ids.size() * sizeof(uint32_t);
         c->bvh_off_recs = nb;
         c->bvh_off_ids = nb + rb;
@@ -828,6 +859,8 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm)
         for (int k = 0; k < 3; ++k) c->bvh_centre[k] = bvh.centre[k];
         c->bvh_radius = bvh.radius;
         c->bvh_rmax = bvh.r_max;
+        c->bvh_plan = mirt::bvh_plan_of(bvh);
+        c->bvh_on_device = false;
     }
     c->have_scene = true;
     return MIRT_OK;
@@ -837,8 +870,39 @@ int mirt_ctx_set_scene(MirtContext* c, const MirtScene* s) { return set_scene(c,
 
 int mirt_ctx_set_scene_ex(MirtContext* c, const MirtScene* s, uint32_t flags)
 {
-    if (flags & ~(uint32_t)MIRT_SCENE_HBM) return fail(MIRT_ERR_BAD_MODE, "unknown set_scene_ex flags 0x%x", flags);
-    return set_scene(c, s, (flags & MIRT_SCENE_HBM) != 0);
+    if (flags & ~(uint32_t)(MIRT_SCENE_HBM | MIRT_SCENE_BVH_DEVICE)) return fail(MIRT_ERR_BAD_MODE, "unknown set_scene_ex flags 0x%x", flags);
+    if ((flags & MIRT_SCENE_BVH_DEVICE) && !(flags & MIRT_SCENE_HBM))
+        return fail(MIRT_ERR_BAD_MODE, "MIRT_SCENE_BVH_DEVICE needs MIRT_SCENE_HBM (flags 0x%x)", flags);
+    return set_scene(c, s, (flags & MIRT_SCENE_HBM) != 0, (flags & MIRT_SCENE_BVH_DEVICE) != 0);
+}
+
+int mirt_ctx_bvh_info(MirtContext* c, MirtBvhInfo* out)
+{
+    if (!c || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/out is null");
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    *out = MirtBvhInfo{};
+    out->plan = c->bvh_plan;
+    out->root = c->bvh_root;
+    out->built_on_device = c->bvh_on_device ? 1u : 0u;
+    for (int k = 0; k < 3; ++k) out->centre[k] = c->bvh_centre[k];
+    out->radius = c->bvh_radius;
+    out->r_max = c->bvh_rmax;
+    return MIRT_OK;
+}
+
+int mirt_ctx_bvh_read(MirtContext* c, void* nodes, size_t nodes_bytes, float* recs, size_t recs_len, uint32_t* ids, size_t ids_len)
+{
+    if (!c) return fail(MIRT_ERR_NULL_POINTER, "ctx is null");
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    const size_t nb = (size_t)c->bvh_plan.n_nodes * sizeof(mirt::BvhNode), n = c->n_spheres;
+    if (nodes_bytes < nb || recs_len < 4 * n || ids_len < n)
+        return fail(MIRT_ERR_OUT_BUFFER, "the tree needs %zu node bytes, %zu record floats and %zu ids", nb, 4 * n, n);
+    if ((nb && !nodes) || (n && (!recs || !ids))) return fail(MIRT_ERR_NULL_POINTER, "nodes/recs/ids is null");
+    HIP_TRY(hipSetDevice(c->device));
+    if (nb) HIP_TRY(hipMemcpy(nodes, c->d_bvh, nb, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(recs, c->d_bvh + c->bvh_off_recs, 16 * n, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(hipMemcpy(ids, c->d_bvh + c->bvh_off_ids, 4 * n, hipMemcpyDeviceToHost));
+    return MIRT_OK;
 }
 
 int mirt_ctx_set_camera(MirtContext* c, const MirtGpuCamera* cam)

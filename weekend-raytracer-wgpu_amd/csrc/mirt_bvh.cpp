@@ -109,44 +109,71 @@ uint32_t split(std::vector<Item>& items, uint32_t b, uint32_t e, uint32_t depth)
 
 namespace mirt {
 
+std::vector<uint32_t> bvh_always_list(const MirtSphere* s, uint32_t n)
+{
+    std::vector<uint32_t> bad, finite_ids;             // boxes that are not finite / the rest
+    std::vector<float> radii;
+    finite_ids.reserve(n);
+    radii.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const double r = std::fabs((double)s[i].radius);
+        bool ok = std::isfinite(r);
+        for (int k = 0; k < 3; ++k) ok = ok && std::isfinite((double)s[i].center[k]) && std::isfinite((double)s[i].center[k] - r) &&
+                                           std::isfinite((double)s[i].center[k] + r) && std::fabs((double)s[i].center[k]) + r < 3.0e38;
+        if (!ok) { bad.push_back(i); continue; }
+        finite_ids.push_back(i);
+        radii.push_back(std::fabs(s[i].radius));
+    }
+    std::vector<uint32_t> always(bad.begin(), bad.begin() + std::min<size_t>(bad.size(), MIRT_BVH_MAX_ALWAYS));
+    if (!radii.empty() && always.size() < MIRT_BVH_MAX_ALWAYS) {
+        std::nth_element(radii.begin(), radii.begin() + radii.size() / 2, radii.end());        // the median; `radii` is not read again
+        const double limit = (double)MIRT_BVH_BIG_RADII * radii[radii.size() / 2];
+        std::vector<uint32_t> big;
+        for (uint32_t i : finite_ids) if (std::fabs((double)s[i].radius) > limit) big.push_back(i);
+        std::sort(big.begin(), big.end(), [s](uint32_t x, uint32_t y) {
+            const float rx = std::fabs(s[x].radius), ry = std::fabs(s[y].radius);
+            return rx > ry || (rx == ry && x < y);
+        });
+        for (uint32_t i : big) {
+            if (always.size() >= MIRT_BVH_MAX_ALWAYS) break;
+            always.push_back(i);
+        }
+    }
+    std::sort(always.begin(), always.end());
+    return always;
+}
+
+void bvh_round_bounds(double rad, double rmax, float* radius, float* r_max)
+{
+    *radius = up(rad * (1.0 + 0x1p-20));
+    *r_max = up(rmax * (1.0 + 0x1p-20));
+    if (!std::isfinite(*radius)) *radius = 3.0e38f;
+    if (!std::isfinite(*r_max)) *r_max = 3.0e38f;
+}
+
+MirtBvhPlan bvh_plan_of(const BvhBuild& b)
+{
+    MirtBvhPlan p{};
+    p.n_nodes = (uint32_t)b.nodes.size();
+    p.n_leaves = b.n_leaves;
+    p.n_leaf_spheres = (uint32_t)b.ids.size() - b.n_always;
+    p.n_always = b.n_always;
+    p.max_depth = b.max_depth;
+    p.max_leaf = b.max_leaf;
+    p.device_bytes = 64ull * b.nodes.size() + 20ull * b.ids.size();
+    return p;
+}
+
 int build_bvh(const MirtSphere* s, uint32_t n, BvhBuild* out)
 {
     try {
         *out = BvhBuild{};
         std::vector<Item> items;
         items.reserve(n);
-        std::vector<uint32_t> bad, finite_ids;             // boxes that are not finite / the rest
-        std::vector<float> radii;
-        for (uint32_t i = 0; i < n; ++i) {
-            const double r = std::fabs((double)s[i].radius);
-            bool ok = std::isfinite(r);
-            for (int k = 0; k < 3; ++k) ok = ok && std::isfinite((double)s[i].center[k]) && std::isfinite((double)s[i].center[k] - r) &&
-                                               std::isfinite((double)s[i].center[k] + r) && std::fabs((double)s[i].center[k]) + r < 3.0e38;
-            if (!ok) { bad.push_back(i); continue; }
-            finite_ids.push_back(i);
-            radii.push_back(std::fabs(s[i].radius));
-        }
         // the always-tested list: boxes that are not finite, then the largest spheres above MIRT_BVH_BIG_RADII median radii
-        std::vector<uint32_t> always(bad.begin(), bad.begin() + std::min<size_t>(bad.size(), MIRT_BVH_MAX_ALWAYS));
+        const std::vector<uint32_t> always = bvh_always_list(s, n);
         std::vector<unsigned char> in_always(n, 0);
         for (uint32_t i : always) in_always[i] = 1;
-        if (!radii.empty() && always.size() < MIRT_BVH_MAX_ALWAYS) {
-            std::vector<float> sorted = radii;
-            std::nth_element(sorted.begin(), sorted.begin() + sorted.size() / 2, sorted.end());
-            const double limit = (double)MIRT_BVH_BIG_RADII * sorted[sorted.size() / 2];
-            std::vector<uint32_t> big;
-            for (uint32_t i : finite_ids) if (std::fabs((double)s[i].radius) > limit) big.push_back(i);
-            std::sort(big.begin(), big.end(), [s](uint32_t x, uint32_t y) {
-                const float rx = std::fabs(s[x].radius), ry = std::fabs(s[y].radius);
-                return rx > ry || (rx == ry && x < y);
-            });
-            for (uint32_t i : big) {
-                if (always.size() >= MIRT_BVH_MAX_ALWAYS) break;
-                always.push_back(i);
-                in_always[i] = 1;
-            }
-        }
-        std::sort(always.begin(), always.end());
         out->n_always = (uint32_t)always.size();
         out->recs.reserve(4ull * n);
         out->ids.reserve(n);
@@ -190,10 +217,7 @@ int build_bvh(const MirtSphere* s, uint32_t n, BvhBuild* out)
                 rmax = std::max(rmax, std::fabs((double)s[it.id].radius));
             }
             for (int k = 0; k < 3; ++k) out->centre[k] = (float)cen[k];
-            out->radius = up(rad * (1.0 + 0x1p-20));
-            out->r_max = up(rmax * (1.0 + 0x1p-20));
-            if (!std::isfinite(out->radius)) out->radius = 3.0e38f;
-            if (!std::isfinite(out->r_max)) out->r_max = 3.0e38f;
+            bvh_round_bounds(rad, rmax, &out->radius, &out->r_max);
         }
 
         // depth-first build: a node's index is given when it is created, the children's references and boxes are filled in the parent
@@ -248,12 +272,6 @@ extern "C" int mirt_bvh_plan(const MirtSphere* spheres, uint32_t n_spheres, Mirt
     mirt::BvhBuild b;
     const int rc = mirt::build_bvh(spheres, n_spheres, &b);
     if (rc != MIRT_OK) return rc;
-    out->n_nodes = (uint32_t)b.nodes.size();
-    out->n_leaves = b.n_leaves;
-    out->n_leaf_spheres = (uint32_t)b.ids.size() - b.n_always;
-    out->n_always = b.n_always;
-    out->max_depth = b.max_depth;
-    out->max_leaf = b.max_leaf;
-    out->device_bytes = 64ull * b.nodes.size() + 20ull * b.ids.size();
+    *out = mirt::bvh_plan_of(b);
     return MIRT_OK;
 }

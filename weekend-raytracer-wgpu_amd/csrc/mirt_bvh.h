@@ -37,4 +37,41 @@ struct BvhBuild {
 // Builds the tree over spheres[0 .. n) (n <= MIRT_SCENE_HBM_MAX_SPHERES).  Deterministic.  MIRT_OK or MIRT_ERR_ALLOC.
 int build_bvh(const MirtSphere* spheres, uint32_t n, BvhBuild* out);
 
+// The always-tested list of those spheres, sorted by index (at most MIRT_BVH_MAX_ALWAYS entries): the spheres whose box is not finite,
+// in index order, then the largest of those above MIRT_BVH_BIG_RADII median radii (ties to the lower index).  One rule for both
+// builders (build_bvh above, build_bvh_device below).  O(n); may throw std::bad_alloc.
+std::vector<uint32_t> bvh_always_list(const MirtSphere* spheres, uint32_t n);
+
+// bvh_radius / bvh_rmax from the exact maxima `rad` (distance from the centre to the farthest box corner) and `rmax` (largest
+// |radius|): rounded up with a 2^-20 margin, clamped to 3.0e38.
+void bvh_round_bounds(double rad, double rmax, float* radius, float* r_max);
+
+// MirtBvhPlan of a finished host build
+MirtBvhPlan bvh_plan_of(const BvhBuild& b);
+
+// ---- the device builder (mirt_bvh_device.hip): MIRT_SCENE_HBM | MIRT_SCENE_BVH_DEVICE ----
+// Scratch of the device builder (sort keys, the level-by-level topology, reduction partials, the sort's temporary storage): owned by
+// the context, grows, never shrinks.
+struct BvhDeviceScratch {
+    unsigned char* d = nullptr;
+    size_t         cap = 0;
+};
+
+struct BvhDeviceResult {
+    MirtBvhPlan plan{};
+    uint32_t    root = kBvhLeaf;
+    float       centre[3] = {0.0f, 0.0f, 0.0f};
+    float       radius = 0.0f, r_max = 0.0f;
+    size_t      off_recs = 0, off_ids = 0;     // byte offsets of the records / ids in *d_bvh (nodes at 0)
+    double      always_ms = 0.0;               // host: the always-tested list
+    double      kernels_ms = 0.0;              // device: first launch to the tree being ready
+    uint32_t    levels = 0;
+};
+
+// Builds the tree of `spheres` (host copy: the always list only) from their prepared device copy `d_prepared` ([n] PreparedSphere,
+// already uploaded) on `stream`, into *d_bvh (nodes | records | ids, grown when too small).  Synchronous: the tree is ready when it
+// returns.  `always` = bvh_always_list(spheres, n).  MIRT_OK, MIRT_ERR_ALLOC or MIRT_ERR_HIP.
+int build_bvh_device(const std::vector<uint32_t>& always, uint32_t n, const void* d_prepared, void* hip_stream, BvhDeviceScratch* scratch,
+                     unsigned char** d_bvh, size_t* cap_bvh, BvhDeviceResult* out);
+
 }  // namespace mirt

@@ -383,7 +383,8 @@ int mirt_node_set_scene(MirtNode* nd, const MirtScene* scene)
 int mirt_node_set_scene_ex(MirtNode* nd, const MirtScene* scene, uint32_t flags)
 {
     if (!nd || !scene) return mirt::set_error(MIRT_ERR_NULL_POINTER, "node/scene is null");
-    if (flags & ~(uint32_t)MIRT_SCENE_HBM) return mirt::set_error(MIRT_ERR_BAD_MODE, "unknown set_scene_ex flags 0x%x", flags);
+    if ((flags & ~(uint32_t)(MIRT_SCENE_HBM | MIRT_SCENE_BVH_DEVICE)) || flags == MIRT_SCENE_BVH_DEVICE)     // the device builder only with MIRT_SCENE_HBM
+        return mirt::set_error(MIRT_ERR_BAD_MODE, "unknown set_scene_ex flags 0x%x", flags);
     nd->have_scene = false;
     for (uint32_t i = 0; i < nd->n; ++i) {
         const int rc = mirt_ctx_set_scene_ex(nd->ctx[i], scene, flags);

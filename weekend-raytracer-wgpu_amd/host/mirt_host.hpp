@@ -36,6 +36,8 @@ inline int set_scene_any_size(MirtContext* ctx, const MirtScene& sc)
 }
 // mirt_ctx_set_scene_ex: flags = MIRT_SCENE_*
 inline void set_scene(MirtContext* ctx, const MirtScene& sc, uint32_t flags) { check(mirt_ctx_set_scene_ex(ctx, &sc, flags)); }
+// mirt_ctx_bvh_info: the tree of the context's MIRT_SCENE_HBM scene (built on the host, or on the device with MIRT_SCENE_BVH_DEVICE)
+inline MirtBvhInfo bvh_info(MirtContext* ctx) { MirtBvhInfo info; check(mirt_ctx_bvh_info(ctx, &info)); return info; }
 
 // Angle — angle.rs:1-50
 class Angle {

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import check, lib
-from .context import Context, SceneData, _stream_arg, params_out_rows
+from .context import Context, SceneData, _stream_arg, params_out_rows, scene_flags
 
 
 class _MemberContext(Context):
@@ -56,11 +56,13 @@ class Node:
         except Exception:
             pass
 
-    def set_scene(self, scene: SceneData, *, hbm: bool = False) -> None:
-        """mirt_node_set_scene; hbm=True: mirt_node_set_scene_ex(MIRT_SCENE_HBM) on every member (Context.set_scene)."""
+    def set_scene(self, scene: SceneData, *, hbm: bool = False, bvh: str = "host") -> None:
+        """mirt_node_set_scene; hbm=True: mirt_node_set_scene_ex(MIRT_SCENE_HBM) on every member (Context.set_scene); bvh="device":
+        | MIRT_SCENE_BVH_DEVICE, every member builds its own tree on its own device."""
+        flags = scene_flags(hbm, bvh)
         c = scene.as_c()
-        if hbm:
-            check(lib().mirt_node_set_scene_ex(self._h, C.byref(c), _abi.MIRT_SCENE_HBM))
+        if flags:
+            check(lib().mirt_node_set_scene_ex(self._h, C.byref(c), flags))
         else:
             check(lib().mirt_node_set_scene(self._h, C.byref(c)))
         self._scene = scene
