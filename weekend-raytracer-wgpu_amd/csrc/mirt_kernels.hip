@@ -171,6 +171,22 @@ MIRT_DEV uint32_t sat_u8(float f)    // Rust `as u8` (math.rs:15-17)
 // predicate is a loop-carried lane mask); the builtin takes the lane mask itself.
 MIRT_DEV unsigned long long ballot_(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
+// The pool kernel's pick: max over the queues of (depth << 3) + (7 - k), on the scalar unit -- two instructions per queue.
+// Written out because the compiler selects a chain of `a > b ? a : b` over four uniform values as v_max3_u32 (two v_mov, the
+// VALU instruction, a hazard wait and a v_readfirstlane in the middle of scalar code) and turns the key's shift-and-add into
+// shift + or.  The depths are wave-uniform; readfirstlane says so to the register allocator where it has lost track of that.
+template <uint32_t K, uint32_t N>
+MIRT_DEV uint32_t deepest_key(const uint32_t (&depth)[N], uint32_t key = 0u)
+{
+    if constexpr (K < N) {
+        const uint32_t d = __builtin_amdgcn_readfirstlane(depth[K]);
+        uint32_t r;
+        if constexpr (K == 0) asm("s_lshl3_add_u32 %0, %1, %2" : "=s"(r) : "s"(d), "I"(7 - (int)K) : "scc");
+        else asm("s_lshl3_add_u32 %0, %2, %3\n\ts_max_u32 %0, %0, %1" : "=&s"(r) : "s"(key), "s"(d), "I"(7 - (int)K) : "scc");
+        return deepest_key<K + 1, N>(depth, r);
+    } else return key;
+}
+
 MIRT_DEV float clamp01(float x) { return (x < 0.0f) ? 0.0f : ((x > 1.0f) ? 1.0f : x); }
 
 MIRT_DEV f3 texel_at(const RenderArgs& A_unused, uint64_t g)

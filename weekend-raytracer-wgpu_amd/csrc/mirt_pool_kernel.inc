@@ -108,12 +108,7 @@ __global__ __launch_bounds__(THREADS, MINW) void MIRT_POOL_KERNEL_NAME(RenderArg
             stamps.mark(6);                            // the previous step's tail: classification, fast-forward test, store, push
             if (!ff) {
                 // ---- pick the deepest queue: max over keys depth << 3 | (7 - op); ties go to the lower op ----
-                uint32_t key = 0;
-#pragma unroll
-                for (uint32_t k = 0; k < kNumOps; ++k) {
-                    const uint32_t kk = (tail[k] << 3) | (7u - k);
-                    key = (kk > key) ? kk : key;
-                }
+                const uint32_t key = deepest_key<0>(tail);
                 const uint32_t depth = key >> 3;
                 if (depth == 0) break;                     // every queue empty: strip finished
                 my_k = 7u - (key & 7u);
