@@ -387,6 +387,26 @@ int mirt_ctx_bvh_info(MirtContext* ctx, MirtBvhInfo* out);
  * the original index of every record (always-tested list first).  Blocking; meant for tests, like mirt_ctx_accum_read.
  * MIRT_ERR_OUT_BUFFER if a buffer is too small (nodes_bytes in bytes, recs_len in floats, ids_len in entries). */
 int mirt_ctx_bvh_read(MirtContext* ctx, void* nodes, size_t nodes_bytes, float* recs, size_t recs_len, uint32_t* ids, size_t ids_len);
+/* ---- moving the spheres of a MIRT_SCENE_HBM scene in place ----
+ * Spheres first .. first + count of the context's MIRT_SCENE_HBM scene take center[0..3] and radius from the `count` records given
+ * (MirtSphere, 32 bytes each).  material_idx and the padding of the input are NOT READ: a sphere keeps its material, so everything a
+ * scene's materials decide stays valid.  r * r and 1 / r are computed on the device with the single IEEE operations set_scene uses.
+ * The tree keeps its topology and its always-tested list (a performance rule: a tree sphere that grows, or becomes non-finite, stays in
+ * the tree); every child box is recomputed bottom-up by the host formula and the traversal bounds are reduced again, always over the
+ * whole tree, whichever builder made it.  The image is byte-identical to the flat scan's and to a fresh set_scene_ex of the moved
+ * world; a tree whose spheres moved far culls worse (mirt_ctx_bvh_refits tells a host how often it has refitted; rebuild with
+ * set_scene_ex).
+ * Like set_scene the call first waits for the device -- renders in flight on caller streams, and whatever was queued to produce
+ * d_spheres -- and returns when the tree is ready.  The accumulation buffer is not touched (reset it, as after set_camera).
+ *   mirt_ctx_update_spheres          reads `spheres` from host memory;
+ *   mirt_ctx_update_spheres_device   reads `d_spheres` from memory of the context's device (4-byte aligned), device to device.
+ * MIRT_ERR_NULL_POINTER: ctx is null, or the records are with count > 0;  MIRT_ERR_NO_SCENE: no scene, or not a MIRT_SCENE_HBM one;
+ * MIRT_ERR_BAD_ROWS: first + count > n_spheres (in 64 bits);  count == 0: MIRT_OK without device work.  An argument error changes
+ * nothing; a failure after the first write leaves the context with no scene. */
+int      mirt_ctx_update_spheres(MirtContext* ctx, uint32_t first, uint32_t count, const MirtSphere* spheres);
+int      mirt_ctx_update_spheres_device(MirtContext* ctx, uint32_t first, uint32_t count, const void* d_spheres);
+/* Successful updates (count > 0) since the scene was set; 0 after every set_scene*, and for a null ctx. */
+uint32_t mirt_ctx_bvh_refits(const MirtContext* ctx);
 
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by
@@ -553,6 +573,8 @@ void mirt_node_destroy(MirtNode* node);
 int  mirt_node_set_scene(MirtNode* node, const MirtScene* scene);
 /* mirt_ctx_set_scene_ex on every member (flags: MIRT_SCENE_*; checked before any member is touched). */
 int  mirt_node_set_scene_ex(MirtNode* node, const MirtScene* scene, uint32_t flags);
+/* mirt_ctx_update_spheres on every member (host pointer).  If a member fails, the node has no scene until a set_scene* succeeds. */
+int  mirt_node_update_spheres(MirtNode* node, uint32_t first, uint32_t count, const MirtSphere* spheres);
 /* mirt_ctx_set_camera on every member (host-side only). */
 int  mirt_node_set_camera(MirtNode* node, const MirtGpuCamera* camera);
 /* Render the band into HOST memory (mirt_params_out_rows(params) * width * 4 bytes); blocking. */

@@ -13,7 +13,13 @@
            them on stderr when MIRT_BVH_TIMING is set); n_nodes / max_depth; tests and nodes per ray; kernel ms at 1080p x 16 spp
   --bvh host (default) / device: the rtiow and field cases with that builder
 
-usage: python tools/hbm_scene_rates.py [--reps 5] [--fields 10000,100000,1000000] [--bvh host|device|both] [--soup 100000]
+  --update in-place updates (mirt_ctx_update_spheres / _device) on the same fields, device-built tree: one process, alternating with
+           the mirt_ctx_set_scene_ex(HBM | BVH_DEVICE) of the same moved world that they replace; median of --reps after a warm-up; the
+           update's parts between events (scatter, refit levels, bounds: MIRT_BVH_TIMING); then kernel ms at 1080p x 16 spp and tests /
+           nodes per ray after every small sphere moved by up to 0.25, 1 and 4 median radii in x and z -- the refitted tree against
+           a fresh device tree and a fresh host tree of the same world: after how much motion a rebuild pays
+
+usage: python tools/hbm_scene_rates.py [--reps 5] [--fields 10000,100000,1000000] [--bvh host|device|both] [--soup 100000] [--update]
 """
 from __future__ import annotations
 
@@ -93,23 +99,27 @@ def field_case(n: int, reps: int, bvh: str = "host"):
     ctx.close()
 
 
-def _timed_set_scene(ctx, sd, bvh: str):
-    """-> (wall ms of the set_scene call, the device build's parts as the library reports them on stderr, or {})."""
+def _timed_stderr(fn, pattern):
+    """-> (wall ms of fn(), {key: value} the library reported on stderr meanwhile)."""
     sys.stderr.flush()
     with tempfile.TemporaryFile() as tmp:
         saved = os.dup(2)
         os.dup2(tmp.fileno(), 2)
         try:
             t0 = time.perf_counter()
-            ctx.set_scene(sd, hbm=True, bvh=bvh)
+            fn()
             wall = (time.perf_counter() - t0) * 1e3
         finally:
             os.dup2(saved, 2)
             os.close(saved)
         tmp.seek(0)
         text = tmp.read().decode(errors="replace")
-    parts = {k: float(v) for k, v in re.findall(r"(always_ms|upload_ms|kernels_ms)=([0-9.]+)", text)}
-    return wall, parts
+    return wall, {k: float(v) for k, v in re.findall(pattern, text)}
+
+
+def _timed_set_scene(ctx, sd, bvh: str):
+    """-> (wall ms of the set_scene call, the device build's parts as the library reports them on stderr, or {})."""
+    return _timed_stderr(lambda: ctx.set_scene(sd, hbm=True, bvh=bvh), r"(always_ms|upload_ms|kernels_ms)=([0-9.]+)")
 
 
 def builders_case(name: str, arr, mats, tex, eye, reps: int):
@@ -152,6 +162,83 @@ def builders_case(name: str, arr, mats, tex, eye, reps: int):
     print(json.dumps(out), flush=True)
 
 
+def _jittered(arr, radii: float, seed: int):
+    """Every small sphere of an rtiow_field moved by up to `radii` median radii in x and z."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = arr.copy()
+    step = radii * float(np.median(arr["radius"][5:]))
+    out["center"][5:, 0] += rng.uniform(-step, step, len(arr) - 5).astype(np.float32)
+    out["center"][5:, 2] += rng.uniform(-step, step, len(arr) - 5).astype(np.float32)
+    return out
+
+
+def update_case(n: int, reps: int):
+    import numpy as np
+    import torch
+    os.environ["MIRT_BVH_TIMING"] = "1"
+    med = statistics.median
+    arr, mats, tex = rtiow_field(n, seed=n)
+    eye = (40, 6, 30)
+    cam, cam_count = look(W, H, eye, (0, 0, 0), vfov=35), look(480, 270, eye, (0, 0, 0), vfov=35)
+    worlds = [_jittered(arr, 0.25, 1), _jittered(arr, 0.25, 2)]
+    scenes = [scene_from_arrays(cam, w, mats, tex) for w in worlds]
+    d_worlds = [torch.from_numpy(w.view(np.uint8).copy()).to("cuda:0") for w in worlds]
+    ctx, ctx_rebuild = m.Context(0), m.Context(0)
+    ctx.set_scene(scene_from_arrays(cam, arr, mats, tex), hbm=True, bvh="device")
+    refit_pat, build_pat = r"(scatter_ms|refit_ms|bounds_ms|levels)=([0-9.]+)", r"(always_ms|upload_ms|kernels_ms)=([0-9.]+)"
+    wall = {"update_spheres": [], "update_spheres_device": [], "rebuild": []}
+    parts = {}
+    for rnd in range(reps + 1):                                     # round 0 = warm-up (the refit's schedule, allocations, code objects)
+        k = rnd & 1
+        t_host, p_host = _timed_stderr(lambda: ctx.update_spheres(0, worlds[k]), refit_pat)
+        t_dev, p_dev = _timed_stderr(lambda: ctx.update_spheres_device(0, n, d_worlds[1 - k].data_ptr()), refit_pat)
+        t_build, p_build = _timed_stderr(lambda: ctx_rebuild.set_scene(scenes[k], hbm=True, bvh="device"), build_pat)
+        if rnd:
+            wall["update_spheres"].append(t_host)
+            wall["update_spheres_device"].append(t_dev)
+            wall["rebuild"].append(t_build)
+            for src, pt in (("host", p_host), ("device", p_dev), ("rebuild", p_build)):
+                for key, v in pt.items():
+                    parts.setdefault(f"{src}_{key}", []).append(v)
+    out = {"case": "update", "world": f"rtiow_field({n})", "n_spheres": n, "reps": reps, "n_nodes": ctx.bvh_info()["plan"]["n_nodes"],
+           "refits": ctx.bvh_refits()}
+    for k, v in wall.items():
+        out[f"{k}_ms"] = round(med(v), 3)
+        out[f"{k}_all_ms"] = [round(x, 3) for x in v]
+    out.update({k: round(med(v), 3) for k, v in parts.items()})
+    out["rebuild_over_update"] = round(out["rebuild_ms"] / out["update_spheres_ms"], 2)
+    out["rebuild_over_update_device"] = round(out["rebuild_ms"] / out["update_spheres_device_ms"], 2)
+    print(json.dumps(out), flush=True)
+
+    # how much worse a refitted tree culls, and renders, than a fresh one of the same world
+    p = m.make_params(W, H, 16, mode=m.MIRT_MODE_PT, num_bounces=8)
+    pc = m.make_params(480, 270, 2, mode=m.MIRT_MODE_PT, num_bounces=8, flags=m.MIRT_FLAG_COUNT_WORK | m.MIRT_FLAG_COUNT_GRID)
+    for radii in (0.25, 1.0, 4.0):
+        moved = _jittered(arr, radii, 3)
+        sd = scene_from_arrays(cam, moved, mats, tex)
+        row = {"case": "update_culling", "world": f"rtiow_field({n})", "n_spheres": n, "jitter_median_radii": radii, "spp": 16, "width": W, "height": H}
+        for name in ("refitted", "fresh_device", "fresh_host"):
+            if name == "refitted":
+                ctx.set_scene(scene_from_arrays(cam, arr, mats, tex), hbm=True, bvh="device")
+                ctx.update_spheres(0, moved)
+            else:
+                ctx.set_scene(sd, hbm=True, bvh="device" if name == "fresh_device" else "host")
+            kernel_ms(ctx, p)
+            ts = [kernel_ms(ctx, p) for _ in range(reps)]
+            ctx.set_camera(cam_count)
+            ctx.render(pc)
+            st = ctx.stats()
+            row[name] = {"render_ms": round(med(ts), 3), "render_all_ms": [round(x, 3) for x in ts],
+                         "tests_per_ray": round(st["sphere_tests"] / st["rays"], 2), "nodes_per_ray": round(st["grid_cells"] / st["rays"], 2)}
+        row["render_refitted_over_fresh_host"] = round(row["refitted"]["render_ms"] / row["fresh_host"]["render_ms"], 3)
+        row["render_refitted_over_fresh_device"] = round(row["refitted"]["render_ms"] / row["fresh_device"]["render_ms"], 3)
+        row["tests_refitted_over_fresh_host"] = round(row["refitted"]["tests_per_ray"] / row["fresh_host"]["tests_per_ray"], 3)
+        print(json.dumps(row), flush=True)
+    ctx.close()
+    ctx_rebuild.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--reps", type=int, default=5)
@@ -159,8 +246,13 @@ def main() -> None:
     ap.add_argument("--skip-rtiow", action="store_true")
     ap.add_argument("--bvh", choices=("host", "device", "both"), default="host")
     ap.add_argument("--soup", type=int, default=100000, help="--bvh both: spheres of the clustered soup (0: none)")
+    ap.add_argument("--update", action="store_true", help="in-place updates against the device rebuild they replace")
     a = ap.parse_args()
     fields = [int(x) for x in a.fields.split(",") if x]
+    if a.update:
+        for n in fields:
+            update_case(n, a.reps)
+        return
     if a.bvh == "both":
         for n in fields:
             arr, mats, tex = rtiow_field(n, seed=n)

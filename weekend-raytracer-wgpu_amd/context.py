@@ -53,7 +53,7 @@ def make_params(width: int, height: int, spp: int, *, mode: int = _abi.MIRT_MODE
     return p
 
 
-def set_scene_any_size(target, scene: SceneData) -> None:
+def set_scene_any_size(target, scene: SceneData) -> bool:
     """`target.set_scene(scene)` (a Context or a Node); a world the LDS layouts refuse (MIRT_ERR_SCENE_TOO_LARGE) is set again with
     MIRT_SCENE_HBM, so that the reference's host objects -- `Layer::set_data` takes any `Vec<Box<Sphere>>` -- take any world."""
     try:
@@ -62,6 +62,8 @@ def set_scene_any_size(target, scene: SceneData) -> None:
         if e.status != _abi.MIRT_ERR_SCENE_TOO_LARGE:
             raise
         target.set_scene(scene, hbm=True)
+        return True                          # an HBM scene: its spheres can be moved in place (update_spheres)
+    return False
 
 
 def bvh_plan(spheres) -> dict:
@@ -88,6 +90,38 @@ def scene_flags(hbm: bool, bvh: str) -> int:
     if bvh == "device" and not hbm:
         raise ValueError("bvh='device' needs hbm=True (MIRT_SCENE_BVH_DEVICE only together with MIRT_SCENE_HBM)")
     return (_abi.MIRT_SCENE_HBM if hbm else 0) | (_abi.MIRT_SCENE_BVH_DEVICE if bvh == "device" else 0)
+
+
+# MirtSphere as a numpy record (32 bytes): what update_spheres takes for large worlds
+SPHERE_DTYPE = np.dtype([("center", "<f4", (4,)), ("radius", "<f4"), ("material_idx", "<u4"), ("_pad", "<u4", (2,))])
+
+
+def sphere_records(spheres) -> tuple:
+    """`spheres` for the update_spheres wrappers -> (address, count, keep-alive object): a one-dimensional SPHERE_DTYPE numpy array, a
+    ctypes array of MirtSphere or a list / tuple of Sphere (anything with to_c() -> MirtSphere) or MirtSphere.  Anything else:
+    ValueError, before the library is called."""
+    if isinstance(spheres, np.ndarray):
+        if spheres.dtype != SPHERE_DTYPE or spheres.ndim != 1:
+            raise ValueError(f"spheres must be a one-dimensional SPHERE_DTYPE array, not {spheres.dtype} of shape {spheres.shape}")
+        arr = np.ascontiguousarray(spheres)
+        return C.c_void_p(arr.ctypes.data if len(arr) else None), len(arr), arr
+    if isinstance(spheres, C.Array):
+        if spheres._type_ is not _abi.MirtSphere:
+            raise ValueError(f"spheres must be a ctypes array of MirtSphere, not of {spheres._type_.__name__}")
+        return C.cast(spheres, C.c_void_p), len(spheres), spheres
+    if isinstance(spheres, (list, tuple)):
+        recs = [s if isinstance(s, _abi.MirtSphere) else s.to_c() if hasattr(s, "to_c") else None for s in spheres]
+        if not all(isinstance(s, _abi.MirtSphere) for s in recs):
+            raise ValueError("spheres must hold Sphere / MirtSphere records only")
+        arr = (_abi.MirtSphere * max(1, len(recs)))(*recs)
+        return C.cast(arr, C.c_void_p), len(spheres), arr
+    raise ValueError(f"spheres must be a SPHERE_DTYPE array, a ctypes MirtSphere array or a list of Sphere, not {type(spheres).__name__}")
+
+
+def _check_range(first, count) -> None:
+    for name, v in (("first", first), ("count", count)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
 
 
 def params_out_rows(params: _abi.MirtParams) -> int:
@@ -170,6 +204,26 @@ class Context:
         check(lib().mirt_ctx_bvh_read(self._h, nodes.ctypes.data_as(C.c_void_p), nodes.nbytes, recs.ctypes.data_as(C.c_void_p), recs.size,
                                       ids.ctypes.data_as(C.c_void_p), ids.size))
         return nodes, recs, ids
+
+    def update_spheres(self, first: int, spheres) -> None:
+        """mirt_ctx_update_spheres: spheres first .. first + len(spheres) of the MIRT_SCENE_HBM scene take centre and radius from
+        `spheres` (see sphere_records; material_idx is not read), the tree is refitted on the device.  Blocking."""
+        ptr, count, keep = sphere_records(spheres)
+        _check_range(first, count)
+        check(lib().mirt_ctx_update_spheres(self._h, int(first), count, ptr))
+        del keep
+
+    def update_spheres_device(self, first: int, count: int, d_ptr: int) -> None:
+        """mirt_ctx_update_spheres_device: the same from `count` 32-byte MirtSphere records in memory of this context's device at
+        address `d_ptr` (e.g. a torch tensor's data_ptr(); what was queued to produce them is waited for)."""
+        _check_range(first, count)
+        if not isinstance(d_ptr, (int, np.integer)) or isinstance(d_ptr, bool) or int(d_ptr) < 0:
+            raise ValueError(f"d_ptr must be a device address, not {d_ptr!r}")
+        check(lib().mirt_ctx_update_spheres_device(self._h, int(first), int(count), C.c_void_p(int(d_ptr))))
+
+    def bvh_refits(self) -> int:
+        """mirt_ctx_bvh_refits: successful updates since the scene was set (0 after every set_scene)."""
+        return int(lib().mirt_ctx_bvh_refits(self._h))
 
     def set_camera(self, camera: _abi.MirtGpuCamera) -> None:
         check(lib().mirt_ctx_set_camera(self._h, C.byref(camera)))

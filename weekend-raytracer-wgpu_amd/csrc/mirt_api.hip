@@ -449,6 +449,11 @@ struct MirtContext {
     MirtBvhPlan    bvh_plan{};               // of the tree in d_bvh, whichever builder made it (mirt_ctx_bvh_info)
     bool           bvh_on_device = false;    // MIRT_SCENE_BVH_DEVICE built it
     mirt::BvhDeviceScratch bvh_scratch;      // the device builder's temporary storage: grows, never shrinks
+    // mirt_ctx_update_spheres*: the schedule of a refit (prepared at the scene's first update) and the updates since the scene was set
+    std::vector<uint32_t> bvh_levels;        // a device-built tree's level ranges, kept from its build
+    mirt::BvhRefit bvh_refit;
+    mirt::BvhDeviceScratch bvh_stage;        // the records of a host update on their way to the scatter: grows with the largest count
+    uint32_t       bvh_refits = 0;
 };
 
 extern "C" {
@@ -644,7 +649,7 @@ void mirt_ctx_destroy(MirtContext* c)
     if (c->zero_stream) (void)hipStreamSynchronize(c->zero_stream);
     if (c->frame_stream_b) (void)hipStreamSynchronize(c->frame_stream_b);
     if (!c->untimed_streams.empty()) (void)hipDeviceSynchronize();      // launches without an event may still read the tables freed below
-    (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_bvh); (void)hipFree(c->bvh_scratch.d); (void)hipFree(c->d_texels);
+    (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_bvh); (void)hipFree(c->bvh_scratch.d); (void)hipFree(c->bvh_stage.d); (void)hipFree(c->d_texels);
     (void)hipFree(c->d_sky); (void)hipFree(c->d_counters); (void)hipFree(c->d_work_counter); (void)hipFree(c->d_out); (void)hipFree(c->d_accum);
     for (hipEvent_t ev : c->ev_begin) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_end) (void)hipEventDestroy(ev);
@@ -704,6 +709,8 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm, bool bvh_devi
     c->have_scene = false;
     c->fits_flat = fits_flat;
     c->hbm = hbm;
+    c->bvh_refits = 0;
+    c->bvh_refit.ready = false;
 
     // mode-specific validity is decided here once and reported by the render call that needs it
     c->pt_scene_status = MIRT_OK;
@@ -843,6 +850,7 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm, bool bvh_devi
         c->bvh_rmax = dev_bvh.r_max;
         c->bvh_plan = dev_bvh.plan;
         c->bvh_on_device = true;
+        c->bvh_levels.swap(dev_bvh.level_first);
         if (std::getenv("MIRT_BVH_TIMING"))       // tools/hbm_scene_rates.py: the parts of a device build
             std::fprintf(stderr, "mirt_bvh_device: n=%u always_ms=%.3f upload_ms=%.3f kernels_ms=%.3f levels=%u\n", s->n_spheres, dev_bvh.always_ms,
                          upload_ms, dev_bvh.kernels_ms, dev_bvh.levels);
@@ -904,6 +912,66 @@ int mirt_ctx_bvh_read(MirtContext* c, void* nodes, size_t nodes_bytes, float* re
     if (n) HIP_TRY(hipMemcpy(ids, c->d_bvh + c->bvh_off_ids, 4 * n, hipMemcpyDeviceToHost));
     return MIRT_OK;
 }
+
+// mirt_ctx_update_spheres (host pointer) and mirt_ctx_update_spheres_device
+static int update_spheres(MirtContext* c, uint32_t first, uint32_t count, const void* spheres, bool on_device)
+{
+    if (!c) return fail(MIRT_ERR_NULL_POINTER, "ctx is null");
+    if (count && !spheres) return fail(MIRT_ERR_NULL_POINTER, "spheres is null");
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if ((uint64_t)first + count > c->n_spheres)
+        return fail(MIRT_ERR_BAD_ROWS, "spheres [%u, %llu) of a scene of %u", first, (unsigned long long)first + count, c->n_spheres);
+    if (!count) return MIRT_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());      // renders may be in flight on caller streams; whatever produced a device source has finished too
+    mirt::BvhTables t;
+    t.d_bvh = c->d_bvh;
+    t.off_recs = c->bvh_off_recs;
+    t.off_ids = c->bvh_off_ids;
+    t.d_prepared = c->d_spheres;
+    t.n = c->n_spheres;
+    t.n_nodes = c->bvh_plan.n_nodes;
+    t.n_always = c->bvh_n_always;
+    t.root = c->bvh_root;
+    int rc;
+    if (!c->bvh_refit.ready &&            // once per scene; nothing of the scene is written yet
+        (rc = mirt::refit_prepare(&c->bvh_refit, t, c->bvh_on_device ? &c->bvh_levels : nullptr, c->stream, &c->bvh_scratch)) != MIRT_OK)
+        return rc;
+    // from the first write on, a failure leaves NO scene (as set_scene does)
+    c->have_scene = false;
+    float centre[3], radius, r_max, parts[3];
+    const bool timed = std::getenv("MIRT_BVH_TIMING") != nullptr;
+    if ((rc = mirt::refit_bvh_device(c->bvh_refit, t, c->stream, &c->bvh_scratch, &c->bvh_stage, first, count, spheres, on_device, centre, &radius, &r_max,
+                                     timed ? parts : nullptr)) != MIRT_OK)
+        return rc;
+    if (c->n_spheres == 3) {              // the host copy of a three-sphere scene (RenderArgs.sph3): {centre, r * r} as the device computed them
+        mirt::PreparedSphere prep[3];
+        HIP_TRY(hipMemcpy(prep, c->d_spheres, sizeof prep, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < 3; ++i)
+            for (int k = 0; k < 4; ++k) c->sph3[4 * i + k] = (&prep[i].cx)[k];
+    }
+    for (int k = 0; k < 3; ++k) c->bvh_centre[k] = centre[k];
+    c->bvh_radius = radius;
+    c->bvh_rmax = r_max;
+    ++c->bvh_refits;
+    c->have_scene = true;
+    if (timed)                            // tools/hbm_scene_rates.py --update: the parts of an update
+        std::fprintf(stderr, "mirt_bvh_refit: n=%u count=%u scatter_ms=%.3f refit_ms=%.3f bounds_ms=%.3f levels=%zu\n", c->n_spheres, count, parts[0],
+                     parts[1], parts[2], c->bvh_refit.level_first.empty() ? (size_t)0 : c->bvh_refit.level_first.size() - 1);
+    return MIRT_OK;
+}
+
+int mirt_ctx_update_spheres(MirtContext* c, uint32_t first, uint32_t count, const MirtSphere* spheres)
+{
+    return update_spheres(c, first, count, spheres, false);
+}
+
+int mirt_ctx_update_spheres_device(MirtContext* c, uint32_t first, uint32_t count, const void* d_spheres)
+{
+    return update_spheres(c, first, count, d_spheres, true);
+}
+
+uint32_t mirt_ctx_bvh_refits(const MirtContext* c) { return (c && c->have_scene && c->hbm) ? c->bvh_refits : 0u; }
 
 int mirt_ctx_set_camera(MirtContext* c, const MirtGpuCamera* cam)
 {

@@ -66,6 +66,7 @@ struct BvhDeviceResult {
     double      always_ms = 0.0;               // host: the always-tested list
     double      kernels_ms = 0.0;              // device: first launch to the tree being ready
     uint32_t    levels = 0;
+    std::vector<uint32_t> level_first;         // first inner node of every level (breadth-first numbering); the last entry = n_nodes
 };
 
 // Builds the tree of `spheres` (host copy: the always list only) from their prepared device copy `d_prepared` ([n] PreparedSphere,
@@ -73,5 +74,38 @@ struct BvhDeviceResult {
 // returns.  `always` = bvh_always_list(spheres, n).  MIRT_OK, MIRT_ERR_ALLOC or MIRT_ERR_HIP.
 int build_bvh_device(const std::vector<uint32_t>& always, uint32_t n, const void* d_prepared, void* hip_stream, BvhDeviceScratch* scratch,
                      unsigned char** d_bvh, size_t* cap_bvh, BvhDeviceResult* out);
+
+// ---- in-place updates (mirt_bvh_device.hip): mirt_ctx_update_spheres* ----
+// What a refit needs beyond the tables, prepared at the first update of a scene and dropped by every set_scene: the always-tested list
+// (ids[0 .. n_always), sorted), the level schedule, and the layout of the builder scratch while updates run:
+//   pos[n] (the inverse of ids) | order[n_nodes] (host-built trees: node indices sorted by depth) | reductions.
+// The records of a host update are staged in a buffer of their own that grows with the largest `count` seen (none for device sources).
+// A device-built tree's levels are the contiguous ranges of BvhDeviceResult.level_first; a host-built tree's are ranges of `order`.
+struct BvhRefit {
+    bool     ready = false;
+    bool     ordered = false;                  // levels index `order` instead of the nodes themselves
+    std::vector<uint32_t> level_first;
+    uint32_t n_always = 0;
+    uint32_t always[MIRT_BVH_MAX_ALWAYS] = {};
+    size_t   off_pos = 0, off_order = 0, off_part = 0, off_partd = 0, off_red = 0, off_d2 = 0;
+};
+
+// The tables of the scene a refit works on (MirtContext's fields, by value).
+struct BvhTables {
+    unsigned char* d_bvh = nullptr;            // nodes | records | ids
+    size_t         off_recs = 0, off_ids = 0;
+    void*          d_prepared = nullptr;       // [n] PreparedSphere
+    uint32_t       n = 0, n_nodes = 0, n_always = 0, root = kBvhLeaf;
+};
+
+// Prepares `st` for the tree in `t` (no write to the scene's tables).  `device_levels`: the builder's level_first of a device-built
+// tree, nullptr for a host-built one (its child references are read back once).  MIRT_OK, MIRT_ERR_ALLOC or MIRT_ERR_HIP.
+int refit_prepare(BvhRefit* st, const BvhTables& t, const std::vector<uint32_t>* device_levels, void* hip_stream, BvhDeviceScratch* scratch);
+
+// Spheres [first, first + count) take centre and radius from `src` ([count] MirtSphere, host memory or -- src_on_device -- memory of
+// this device); rr / inv_r / radius and the test records follow on the device, every child box of the tree is recomputed bottom-up and
+// the traversal bounds are reduced again.  Synchronous.  `parts_ms`, when not null: scatter, refit, bounds between events.
+int refit_bvh_device(const BvhRefit& st, const BvhTables& t, void* hip_stream, BvhDeviceScratch* scratch, BvhDeviceScratch* stage, uint32_t first,
+                     uint32_t count, const void* src, bool src_on_device, float centre[3], float* radius, float* r_max, float parts_ms[3]);
 
 }  // namespace mirt

@@ -22,10 +22,13 @@
 // Nothing here spins or waits on another block, and no value depends on the order in which blocks run.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -384,6 +387,17 @@ int grow(unsigned char** ptr, size_t* cap, size_t need)
 
 uint32_t blocks_for(uint32_t n) { return (n + kBlock - 1u) / kBlock; }
 
+// mirt_bvh.cpp: the sphere around the tree's boxes and the largest radius -- only with a finite item in the tree (else all zero)
+void finish_bounds(const float h_red[kNumRed], double h_d2, float centre[3], float* radius, float* r_max)
+{
+    for (int k = 0; k < 3; ++k) centre[k] = 0.0f;
+    *radius = *r_max = 0.0f;
+    if (h_red[6] <= h_red[9]) {
+        for (int k = 0; k < 3; ++k) centre[k] = (float)(0.5 * ((double)h_red[6 + k] + (double)h_red[9 + k]));
+        mirt::bvh_round_bounds(std::sqrt(h_d2), (double)h_red[12], radius, r_max);
+    }
+}
+
 }  // namespace
 
 int mirt::build_bvh_device(const std::vector<uint32_t>& always, uint32_t n, const void* d_prepared, void* hip_stream, BvhDeviceScratch* scratch,
@@ -443,7 +457,8 @@ int mirt::build_bvh_device(const std::vector<uint32_t>& always, uint32_t n, cons
     }
     struct EventGuard { hipEvent_t a, b; ~EventGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } guard{ ev0, ev1 };
 
-    std::vector<uint32_t> level_first;               // first node of every level; the last entry = n_nodes
+    std::vector<uint32_t>& level_first = r.level_first;   // first node of every level; the last entry = n_nodes
+    level_first.clear();
     uint32_t n_nodes = 0, max_leaf = m <= MIRT_BVH_MAX_LEAF ? m : 0u;
     float h_red[kNumRed];
     double h_d2 = 0.0;
@@ -509,10 +524,193 @@ int mirt::build_bvh_device(const std::vector<uint32_t>& always, uint32_t n, cons
     r.plan.max_leaf = max_leaf;
     r.plan.device_bytes = 64ull * n_nodes + 20ull * n;
     // mirt_bvh.cpp: the sphere around the tree's boxes and the largest radius -- only with a finite item in the tree
-    if (m && h_red[6] <= h_red[9]) {
-        for (int k = 0; k < 3; ++k) r.centre[k] = (float)(0.5 * ((double)h_red[6 + k] + (double)h_red[9 + k]));
-        bvh_round_bounds(std::sqrt(h_d2), (double)h_red[12], &r.radius, &r.r_max);
-    }
+    if (m) finish_bounds(h_red, h_d2, r.centre, &r.radius, &r.r_max);
     *out = r;
+    return MIRT_OK;
+}
+
+// ---- in-place updates: mirt_ctx_update_spheres*  ----
+// The exactness argument never uses the tree's shape, so moved spheres keep the topology, the ids table and the always-tested list of
+// the scene as it was set: 1. scatter the new centres and radii into the prepared spheres and the test records, 2. recompute every
+// child box bottom-up, one launch per level (no atomics, nothing waits on another block), 3. reduce the traversal bounds again in the
+// builder's fixed order.  Works on a tree of either builder.
+namespace {
+
+// pos[ids[j]] = j: the record of every sphere
+__global__ __launch_bounds__(kBlock) void bvh_pos_kernel(const uint32_t* ids, uint32_t n, uint32_t* pos)
+{
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j < n) pos[ids[j]] = j;
+}
+
+// src: [count] MirtSphere (8 words: centre[4], radius, material_idx, 2 x pad); only the centre and the radius are read.
+// r * r and 1.0f / r are the single IEEE operations of set_scene (this file is compiled without contraction, with the correctly
+// rounded division).
+__global__ __launch_bounds__(kBlock) void bvh_scatter_kernel(const float* src, uint32_t first, uint32_t count, const uint32_t* pos,
+                                                             mirt::PreparedSphere* sph, float4* recs)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const float* in = src + 8ull * i;
+    const float cx = in[0], cy = in[1], cz = in[2], r = in[4];
+    const float rr = r * r;
+    const uint32_t id = first + i;
+    mirt::PreparedSphere& o = sph[id];
+    o.cx = cx; o.cy = cy; o.cz = cz; o.rr = rr;
+    o.inv_r = 1.0f / r;
+    o.radius = r;
+    recs[pos[id]] = make_float4(cx, cy, cz, rr);
+}
+
+// child_box with the spheres of a leaf taken from the ids table (ref's low bits index the records, always list included)
+__device__ inline void refit_child_box(uint32_t ref, const mirt::BvhNode* nodes, const uint32_t* ids, const mirt::PreparedSphere* sph, float lo[3], float hi[3])
+{
+    for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+    if (ref & mirt::kBvhLeaf) {
+        const uint32_t j0 = ref & 0xffffffu, cnt = (ref >> 24) & 0x7fu;
+        for (uint32_t j = j0; j < j0 + cnt; ++j) {
+            float l[3], h[3], c[3];
+            item_box(sph[ids[j]], l, h, c);
+            for (int k = 0; k < 3; ++k) { lo[k] = min_lt(lo[k], l[k]); hi[k] = max_lt(hi[k], h[k]); }
+        }
+    } else {
+        const mirt::BvhNode& nd = nodes[ref];
+        for (int k = 0; k < 3; ++k) { lo[k] = min_lt(nd.lmin[k], nd.rmin[k]); hi[k] = max_lt(nd.lmax[k], nd.rmax[k]); }
+    }
+}
+
+// one level: node order[first + i] (order == nullptr: node first + i); its children's boxes are finished (deeper levels ran before)
+__global__ __launch_bounds__(kBlock) void bvh_refit_kernel(mirt::BvhNode* nodes, const uint32_t* order, uint32_t first, uint32_t count, const uint32_t* ids,
+                                                           const mirt::PreparedSphere* sph)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t g = order ? order[first + i] : first + i;
+    mirt::BvhNode nd = nodes[g];
+    refit_child_box(nd.left, nodes, ids, sph, nd.lmin, nd.lmax);
+    refit_child_box(nd.right, nodes, ids, sph, nd.rmin, nd.rmax);
+    nodes[g] = nd;
+}
+
+}  // namespace
+
+int mirt::refit_prepare(BvhRefit* st, const BvhTables& t, const std::vector<uint32_t>* device_levels, void* hip_stream, BvhDeviceScratch* scratch)
+{
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    BvhRefit s;
+    s.n_always = t.n_always;
+    const uint32_t* ids = reinterpret_cast<const uint32_t*>(t.d_bvh + t.off_ids);
+    if (t.n_always > MIRT_BVH_MAX_ALWAYS || t.n_always > t.n) return mirt::set_error(MIRT_ERR_HIP, "refit: an always-tested list of %u", t.n_always);
+    if (t.n_always) BVH_HIP_TRY(hipMemcpy(s.always, ids, 4ull * t.n_always, hipMemcpyDeviceToHost));
+    std::sort(s.always, s.always + s.n_always);
+    std::vector<uint32_t> order;
+    try {
+        if (device_levels) {
+            s.level_first = *device_levels;
+        } else if (t.n_nodes) {
+            // a host-built tree: {left, right} of every node, once; breadth-first from the root gives the nodes sorted by depth
+            std::vector<uint32_t> kids(2ull * t.n_nodes);
+            BVH_HIP_TRY(hipMemcpy2D(kids.data(), 8, t.d_bvh + offsetof(BvhNode, left), sizeof(BvhNode), 8, t.n_nodes, hipMemcpyDeviceToHost));
+            order.reserve(t.n_nodes);
+            if ((t.root & kBvhLeaf) || t.root >= t.n_nodes) return mirt::set_error(MIRT_ERR_HIP, "refit: root %#x of a tree of %u nodes", t.root, t.n_nodes);
+            order.push_back(t.root);
+            s.level_first.push_back(0u);
+            size_t level_begin = 0;
+            while (level_begin < order.size()) {
+                const size_t level_end = order.size();
+                for (size_t q = level_begin; q < level_end; ++q)
+                    for (int side = 0; side < 2; ++side) {
+                        const uint32_t ref = kids[2ull * order[q] + side];
+                        if (ref & kBvhLeaf) continue;
+                        if (ref >= t.n_nodes || order.size() >= t.n_nodes)
+                            return mirt::set_error(MIRT_ERR_HIP, "refit: child reference %u of node %u in a tree of %u nodes", ref, order[q], t.n_nodes);
+                        order.push_back(ref);
+                    }
+                level_begin = level_end;
+                s.level_first.push_back((uint32_t)level_end);
+            }
+            s.ordered = true;
+        }
+    } catch (const std::bad_alloc&) {
+        return mirt::set_error(MIRT_ERR_ALLOC, "out of host memory preparing the refit of %u nodes", t.n_nodes);
+    }
+    const size_t cap_n = t.n ? t.n : 1u;
+    size_t off = 0;
+    s.off_pos = off;    off += align256(4ull * cap_n);
+    s.off_order = off;  off += align256(4ull * (order.size() ? order.size() : 1u));
+    s.off_part = off;   off += align256(sizeof(float) * kNumRed * kReduceBlocks);
+    s.off_partd = off;  off += align256(sizeof(double) * kReduceBlocks);
+    s.off_red = off;    off += align256(sizeof(float) * 16u);
+    s.off_d2 = off;     off += align256(sizeof(double));
+    int rc;
+    if ((rc = grow(&scratch->d, &scratch->cap, off)) != MIRT_OK) return rc;
+    if (!order.empty()) BVH_HIP_TRY(hipMemcpy(scratch->d + s.off_order, order.data(), 4ull * order.size(), hipMemcpyHostToDevice));
+    if (t.n) {
+        bvh_pos_kernel<<<blocks_for(t.n), kBlock, 0, stream>>>(ids, t.n, reinterpret_cast<uint32_t*>(scratch->d + s.off_pos));
+        BVH_HIP_TRY(hipGetLastError());
+        BVH_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    s.ready = true;
+    *st = std::move(s);
+    return MIRT_OK;
+}
+
+int mirt::refit_bvh_device(const BvhRefit& st, const BvhTables& t, void* hip_stream, BvhDeviceScratch* scratch, BvhDeviceScratch* stage, uint32_t first,
+                           uint32_t count, const void* src, bool src_on_device, float centre[3], float* radius, float* r_max, float parts_ms[3])
+{
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned char* S = scratch->d;
+    mirt::PreparedSphere* sph = static_cast<mirt::PreparedSphere*>(t.d_prepared);
+    BvhNode* nodes = reinterpret_cast<BvhNode*>(t.d_bvh);
+    const uint32_t* ids = reinterpret_cast<const uint32_t*>(t.d_bvh + t.off_ids);
+    const uint32_t* order = st.ordered ? reinterpret_cast<const uint32_t*>(S + st.off_order) : nullptr;
+    float* partials = reinterpret_cast<float*>(S + st.off_part);
+    double* partials_d = reinterpret_cast<double*>(S + st.off_partd);
+    float* red = reinterpret_cast<float*>(S + st.off_red);
+    double* d2 = reinterpret_cast<double*>(S + st.off_d2);
+    AlwaysList al{};
+    al.n = st.n_always;
+    for (uint32_t j = 0; j < al.n; ++j) al.idx[j] = st.always[j];
+    const uint32_t m = t.n - al.n;
+
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } guard{ ev };
+    if (parts_ms) for (int k = 0; k < 4; ++k) BVH_HIP_TRY(hipEventCreate(&ev[k]));
+
+    const float* d_src = static_cast<const float*>(src);
+    if (!src_on_device) {                                  // staged in a buffer that grows with the largest host update
+        int rc;
+        if ((rc = grow(&stage->d, &stage->cap, 32ull * count)) != MIRT_OK) return rc;
+        BVH_HIP_TRY(hipMemcpy(stage->d, src, 32ull * count, hipMemcpyHostToDevice));
+        d_src = reinterpret_cast<const float*>(stage->d);
+    }
+    if (parts_ms) (void)hipEventRecord(ev[0], stream);
+    bvh_scatter_kernel<<<blocks_for(count), kBlock, 0, stream>>>(d_src, first, count, reinterpret_cast<const uint32_t*>(S + st.off_pos), sph,
+                                                                 reinterpret_cast<float4*>(t.d_bvh + t.off_recs));
+    if (parts_ms) (void)hipEventRecord(ev[1], stream);
+    for (size_t l = st.level_first.size(); l-- > 1;) {     // boxes, from the deepest level up
+        const uint32_t lf = st.level_first[l - 1], cnt = st.level_first[l] - lf;
+        if (cnt) bvh_refit_kernel<<<blocks_for(cnt), kBlock, 0, stream>>>(nodes, order, lf, cnt, ids, sph);
+    }
+    if (parts_ms) (void)hipEventRecord(ev[2], stream);
+    float h_red[kNumRed];
+    double h_d2 = 0.0;
+    if (m) {
+        const uint32_t rb = blocks_for(m) < kReduceBlocks ? blocks_for(m) : kReduceBlocks;
+        bvh_reduce_kernel<<<rb, kBlock, 0, stream>>>(sph, m, al, partials);
+        bvh_reduce_final_kernel<<<1, kBlock, 0, stream>>>(partials, rb, red);
+        bvh_corner_kernel<<<rb, kBlock, 0, stream>>>(sph, m, al, red, partials_d);
+        bvh_corner_final_kernel<<<1, kBlock, 0, stream>>>(partials_d, rb, d2);
+        BVH_HIP_TRY(hipGetLastError());
+        BVH_HIP_TRY(hipMemcpyAsync(h_red, red, sizeof h_red, hipMemcpyDeviceToHost, stream));
+        BVH_HIP_TRY(hipMemcpyAsync(&h_d2, d2, sizeof h_d2, hipMemcpyDeviceToHost, stream));
+    }
+    BVH_HIP_TRY(hipGetLastError());
+    if (parts_ms) (void)hipEventRecord(ev[3], stream);
+    BVH_HIP_TRY(hipStreamSynchronize(stream));
+    if (parts_ms) for (int k = 0; k < 3; ++k) { parts_ms[k] = 0.0f; (void)hipEventElapsedTime(&parts_ms[k], ev[k], ev[k + 1]); }
+    for (int k = 0; k < 3; ++k) centre[k] = 0.0f;
+    *radius = *r_max = 0.0f;
+    if (m) finish_bounds(h_red, h_d2, centre, radius, r_max);
     return MIRT_OK;
 }

@@ -394,6 +394,22 @@ int mirt_node_set_scene_ex(MirtNode* nd, const MirtScene* scene, uint32_t flags)
     return MIRT_OK;
 }
 
+int mirt_node_update_spheres(MirtNode* nd, uint32_t first, uint32_t count, const MirtSphere* spheres)
+{
+    if (!nd) return mirt::set_error(MIRT_ERR_NULL_POINTER, "node is null");
+    if (count && !spheres) return mirt::set_error(MIRT_ERR_NULL_POINTER, "spheres is null");
+    if (!nd->have_scene) return mirt::set_error(MIRT_ERR_NO_SCENE, "mirt_node_set_scene has not succeeded");
+    for (uint32_t i = 0; i < nd->n; ++i) {
+        const int rc = mirt_ctx_update_spheres(nd->ctx[i], first, count, spheres);
+        if (rc == MIRT_OK) continue;
+        // every member holds the same scene, so an argument error comes from the first member and has changed nothing; any other
+        // failure leaves members that disagree
+        if (i > 0 || rc == MIRT_ERR_HIP || rc == MIRT_ERR_ALLOC) nd->have_scene = false;
+        return rc;
+    }
+    return MIRT_OK;
+}
+
 int mirt_node_set_camera(MirtNode* nd, const MirtGpuCamera* camera)
 {
     if (!nd || !camera) return mirt::set_error(MIRT_ERR_NULL_POINTER, "node/camera is null");

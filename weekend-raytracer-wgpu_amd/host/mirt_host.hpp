@@ -29,15 +29,38 @@ inline void check(int rc) { if (rc != MIRT_OK) throw MirtError(rc, mirt_last_err
 
 // mirt_ctx_set_scene, and a world the LDS layouts refuse (MIRT_ERR_SCENE_TOO_LARGE) set again with MIRT_SCENE_HBM: the reference's
 // `Layer::set_data` takes any `Vec<Box<Sphere>>`
-inline int set_scene_any_size(MirtContext* ctx, const MirtScene& sc)
+// (*hbm, when given: whether the scene went to device memory -- its spheres can then be moved in place, update_spheres below)
+inline int set_scene_any_size(MirtContext* ctx, const MirtScene& sc, bool* hbm = nullptr)
 {
     const int rc = mirt_ctx_set_scene(ctx, &sc);
+    if (hbm) *hbm = rc == MIRT_ERR_SCENE_TOO_LARGE;
     return rc == MIRT_ERR_SCENE_TOO_LARGE ? mirt_ctx_set_scene_ex(ctx, &sc, MIRT_SCENE_HBM) : rc;
 }
 // mirt_ctx_set_scene_ex: flags = MIRT_SCENE_*
 inline void set_scene(MirtContext* ctx, const MirtScene& sc, uint32_t flags) { check(mirt_ctx_set_scene_ex(ctx, &sc, flags)); }
 // mirt_ctx_bvh_info: the tree of the context's MIRT_SCENE_HBM scene (built on the host, or on the device with MIRT_SCENE_BVH_DEVICE)
 inline MirtBvhInfo bvh_info(MirtContext* ctx) { MirtBvhInfo info; check(mirt_ctx_bvh_info(ctx, &info)); return info; }
+// mirt_ctx_update_spheres: spheres first .. first + count of a MIRT_SCENE_HBM scene take centre and radius from `spheres` (material_idx
+// is not read); the BVH is refitted on the device.  mirt_ctx_bvh_refits counts the updates since the scene was set.
+inline void update_spheres(MirtContext* ctx, uint32_t first, const std::vector<MirtSphere>& spheres)
+{
+    check(mirt_ctx_update_spheres(ctx, first, (uint32_t)spheres.size(), spheres.data()));
+}
+// the same from records in memory of the context's device
+inline void update_spheres_device(MirtContext* ctx, uint32_t first, uint32_t count, const void* d_spheres)
+{
+    check(mirt_ctx_update_spheres_device(ctx, first, count, d_spheres));
+}
+inline uint32_t bvh_refits(const MirtContext* ctx) { return mirt_ctx_bvh_refits(ctx); }
+// move_spheres of Layer / Raytracer: held[first ..] take centre and radius of `spheres` and keep their material
+inline void move_held_spheres(std::vector<MirtSphere>& held, uint32_t first, const std::vector<MirtSphere>& spheres)
+{
+    if ((uint64_t)first + spheres.size() > held.size()) throw MirtError(MIRT_ERR_BAD_ROWS, "move_spheres: range beyond the scene's spheres");
+    for (size_t i = 0; i < spheres.size(); ++i) {
+        for (int k = 0; k < 4; ++k) held[first + i].center[k] = spheres[i].center[k];
+        held[first + i].radius = spheres[i].radius;
+    }
+}
 
 // Angle — angle.rs:1-50
 class Angle {
@@ -236,18 +259,28 @@ public:
     // layer.rs:264-282 — the hot path: one FFI call
     void set_data(const RenderParams& rp)
     {
-        const uint32_t w = (uint32_t)vp_size[0], h = (uint32_t)vp_size[1];
         if (!ctx_) check(mirt_ctx_create(device_, &ctx_));
-        MirtScene sc{};
-        sc.camera = &camera;
-        sc.spheres = world.data(); sc.n_spheres = (uint32_t)world.size();
-        sc.materials = material_data_.data(); sc.n_materials = (uint32_t)material_data_.size();
-        sc.texels = global_texture_data_.data(); sc.n_texels = global_texture_data_.size() / 3;
-        check(set_scene_any_size(ctx_, sc));               // a world beyond the LDS budget: MIRT_SCENE_HBM
-        MirtParams p{};
-        p.width = w; p.height = h; p.spp = rp.sampling.num_samples_per_pixel; p.mode = MIRT_MODE_PARITY;
-        rgba_.assign((size_t)w * h * 4, 0);
-        check(mirt_ctx_render(ctx_, &p, rgba_.data(), rgba_.size()));
+        upload(world);
+        render(rp);
+    }
+
+    // Spheres first .. of `world` take centre and radius of `spheres` (they keep their material).  After a set_data whose world went to
+    // device memory (MIRT_SCENE_HBM) the resident scene is updated in place and its BVH refitted; any other resident scene is set again;
+    // before the first set_data only `world` changes.  With `rp` the image is rendered again, as set_data does.  `world` changes only
+    // when the device call succeeded.
+    void move_spheres(uint32_t first, const std::vector<MirtSphere>& spheres, const RenderParams* rp = nullptr)
+    {
+        std::vector<MirtSphere> moved = world;
+        move_held_spheres(moved, first, spheres);
+        if (ctx_ && hbm_) {
+            const int rc = mirt_ctx_update_spheres(ctx_, first, (uint32_t)spheres.size(), spheres.data());
+            if (rc != MIRT_OK && rc != MIRT_ERR_BAD_ROWS && rc != MIRT_ERR_NULL_POINTER) hbm_ = false;   // no scene any more: the next call sets one
+            check(rc);
+        } else if (ctx_) {
+            upload(moved);
+        }
+        world.swap(moved);
+        if (ctx_ && rp) render(*rp);
     }
 
     // layer.rs:182-186: ImageBuffer<Rgb<u8>> view
@@ -270,9 +303,30 @@ public:
     const std::vector<MirtMaterial>& material_data() const { return material_data_; }
     const std::vector<float>& global_texture_data() const { return global_texture_data_; }
 
+    MirtContext* context() const { return ctx_; }      // nullptr before the first set_data
+
 private:
+    void upload(const std::vector<MirtSphere>& spheres)
+    {
+        MirtScene sc{};
+        sc.camera = &camera;
+        sc.spheres = spheres.data(); sc.n_spheres = (uint32_t)spheres.size();
+        sc.materials = material_data_.data(); sc.n_materials = (uint32_t)material_data_.size();
+        sc.texels = global_texture_data_.data(); sc.n_texels = global_texture_data_.size() / 3;
+        hbm_ = false;
+        check(set_scene_any_size(ctx_, sc, &hbm_));        // a world beyond the LDS budget: MIRT_SCENE_HBM
+    }
+    void render(const RenderParams& rp)
+    {
+        const uint32_t w = (uint32_t)vp_size[0], h = (uint32_t)vp_size[1];
+        MirtParams p{};
+        p.width = w; p.height = h; p.spp = rp.sampling.num_samples_per_pixel; p.mode = MIRT_MODE_PARITY;
+        rgba_.assign((size_t)w * h * 4, 0);
+        check(mirt_ctx_render(ctx_, &p, rgba_.data(), rgba_.size()));
+    }
     int device_;
     MirtContext* ctx_ = nullptr;
+    bool hbm_ = false;                                   // ctx_ holds a MIRT_SCENE_HBM scene
     std::vector<MirtMaterial> material_data_;
     std::vector<float> global_texture_data_;
     std::vector<uint8_t> rgba_;
@@ -382,6 +436,26 @@ public:
         accumulated_ = -1;                                                 // render_progress.reset()
     }
 
+    // Spheres first .. of the scene take centre and radius of `spheres` (they keep their material): in place, with a refit of the BVH, when
+    // the scene is in device memory (MIRT_SCENE_HBM); any other scene is set again.  The accumulation restarts (render_progress.reset()).
+    // The held spheres change only when the device call succeeded.
+    void move_spheres(uint32_t first, const std::vector<MirtSphere>& spheres)
+    {
+        std::vector<MirtSphere> moved = spheres_;
+        move_held_spheres(moved, first, spheres);
+        if (hbm_) {
+            const int rc = node_ ? mirt_node_update_spheres(node_, first, (uint32_t)spheres.size(), spheres.data())
+                                 : mirt_ctx_update_spheres(ctx_, first, (uint32_t)spheres.size(), spheres.data());
+            if (rc != MIRT_OK && rc != MIRT_ERR_BAD_ROWS && rc != MIRT_ERR_NULL_POINTER) hbm_ = false;   // no scene any more: the next call sets one
+            check(rc);
+            spheres_.swap(moved);
+        } else {
+            spheres_.swap(moved);
+            try { upload(); } catch (...) { spheres_.swap(moved); throw; }
+        }
+        accumulated_ = -1;
+    }
+
     // all max_samples_per_pixel samples in one launch
     std::vector<uint8_t> render(uint64_t seed = 0, uint32_t flags = 0)
     {
@@ -455,10 +529,11 @@ private:
         sc.sky = have_sky_ ? &sky_ : nullptr;
         if (node_) {                                       // a world beyond the LDS budget: MIRT_SCENE_HBM
             int rc = mirt_node_set_scene(node_, &sc);
-            if (rc == MIRT_ERR_SCENE_TOO_LARGE) rc = mirt_node_set_scene_ex(node_, &sc, MIRT_SCENE_HBM);
+            hbm_ = rc == MIRT_ERR_SCENE_TOO_LARGE;
+            if (hbm_) rc = mirt_node_set_scene_ex(node_, &sc, MIRT_SCENE_HBM);
             check(rc);
         } else {
-            check(set_scene_any_size(ctx_, sc));
+            check(set_scene_any_size(ctx_, sc, &hbm_));
         }
     }
     RenderParams rp_;
@@ -471,6 +546,7 @@ private:
     MirtContext* ctx_ = nullptr;
     MirtNode* node_ = nullptr;
     int accumulated_ = -1;
+    bool hbm_ = false;                                   // the context / node holds a MIRT_SCENE_HBM scene
 };
 
 }  // namespace mirt_host

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import check, lib
-from .context import Context, SceneData, _stream_arg, params_out_rows, scene_flags
+from .context import Context, SceneData, _check_range, _stream_arg, params_out_rows, scene_flags, sphere_records
 
 
 class _MemberContext(Context):
@@ -66,6 +66,13 @@ class Node:
         else:
             check(lib().mirt_node_set_scene(self._h, C.byref(c)))
         self._scene = scene
+
+    def update_spheres(self, first: int, spheres) -> None:
+        """mirt_node_update_spheres: Context.update_spheres on every member (host records only)."""
+        ptr, count, keep = sphere_records(spheres)
+        _check_range(first, count)
+        check(lib().mirt_node_update_spheres(self._h, int(first), count, ptr))
+        del keep
 
     def set_camera(self, camera: _abi.MirtGpuCamera) -> None:
         check(lib().mirt_node_set_camera(self._h, C.byref(camera)))

@@ -356,6 +356,39 @@ _ASSET_FIXTURES = {
 }
 
 
+def _moved(held: Sequence[Sphere], first, spheres: Sequence[Sphere]) -> Tuple[int, List[Sphere]]:
+    """move_spheres: (first as an int, the new spheres first .. first + len(spheres)) -- centre and radius from `spheres`, the
+    material they had."""
+    spheres = list(spheres)
+    if not isinstance(first, (int, np.integer)) or isinstance(first, bool) or first < 0 or int(first) + len(spheres) > len(held):
+        raise ValueError(f"spheres [{first}, {first}+{len(spheres)}) of a scene of {len(held)}")
+    if not all(isinstance(s, Sphere) for s in spheres):
+        raise ValueError("spheres must be Sphere objects")
+    first = int(first)
+    return first, [Sphere(s.center, s.radius, held[first + i].material_idx) for i, s in enumerate(spheres)]
+
+
+def _spliced(held: Sequence[Sphere], first: int, moved: Sequence[Sphere]) -> List[Sphere]:
+    out = list(held)
+    out[first:first + len(moved)] = moved
+    return out
+
+
+def _move_resident(owner, target, first: int, moved: Sequence[Sphere], scene_data) -> None:
+    """The device side of move_spheres of `owner` (a Layer or a Raytracer) on `target` (its Context or Node): an HBM scene is updated
+    in place, any other is set again from `scene_data()` (the moved scene).  `owner._hbm` says which the target holds afterwards; a
+    failure other than a refused argument may leave the target without a scene, so the owner's next move sets one."""
+    if not owner._hbm:
+        owner._hbm = set_scene_any_size(target, scene_data())
+        return
+    try:
+        target.update_spheres(first, moved)
+    except MirtError as e:
+        if e.status not in (_abi.MIRT_ERR_BAD_ROWS, _abi.MIRT_ERR_NULL_POINTER):
+            owner._hbm = False
+        raise
+
+
 def _jpeg_check(rc: int) -> None:
     if rc != 0:
         raise MirtError(rc, (lib().mirt_jpeg_last_error() or b"").decode())
@@ -407,6 +440,7 @@ class Layer:
         self._devices = list(devices) if devices is not None else None
         self._node: Optional[Node] = None
         self._rgba: Optional[np.ndarray] = None
+        self._hbm = False               # the context / node holds a MIRT_SCENE_HBM scene (move_spheres updates it in place)
         self.last_stats: Optional[dict] = None
 
     @staticmethod
@@ -448,15 +482,33 @@ class Layer:
         if self._devices is not None:
             if self._node is None:
                 self._node = Node(self._devices)
-            set_scene_any_size(self._node, self.scene_data())
+            self._hbm = set_scene_any_size(self._node, self.scene_data())
             self._rgba = self._node.render(params)
             self.last_stats = self._node.stats()
             return
         if self._ctx is None:
             self._ctx = Context(self._device)
-        set_scene_any_size(self._ctx, self.scene_data())       # worlds beyond the LDS budget: MIRT_SCENE_HBM
+        self._hbm = set_scene_any_size(self._ctx, self.scene_data())       # worlds beyond the LDS budget: MIRT_SCENE_HBM
         self._rgba = self._ctx.render(params)
         self.last_stats = self._ctx.stats()
+
+    def move_spheres(self, first: int, spheres: Sequence[Sphere], render_params: Optional[RenderParams] = None) -> None:
+        """Spheres first .. first + len(spheres) of `world` take the centre and the radius of `spheres` (they keep their material).
+        After a set_data whose world went to device memory (MIRT_SCENE_HBM) the resident scene is updated in place and its BVH
+        refitted (mirt_ctx_update_spheres / mirt_node_update_spheres); any other resident scene is set again; before the first
+        set_data only `world` changes.  With `render_params` the image is rendered again, as set_data does.  `world` changes only
+        when the device call succeeded."""
+        first, moved = _moved(self.world, first, spheres)
+        target = self._node if self._devices is not None else self._ctx
+        if target is not None:
+            _move_resident(self, target, first, moved,
+                           lambda: SceneData(self.camera.c, [s.to_c() for s in _spliced(self.world, first, moved)], list(self.material_data),
+                                             self.global_texture_data))
+        self.world[first:first + len(moved)] = moved
+        if target is not None and render_params is not None:
+            w, h = int(self.vp_size[0]), int(self.vp_size[1])
+            self._rgba = target.render(make_params(w, h, render_params.sampling.num_samples_per_pixel, mode=_abi.MIRT_MODE_PARITY))
+            self.last_stats = target.stats()
 
     def register_texture(self) -> np.ndarray:         # layer.rs:150-176: the RGBA8 bytes imgui would receive
         if self._rgba is None:
@@ -520,7 +572,7 @@ class Raytracer:
         self.sky_state = sky_state
         self._ctx = Node(list(devices)) if devices is not None else Context(device)    # the same calls on either
         self._on_node = devices is not None
-        set_scene_any_size(self._ctx, self.scene_data())           # worlds beyond the LDS budget: MIRT_SCENE_HBM
+        self._hbm = set_scene_any_size(self._ctx, self.scene_data())   # worlds beyond the LDS budget: MIRT_SCENE_HBM
         self._frames_queued = 0         # render_frame_device: frame k goes to frame stream k & 1
         self.last_stats: Optional[dict] = None
         self._accumulated = None        # RenderProgress (mod.rs:615-679): None = reset pending
@@ -594,6 +646,18 @@ class Raytracer:
         self.camera = GpuCamera.new(render_params.camera, render_params.viewport_size)
         self._ctx.set_camera(self.camera.c)
         self._accumulated = None                               # render_progress.reset() mod.rs:385
+
+    def move_spheres(self, first: int, spheres: Sequence[Sphere]) -> None:
+        """Spheres first .. first + len(spheres) of the scene take the centre and the radius of `spheres` (they keep their material).
+        A scene in device memory (MIRT_SCENE_HBM) is updated in place and its BVH refitted on the device (mirt_ctx_update_spheres);
+        any other scene is set again.  The progressive accumulation restarts, as the reference's does on any scene change
+        (`render_progress.reset()`).  The held spheres change only when the device call succeeded."""
+        first, moved = _moved(self.spheres, first, spheres)
+        _move_resident(self, self._ctx, first, moved,
+                       lambda: SceneData(self.camera.c, [s.to_c() for s in _spliced(self.spheres, first, moved)], list(self.material_data),
+                                         self.global_texture_data, self.sky_state))
+        self.spheres[first:first + len(moved)] = moved
+        self._accumulated = None
 
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
         """All `max_samples_per_pixel` samples in one launch -> RGBA8 [h][w][4].
