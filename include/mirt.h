@@ -405,8 +405,30 @@ int mirt_ctx_bvh_read(MirtContext* ctx, void* nodes, size_t nodes_bytes, float* 
  * nothing; a failure after the first write leaves the context with no scene. */
 int      mirt_ctx_update_spheres(MirtContext* ctx, uint32_t first, uint32_t count, const MirtSphere* spheres);
 int      mirt_ctx_update_spheres_device(MirtContext* ctx, uint32_t first, uint32_t count, const void* d_spheres);
-/* Successful updates (count > 0) since the scene was set; 0 after every set_scene*, and for a null ctx. */
+/* Successful updates (count > 0) since the scene was set; 0 after every set_scene* and set_spheres*, and for a null ctx. */
 uint32_t mirt_ctx_bvh_refits(const MirtContext* ctx);
+/* ---- replacing the spheres of a MIRT_SCENE_HBM scene ----
+ * The context's MIRT_SCENE_HBM scene gets a new sphere table of `n_spheres` records (MirtSphere, 32 bytes each): center[0..3], radius and
+ * -- unlike update_spheres -- material_idx are read; center[3] and _pad are NOT READ.  The count may differ from the resident one and
+ * may be 0 (then the pointer may be null).  Camera, materials, texels and sky stay resident and are not uploaded again.  Everything
+ * set_scene derives from the spheres is derived again ON THE DEVICE: the material-index check, the census of scatter routines, the
+ * always-tested list (the rule above, entry for entry), the prepared spheres, and the tree by the MIRT_SCENE_BVH_DEVICE builder -- whichever
+ * builder made the tree before.  Afterwards the context cannot be told from one that received a fresh
+ * mirt_ctx_set_scene_ex(MIRT_SCENE_HBM | MIRT_SCENE_BVH_DEVICE) of a scene with these spheres and what it already holds: the bytes of
+ * mirt_ctx_bvh_read, mirt_ctx_bvh_info (built_on_device = 1), images, sums, work counters, mirt_ctx_last_kernel, the status of render
+ * calls, mirt_ctx_bvh_refits == 0.
+ * Like set_scene the call first waits for the device -- renders in flight on caller streams, and whatever was queued to produce
+ * d_spheres -- and returns when the tree is ready.  The accumulation buffer is not touched (reset it, as after set_camera).
+ *   mirt_ctx_set_spheres          reads `spheres` from host memory (one copy to the device, then the same path);
+ *   mirt_ctx_set_spheres_device   reads `d_spheres` from memory of the context's device (4-byte aligned): nothing leaves the device but
+ *                                 the census word and the list (under 300 bytes).
+ * MIRT_ERR_NULL_POINTER: ctx is null, or the records are with n_spheres > 0;  MIRT_ERR_NO_SCENE: no scene, or not a MIRT_SCENE_HBM one;
+ * MIRT_ERR_SCENE_TOO_LARGE: above MIRT_SCENE_HBM_MAX_SPHERES, before any sphere is read.  An argument error changes nothing; a failure
+ * after the first write leaves the context with no scene.  A material_idx >= n_materials does not refuse the call: as after set_scene
+ * the path-traced render calls answer MIRT_ERR_MATERIAL_INDEX until a set_spheres* or set_scene* without one; the materials' own
+ * verdict (MIRT_ERR_TEXEL_RANGE) stays as set_scene found it. */
+int      mirt_ctx_set_spheres(MirtContext* ctx, const MirtSphere* spheres, uint32_t n_spheres);
+int      mirt_ctx_set_spheres_device(MirtContext* ctx, const void* d_spheres, uint32_t n_spheres);
 
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by
@@ -575,6 +597,8 @@ int  mirt_node_set_scene(MirtNode* node, const MirtScene* scene);
 int  mirt_node_set_scene_ex(MirtNode* node, const MirtScene* scene, uint32_t flags);
 /* mirt_ctx_update_spheres on every member (host pointer).  If a member fails, the node has no scene until a set_scene* succeeds. */
 int  mirt_node_update_spheres(MirtNode* node, uint32_t first, uint32_t count, const MirtSphere* spheres);
+/* mirt_ctx_set_spheres on every member (host pointer; a device pointer belongs to one device).  The same rule on a failing member. */
+int  mirt_node_set_spheres(MirtNode* node, const MirtSphere* spheres, uint32_t n_spheres);
 /* mirt_ctx_set_camera on every member (host-side only). */
 int  mirt_node_set_camera(MirtNode* node, const MirtGpuCamera* camera);
 /* Render the band into HOST memory (mirt_params_out_rows(params) * width * 4 bytes); blocking. */

@@ -263,6 +263,8 @@ extern "C" {
     pub fn mirt_ctx_update_spheres(ctx: *mut MirtContext, first: u32, count: u32, spheres: *const MirtSphere) -> c_int;
     pub fn mirt_ctx_update_spheres_device(ctx: *mut MirtContext, first: u32, count: u32, d_spheres: *const c_void) -> c_int;
     pub fn mirt_ctx_bvh_refits(ctx: *const MirtContext) -> u32;
+    pub fn mirt_ctx_set_spheres(ctx: *mut MirtContext, spheres: *const MirtSphere, n_spheres: u32) -> c_int;
+    pub fn mirt_ctx_set_spheres_device(ctx: *mut MirtContext, d_spheres: *const c_void, n_spheres: u32) -> c_int;
     pub fn mirt_ctx_set_camera(ctx: *mut MirtContext, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_ctx_render(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
@@ -292,6 +294,7 @@ extern "C" {
     pub fn mirt_node_set_scene(node: *mut MirtNode, scene: *const MirtScene) -> c_int;
     pub fn mirt_node_set_scene_ex(node: *mut MirtNode, scene: *const MirtScene, flags: u32) -> c_int;
     pub fn mirt_node_update_spheres(node: *mut MirtNode, first: u32, count: u32, spheres: *const MirtSphere) -> c_int;
+    pub fn mirt_node_set_spheres(node: *mut MirtNode, spheres: *const MirtSphere, n_spheres: u32) -> c_int;
     pub fn mirt_node_set_camera(node: *mut MirtNode, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_node_render(node: *mut MirtNode, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_node_render_device(node: *mut MirtNode, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;

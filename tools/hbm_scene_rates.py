@@ -19,7 +19,13 @@
            nodes per ray after every small sphere moved by up to 0.25, 1 and 4 median radii in x and z -- the refitted tree against
            a fresh device tree and a fresh host tree of the same world: after how much motion a rebuild pays
 
-usage: python tools/hbm_scene_rates.py [--reps 5] [--fields 10000,100000,1000000] [--bvh host|device|both] [--soup 100000] [--update]
+  --set-spheres a whole new sphere table for a resident scene (mirt_ctx_set_spheres / _device) on the same fields, one process per
+           field (give one --fields value per run): the three routes to a device-built tree of the same world, alternating on two
+           contexts -- (a) mirt_ctx_set_scene_ex(HBM | BVH_DEVICE) from host memory, (b) mirt_ctx_set_spheres from host memory,
+           (c) mirt_ctx_set_spheres_device from a torch buffer; wall time, median of --reps after a warm-up; the parts the library
+           reports (MIRT_BVH_TIMING): (a) always list, upload, build kernels; (b), (c) census, always list, prepare, build kernels
+
+usage: python tools/hbm_scene_rates.py [--reps 5] [--fields 10000,100000,1000000] [--bvh host|device|both] [--soup 100000] [--update | --set-spheres]
 """
 from __future__ import annotations
 
@@ -239,6 +245,50 @@ def update_case(n: int, reps: int):
     ctx_rebuild.close()
 
 
+def set_spheres_case(n: int, reps: int):
+    import numpy as np
+    import torch
+    os.environ["MIRT_BVH_TIMING"] = "1"
+    med = statistics.median
+    arr, mats, tex = rtiow_field(n, seed=n)
+    cam = look(W, H, (40, 6, 30), (0, 0, 0), vfov=35)
+    worlds = [_jittered(arr, 0.25, 1), _jittered(arr, 0.25, 2)]        # two worlds in turn: no call finds its own result in place
+    scenes = [scene_from_arrays(cam, w, mats, tex) for w in worlds]
+    d_worlds = [torch.from_numpy(w.view(np.uint8).copy()).to("cuda:0") for w in worlds]
+    ctx, ctx_rebuild = m.Context(0), m.Context(0)
+    ctx.set_scene(scene_from_arrays(cam, arr, mats, tex), hbm=True, bvh="device")
+    set_pat, build_pat = r"(census_ms|always_ms|prepare_ms|kernels_ms)=([0-9.]+)", r"(always_ms|upload_ms|kernels_ms)=([0-9.]+)"
+    wall = {"set_scene_ex": [], "set_spheres": [], "set_spheres_device": []}
+    parts = {}
+    for rnd in range(reps + 1):                                     # round 0 = warm-up (allocations, code objects)
+        k = rnd & 1
+        t_build, p_build = _timed_stderr(lambda: ctx_rebuild.set_scene(scenes[k], hbm=True, bvh="device"), build_pat)
+        t_host, p_host = _timed_stderr(lambda: ctx.set_spheres(worlds[k]), set_pat)
+        t_dev, p_dev = _timed_stderr(lambda: ctx.set_spheres_device(n, d_worlds[1 - k].data_ptr()), set_pat)
+        if rnd:
+            wall["set_scene_ex"].append(t_build)
+            wall["set_spheres"].append(t_host)
+            wall["set_spheres_device"].append(t_dev)
+            for src, pt in (("set_scene_ex", p_build), ("set_spheres", p_host), ("set_spheres_device", p_dev)):
+                for key, v in pt.items():
+                    parts.setdefault(f"{src}_{key}", []).append(v)
+    ctx.set_spheres(worlds[0])                                      # the three routes end in the same tree
+    ctx_rebuild.set_scene(scenes[0], hbm=True, bvh="device")
+    same = all(np.array_equal(x, y) for x, y in zip(ctx.bvh_read(), ctx_rebuild.bvh_read()))
+    plan = ctx.bvh_info()["plan"]
+    out = {"case": "set_spheres", "world": f"rtiow_field({n})", "n_spheres": n, "reps": reps, "n_nodes": plan["n_nodes"], "n_always": plan["n_always"],
+           "same_tree_bytes": bool(same)}
+    for k, v in wall.items():
+        out[f"{k}_ms"] = round(med(v), 3)
+        out[f"{k}_all_ms"] = [round(x, 3) for x in v]
+    out.update({k: round(med(v), 3) for k, v in parts.items()})
+    out["set_spheres_over_set_scene_ex"] = round(out["set_spheres_ms"] / out["set_scene_ex_ms"], 3)
+    out["set_spheres_device_over_set_scene_ex"] = round(out["set_spheres_device_ms"] / out["set_scene_ex_ms"], 3)
+    print(json.dumps(out), flush=True)
+    ctx.close()
+    ctx_rebuild.close()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--reps", type=int, default=5)
@@ -247,8 +297,13 @@ def main() -> None:
     ap.add_argument("--bvh", choices=("host", "device", "both"), default="host")
     ap.add_argument("--soup", type=int, default=100000, help="--bvh both: spheres of the clustered soup (0: none)")
     ap.add_argument("--update", action="store_true", help="in-place updates against the device rebuild they replace")
+    ap.add_argument("--set-spheres", action="store_true", help="a new sphere table by set_spheres / set_spheres_device against set_scene_ex")
     a = ap.parse_args()
     fields = [int(x) for x in a.fields.split(",") if x]
+    if a.set_spheres:
+        for n in fields:
+            set_spheres_case(n, a.reps)
+        return
     if a.update:
         for n in fields:
             update_case(n, a.reps)

@@ -191,6 +191,8 @@ SYMBOLS = {
     "mirt_ctx_bvh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "mirt_ctx_update_spheres": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "mirt_ctx_update_spheres_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "mirt_ctx_set_spheres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "mirt_ctx_set_spheres_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "mirt_ctx_bvh_refits": (C.c_uint32, [C.c_void_p]),
     "mirt_ctx_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_ctx_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
@@ -221,6 +223,7 @@ SYMBOLS = {
     "mirt_node_set_scene": (C.c_int, [C.c_void_p, _P(MirtScene)]),
     "mirt_node_set_scene_ex": (C.c_int, [C.c_void_p, _P(MirtScene), C.c_uint32]),
     "mirt_node_update_spheres": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "mirt_node_set_spheres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "mirt_node_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_node_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_node_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -221,6 +221,23 @@ class Context:
             raise ValueError(f"d_ptr must be a device address, not {d_ptr!r}")
         check(lib().mirt_ctx_update_spheres_device(self._h, int(first), int(count), C.c_void_p(int(d_ptr))))
 
+    def set_spheres(self, spheres) -> None:
+        """mirt_ctx_set_spheres: the MIRT_SCENE_HBM scene gets `spheres` (see sphere_records; centre, radius and material_idx are
+        read) as its new sphere table -- any count, 0 included -- and a tree built on the device; camera, materials, texels and sky
+        stay.  The context is then what set_scene(..., hbm=True, bvh="device") of that scene leaves.  Blocking."""
+        ptr, count, keep = sphere_records(spheres)
+        _check_range(0, count)
+        check(lib().mirt_ctx_set_spheres(self._h, ptr, count))
+        del keep
+
+    def set_spheres_device(self, count: int, d_ptr: int) -> None:
+        """mirt_ctx_set_spheres_device: the same from `count` 32-byte MirtSphere records in memory of this context's device at
+        address `d_ptr` (e.g. a torch tensor's data_ptr(); what was queued to produce them is waited for)."""
+        _check_range(0, count)
+        if not isinstance(d_ptr, (int, np.integer)) or isinstance(d_ptr, bool) or int(d_ptr) < 0:
+            raise ValueError(f"d_ptr must be a device address, not {d_ptr!r}")
+        check(lib().mirt_ctx_set_spheres_device(self._h, C.c_void_p(int(d_ptr)) if int(count) else None, int(count)))
+
     def bvh_refits(self) -> int:
         """mirt_ctx_bvh_refits: successful updates since the scene was set (0 after every set_scene)."""
         return int(lib().mirt_ctx_bvh_refits(self._h))

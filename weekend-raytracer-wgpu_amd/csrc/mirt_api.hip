@@ -397,6 +397,9 @@ struct MirtContext {
     uint32_t queue_routine[5] = {0, 1, 2, 3, 4};   // dense numbering of the routines present (pool kernel queues)
     int      pt_scene_status = MIRT_OK;
     int      parity_scene_status = MIRT_OK;
+    // the materials' part of the two verdicts, kept for mirt_ctx_set_spheres*: what the tables say whatever the spheres are
+    int      pt_materials_status = MIRT_OK;
+    int      parity_materials_status = MIRT_OK;   // of a world that is not empty
     MirtGpuCamera         cam{};          // host copy; travels by value with every launch (RenderArgs.cam)
     mirt::PreparedSphere* d_spheres = nullptr;
     MirtMaterial*         d_mats = nullptr;
@@ -662,6 +665,32 @@ void mirt_ctx_destroy(MirtContext* c)
     delete c;
 }
 
+// Which scatter routines can a path meet?  (decides the path-traced schedule; the pool kernel numbers the routines present densely
+// so that scenes with <= 3 of them run a 4-queue build.)  seen: bit min(GpuMaterial.id, 4) of every sphere's material;
+// routine_queue: routine id -> queue of the pool kernel.
+static void set_routines(MirtContext* c, uint32_t seen, uint32_t routine_queue[5])
+{
+    c->n_shading_routines = (uint32_t)__builtin_popcount(seen);
+    uint32_t q = 0;
+    for (uint32_t r = 0; r < 5; ++r) if (seen & (1u << r)) { routine_queue[r] = q; c->queue_routine[q] = r; ++q; }
+    for (uint32_t r = 0; r < 5; ++r) if (!(seen & (1u << r))) { routine_queue[r] = q; c->queue_routine[q] = r; ++q; }
+}
+
+// the tree build_bvh_device has just left in c->d_bvh becomes the context's
+static void adopt_device_tree(MirtContext* c, mirt::BvhDeviceResult* r)
+{
+    c->bvh_off_recs = r->off_recs;
+    c->bvh_off_ids = r->off_ids;
+    c->bvh_root = r->root;
+    c->bvh_n_always = r->plan.n_always;
+    for (int k = 0; k < 3; ++k) c->bvh_centre[k] = r->centre[k];
+    c->bvh_radius = r->radius;
+    c->bvh_rmax = r->r_max;
+    c->bvh_plan = r->plan;
+    c->bvh_on_device = true;
+    c->bvh_levels.swap(r->level_first);
+}
+
 // mirt_ctx_set_scene (hbm = false) and mirt_ctx_set_scene_ex (hbm = true: MIRT_SCENE_HBM; bvh_device: | MIRT_SCENE_BVH_DEVICE)
 static int set_scene(MirtContext* c, const MirtScene* s, bool hbm, bool bvh_device = false)
 {
@@ -713,32 +742,29 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm, bool bvh_devi
     c->bvh_refit.ready = false;
 
     // mode-specific validity is decided here once and reported by the render call that needs it
+    // (the spheres first, then the materials -- whose verdict mirt_ctx_set_spheres* keeps)
     c->pt_scene_status = MIRT_OK;
     for (uint32_t i = 0; i < s->n_spheres && c->pt_scene_status == MIRT_OK; ++i)
         if (s->spheres[i].material_idx >= s->n_materials) c->pt_scene_status = MIRT_ERR_MATERIAL_INDEX;
-    for (uint32_t i = 0; i < s->n_materials && c->pt_scene_status == MIRT_OK; ++i) {
+    c->pt_materials_status = MIRT_OK;
+    for (uint32_t i = 0; i < s->n_materials && c->pt_materials_status == MIRT_OK; ++i) {
         const MirtMaterial& m = s->materials[i];
-        if ((m.id == 0 || m.id == 1 || m.id == 3) && !desc_ok(m.desc1, s->n_texels)) c->pt_scene_status = MIRT_ERR_TEXEL_RANGE;
-        if (m.id == 3 && !desc_ok(m.desc2, s->n_texels)) c->pt_scene_status = MIRT_ERR_TEXEL_RANGE;
+        if ((m.id == 0 || m.id == 1 || m.id == 3) && !desc_ok(m.desc1, s->n_texels)) c->pt_materials_status = MIRT_ERR_TEXEL_RANGE;
+        if (m.id == 3 && !desc_ok(m.desc2, s->n_texels)) c->pt_materials_status = MIRT_ERR_TEXEL_RANGE;
     }
+    if (c->pt_scene_status == MIRT_OK) c->pt_scene_status = c->pt_materials_status;
     uint32_t routine_queue[5] = {0, 1, 2, 3, 4};    // routine id -> queue of the pool kernel
-    {   // which scatter routines can a path meet?  (decides the path-traced schedule; the pool kernel
-        // numbers the routines present densely so that scenes with <= 3 of them run a 4-queue build)
+    {
         uint32_t seen = 0;
         for (uint32_t i = 0; i < s->n_spheres; ++i) {
             const uint32_t mi = s->spheres[i].material_idx;
             if (mi < s->n_materials) { const uint32_t id = s->materials[mi].id; seen |= 1u << (id < 4u ? id : 4u); }
         }
-        c->n_shading_routines = (uint32_t)__builtin_popcount(seen);
-        uint32_t q = 0;
-        for (uint32_t r = 0; r < 5; ++r) if (seen & (1u << r)) { routine_queue[r] = q; c->queue_routine[q] = r; ++q; }
-        for (uint32_t r = 0; r < 5; ++r) if (!(seen & (1u << r))) { routine_queue[r] = q; c->queue_routine[q] = r; ++q; }
+        set_routines(c, seen, routine_queue);
     }
-    c->parity_scene_status = MIRT_OK;
-    if (s->n_spheres > 0) {   // layer.rs:345-349 reads material_data[2] on every primary hit
-        if (s->n_materials < 3) c->parity_scene_status = MIRT_ERR_MATERIAL_INDEX;
-        else if (!desc_ok(s->materials[2].desc1, s->n_texels)) c->parity_scene_status = MIRT_ERR_TEXEL_RANGE;
-    }
+    // layer.rs:345-349 reads material_data[2] on every primary hit
+    c->parity_materials_status = s->n_materials < 3 ? MIRT_ERR_MATERIAL_INDEX : !desc_ok(s->materials[2].desc1, s->n_texels) ? MIRT_ERR_TEXEL_RANGE : MIRT_OK;
+    c->parity_scene_status = s->n_spheres > 0 ? c->parity_materials_status : MIRT_OK;
 
     std::vector<mirt::PreparedSphere> prep(s->n_spheres);
     for (uint32_t i = 0; i < s->n_spheres; ++i) {
@@ -841,16 +867,7 @@ static int set_scene(MirtContext* c, const MirtScene* s, bool hbm, bool bvh_devi
     if (hbm && bvh_device) {                     // the tree from the prepared spheres just uploaded, on the context's stream; synchronous
         const double upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_upload).count();
         if ((rc = mirt::build_bvh_device(bvh_always, s->n_spheres, c->d_spheres, c->stream, &c->bvh_scratch, &c->d_bvh, &c->cap_bvh, &dev_bvh)) != MIRT_OK) return rc;
-        c->bvh_off_recs = dev_bvh.off_recs;
-        c->bvh_off_ids = dev_bvh.off_ids;
-        c->bvh_root = dev_bvh.root;
-        c->bvh_n_always = dev_bvh.plan.n_always;
-        for (int k = 0; k < 3; ++k) c->bvh_centre[k] = dev_bvh.centre[k];
-        c->bvh_radius = dev_bvh.radius;
-        c->bvh_rmax = dev_bvh.r_max;
-        c->bvh_plan = dev_bvh.plan;
-        c->bvh_on_device = true;
-        c->bvh_levels.swap(dev_bvh.level_first);
+        adopt_device_tree(c, &dev_bvh);
         if (std::getenv("MIRT_BVH_TIMING"))       // tools/hbm_scene_rates.py: the parts of a device build
             std::fprintf(stderr, "mirt_bvh_device: n=%u always_ms=%.3f upload_ms=%.3f kernels_ms=%.3f levels=%u\n", s->n_spheres, dev_bvh.always_ms,
                          upload_ms, dev_bvh.kernels_ms, dev_bvh.levels);
@@ -972,6 +989,64 @@ int mirt_ctx_update_spheres_device(MirtContext* c, uint32_t first, uint32_t coun
 }
 
 uint32_t mirt_ctx_bvh_refits(const MirtContext* c) { return (c && c->have_scene && c->hbm) ? c->bvh_refits : 0u; }
+
+// mirt_ctx_set_spheres (host pointer) and mirt_ctx_set_spheres_device: a new sphere table for the resident MIRT_SCENE_HBM scene, its
+// materials, texels, camera and sky kept; afterwards the context is what set_scene_ex(HBM | BVH_DEVICE) of that scene leaves.
+static int set_spheres(MirtContext* c, const void* spheres, uint32_t n, bool on_device)
+{
+    if (!c) return fail(MIRT_ERR_NULL_POINTER, "ctx is null");
+    if (n && !spheres) return fail(MIRT_ERR_NULL_POINTER, "spheres is null");
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (n > MIRT_SCENE_HBM_MAX_SPHERES)                              // before any sphere is read
+        return fail(MIRT_ERR_SCENE_TOO_LARGE, "%u spheres exceed MIRT_SCENE_HBM_MAX_SPHERES (%u)", n, (unsigned)MIRT_SCENE_HBM_MAX_SPHERES);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());      // renders may be in flight on caller streams; whatever produced a device source has finished too
+    const bool timed = std::getenv("MIRT_BVH_TIMING") != nullptr;
+    int rc;
+    const void* d_wire = spheres;
+    if (!on_device && n) {                // host records go through the staging buffer of the host updates
+        if ((rc = ensure_capacity(&c->bvh_stage.d, &c->bvh_stage.cap, 32ull * n)) != MIRT_OK) return rc;
+        HIP_TRY(hipMemcpy(c->bvh_stage.d, spheres, 32ull * n, hipMemcpyHostToDevice));
+        d_wire = c->bvh_stage.d;
+    }
+    // the census and the always-tested list write the builder scratch only -- where a refit keeps its tables
+    c->bvh_refit.ready = false;
+    mirt::SpheresCensus census;
+    if ((rc = mirt::census_spheres_device(d_wire, n, c->d_mats, c->n_mats, c->stream, &c->bvh_scratch, timed, &census)) != MIRT_OK) return rc;
+    // from the first write on, a failure leaves NO scene (as set_scene does)
+    c->have_scene = false;
+    c->bvh_refits = 0;
+    c->bvh_levels.clear();
+    c->pt_scene_status = census.bad_material_index ? MIRT_ERR_MATERIAL_INDEX : c->pt_materials_status;
+    c->parity_scene_status = n > 0 ? c->parity_materials_status : MIRT_OK;
+    uint32_t routine_queue[5] = {0, 1, 2, 3, 4};
+    set_routines(c, census.routines_seen, routine_queue);
+    c->has_image_texture = census.has_image_texture;
+    if ((rc = ensure_capacity(&c->d_spheres, &c->cap_spheres, (size_t)n)) != MIRT_OK) return rc;
+    float prepare_ms = 0.0f;
+    if ((rc = mirt::prepare_spheres_device(d_wire, n, c->d_mats, c->n_mats, routine_queue, c->d_spheres, c->stream, timed ? &prepare_ms : nullptr)) != MIRT_OK)
+        return rc;
+    mirt::BvhDeviceResult dev_bvh;
+    if ((rc = mirt::build_bvh_device(census.always, n, c->d_spheres, c->stream, &c->bvh_scratch, &c->d_bvh, &c->cap_bvh, &dev_bvh)) != MIRT_OK) return rc;
+    c->n_spheres = n;
+    for (int k = 0; k < 12; ++k) c->sph3[k] = 0.0f;
+    if (n == 3) {                         // the host copy of a three-sphere scene (RenderArgs.sph3): {centre, r * r} as the device computed them
+        mirt::PreparedSphere prep[3];
+        HIP_TRY(hipMemcpy(prep, c->d_spheres, sizeof prep, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < 3; ++i)
+            for (int k = 0; k < 4; ++k) c->sph3[4 * i + k] = (&prep[i].cx)[k];
+    }
+    adopt_device_tree(c, &dev_bvh);
+    c->have_scene = true;
+    if (timed)                            // tools/hbm_scene_rates.py --set-spheres: the parts of the call
+        std::fprintf(stderr, "mirt_set_spheres: n=%u census_ms=%.3f always_ms=%.3f prepare_ms=%.3f kernels_ms=%.3f\n", n, census.census_ms,
+                     census.always_ms, prepare_ms, dev_bvh.kernels_ms);
+    return MIRT_OK;
+}
+
+int mirt_ctx_set_spheres(MirtContext* c, const MirtSphere* spheres, uint32_t n_spheres) { return set_spheres(c, spheres, n_spheres, false); }
+
+int mirt_ctx_set_spheres_device(MirtContext* c, const void* d_spheres, uint32_t n_spheres) { return set_spheres(c, d_spheres, n_spheres, true); }
 
 int mirt_ctx_set_camera(MirtContext* c, const MirtGpuCamera* cam)
 {

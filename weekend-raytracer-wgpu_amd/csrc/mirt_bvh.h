@@ -71,7 +71,7 @@ struct BvhDeviceResult {
 
 // Builds the tree of `spheres` (host copy: the always list only) from their prepared device copy `d_prepared` ([n] PreparedSphere,
 // already uploaded) on `stream`, into *d_bvh (nodes | records | ids, grown when too small).  Synchronous: the tree is ready when it
-// returns.  `always` = bvh_always_list(spheres, n).  MIRT_OK, MIRT_ERR_ALLOC or MIRT_ERR_HIP.
+// returns.  `always` = bvh_always_list(spheres, n), or the same list from census_spheres_device.  MIRT_OK, MIRT_ERR_ALLOC or MIRT_ERR_HIP.
 int build_bvh_device(const std::vector<uint32_t>& always, uint32_t n, const void* d_prepared, void* hip_stream, BvhDeviceScratch* scratch,
                      unsigned char** d_bvh, size_t* cap_bvh, BvhDeviceResult* out);
 
@@ -107,5 +107,25 @@ int refit_prepare(BvhRefit* st, const BvhTables& t, const std::vector<uint32_t>*
 // the traversal bounds are reduced again.  Synchronous.  `parts_ms`, when not null: scatter, refit, bounds between events.
 int refit_bvh_device(const BvhRefit& st, const BvhTables& t, void* hip_stream, BvhDeviceScratch* scratch, BvhDeviceScratch* stage, uint32_t first,
                      uint32_t count, const void* src, bool src_on_device, float centre[3], float* radius, float* r_max, float parts_ms[3]);
+
+// ---- a new sphere table from device memory (mirt_bvh_device.hip): mirt_ctx_set_spheres* ----
+// What set_scene learns from a scene's spheres, learnt on the device from [n] MirtSphere in device memory (4-byte aligned) and the
+// resident MirtMaterial table.
+struct SpheresCensus {
+    bool     bad_material_index = false;       // a material_idx >= n_mats
+    uint32_t routines_seen = 0;                // bit min(materials[mi].id, 4) of every sphere whose index is in range
+    bool     has_image_texture = false;        // such a sphere's material has a texture larger than 1x1
+    std::vector<uint32_t> always;              // == bvh_always_list of the same spheres
+    float    census_ms = 0.0f, always_ms = 0.0f;   // between events, when timed
+};
+
+// The census and the always-tested list; writes `scratch` only (whatever a refit kept there is gone).  Synchronous.
+int census_spheres_device(const void* d_wire, uint32_t n, const void* d_mats, uint32_t n_mats, void* hip_stream, BvhDeviceScratch* scratch, bool timed,
+                          SpheresCensus* out);
+
+// d_prepared[i] = the PreparedSphere of wire record i (op = routine_queue[min(id, 4)] of its material; 4 without one).  Queued on the
+// stream; waits for it only when `ms` (the kernel's time) is asked for.
+int prepare_spheres_device(const void* d_wire, uint32_t n, const void* d_mats, uint32_t n_mats, const uint32_t routine_queue[5], void* d_prepared,
+                           void* hip_stream, float* ms);
 
 }  // namespace mirt

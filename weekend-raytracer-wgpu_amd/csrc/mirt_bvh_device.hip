@@ -5,7 +5,8 @@
 // claim to bound.  This builder keeps those three properties, leaves of at most MIRT_BVH_MAX_LEAF spheres and a depth of at most
 // MIRT_BVH_MAX_DEPTH (the traversal stack of nearest_hit_bvh drops a push beyond it: a deeper tree renders a wrong image), and builds
 // a Morton-order tree instead of the host's binned SAH tree:
-//   1. the always-tested list is the host rule's (bvh_always_list, host, O(n)); tree item t is the t-th sphere not on it;
+//   1. the always-tested list is the host rule's (bvh_always_list on the host, or the same list made on the device by
+//      census_spheres_device at the end of this file); tree item t is the t-th sphere not on it;
 //   2. keys: the centroid box of the tree items (device reduction), every centre quantised inside it in fp64 to 13 bits per axis
 //      (cubic cells: the longest extent divides every axis), and key = morton << 24 | t -- unique, so the sorted order is a pure
 //      function of the input;
@@ -712,5 +713,218 @@ int mirt::refit_bvh_device(const BvhRefit& st, const BvhTables& t, void* hip_str
     for (int k = 0; k < 3; ++k) centre[k] = 0.0f;
     *radius = *r_max = 0.0f;
     if (m) finish_bounds(h_red, h_d2, centre, radius, r_max);
+    return MIRT_OK;
+}
+
+// ---- a new sphere table from wire records in device memory: mirt_ctx_set_spheres*  ----
+// Everything set_scene derives from the spheres on the host, derived on the device from [n] MirtSphere (8 words: centre[4], radius,
+// material_idx, 2 x pad; words 3, 6 and 7 are never read; 4-byte aligned) and the resident MirtMaterial table: the census (is a
+// material index out of range, which scatter routines occur, does a used material carry an image texture), the always-tested list
+// of bvh_always_list, and the PreparedSphere table.  As above, nothing waits on another block and every result is a pure function of
+// the input.
+namespace {
+
+constexpr uint32_t kCensusBadIndex = 1u << 5;      // above the five routine bits
+constexpr uint32_t kCensusImage = 1u << 6;
+constexpr uint32_t kAlwaysKeyBits = 57;            // 24 index bits, 32 radius bits, the "box is not finite" bit
+constexpr uint64_t kAlwaysBad = 1ull << 56;
+
+__device__ inline void block_reduce_or(uint32_t v, uint32_t* out)
+{
+    __shared__ uint32_t sh[kBlock];
+    const uint32_t tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+    for (uint32_t s = kBlock / 2; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] |= sh[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) *out = sh[0];
+}
+
+// routines seen (bit min(id, 4) of every sphere with a material) | kCensusBadIndex | kCensusImage -> partials[gridDim.x]
+__global__ __launch_bounds__(kBlock) void census_kernel(const uint32_t* wire, uint32_t n, const MirtMaterial* mats, uint32_t n_mats, uint32_t* partials)
+{
+    uint32_t v = 0u;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const uint32_t mi = wire[8ull * i + 5u];
+        if (mi >= n_mats) { v |= kCensusBadIndex; continue; }
+        const MirtMaterial m = mats[mi];
+        v |= 1u << (m.id < 4u ? m.id : 4u);
+        if ((uint64_t)m.desc1.width * m.desc1.height > 1u || (uint64_t)m.desc2.width * m.desc2.height > 1u) v |= kCensusImage;
+    }
+    block_reduce_or(v, partials + blockIdx.x);
+}
+
+__global__ __launch_bounds__(kBlock) void census_final_kernel(const uint32_t* partials, uint32_t n_part, uint32_t* out)
+{
+    uint32_t v = 0u;
+    for (uint32_t i = threadIdx.x; i < n_part; i += kBlock) v |= partials[i];
+    block_reduce_or(v, out);
+}
+
+// One key per sphere whose ascending order is: the spheres with a finite box by |radius| descending, ties by index ascending, then
+// the others by index.  bvh_always_list's test of a box (mirt_bvh.cpp), in fp64: c - r and c + r of two finite floats are finite.
+__global__ __launch_bounds__(kBlock) void always_keys_kernel(const float* wire, uint32_t n, uint64_t* keys)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float* in = wire + 8ull * i;
+    const float r = __builtin_fabsf(in[4]);
+    bool ok = finite_f(r);
+    for (int k = 0; k < 3; ++k) {
+        const float c = in[k];
+        ok = ok && finite_f(c) && __builtin_fabs((double)c) + (double)r < 3.0e38;
+    }
+    keys[i] = ok ? ((uint64_t)(0xffffffffu - __float_as_uint(r)) << kIndexBits) | (uint64_t)i : kAlwaysBad | (uint64_t)i;
+}
+
+// One block of MIRT_BVH_MAX_ALWAYS threads over the sorted keys: the first spheres without a finite box, then -- while room is left --
+// the largest of those above MIRT_BVH_BIG_RADII median radii; the list sorted by index (every thread ranks its own entry).
+__global__ __launch_bounds__(MIRT_BVH_MAX_ALWAYS) void always_list_kernel(const uint64_t* keys, uint32_t n, AlwaysList* out)
+{
+    __shared__ uint32_t sh_idx[MIRT_BVH_MAX_ALWAYS];
+    __shared__ uint32_t sh_valid[MIRT_BVH_MAX_ALWAYS];
+    // m = the spheres with a finite box = the first key with kAlwaysBad (every thread searches: 24 reads of the same words)
+    uint32_t lo = 0u, hi = n;
+    while (lo < hi) {
+        const uint32_t h = lo + (hi - lo) / 2u;
+        if (keys[h] < kAlwaysBad) lo = h + 1u; else hi = h;
+    }
+    const uint32_t m = lo, n_bad = n - m, nb = n_bad < MIRT_BVH_MAX_ALWAYS ? n_bad : MIRT_BVH_MAX_ALWAYS;
+    const uint32_t j = threadIdx.x;
+    uint32_t idx = 0u, valid = 0u;
+    if (j < nb) {
+        idx = (uint32_t)(keys[m + j] & ((1ull << kIndexBits) - 1ull));
+        valid = 1u;
+    } else if (j - nb < m) {
+        // the median: position m / 2 of the ascending radii = position m - 1 - m / 2 here
+        const float median = __uint_as_float(0xffffffffu - (uint32_t)(keys[m - 1u - m / 2u] >> kIndexBits));
+        const uint64_t key = keys[j - nb];
+        const float r = __uint_as_float(0xffffffffu - (uint32_t)(key >> kIndexBits));
+        idx = (uint32_t)(key & ((1ull << kIndexBits) - 1ull));
+        valid = (double)r > (double)MIRT_BVH_BIG_RADII * (double)median ? 1u : 0u;
+    }
+    sh_idx[j] = idx;
+    sh_valid[j] = valid;
+    __syncthreads();
+    uint32_t rank = 0u, total = 0u;
+    for (uint32_t k = 0; k < MIRT_BVH_MAX_ALWAYS; ++k) {
+        total += sh_valid[k];
+        if (sh_valid[k] && sh_idx[k] < idx) ++rank;
+    }
+    if (valid) out->idx[rank] = idx;
+    if (j == 0) out->n = total;
+}
+
+struct QueueMap { uint32_t q[5]; };               // routine min(id, 4) -> queue of the pool kernel
+
+// wire record -> PreparedSphere; r * r and 1.0f / r are the single IEEE operations of set_scene
+__global__ __launch_bounds__(kBlock) void prepare_kernel(const float* wire, uint32_t n, const MirtMaterial* mats, uint32_t n_mats, QueueMap map,
+                                                         mirt::PreparedSphere* sph)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float* in = wire + 8ull * i;
+    const float r = in[4];
+    const uint32_t mi = reinterpret_cast<const uint32_t*>(in)[5];
+    uint32_t routine = 4u;
+    if (mi < n_mats) { const uint32_t id = mats[mi].id; if (id < 4u) routine = id; }
+    mirt::PreparedSphere o;
+    o.cx = in[0]; o.cy = in[1]; o.cz = in[2];
+    o.rr = r * r;
+    o.inv_r = 1.0f / r;
+    o.radius = r;
+    o.material_idx = mi;
+    o.op = map.q[routine];
+    sph[i] = o;
+}
+
+struct Events {
+    hipEvent_t e[4] = { nullptr, nullptr, nullptr, nullptr };
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+}  // namespace
+
+int mirt::census_spheres_device(const void* d_wire, uint32_t n, const void* d_mats, uint32_t n_mats, void* hip_stream, BvhDeviceScratch* scratch,
+                                bool timed, SpheresCensus* out)
+{
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    SpheresCensus r;
+    if (!n) { *out = std::move(r); return MIRT_OK; }
+    // scratch: keys (in, sorted) | census partials | census word | the list | the sort's storage
+    size_t sort_bytes = 0;
+    BVH_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)n, 0u, kAlwaysKeyBits, stream));
+    size_t off = 0;
+    const size_t o_keys_in = off;  off += align256(8ull * n);
+    const size_t o_keys = off;     off += align256(8ull * n);
+    const size_t o_part = off;     off += align256(sizeof(uint32_t) * kReduceBlocks);
+    const size_t o_word = off;     off += align256(sizeof(uint32_t));
+    const size_t o_list = off;     off += align256(sizeof(AlwaysList));
+    const size_t o_sort = off;     off += align256(sort_bytes);
+    int rc;
+    if ((rc = grow(&scratch->d, &scratch->cap, off)) != MIRT_OK) return rc;
+    unsigned char* S = scratch->d;
+    uint64_t* keys_in = reinterpret_cast<uint64_t*>(S + o_keys_in);
+    uint64_t* keys = reinterpret_cast<uint64_t*>(S + o_keys);
+    uint32_t* partials = reinterpret_cast<uint32_t*>(S + o_part);
+    uint32_t* word = reinterpret_cast<uint32_t*>(S + o_word);
+    AlwaysList* list = reinterpret_cast<AlwaysList*>(S + o_list);
+
+    Events ev;
+    if (timed) for (int k = 0; k < 3; ++k) BVH_HIP_TRY(hipEventCreate(&ev.e[k]));
+    if (timed) (void)hipEventRecord(ev.e[0], stream);
+    const uint32_t rb = blocks_for(n) < kReduceBlocks ? blocks_for(n) : kReduceBlocks;
+    census_kernel<<<rb, kBlock, 0, stream>>>(static_cast<const uint32_t*>(d_wire), n, static_cast<const MirtMaterial*>(d_mats), n_mats, partials);
+    census_final_kernel<<<1, kBlock, 0, stream>>>(partials, rb, word);
+    if (timed) (void)hipEventRecord(ev.e[1], stream);
+    always_keys_kernel<<<blocks_for(n), kBlock, 0, stream>>>(static_cast<const float*>(d_wire), n, keys_in);
+    BVH_HIP_TRY(hipGetLastError());
+    BVH_HIP_TRY(rocprim::radix_sort_keys(S + o_sort, sort_bytes, keys_in, keys, (size_t)n, 0u, kAlwaysKeyBits, stream));
+    always_list_kernel<<<1, MIRT_BVH_MAX_ALWAYS, 0, stream>>>(keys, n, list);
+    BVH_HIP_TRY(hipGetLastError());
+    if (timed) (void)hipEventRecord(ev.e[2], stream);
+    uint32_t h_word = 0;
+    AlwaysList h_list{};
+    BVH_HIP_TRY(hipMemcpyAsync(&h_word, word, sizeof h_word, hipMemcpyDeviceToHost, stream));
+    BVH_HIP_TRY(hipMemcpyAsync(&h_list, list, sizeof h_list, hipMemcpyDeviceToHost, stream));
+    BVH_HIP_TRY(hipStreamSynchronize(stream));
+    if (timed) {
+        (void)hipEventElapsedTime(&r.census_ms, ev.e[0], ev.e[1]);
+        (void)hipEventElapsedTime(&r.always_ms, ev.e[1], ev.e[2]);
+    }
+    if (h_list.n > MIRT_BVH_MAX_ALWAYS || h_list.n > n) return mirt::set_error(MIRT_ERR_HIP, "set_spheres: an always-tested list of %u", h_list.n);
+    r.routines_seen = h_word & 31u;
+    r.bad_material_index = (h_word & kCensusBadIndex) != 0u;
+    r.has_image_texture = (h_word & kCensusImage) != 0u;
+    try {
+        r.always.assign(h_list.idx, h_list.idx + h_list.n);
+    } catch (const std::bad_alloc&) {
+        return mirt::set_error(MIRT_ERR_ALLOC, "out of host memory");
+    }
+    *out = std::move(r);
+    return MIRT_OK;
+}
+
+int mirt::prepare_spheres_device(const void* d_wire, uint32_t n, const void* d_mats, uint32_t n_mats, const uint32_t routine_queue[5], void* d_prepared,
+                                 void* hip_stream, float* ms)
+{
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (ms) *ms = 0.0f;
+    if (!n) return MIRT_OK;
+    QueueMap map;
+    for (int k = 0; k < 5; ++k) map.q[k] = routine_queue[k];
+    Events ev;
+    if (ms) for (int k = 0; k < 2; ++k) BVH_HIP_TRY(hipEventCreate(&ev.e[k]));
+    if (ms) (void)hipEventRecord(ev.e[0], stream);
+    prepare_kernel<<<blocks_for(n), kBlock, 0, stream>>>(static_cast<const float*>(d_wire), n, static_cast<const MirtMaterial*>(d_mats), n_mats, map,
+                                                         static_cast<mirt::PreparedSphere*>(d_prepared));
+    BVH_HIP_TRY(hipGetLastError());
+    if (ms) {                                              // untimed: the builder that follows on this stream waits for it
+        (void)hipEventRecord(ev.e[1], stream);
+        BVH_HIP_TRY(hipStreamSynchronize(stream));
+        (void)hipEventElapsedTime(ms, ev.e[0], ev.e[1]);
+    }
     return MIRT_OK;
 }

@@ -410,6 +410,21 @@ int mirt_node_update_spheres(MirtNode* nd, uint32_t first, uint32_t count, const
     return MIRT_OK;
 }
 
+int mirt_node_set_spheres(MirtNode* nd, const MirtSphere* spheres, uint32_t n_spheres)
+{
+    if (!nd) return mirt::set_error(MIRT_ERR_NULL_POINTER, "node is null");
+    if (n_spheres && !spheres) return mirt::set_error(MIRT_ERR_NULL_POINTER, "spheres is null");
+    if (!nd->have_scene) return mirt::set_error(MIRT_ERR_NO_SCENE, "mirt_node_set_scene has not succeeded");
+    for (uint32_t i = 0; i < nd->n; ++i) {
+        const int rc = mirt_ctx_set_spheres(nd->ctx[i], spheres, n_spheres);
+        if (rc == MIRT_OK) continue;
+        // as in mirt_node_update_spheres: an argument error comes from the first member and has changed nothing
+        if (i > 0 || rc == MIRT_ERR_HIP || rc == MIRT_ERR_ALLOC) nd->have_scene = false;
+        return rc;
+    }
+    return MIRT_OK;
+}
+
 int mirt_node_set_camera(MirtNode* nd, const MirtGpuCamera* camera)
 {
     if (!nd || !camera) return mirt::set_error(MIRT_ERR_NULL_POINTER, "node/camera is null");

@@ -52,6 +52,17 @@ inline void update_spheres_device(MirtContext* ctx, uint32_t first, uint32_t cou
     check(mirt_ctx_update_spheres_device(ctx, first, count, d_spheres));
 }
 inline uint32_t bvh_refits(const MirtContext* ctx) { return mirt_ctx_bvh_refits(ctx); }
+// mirt_ctx_set_spheres: a MIRT_SCENE_HBM scene gets `spheres` as its new sphere table (any count; material_idx is read) and a tree built
+// on the device; camera, materials, texels and sky stay resident.
+inline void set_spheres(MirtContext* ctx, const std::vector<MirtSphere>& spheres)
+{
+    check(mirt_ctx_set_spheres(ctx, spheres.data(), (uint32_t)spheres.size()));
+}
+// the same from records in memory of the context's device
+inline void set_spheres_device(MirtContext* ctx, const void* d_spheres, uint32_t n_spheres)
+{
+    check(mirt_ctx_set_spheres_device(ctx, d_spheres, n_spheres));
+}
 // move_spheres of Layer / Raytracer: held[first ..] take centre and radius of `spheres` and keep their material
 inline void move_held_spheres(std::vector<MirtSphere>& held, uint32_t first, const std::vector<MirtSphere>& spheres)
 {
@@ -283,6 +294,23 @@ public:
         if (ctx_ && rp) render(*rp);
     }
 
+    // `world` becomes `spheres` (any count, their material indices taken).  A resident MIRT_SCENE_HBM scene gets the new sphere table in
+    // place (mirt_ctx_set_spheres); any other resident scene is set again; before the first set_data only `world` changes.  With `rp` the
+    // image is rendered again.  `world` changes only when the device call succeeded.
+    void set_world(const std::vector<MirtSphere>& spheres, const RenderParams* rp = nullptr)
+    {
+        std::vector<MirtSphere> next = spheres;
+        if (ctx_ && hbm_) {
+            const int rc = mirt_ctx_set_spheres(ctx_, next.data(), (uint32_t)next.size());
+            if (rc != MIRT_OK && rc != MIRT_ERR_SCENE_TOO_LARGE && rc != MIRT_ERR_NULL_POINTER) hbm_ = false;   // no scene any more: the next call sets one
+            check(rc);
+        } else if (ctx_) {
+            upload(next);
+        }
+        world.swap(next);
+        if (ctx_ && rp) render(*rp);
+    }
+
     // layer.rs:182-186: ImageBuffer<Rgb<u8>> view
     std::vector<uint8_t> imgbuf() const
     {
@@ -452,6 +480,25 @@ public:
         } else {
             spheres_.swap(moved);
             try { upload(); } catch (...) { spheres_.swap(moved); throw; }
+        }
+        accumulated_ = -1;
+    }
+
+    // The scene's spheres become `spheres` (any count, their material indices taken): in place, with a tree built on the device, when the
+    // scene is in device memory (MIRT_SCENE_HBM); any other scene is set again.  The accumulation restarts.  The held spheres change only
+    // when the device call succeeded.
+    void set_world(const std::vector<MirtSphere>& spheres)
+    {
+        std::vector<MirtSphere> next = spheres;
+        if (hbm_) {
+            const int rc = node_ ? mirt_node_set_spheres(node_, next.data(), (uint32_t)next.size())
+                                 : mirt_ctx_set_spheres(ctx_, next.data(), (uint32_t)next.size());
+            if (rc != MIRT_OK && rc != MIRT_ERR_SCENE_TOO_LARGE && rc != MIRT_ERR_NULL_POINTER) hbm_ = false;   // no scene any more: the next call sets one
+            check(rc);
+            spheres_.swap(next);
+        } else {
+            spheres_.swap(next);
+            try { upload(); } catch (...) { spheres_.swap(next); throw; }
         }
         accumulated_ = -1;
     }

@@ -74,6 +74,13 @@ class Node:
         check(lib().mirt_node_update_spheres(self._h, int(first), count, ptr))
         del keep
 
+    def set_spheres(self, spheres) -> None:
+        """mirt_node_set_spheres: Context.set_spheres on every member (host records only)."""
+        ptr, count, keep = sphere_records(spheres)
+        _check_range(0, count)
+        check(lib().mirt_node_set_spheres(self._h, ptr, count))
+        del keep
+
     def set_camera(self, camera: _abi.MirtGpuCamera) -> None:
         check(lib().mirt_node_set_camera(self._h, C.byref(camera)))
 

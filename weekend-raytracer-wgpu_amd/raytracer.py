@@ -389,6 +389,29 @@ def _move_resident(owner, target, first: int, moved: Sequence[Sphere], scene_dat
         raise
 
 
+def _world(spheres: Sequence[Sphere]) -> List[Sphere]:
+    """set_world: the new world as a list of Sphere."""
+    spheres = list(spheres)
+    if not all(isinstance(s, Sphere) for s in spheres):
+        raise ValueError("spheres must be Sphere objects")
+    return spheres
+
+
+def _set_world_resident(owner, target, world: Sequence[Sphere], scene_data) -> None:
+    """The device side of set_world of `owner` (a Layer or a Raytracer) on `target` (its Context or Node): an HBM scene gets the new
+    sphere table in place (its materials and texels stay resident, the tree is built on the device), any other is set again from
+    `scene_data()` (the new scene).  `owner._hbm` as in _move_resident."""
+    if not owner._hbm:
+        owner._hbm = set_scene_any_size(target, scene_data())
+        return
+    try:
+        target.set_spheres(world)
+    except MirtError as e:
+        if e.status not in (_abi.MIRT_ERR_SCENE_TOO_LARGE, _abi.MIRT_ERR_NULL_POINTER):
+            owner._hbm = False
+        raise
+
+
 def _jpeg_check(rc: int) -> None:
     if rc != 0:
         raise MirtError(rc, (lib().mirt_jpeg_last_error() or b"").decode())
@@ -505,6 +528,23 @@ class Layer:
                            lambda: SceneData(self.camera.c, [s.to_c() for s in _spliced(self.world, first, moved)], list(self.material_data),
                                              self.global_texture_data))
         self.world[first:first + len(moved)] = moved
+        if target is not None and render_params is not None:
+            w, h = int(self.vp_size[0]), int(self.vp_size[1])
+            self._rgba = target.render(make_params(w, h, render_params.sampling.num_samples_per_pixel, mode=_abi.MIRT_MODE_PARITY))
+            self.last_stats = target.stats()
+
+    def set_world(self, spheres: Sequence[Sphere], render_params: Optional[RenderParams] = None) -> None:
+        """`world` becomes `spheres` (any count; their material indices are taken).  After a set_data whose world went to device
+        memory (MIRT_SCENE_HBM) the resident scene gets the new sphere table and a tree built on the device (mirt_ctx_set_spheres /
+        mirt_node_set_spheres: materials and texels are not uploaded again); any other resident scene is set again; before the first
+        set_data only `world` changes.  With `render_params` the image is rendered again, as set_data does.  `world` changes only
+        when the device call succeeded."""
+        new = _world(spheres)
+        target = self._node if self._devices is not None else self._ctx
+        if target is not None:
+            _set_world_resident(self, target, new,
+                                lambda: SceneData(self.camera.c, [s.to_c() for s in new], list(self.material_data), self.global_texture_data))
+        self.world = new
         if target is not None and render_params is not None:
             w, h = int(self.vp_size[0]), int(self.vp_size[1])
             self._rgba = target.render(make_params(w, h, render_params.sampling.num_samples_per_pixel, mode=_abi.MIRT_MODE_PARITY))
@@ -657,6 +697,18 @@ class Raytracer:
                        lambda: SceneData(self.camera.c, [s.to_c() for s in _spliced(self.spheres, first, moved)], list(self.material_data),
                                          self.global_texture_data, self.sky_state))
         self.spheres[first:first + len(moved)] = moved
+        self._accumulated = None
+
+    def set_world(self, spheres: Sequence[Sphere]) -> None:
+        """The scene's spheres become `spheres` (any count; their material indices are taken).  A scene in device memory
+        (MIRT_SCENE_HBM) gets the new sphere table in place and a tree built on the device (mirt_ctx_set_spheres /
+        mirt_node_set_spheres); any other scene is set again.  The progressive accumulation restarts.  The held spheres change only
+        when the device call succeeded."""
+        new = _world(spheres)
+        _set_world_resident(self, self._ctx, new,
+                            lambda: SceneData(self.camera.c, [s.to_c() for s in new], list(self.material_data), self.global_texture_data,
+                                              self.sky_state))
+        self.spheres = new
         self._accumulated = None
 
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
