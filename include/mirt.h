@@ -342,7 +342,13 @@ int mirt_ctx_set_scene(MirtContext* ctx, const MirtScene* scene);
  *   MIRT_FLAG_NO_GRID           the flat scan of the sphere table in device memory (render_pt_hbm_kernel<...,false,...>);
  *   MIRT_FLAG_COUNT_WORK        alone: counts that flat scan (every counter equals the oracle's); with MIRT_FLAG_COUNT_GRID: counts the
  *                               BVH build (sphere_tests = tests performed, grid_cells / grid_wave_cells = BVH nodes visited);
- *   MIRT_FLAG_KERNEL_STRIP / _POOL / _TEXEL_TILES: schedule hints, ignored;
+ *   MIRT_FLAG_KERNEL_POOL       on the BVH build (no MIRT_FLAG_NO_GRID; counting launches: with MIRT_FLAG_COUNT_GRID): the pooled schedule,
+ *                               render_pt_pool_hbm_kernel<THREADS,SLOTS,MINW,COUNT,HOSEK> (a progressive frame: render_pt_pool_hbm_frame_kernel;
+ *                               MIRT_FLAG_FAST_MATH: "fast_build::" + the name) -- a wave keeps a pool of paths in LDS and refills the lanes
+ *                               whose paths have ended instead of idling them.  Same image, same sums.  OPT-IN: no sample
+ *                               count selects it by default.  Not pooled, and run exactly as without the flag: num_bounces > 255,
+ *                               frame_spp > 0, and a tree so deep that no geometry fits LDS (mirt_bvh_pool_plan: slots == 0);
+ *   MIRT_FLAG_KERNEL_STRIP      wins over _POOL as everywhere else: the default kernel;  MIRT_FLAG_TEXEL_TILES: ignored;
  *   parity mode                 the layer.rs flat scan with the spheres in device memory (render_parity_hbm_kernel).
  * The BVH: binned SAH over the sphere centres, binary, leaves of at most MIRT_BVH_MAX_LEAF spheres, depth at most MIRT_BVH_MAX_DEPTH by
  * construction; up to MIRT_BVH_MAX_ALWAYS spheres (those larger than MIRT_BVH_BIG_RADII median radii, and those whose box is not finite)
@@ -382,6 +388,17 @@ typedef struct MirtBvhInfo {
     float       centre[3], radius, r_max;
 } MirtBvhInfo;
 int mirt_ctx_bvh_info(MirtContext* ctx, MirtBvhInfo* out);
+/* The geometry MIRT_FLAG_KERNEL_POOL would run on a MIRT_SCENE_HBM scene whose tree is `max_depth` deep (MirtBvhInfo.plan.max_depth):
+ * HOST-ONLY, the function the launch itself uses.  hosek != 0: the launch stages the Hosek sky.  lds_bytes_per_cu = LDS of a compute
+ * unit (0 = gfx950's 163 840).  A block holds the camera (96 bytes, + 144 of sky) and, per wave of 64 threads, a pool of
+ * 50 * slots + 384 bytes and 64 traversal stacks of stack_entries == max_depth node references (256 * max_depth bytes):
+ *   lds_bytes_per_block = 96 (+ 144) + threads / 64 * (50 * slots + 384 + 256 * max_depth),
+ *   waves_per_cu        = waves the launch keeps resident per compute unit: whole blocks, at most 16 waves.
+ * The rule: of the slot counts 112, 96, 80 and 64 the largest that leaves 16 waves resident; where none does, the one that keeps most
+ * waves (the larger pools on a tie).  slots == 0 (all fields 0): not one block fits, and the launch runs the strip kernel.
+ * MIRT_ERR_NULL_POINTER: out is null;  MIRT_ERR_BAD_ROWS: max_depth > MIRT_BVH_MAX_DEPTH. */
+typedef struct MirtBvhPoolPlan { uint32_t threads, slots, waves_per_cu, stack_entries, lds_bytes_per_block; } MirtBvhPoolPlan;
+int mirt_bvh_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtBvhPoolPlan* out);
 /* Copies the tree to the host: plan.n_nodes nodes of 64 bytes {left box min[3] max[3], right box min[3] max[3], left, right, 2 x u32 pad}
  * (a reference with bit 31 set is a leaf: bits 24..30 = sphere count, bits 0..23 = first record), 4 floats {centre, r * r} per sphere and
  * the original index of every record (always-tested list first).  Blocking; meant for tests, like mirt_ctx_accum_read.

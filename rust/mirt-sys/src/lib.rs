@@ -186,6 +186,17 @@ pub struct MirtBvhInfo {
     pub r_max: f32,
 }
 
+/// `mirt_bvh_pool_plan`: the geometry `MIRT_FLAG_KERNEL_POOL` runs on a `MIRT_SCENE_HBM` scene (host only; `slots == 0`: none fits).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtBvhPoolPlan {
+    pub threads: u32,
+    pub slots: u32,
+    pub waves_per_cu: u32,
+    pub stack_entries: u32,
+    pub lds_bytes_per_block: u32,
+}
+
 /// `mirt_ctx_set_scene_ex` / `mirt_node_set_scene_ex` flags: the scene's tables in device memory, nearest hit through a BVH
 /// (worlds beyond the LDS budget, up to `MIRT_SCENE_HBM_MAX_SPHERES`).
 pub const MIRT_SCENE_HBM: u32 = 1 << 0;
@@ -258,6 +269,7 @@ extern "C" {
     pub fn mirt_ctx_set_scene(ctx: *mut MirtContext, scene: *const MirtScene) -> c_int;
     pub fn mirt_ctx_set_scene_ex(ctx: *mut MirtContext, scene: *const MirtScene, flags: u32) -> c_int;
     pub fn mirt_bvh_plan(spheres: *const MirtSphere, n_spheres: u32, out: *mut MirtBvhPlan) -> c_int;
+    pub fn mirt_bvh_pool_plan(max_depth: u32, hosek: u32, lds_bytes_per_cu: u64, out: *mut MirtBvhPoolPlan) -> c_int;
     pub fn mirt_ctx_bvh_info(ctx: *mut MirtContext, out: *mut MirtBvhInfo) -> c_int;
     pub fn mirt_ctx_bvh_read(ctx: *mut MirtContext, nodes: *mut c_void, nodes_bytes: usize, recs: *mut f32, recs_len: usize, ids: *mut u32, ids_len: usize) -> c_int;
     pub fn mirt_ctx_update_spheres(ctx: *mut MirtContext, first: u32, count: u32, spheres: *const MirtSphere) -> c_int;

@@ -2,8 +2,11 @@
 """A/B several builds of libmirt.so on one workload in ONE process, interleaved rounds (cdna_hip_programming.md
 §5.4 rule 24): kernel time from the library's own HIP events, images compared with the first build's.
 
-    python tools/ab_libs.py [--scene three_spheres] [--size 1920x1080] [--spp 1000] [--rounds 5] [--flags 0]
+    python tools/ab_libs.py [--scene three_spheres] [--size 1920x1080] [--spp 1000] [--rounds 5] [--flags 0] [--hbm]
                             [--allow-diff] lib_a.so lib_b.so lib_b.so@MIRT_PINHOLE=0 ...
+
+`--hbm` sets the scene with mirt_ctx_set_scene_ex(MIRT_SCENE_HBM): the BVH kernels of DESIGN.md 10.  The same library given twice
+measures the spread of identical runs beside a difference between two builds.
 
 `lib.so@NAME=VALUE[,NAME=VALUE]` creates that build's context with the tuning variables set (they are read once, in
 mirt_ctx_create), so one build can appear several times with different knobs.
@@ -33,6 +36,7 @@ ap.add_argument("--flags", type=lambda s: int(s, 0), default=0)
 ap.add_argument("--mode", default="pt")
 ap.add_argument("--bounces", type=int, default=8)
 ap.add_argument("--allow-diff", action="store_true")
+ap.add_argument("--hbm", action="store_true", help="set the scene with MIRT_SCENE_HBM (tables and a BVH in device memory)")
 ap.add_argument("libs", nargs="+")
 a = ap.parse_args()
 w, h = map(int, a.size.split("x"))
@@ -57,8 +61,14 @@ for spec in a.libs:
             else:
                 os.environ[k] = v
     sc = sd.as_c()
-    assert lib.mirt_ctx_set_scene(ctx, C.byref(sc)) == 0, lib.mirt_last_error()
-    libs.append((Path(path).name + ("@" + envs if envs else ""), lib, ctx))
+    if a.hbm:
+        assert lib.mirt_ctx_set_scene_ex(ctx, C.byref(sc), _abi.MIRT_SCENE_HBM) == 0, lib.mirt_last_error()
+    else:
+        assert lib.mirt_ctx_set_scene(ctx, C.byref(sc)) == 0, lib.mirt_last_error()
+    name = Path(path).name + ("@" + envs if envs else "")
+    while any(name == n for n, _, _ in libs):                                        # the same build twice: the spread of identical runs
+        name += "'"
+    libs.append((name, lib, ctx))
 
 
 def render(lib, ctx):

@@ -25,7 +25,16 @@
            (c) mirt_ctx_set_spheres_device from a torch buffer; wall time, median of --reps after a warm-up; the parts the library
            reports (MIRT_BVH_TIMING): (a) always list, upload, build kernels; (b), (c) census, always list, prepare, build kernels
 
-usage: python tools/hbm_scene_rates.py [--reps 5] [--fields 10000,100000,1000000] [--bvh host|device|both] [--soup 100000] [--update | --set-spheres]
+  --pool   the pooled schedule (MIRT_FLAG_KERNEL_POOL on an HBM scene: render_pt_pool_hbm_kernel) against the default
+           strip kernel on the worlds of DESIGN.md 10.2: RTIOW at 1080p x 2 / 16 / 128 spp, the 10 k / 100 k / 1 M fields at 16 and
+           128 spp.  One child process per world, each under its own time limit (--step-timeout), the next one only after the last
+           has ended well; inside a child both kernels run on one context in alternating windows -- a window is as many launches as
+           add up to --window-ms of kernel time, its figure their mean -- and the median of --reps windows after a warm-up window of
+           each is reported, with the images compared once.  MIRT_HBM_POOL_SLOTS / MIRT_POOL_BLOCKS_PER_CU (A/B runs of the geometry)
+           pass through to the children and are recorded.  --pool-counts adds the lane use of both schedules from counting launches
+           (480x270 x 32 spp): traversal = grid_cells / (64 grid_wave_cells), step = lane_iterations / (64 wave_iterations).
+
+usage: python tools/hbm_scene_rates.py [--reps 5] [--fields 10000,100000,1000000] [--bvh host|device|both] [--soup 100000] [--update | --set-spheres | --pool]
 """
 from __future__ import annotations
 
@@ -289,6 +298,81 @@ def set_spheres_case(n: int, reps: int):
     ctx_rebuild.close()
 
 
+def _window_ms(ctx, p, window_ms: float) -> tuple:
+    """One timing window: launches until their kernel times add up to window_ms -> (mean kernel ms, launches)."""
+    total, n = 0.0, 0
+    while n == 0 or total < window_ms:
+        total += kernel_ms(ctx, p)
+        n += 1
+    return total / n, n
+
+
+def pool_world(world: str, reps: int, window_ms: float, bvh: str, counts: bool):
+    """One world of --pool, in this process: strip and pooled kernel on ONE context, alternating windows."""
+    import numpy as np
+    if world == "rtiow":
+        sd, spps, name = scene_data("rtiow_final", W, H), (2, 16, 128), "rtiow"
+        sdc = scene_data("rtiow_final", 480, 270)
+    else:
+        n = int(world)
+        arr, mats, tex = rtiow_field(n, seed=n)
+        sd, spps, name = scene_from_arrays(look(W, H, (40, 6, 30), (0, 0, 0), vfov=35), arr, mats, tex), (16, 128), f"rtiow_field({n})"
+        sdc = scene_from_arrays(look(480, 270, (40, 6, 30), (0, 0, 0), vfov=35), arr, mats, tex)
+    ctx = m.Context(0)
+    ctx.set_scene(sd, hbm=True, bvh=bvh)
+    depth = ctx.bvh_info()["plan"]["max_depth"]
+    knobs = {k: os.environ[k] for k in ("MIRT_HBM_POOL_SLOTS", "MIRT_POOL_BLOCKS_PER_CU") if k in os.environ}
+    for spp in spps:
+        ps = {"strip": m.make_params(W, H, spp, mode=m.MIRT_MODE_PT, num_bounces=8),
+              "pool": m.make_params(W, H, spp, mode=m.MIRT_MODE_PT, num_bounces=8, flags=m.MIRT_FLAG_KERNEL_POOL)}
+        imgs, kernels = {}, {}
+        for k, p in ps.items():                                     # warm-up: one window of each, and the images compared once
+            imgs[k] = ctx.render(p)
+            kernels[k] = ctx.last_kernel()
+            _window_ms(ctx, p, window_ms)
+        t, launches = {"strip": [], "pool": []}, 0
+        for _ in range(reps):                                       # alternating windows
+            for k, p in ps.items():
+                ms, launches = _window_ms(ctx, p, window_ms)
+                t[k].append(ms)
+        strip, pool = statistics.median(t["strip"]), statistics.median(t["pool"])
+        print(json.dumps({"case": "pool", "world": name, "bvh": bvh, "max_depth": depth, "spp": spp, "width": W, "height": H, "strip_ms": round(strip, 3),
+                          "pool_ms": round(pool, 3), "pool_over_strip": round(pool / strip, 3), "images_equal": bool(np.array_equal(imgs["strip"], imgs["pool"])),
+                          "strip_kernel": kernels["strip"], "pool_kernel": kernels["pool"], "plan": m.bvh_pool_plan(depth), "knobs": knobs,
+                          "window_ms": window_ms, "launches_in_last_window": launches,
+                          "strip_all_ms": [round(x, 3) for x in t["strip"]], "pool_all_ms": [round(x, 3) for x in t["pool"]]}), flush=True)
+    if counts:                                                      # deterministic: no timer
+        ctx.set_scene(sdc, hbm=True, bvh=bvh)
+        row = {"case": "pool_lane_use", "world": name, "bvh": bvh, "width": 480, "height": 270, "spp": 32}
+        count = m.MIRT_FLAG_COUNT_WORK | m.MIRT_FLAG_COUNT_GRID
+        for k, flags in (("strip", count), ("pool", count | m.MIRT_FLAG_KERNEL_POOL)):
+            ctx.render(m.make_params(480, 270, 32, mode=m.MIRT_MODE_PT, num_bounces=8, flags=flags))
+            st = ctx.stats()
+            row[k] = {"kernel": ctx.last_kernel(), "traversal_lane_use": round(st["grid_cells"] / (64.0 * st["grid_wave_cells"]), 4),
+                      "step_lane_use": round(st["lane_iterations"] / (64.0 * st["wave_iterations"]), 4), "rays": st["rays"],
+                      "grid_cells": st["grid_cells"], "grid_wave_cells": st["grid_wave_cells"], "lane_iterations": st["lane_iterations"],
+                      "wave_iterations": st["wave_iterations"]}
+        print(json.dumps(row), flush=True)
+    ctx.close()
+
+
+def pool_cases(a, fields) -> int:
+    """--pool: one child per world under its own time limit; nothing more is started after a child that did not end well."""
+    import subprocess
+    worlds = ([] if a.skip_rtiow else ["rtiow"]) + [str(n) for n in fields]
+    for world in worlds:
+        cmd = [sys.executable, str(Path(__file__).resolve()), "--pool-world", world, "--reps", str(a.reps), "--window-ms", str(a.window_ms),
+               "--bvh", a.bvh] + (["--pool-counts"] if a.pool_counts else [])
+        try:
+            rc = subprocess.run(cmd, timeout=a.step_timeout).returncode
+        except subprocess.TimeoutExpired:
+            rc = 124
+        if rc != 0:
+            print(json.dumps({"case": "pool", "world": world, "error": f"child ended with status {rc}; nothing further was run"}), flush=True)
+            return rc
+    return 0
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--reps", type=int, default=5)
@@ -298,8 +382,19 @@ def main() -> None:
     ap.add_argument("--soup", type=int, default=100000, help="--bvh both: spheres of the clustered soup (0: none)")
     ap.add_argument("--update", action="store_true", help="in-place updates against the device rebuild they replace")
     ap.add_argument("--set-spheres", action="store_true", help="a new sphere table by set_spheres / set_spheres_device against set_scene_ex")
+    ap.add_argument("--pool", action="store_true", help="the pooled schedule of HBM scenes against the strip kernel, one child process per world")
+    ap.add_argument("--pool-counts", action="store_true", help="--pool: also the lane use of both schedules from counting launches")
+    ap.add_argument("--pool-world", default="", help=argparse.SUPPRESS)          # a child of --pool: rtiow, or a field's sphere count
+    ap.add_argument("--window-ms", type=float, default=100.0, help="--pool: kernel time of one timing window")
+    ap.add_argument("--step-timeout", type=float, default=240.0, help="--pool: seconds a world's child process may take")
     a = ap.parse_args()
     fields = [int(x) for x in a.fields.split(",") if x]
+    if a.pool_world:
+        pool_world(a.pool_world, a.reps, a.window_ms, "host" if a.bvh == "both" else a.bvh, a.pool_counts)
+        return
+    if a.pool:
+        a.bvh = "host" if a.bvh == "both" else a.bvh
+        sys.exit(pool_cases(a, fields))
     if a.set_spheres:
         for n in fields:
             set_spheres_case(n, a.reps)

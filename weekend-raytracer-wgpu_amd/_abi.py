@@ -140,6 +140,14 @@ class MirtBvhInfo(C.Structure):
                 "centre": [float(v) for v in self.centre], "radius": float(self.radius), "r_max": float(self.r_max)}
 
 
+class MirtBvhPoolPlan(C.Structure):
+    _fields_ = [("threads", C.c_uint32), ("slots", C.c_uint32), ("waves_per_cu", C.c_uint32), ("stack_entries", C.c_uint32),
+                ("lds_bytes_per_block", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MirtStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("kernel_ms_total", C.c_double), ("launches", C.c_uint64),
                 ("samples", C.c_uint64), ("rays", C.c_uint64),
@@ -188,6 +196,7 @@ SYMBOLS = {
     "mirt_ctx_set_scene_ex": (C.c_int, [C.c_void_p, _P(MirtScene), C.c_uint32]),
     "mirt_bvh_plan": (C.c_int, [C.c_void_p, C.c_uint32, _P(MirtBvhPlan)]),
     "mirt_ctx_bvh_info": (C.c_int, [C.c_void_p, _P(MirtBvhInfo)]),
+    "mirt_bvh_pool_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, _P(MirtBvhPoolPlan)]),
     "mirt_ctx_bvh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "mirt_ctx_update_spheres": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "mirt_ctx_update_spheres_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),

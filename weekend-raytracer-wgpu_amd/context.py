@@ -76,6 +76,15 @@ def bvh_plan(spheres) -> dict:
     return out.as_dict()
 
 
+def bvh_pool_plan(max_depth: int, hosek: bool = False, lds_bytes_per_cu: int = 0) -> dict:
+    """mirt_bvh_pool_plan: the geometry MIRT_FLAG_KERNEL_POOL runs on a MIRT_SCENE_HBM scene whose tree is `max_depth` deep
+    (Context.bvh_info()["plan"]["max_depth"]), host only: {"threads", "slots", "waves_per_cu", "stack_entries",
+    "lds_bytes_per_block"}; slots == 0: none fits and the launch runs the strip kernel.  lds_bytes_per_cu = 0: gfx950's 163 840."""
+    out = _abi.MirtBvhPoolPlan()
+    check(lib().mirt_bvh_pool_plan(int(max_depth), 1 if hosek else 0, int(lds_bytes_per_cu), C.byref(out)))
+    return out.as_dict()
+
+
 # one inner node as mirt_ctx_bvh_read returns it (csrc/mirt_bvh.h: BvhNode, 64 bytes)
 BVH_NODE_DTYPE = np.dtype([("lmin", "<f4", (3,)), ("lmax", "<f4", (3,)), ("rmin", "<f4", (3,)), ("rmax", "<f4", (3,)),
                            ("left", "<u4"), ("right", "<u4"), ("pad", "<u4", (2,))])

@@ -290,6 +290,7 @@ struct Tuning {
     uint32_t static_block = 0;        // MIRT_STATIC_BLOCK=64/128/256 (A/B runs): threads per block of the launches that run one unit per wave
     int      static_grid = -1;        // MIRT_STATIC_GRID=k (A/B runs): launches with one unit per wave run k x the resident blocks instead, units dealt round-robin
     int      timing = -1;             // MIRT_TIMING=0/1: the context's initial mirt_ctx_set_timing state (A/B runs; default 1)
+    uint32_t hbm_pool_slots = 0;      // MIRT_HBM_POOL_SLOTS=n (A/B runs): the pooled build of MIRT_SCENE_HBM scenes takes this one of kBvhPoolSlotChoices
     bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
 };
 
@@ -317,8 +318,33 @@ Tuning read_tuning()
     if (const char* e = std::getenv("MIRT_STATIC_GRID")) { const int v = std::atoi(e); if (v >= 1 && v <= 64) t.static_grid = v; }
     if (const char* e = std::getenv("MIRT_TIMING")) t.timing = (e[0] == '0') ? 0 : 1;
     if (const char* e = std::getenv("MIRT_EXT_EVENTS")) t.ext_events = e[0] != '0';
+    if (const char* e = std::getenv("MIRT_HBM_POOL_SLOTS")) {
+        const uint32_t v = (uint32_t)std::atoi(e);
+        for (uint32_t s : mirt::kBvhPoolSlotChoices) if (v == s) t.hbm_pool_slots = v;
+    }
     if (const char* e = std::getenv("MIRT_GRID_BIG")) { const double v = std::atof(e); if (v >= 1.0 && v <= 1024.0) t.grid_big = v; }
     return t;
+}
+
+// The geometry of the pooled kernel of MIRT_SCENE_HBM scenes (mirt_bvh_pool_plan; the launch calls this very function) for a tree
+// `max_depth` deep: per block the camera (+ sky), and per wave a pool and 64 stacks of max_depth entries.  The rule (mirt_kernels.h,
+// DESIGN.md 10.6): the first of kBvhPoolSlotChoices -- largest pools first -- that leaves kBvhPoolWavesPerCu waves resident, else the
+// choice with most waves, the larger pools on a tie.  slots == 0: not even one block fits.  `only_slots` != 0 (A/B runs): that choice alone.
+MirtBvhPoolPlan plan_bvh_pool(uint32_t max_depth, bool hosek, uint64_t lds_per_cu, uint32_t only_slots)
+{
+    MirtBvhPoolPlan best{};
+    const uint32_t waves = mirt::kBvhPoolThreads / 64u;
+    const uint64_t scene = kx::scene_lds_bytes_grid(0u, hosek);
+    for (uint32_t slots : mirt::kBvhPoolSlotChoices) {
+        if (only_slots != 0u && slots != only_slots) continue;
+        const uint64_t block = scene + (uint64_t)waves * (mirt::bvh_pool_bytes_per_wave(slots) + 256ull * max_depth);
+        uint64_t blocks = lds_per_cu / block;
+        if (blocks > mirt::kBvhPoolWavesPerCu / waves) blocks = mirt::kBvhPoolWavesPerCu / waves;
+        if ((uint32_t)blocks * waves > best.waves_per_cu)
+            best = MirtBvhPoolPlan{ mirt::kBvhPoolThreads, slots, (uint32_t)blocks * waves, max_depth, (uint32_t)block };
+        if (best.waves_per_cu == mirt::kBvhPoolWavesPerCu) break;
+    }
+    return best;
 }
 
 // A camera whose thin-lens offset is exactly zero for every lens draw, so that `origin = eye + lens_radius * (...)`
@@ -590,6 +616,15 @@ int mirt_grid_plan(const MirtSphere* spheres, uint32_t n_spheres, uint64_t lds_b
     out->n_big = gh->n_big;
     const size_t beside = kx::scene_lds_bytes_grid(n_spheres, true) + grid.size();
     out->pool_slots = beside < lds ? kx::pool_config_grid(lds - beside).slots : 0u;
+    return MIRT_OK;
+}
+
+int mirt_bvh_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtBvhPoolPlan* out)
+{
+    if (!out) return fail(MIRT_ERR_NULL_POINTER, "out is null");
+    *out = MirtBvhPoolPlan{};
+    if (max_depth > MIRT_BVH_MAX_DEPTH) return fail(MIRT_ERR_BAD_ROWS, "max_depth %u exceeds MIRT_BVH_MAX_DEPTH (%u)", max_depth, (unsigned)MIRT_BVH_MAX_DEPTH);
+    *out = plan_bvh_pool(max_depth, hosek != 0u, lds_bytes_per_cu ? lds_bytes_per_cu : (uint64_t)160 * 1024, 0u);
     return MIRT_OK;
 }
 
@@ -1252,8 +1287,21 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
                       (!pool && p->spp >= mirt::kPoolMinSppGrid && c->n_shading_routines >= 1 && pool_grid_waves_per_cu >= 16));
     if (tune.pool_grid == 0) pool_grid = false;
     if (pool_grid) pool = true;
-    const mirt::PoolConfig pcu = pool_grid ? pcg : pc;                 // the geometry of the pool kernel that will run
-    const uint32_t resident_pool_waves = pool_grid ? pool_grid_waves_per_cu : pool_waves_per_cu;
+    // MIRT_SCENE_HBM scene: the strip kernel (parity kernel) with the tables in device memory -- the BVH build unless NO_GRID asks for the
+    // flat scan or a counting launch asks for the flat scan's counters (COUNT_WORK without COUNT_GRID); tile hints do not apply.
+    // MIRT_FLAG_KERNEL_POOL on the BVH build: the pooled kernel (render_pt_pool_hbm_kernel) where the pool's own limits allow it -- 8-bit
+    // bounce counters, no per-frame RNG stream, a geometry that fits beside the stacks of a tree this deep -- and _STRIP does not object.
+    // Never by default: DESIGN.md 10.6 has the measured crossovers.
+    const bool hbm = c->hbm;
+    const bool hbm_bvh = hbm && pt && !(p->flags & MIRT_FLAG_NO_GRID) && (!count || (p->flags & MIRT_FLAG_COUNT_GRID));
+    MirtBvhPoolPlan hbm_plan{};
+    if (hbm_bvh && (p->flags & MIRT_FLAG_KERNEL_POOL) && !(p->flags & MIRT_FLAG_KERNEL_STRIP) && !frame_stream && p->num_bounces <= 255u)
+        hbm_plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, tune.hbm_pool_slots);
+    const bool pool_hbm = hbm_plan.slots != 0u && hbm_plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
+    if (pool_hbm) pool = true;
+    // the geometry of the pool kernel that will run
+    const mirt::PoolConfig pcu = pool_hbm ? mirt::PoolConfig{ hbm_plan.threads, hbm_plan.slots, hbm_plan.lds_bytes_per_block } : pool_grid ? pcg : pc;
+    const uint32_t resident_pool_waves = pool_hbm ? hbm_plan.waves_per_cu : pool_grid ? pool_grid_waves_per_cu : pool_waves_per_cu;
 
     mirt::RenderArgs a{};
     a.cam = c->cam;
@@ -1323,10 +1371,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     a.grid_flat_y = (use_grid && c->grid_flat_y) ? 1u : 0u;
     // (the strip kernel's grid build keeps a camera-ray candidate list per wave behind the blob: 4 waves x 48 bytes)
     a.lds_bytes = use_grid ? (uint32_t)(scene_lds_g + a.grid_bytes + (pool ? pcu.lds_bytes : 4u * 48u)) : (uint32_t)(scene_lds + (pool ? pcu.lds_bytes : 0));
-    // MIRT_SCENE_HBM scene: the strip kernel (parity kernel) with the tables in device memory -- the BVH build unless NO_GRID asks for the
-    // flat scan or a counting launch asks for the flat scan's counters (COUNT_WORK without COUNT_GRID); pool / tile / strip hints do not apply
-    const bool hbm = c->hbm;
-    const bool hbm_bvh = hbm && pt && !(p->flags & MIRT_FLAG_NO_GRID) && (!count || (p->flags & MIRT_FLAG_COUNT_GRID));
+    if (pool_hbm) a.lds_bytes = hbm_plan.lds_bytes_per_block;     // camera (+ sky), the block's pools, its waves' traversal stacks
     if (hbm) {
         a.bvh_nodes = reinterpret_cast<const float4*>(c->d_bvh);
         a.bvh_recs = reinterpret_cast<const float4*>(c->d_bvh + c->bvh_off_recs);
@@ -1336,6 +1381,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
         for (int k = 0; k < 3; ++k) a.bvh_centre[k] = c->bvh_centre[k];
         a.bvh_radius = c->bvh_radius;
         a.bvh_rmax = c->bvh_rmax;
+        a.bvh_stack_entries = pool_hbm ? hbm_plan.stack_entries : 0u;
     }
     if (!use_grid && !c->fits_flat && !hbm)
         return fail(MIRT_ERR_SCENE_TOO_LARGE, "this scene only fits LDS in the grid build of the path-traced mode "
@@ -1346,7 +1392,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     //  a tiny frame with many samples per pixel needs the lanes of a wave on the samples)
     bool by_pixel = pt && !pool && !count && (p->spp < mirt::kByPixelMaxSpp || (c->n_shading_routines <= 1 && npix >= 64ull * 4u * c->cu_count));
     if (tune.by_pixel >= 0) by_pixel = pt && !pool && !count && tune.by_pixel == 1;
-    if (hbm_bvh && !count) by_pixel = true;              // the BVH build: lane = pixel at every sample count
+    if (hbm_bvh && !count && !pool_hbm) by_pixel = true;  // the BVH build's strip kernel: lane = pixel at every sample count
     if (frame_stream) by_pixel = true;                    // also for counting launches (flat scan) and any spp
     // parity mode: lane = pixel at EVERY sample count, counting or not (round 3: below 64 spp).  The reference's loop returns at the first
     // terminating sample (layer.rs:320-378), which a lane that walks its own pixel's samples does too, while lane = sample computes 64
@@ -1391,11 +1437,20 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
         if (tune.static_units >= 0) a.static_units = (uint32_t)tune.static_units;
     }
 
+    // the opt-in fast-math build of the path-traced kernels; counting launches always run the exact build
+    const bool fast = pt && !count && (p->flags & MIRT_FLAG_FAST_MATH);
     uint32_t blocks;
     if (pool) {
         uint32_t per_cu = (uint32_t)(c->lds_per_cu / (a.lds_bytes ? a.lds_bytes : 1));
         const uint32_t by_waves = 32u / (pcu.threads / 64u);   // upper bound; LDS decides (6 blocks of 4 waves with 112-slot pools)
         if (per_cu > by_waves) per_cu = by_waves;
+        if (pool_hbm) {                                        // the plan's waves, and no more blocks than the build's registers keep resident
+            const uint32_t planned = hbm_plan.waves_per_cu / (pcu.threads / 64u);
+            const uint32_t fit = fast ? kf::hbm_pool_blocks_per_cu(pcu.slots, hosek, count, a.lds_bytes, frame)
+                                      : kx::hbm_pool_blocks_per_cu(pcu.slots, hosek, count, a.lds_bytes, frame);
+            if (per_cu > planned) per_cu = planned;
+            if (fit >= 1u && per_cu > fit) per_cu = fit;
+        }
         if (tune.pool_blocks_per_cu >= 1 && tune.pool_blocks_per_cu < per_cu) per_cu = tune.pool_blocks_per_cu;
         if (per_cu == 0u) per_cu = 1u;
         blocks = (uint32_t)c->cu_count * per_cu;
@@ -1457,11 +1512,13 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     const bool ext_events = tune.ext_events && need_end;
     if (timed && !ext_events) HIP_TRY(hipEventRecord(c->ev_begin[ev], stream));
     const mirt::LaunchOn on = ext_events ? mirt::LaunchOn(stream, timed ? c->ev_begin[ev] : nullptr, c->ev_end[ev]) : mirt::LaunchOn(stream);
-    // the opt-in fast-math build of the path-traced kernels; counting launches always run the exact build
-    const bool fast = pt && !count && (p->flags & MIRT_FLAG_FAST_MATH);
     const char* tf[2] = { "false", "true" };
     char kname[112] = "";
-    if (hbm) {
+    if (pool_hbm) {
+        HIP_TRY(fast ? kf::launch_pt_pool_hbm(a, blocks, pcu.slots, count, on) : kx::launch_pt_pool_hbm(a, blocks, pcu.slots, count, on));
+        snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_pool_hbm%s_kernel<%u,%u,%u,%s,%s>", fast ? "fast_build::" : "", kframe, pcu.threads,
+                 pcu.slots, count ? 1u : mirt::kBvhPoolMinWaves, tf[count], tf[hosek]);
+    } else if (hbm) {
         if (p->mode == MIRT_MODE_PARITY) {
             HIP_TRY(kx::launch_parity_hbm(a, blocks, count, by_pixel, on));
             snprintf(c->last_kernel, sizeof c->last_kernel, "render_parity_hbm_kernel<%s,%s>", tf[count], tf[by_pixel]);

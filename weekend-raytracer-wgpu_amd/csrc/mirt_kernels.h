@@ -217,9 +217,22 @@ struct RenderArgs {
     uint32_t        bvh_n_always;
     float           bvh_centre[3];         // a sphere around every tree sphere's box, and the largest |radius| in the tree:
     float           bvh_radius, bvh_rmax;  // the traversal's rounding bound (nearest_hit_bvh)
+    uint32_t        bvh_stack_entries;     // render_pt_pool_hbm_kernel: node references per lane of a wave's traversal stacks = the depth of the
+                                           // resident tree (MirtBvhInfo.plan.max_depth); the strip builds always keep MIRT_BVH_MAX_DEPTH
 };
 // MIRT_SCENE_HBM, BVH build: every wave keeps 64 per-lane traversal stacks of MIRT_BVH_MAX_DEPTH node references in LDS
 constexpr uint32_t kBvhStackBytesPerWave = 64u * MIRT_BVH_MAX_DEPTH * 4u;
+
+// MIRT_SCENE_HBM, pooled build (render_pt_pool_hbm_kernel, MIRT_FLAG_KERNEL_POOL): 256-thread blocks whose waves keep a
+// two-queue pool (WavePoolLayout<SLOTS, 1>: 50 x SLOTS + 384 bytes) and, behind the block's pools, 64 traversal stacks of as many
+// entries as the resident tree is deep (256 x depth bytes per wave).  The geometry is chosen per launch by plan_bvh_pool (mirt_api.hip,
+// mirt_bvh_pool_plan): the largest pools that leave kBvhPoolWavesPerCu waves resident, or, where no choice does, the choice that keeps
+// most waves (the larger pools on a tie).  The non-counting builds are held to the registers of that many waves.
+constexpr uint32_t kBvhPoolThreads = 256;
+constexpr uint32_t kBvhPoolMinWaves = 4;                          // waves per SIMD (launch bounds): 16 per CU
+constexpr uint32_t kBvhPoolWavesPerCu = 4u * kBvhPoolMinWaves;
+constexpr uint32_t kBvhPoolSlotChoices[4] = { 112, 96, 80, 64 };
+constexpr uint32_t bvh_pool_bytes_per_wave(uint32_t slots) { return 50u * slots + 384u; }     // == WavePoolLayout<slots, 1>::kBytes (static_assert in the kernel)
 
 // The parts of a tile-interleaved frame and where they go (assemble_parts_kernel).  Two forms:
 //   table  (part_stride_px == 0): parts[i] is part i's compact buffer, n_parts <= kAssembleMaxParts (the node's members);
@@ -252,12 +265,17 @@ uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pi
 hipError_t launch_pt_pool(const RenderArgs& a, uint32_t grid_blocks, uint32_t cfg, bool count, uint32_t nq, LaunchOn stream);
 hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
 uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame = false);
+hipError_t launch_pt_pool_hbm(const RenderArgs& a, uint32_t grid_blocks, uint32_t slots, bool count, LaunchOn stream);
+uint32_t   hbm_pool_blocks_per_cu(uint32_t slots, bool hosek, bool count, uint32_t lds_bytes, bool frame = false);
 }
 namespace exact_build {
 // MIRT_SCENE_HBM scenes: the strip kernel with the scene in device memory -- a flat scan (bvh = false) or the BVH traversal -- and
 // the parity kernel's flat scan reading the spheres from device memory
 hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
 uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame = false);
+// ... and the pooled build of `slots` path slots per wave (kBvhPoolSlotChoices); blocks per CU 0: no such build
+hipError_t launch_pt_pool_hbm(const RenderArgs& a, uint32_t grid_blocks, uint32_t slots, bool count, LaunchOn stream);
+uint32_t   hbm_pool_blocks_per_cu(uint32_t slots, bool hosek, bool count, uint32_t lds_bytes, bool frame = false);
 hipError_t launch_parity_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);
 uint32_t   parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
 hipError_t launch_parity(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);

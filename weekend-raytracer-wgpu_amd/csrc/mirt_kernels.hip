@@ -1621,7 +1621,8 @@ MIRT_DEV uint32_t strip_candidates(const RenderArgs& AP, const SceneLds& S, uint
 //
 // Traversal: near child first, the far one on a per-lane stack in LDS of MIRT_BVH_MAX_DEPTH entries.  An entry is pushed only at an
 // inner node, at most one per level of the path from the root, and the builder bounds the depth (mirt_bvh.cpp): the stack cannot
-// fill; a push past its end is not written in any case.
+// fill; a push past its end is not written in any case.  `stack_cap` = the entries the caller's stack holds: MIRT_BVH_MAX_DEPTH in the
+// strip kernels; the pooled kernel sizes its stacks by the resident tree's depth (RenderArgs.bvh_stack_entries).
 constexpr uint32_t kBvhLeafRef = 0x80000000u;      // mirt_bvh.h: kBvhLeaf -- count in bits 24..30, first record in bits 0..23
 constexpr uint32_t kBvhStack = MIRT_BVH_MAX_DEPTH;
 constexpr float    kBvhSlack = 1.0f + 0x1p-9f;
@@ -1647,7 +1648,8 @@ MIRT_DEV void bvh_slab(float4 lo_hi_a, float4 lo_hi_b, float4 lo_hi_c, int first
 }
 
 template <bool COUNT>
-MIRT_DEV int nearest_hit_bvh(f3 ro, f3 rd, bool alive, float& closest_out, Work<COUNT>& work, uint32_t lane, uint32_t* stack)
+MIRT_DEV int nearest_hit_bvh(f3 ro, f3 rd, bool alive, float& closest_out, Work<COUNT>& work, uint32_t lane, uint32_t* stack,
+                             uint32_t stack_cap = kBvhStack)
 {
     const RenderArgs& A = per_strip_args();          // the tree's pointers and bounds: read where they are used, not held across the path
     const float a = dot(rd, rd);
@@ -1696,7 +1698,7 @@ MIRT_DEV int nearest_hit_bvh(f3 ro, f3 rd, bool alive, float& closest_out, Work<
                 if (vl & vr) {
                     const bool left_first = !(tnr < tnl);
                     ref = left_first ? lref : rref;
-                    if (sp < kBvhStack) { stack[sp * 64u + lane] = left_first ? rref : lref; ++sp; }
+                    if (sp < stack_cap) { stack[sp * 64u + lane] = left_first ? rref : lref; ++sp; }
                 } else if (vl | vr) {
                     ref = vl ? lref : rref;
                 } else {
@@ -2127,6 +2129,38 @@ struct WavePoolLayout {
 #undef MIRT_POOL_KERNEL_TILE
 #undef MIRT_POOL_KERNEL_FRAME
 
+// ------------------------------------------------------------------------------------------
+// render_pt_pool_hbm — the pooled schedule for MIRT_SCENE_HBM scenes (mirt_pool_hbm_kernel.inc)
+// ------------------------------------------------------------------------------------------
+// Its pool is WavePoolLayout<SLOTS, 1> (two queues), its slots the same three uint4 -- but a sphere id of such a scene needs 24 bits
+// (MIRT_SCENE_HBM_MAX_SPHERES), so the id leaves the first vector's state word for the third vector's fourth word, free in non-grid builds:
+//   q0 = {hit point, pixel << 12 | bounce << 16 | has_miss << 24}      (bits 0..11, the LDS builds' sphere id, stay zero)
+//   q1 = {incoming direction rd, rng}
+//   q2 = {throughput, sphere id | hit << 31}                           (id in bits 0..23; 0 without a hit)
+struct PoolHbmState {
+    static constexpr uint32_t kIdBits = 24, kPixelShift = 12, kBounceShift = 16, kMissShift = 24, kHitShift = 31;
+    static_assert(MIRT_SCENE_HBM_MAX_SPHERES <= (1u << kIdBits), "a sphere id must fit the id field");
+    static_assert(kIdBits <= kHitShift, "the hit bit lies above the id");
+    static_assert(kStripPixels <= (1u << (kBounceShift - kPixelShift)), "a strip's pixel index must fit its field");
+    static_assert(kMissShift - kBounceShift == 8, "bounce counters are 8 bit (the host pools no launch with num_bounces > 255)");
+    static MIRT_DEV uint32_t flags(uint32_t pixel, uint32_t bounce, uint32_t miss) { return (pixel << kPixelShift) | (bounce << kBounceShift) | (miss << kMissShift); }
+    static MIRT_DEV uint32_t hit_word(int nb) { return nb < 0 ? 0u : ((uint32_t)nb | (1u << kHitShift)); }
+    static MIRT_DEV uint32_t id(uint32_t hit_word) { return hit_word & ((1u << kIdBits) - 1u); }
+    static MIRT_DEV uint32_t pixel(uint32_t fl) { return (fl >> kPixelShift) & ((1u << (kBounceShift - kPixelShift)) - 1u); }
+    static MIRT_DEV uint32_t bounce(uint32_t fl) { return (fl >> kBounceShift) & 0xffu; }
+    static MIRT_DEV uint32_t miss(uint32_t fl) { return (fl >> kMissShift) & 1u; }
+};
+#define MIRT_POOL_HBM_KERNEL_FRAME false
+#define MIRT_POOL_HBM_KERNEL_NAME render_pt_pool_hbm_kernel
+#include "mirt_pool_hbm_kernel.inc"
+#undef MIRT_POOL_HBM_KERNEL_NAME
+#undef MIRT_POOL_HBM_KERNEL_FRAME
+#define MIRT_POOL_HBM_KERNEL_FRAME true
+#define MIRT_POOL_HBM_KERNEL_NAME render_pt_pool_hbm_frame_kernel
+#include "mirt_pool_hbm_kernel.inc"
+#undef MIRT_POOL_HBM_KERNEL_NAME
+#undef MIRT_POOL_HBM_KERNEL_FRAME
+
 #ifdef MIRT_ISA_PROBES
 #include "mirt_isa_probes.inc"       // tools/isa_mix.py; never part of libmirt.so
 #endif
@@ -2387,6 +2421,43 @@ uint32_t parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, u
     return blocks_per_cu(reinterpret_cast<const void*>(parity_hbm_kernel(count, by_pixel)), threads, lds_bytes);
 }
 #endif
+
+// ---- MIRT_SCENE_HBM scenes, pooled (MIRT_FLAG_KERNEL_POOL): one build per geometry of kBvhPoolSlotChoices ----
+template <uint32_t SL>
+static StripKernel hbm_pool_kernel_(bool count, bool hosek, bool frame)
+{
+    constexpr uint32_t T = kBvhPoolThreads, MW = kBvhPoolMinWaves;
+#ifdef MIRT_FAST_MATH
+    if (count) return nullptr;                   // the counting builds exist in the exact build only
+#else
+    if (count) return frame ? (hosek ? render_pt_pool_hbm_frame_kernel<T, SL, 1, true, true> : render_pt_pool_hbm_frame_kernel<T, SL, 1, true, false>)
+                            : (hosek ? render_pt_pool_hbm_kernel<T, SL, 1, true, true> : render_pt_pool_hbm_kernel<T, SL, 1, true, false>);
+#endif
+    return frame ? (hosek ? render_pt_pool_hbm_frame_kernel<T, SL, MW, false, true> : render_pt_pool_hbm_frame_kernel<T, SL, MW, false, false>)
+                 : (hosek ? render_pt_pool_hbm_kernel<T, SL, MW, false, true> : render_pt_pool_hbm_kernel<T, SL, MW, false, false>);
+}
+
+static StripKernel hbm_pool_kernel(uint32_t slots, bool count, bool hosek, bool frame)
+{
+    if (slots == kBvhPoolSlotChoices[0]) return hbm_pool_kernel_<kBvhPoolSlotChoices[0]>(count, hosek, frame);
+    if (slots == kBvhPoolSlotChoices[1]) return hbm_pool_kernel_<kBvhPoolSlotChoices[1]>(count, hosek, frame);
+    if (slots == kBvhPoolSlotChoices[2]) return hbm_pool_kernel_<kBvhPoolSlotChoices[2]>(count, hosek, frame);
+    if (slots == kBvhPoolSlotChoices[3]) return hbm_pool_kernel_<kBvhPoolSlotChoices[3]>(count, hosek, frame);
+    return nullptr;
+}
+
+hipError_t launch_pt_pool_hbm(const RenderArgs& a, uint32_t grid_blocks, uint32_t slots, bool count, LaunchOn stream)
+{
+    const StripKernel k = hbm_pool_kernel(slots, count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, is_frame(a));
+    if (!k) return hipErrorInvalidValue;
+    return launch_with_lds(k, dim3(grid_blocks), dim3(kBvhPoolThreads), a, stream);
+}
+
+uint32_t hbm_pool_blocks_per_cu(uint32_t slots, bool hosek, bool count, uint32_t lds_bytes, bool frame)
+{
+    const StripKernel k = hbm_pool_kernel(slots, count, hosek, frame);
+    return k ? blocks_per_cu(reinterpret_cast<const void*>(k), kBvhPoolThreads, lds_bytes) : 0u;
+}
 
 // builds of the pool kernel by scatter queues: 3 and 5 for every geometry; 1, 2 and 4 as well (FEW = true) for the default and the
 // tile geometry -- a scene with fewer shading routines than queues would carry empty queues through every pick and push

@@ -40,6 +40,14 @@ inline int set_scene_any_size(MirtContext* ctx, const MirtScene& sc, bool* hbm =
 inline void set_scene(MirtContext* ctx, const MirtScene& sc, uint32_t flags) { check(mirt_ctx_set_scene_ex(ctx, &sc, flags)); }
 // mirt_ctx_bvh_info: the tree of the context's MIRT_SCENE_HBM scene (built on the host, or on the device with MIRT_SCENE_BVH_DEVICE)
 inline MirtBvhInfo bvh_info(MirtContext* ctx) { MirtBvhInfo info; check(mirt_ctx_bvh_info(ctx, &info)); return info; }
+// mirt_bvh_pool_plan: the geometry MIRT_FLAG_KERNEL_POOL runs on a MIRT_SCENE_HBM scene whose tree is `max_depth` deep (host only;
+// slots == 0: none fits, the launch runs the strip kernel)
+inline MirtBvhPoolPlan bvh_pool_plan(uint32_t max_depth, bool hosek = false, uint64_t lds_bytes_per_cu = 0)
+{
+    MirtBvhPoolPlan plan;
+    check(mirt_bvh_pool_plan(max_depth, hosek ? 1u : 0u, lds_bytes_per_cu, &plan));
+    return plan;
+}
 // mirt_ctx_update_spheres: spheres first .. first + count of a MIRT_SCENE_HBM scene take centre and radius from `spheres` (material_idx
 // is not read); the BVH is refitted on the device.  mirt_ctx_bvh_refits counts the updates since the scene was set.
 inline void update_spheres(MirtContext* ctx, uint32_t first, const std::vector<MirtSphere>& spheres)
