@@ -447,6 +447,45 @@ uint32_t mirt_ctx_bvh_refits(const MirtContext* ctx);
 int      mirt_ctx_set_spheres(MirtContext* ctx, const MirtSphere* spheres, uint32_t n_spheres);
 int      mirt_ctx_set_spheres_device(MirtContext* ctx, const void* d_spheres, uint32_t n_spheres);
 
+/* ---- ray queries against a MIRT_SCENE_HBM scene: picking, line of sight, batches of rays ----
+ * Every ray gets the answer of the flat scan over the resident sphere table, by the renderer's own arithmetic (the sphere test of the
+ * path-traced kernels): `closest` starts at the ray's t_max (pass 1000.0f for exactly what a path of the renderer gets), a sphere wins
+ * with f < closest, f = the first computed root above MIN_T = 0.001, and on equal f the lower ORIGINAL index wins.  `direction` is not
+ * normalised; t is in units of it.  On a hit: sphere = the original index, t = f, point = fma(t, direction, origin) per component,
+ * normal = inv_r * (point - centre) with inv_r the table's single IEEE 1 / r -- what the renderer shades with: NOT turned towards the
+ * ray, so it points inwards for a negative radius.  On a miss: sphere = MIRT_RAY_MISS and every other field 0.  Every float bit pattern
+ * is legal in a ray (NaN or infinite t_max, a zero direction, non-finite origins): the result is whatever that arithmetic gives, a miss
+ * for a NaN t_max or a zero direction, and the tree walk agrees with it bit for bit.  `_pad` is not read.  Materials are never read: a
+ * material_idx out of range in the scene does not matter here.
+ * flags:
+ *   0                   the BVH walk of the render kernels (trace_rays_kernel<true,...>), lane = ray, rays in the caller's order;
+ *   MIRT_RAYS_FLAT      the flat scan itself (trace_rays_kernel<false,...>): the comparison build, as MIRT_FLAG_NO_GRID is for renders;
+ *   MIRT_RAYS_ANY_HIT   occlusion query: a ray stops at the first sphere it finds with f < t_max and writes sphere = 0 ("something is
+ *                       hit") or MIRT_RAY_MISS, every other field 0; hit or miss is exactly that of the nearest-hit query.  Valid with _FLAT;
+ *   MIRT_RAYS_COUNT     the counting build: fills the counters of MirtRayStats (otherwise 0).  Same results.
+ *   any other bit: MIRT_ERR_BAD_MODE.
+ * MIRT_ERR_NULL_POINTER: ctx is null, or rays / hits is with n_rays > 0;  MIRT_ERR_NO_SCENE: no scene, or not a MIRT_SCENE_HBM one (the LDS
+ * layouts keep no record table and no tree to query);  n_rays == 0: MIRT_OK without device work.
+ *   mirt_ctx_trace_rays          rays and hits in HOST memory: copy, kernel, copy on the context's stream; blocking.
+ *   mirt_ctx_trace_rays_device   rays and hits in memory of the context's device (4-byte aligned), queued on `hip_stream` (NULL = the
+ *                                context's stream; hipStreamLegacy for the default stream, as for mirt_ctx_render_device), no host
+ *                                synchronisation.  The kernel reads the tree as it is when it RUNS; mirt_ctx_set_scene*, _update_spheres*
+ *                                and _set_spheres* wait for the device before they write, so they stay ordered after traces in flight.
+ * Neither touches the accumulation buffer or MirtStats; mirt_ctx_last_kernel reports the trace kernel afterwards; mirt_ctx_synchronize
+ * waits for traces too.  Counting traces (MIRT_RAYS_COUNT) share one counter block: the caller keeps them in order among themselves. */
+typedef struct MirtRay    { float origin[3]; float t_max; float direction[3]; float _pad; } MirtRay;      /* 32 B */
+typedef struct MirtRayHit { float t; uint32_t sphere; float point[3]; float normal[3]; }   MirtRayHit;    /* 32 B */
+#define MIRT_RAY_MISS 0xffffffffu
+enum { MIRT_RAYS_FLAT = 1u << 0, MIRT_RAYS_ANY_HIT = 1u << 1, MIRT_RAYS_COUNT = 1u << 2 };
+/* Of the LAST trace call.  kernel_ms: hipEvent time of its kernel, 0 with mirt_ctx_set_timing(ctx, 0).  The counters are filled by
+ * MIRT_RAYS_COUNT only: rays traced, sphere tests the lanes really performed, roots evaluated, rays with a hit, BVH nodes visited summed
+ * over lanes (leaves included) and BVH loop iterations summed over waves (x 64 = lane slots) -- both 0 for the flat scan. */
+typedef struct MirtRayStats { double kernel_ms; uint64_t rays, sphere_tests, roots, hits, nodes, wave_nodes; } MirtRayStats;
+int mirt_ctx_trace_rays(MirtContext* ctx, const MirtRay* rays, uint32_t n_rays, uint32_t flags, MirtRayHit* hits);
+int mirt_ctx_trace_rays_device(MirtContext* ctx, const void* d_rays, uint32_t n_rays, uint32_t flags, void* d_hits, void* hip_stream);
+/* Waits for the last trace call and reports its statistics (all 0 before the first). */
+int mirt_ctx_trace_stats(MirtContext* ctx, MirtRayStats* out);
+
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by
  * value with each launch, so this neither copies to the device nor synchronises; launches already
@@ -664,6 +703,9 @@ static_assert(sizeof(MirtMaterial) == 32, "GpuMaterial is 32 B (mod.rs:757-765)"
 static_assert(sizeof(MirtGpuCamera) == 96, "GpuCamera is 96 B (mod.rs:681-697)");
 static_assert(sizeof(MirtSkyState) == 144, "GpuSkyState is 144 B (mod.rs:888-896)");
 static_assert(sizeof(MirtCamera) == 48, "Camera is 12 f32 (mod.rs:489-499)");
+static_assert(sizeof(MirtRay) == 32, "MirtRay is two 16-byte loads");
+static_assert(sizeof(MirtRayHit) == 32, "MirtRayHit is two 16-byte stores");
+static_assert(sizeof(MirtRayStats) == 56, "MirtRayStats is a double and six u64");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -671,6 +713,9 @@ _Static_assert(sizeof(MirtMaterial) == 32, "GpuMaterial is 32 B (mod.rs:757-765)
 _Static_assert(sizeof(MirtGpuCamera) == 96, "GpuCamera is 96 B (mod.rs:681-697)");
 _Static_assert(sizeof(MirtSkyState) == 144, "GpuSkyState is 144 B (mod.rs:888-896)");
 _Static_assert(sizeof(MirtCamera) == 48, "Camera is 12 f32 (mod.rs:489-499)");
+_Static_assert(sizeof(MirtRay) == 32, "MirtRay is two 16-byte loads");
+_Static_assert(sizeof(MirtRayHit) == 32, "MirtRayHit is two 16-byte stores");
+_Static_assert(sizeof(MirtRayStats) == 56, "MirtRayStats is a double and six u64");
 #endif
 
 #endif /* MIRT_H */

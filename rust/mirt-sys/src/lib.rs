@@ -197,6 +197,45 @@ pub struct MirtBvhPoolPlan {
     pub lds_bytes_per_block: u32,
 }
 
+/// One ray of `mirt_ctx_trace_rays*`: `direction` is not normalised, `t_max` is the bound `closest` starts from (1000.0 = the renderer's).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtRay {
+    pub origin: [f32; 3],
+    pub t_max: f32,
+    pub direction: [f32; 3],
+    pub _pad: f32,
+}
+
+/// The flat scan's answer for one ray: `sphere == MIRT_RAY_MISS` (and every other field 0) for a miss.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtRayHit {
+    pub t: f32,
+    pub sphere: u32,
+    pub point: [f32; 3],
+    pub normal: [f32; 3],
+}
+
+/// `mirt_ctx_trace_stats`: of the last trace call; the counters are filled by `MIRT_RAYS_COUNT` only.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtRayStats {
+    pub kernel_ms: f64,
+    pub rays: u64,
+    pub sphere_tests: u64,
+    pub roots: u64,
+    pub hits: u64,
+    pub nodes: u64,
+    pub wave_nodes: u64,
+}
+
+pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
+/// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.
+pub const MIRT_RAYS_FLAT: u32 = 1 << 0;
+pub const MIRT_RAYS_ANY_HIT: u32 = 1 << 1;
+pub const MIRT_RAYS_COUNT: u32 = 1 << 2;
+
 /// `mirt_ctx_set_scene_ex` / `mirt_node_set_scene_ex` flags: the scene's tables in device memory, nearest hit through a BVH
 /// (worlds beyond the LDS budget, up to `MIRT_SCENE_HBM_MAX_SPHERES`).
 pub const MIRT_SCENE_HBM: u32 = 1 << 0;
@@ -277,6 +316,9 @@ extern "C" {
     pub fn mirt_ctx_bvh_refits(ctx: *const MirtContext) -> u32;
     pub fn mirt_ctx_set_spheres(ctx: *mut MirtContext, spheres: *const MirtSphere, n_spheres: u32) -> c_int;
     pub fn mirt_ctx_set_spheres_device(ctx: *mut MirtContext, d_spheres: *const c_void, n_spheres: u32) -> c_int;
+    pub fn mirt_ctx_trace_rays(ctx: *mut MirtContext, rays: *const MirtRay, n_rays: u32, flags: u32, hits: *mut MirtRayHit) -> c_int;
+    pub fn mirt_ctx_trace_rays_device(ctx: *mut MirtContext, d_rays: *const c_void, n_rays: u32, flags: u32, d_hits: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ctx_trace_stats(ctx: *mut MirtContext, out: *mut MirtRayStats) -> c_int;
     pub fn mirt_ctx_set_camera(ctx: *mut MirtContext, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_ctx_render(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;

@@ -31,6 +31,12 @@ MIRT_BVH_MAX_LEAF = 4
 MIRT_BVH_MAX_ALWAYS = 64
 MIRT_BVH_BIG_RADII = 4
 
+# mirt_ctx_trace_rays* flags, and the `sphere` of a ray that hits nothing
+MIRT_RAYS_FLAT = 1 << 0
+MIRT_RAYS_ANY_HIT = 1 << 1
+MIRT_RAYS_COUNT = 1 << 2
+MIRT_RAY_MISS = 0xFFFFFFFF
+
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
 MIRT_NODE_RCCL = 1 << 0
@@ -167,6 +173,22 @@ class MirtStats(C.Structure):
                 "texel_fetches": list(self.texel_fetches), "texel_tile_hits": list(self.texel_tile_hits)}
 
 
+class MirtRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_float)]
+
+
+class MirtRayHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("sphere", C.c_uint32), ("point", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class MirtRayStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("rays", C.c_uint64), ("sphere_tests", C.c_uint64), ("roots", C.c_uint64),
+                ("hits", C.c_uint64), ("nodes", C.c_uint64), ("wave_nodes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"kernel_ms": self.kernel_ms, **{k: int(getattr(self, k)) for k, _ in self._fields_[1:]}}
+
+
 class MirtNodeStats(C.Structure):
     _fields_ = [("n_members", C.c_uint32), ("transport", C.c_uint32), ("gather_ms", C.c_double), ("assemble_ms", C.c_double)]
 
@@ -203,6 +225,9 @@ SYMBOLS = {
     "mirt_ctx_set_spheres": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "mirt_ctx_set_spheres_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "mirt_ctx_bvh_refits": (C.c_uint32, [C.c_void_p]),
+    "mirt_ctx_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "mirt_ctx_trace_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mirt_ctx_trace_stats": (C.c_int, [C.c_void_p, _P(MirtRayStats)]),
     "mirt_ctx_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_ctx_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -127,6 +127,47 @@ def sphere_records(spheres) -> tuple:
     raise ValueError(f"spheres must be a SPHERE_DTYPE array, a ctypes MirtSphere array or a list of Sphere, not {type(spheres).__name__}")
 
 
+# MirtRay / MirtRayHit as numpy records (32 bytes each): what trace_rays takes and returns
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("direction", "<f4", (3,)), ("_pad", "<f4")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("sphere", "<u4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,))])
+RAYS_FLAGS = _abi.MIRT_RAYS_FLAT | _abi.MIRT_RAYS_ANY_HIT | _abi.MIRT_RAYS_COUNT
+
+
+def make_rays(origins, directions, t_max=1000.0) -> np.ndarray:
+    """A RAY_DTYPE array from origins [n, 3] (or one origin), directions [n, 3] and t_max (a scalar or [n]); 1000 is the renderer's
+    own bound (MAX_T)."""
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(d), RAY_DTYPE)
+    rays["origin"] = np.asarray(origins, np.float32)
+    rays["direction"] = d
+    rays["t_max"] = np.asarray(t_max, np.float32)
+    return rays
+
+
+def ray_records(rays) -> np.ndarray:
+    """`rays` for trace_rays -> a contiguous one-dimensional RAY_DTYPE array (a view where possible): a RAY_DTYPE array, or a float32
+    array [n, 8] = {origin, t_max, direction, pad} (bit patterns are kept).  Anything else: ValueError, before the library is called."""
+    if not isinstance(rays, np.ndarray):
+        raise ValueError(f"rays must be a numpy array of RAY_DTYPE or float32 [n, 8], not {type(rays).__name__}")
+    if rays.dtype == RAY_DTYPE and rays.ndim == 1:
+        return np.ascontiguousarray(rays)
+    if rays.dtype == np.float32 and rays.ndim == 2 and rays.shape[1] == 8:
+        return np.ascontiguousarray(rays).view(RAY_DTYPE).reshape(-1)
+    raise ValueError(f"rays must be a one-dimensional RAY_DTYPE array or float32 [n, 8], not {rays.dtype} of shape {rays.shape}")
+
+
+def _check_rays_flags(flags) -> int:
+    if not isinstance(flags, (int, np.integer)) or isinstance(flags, bool) or int(flags) & ~RAYS_FLAGS or int(flags) < 0:
+        raise ValueError(f"flags must be a combination of MIRT_RAYS_FLAT, MIRT_RAYS_ANY_HIT and MIRT_RAYS_COUNT, not {flags!r}")
+    return int(flags)
+
+
+def _check_address(name, v) -> int:
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or int(v) <= 0:
+        raise ValueError(f"{name} must be a device address, not {v!r}")
+    return int(v)
+
+
 def _check_range(first, count) -> None:
     for name, v in (("first", first), ("count", count)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
@@ -246,6 +287,35 @@ class Context:
         if not isinstance(d_ptr, (int, np.integer)) or isinstance(d_ptr, bool) or int(d_ptr) < 0:
             raise ValueError(f"d_ptr must be a device address, not {d_ptr!r}")
         check(lib().mirt_ctx_set_spheres_device(self._h, C.c_void_p(int(d_ptr)) if int(count) else None, int(count)))
+
+    # ---- ray queries against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+    def trace_rays(self, rays, flags: int = 0) -> np.ndarray:
+        """mirt_ctx_trace_rays: the flat scan's answer for every ray, by the renderer's own arithmetic -> a RAY_HIT_DTYPE array, one
+        record per ray in the caller's order; `sphere` == MIRT_RAY_MISS (and everything else 0) for a miss.  `rays`: see ray_records
+        (make_rays builds them); flags: MIRT_RAYS_FLAT / _ANY_HIT / _COUNT.  Needs a scene set with hbm=True.  Blocking."""
+        recs = ray_records(rays)
+        flags = _check_rays_flags(flags)
+        hits = np.zeros(len(recs), RAY_HIT_DTYPE)
+        check(lib().mirt_ctx_trace_rays(self._h, C.c_void_p(recs.ctypes.data) if len(recs) else None, len(recs), flags,
+                                        C.c_void_p(hits.ctypes.data) if len(recs) else None))
+        return hits
+
+    def trace_rays_device(self, d_rays: int, n: int, d_hits: int, flags: int = 0, stream: Optional[int] = None) -> None:
+        """mirt_ctx_trace_rays_device: `n` 32-byte MirtRay records at device address `d_rays` -> `n` MirtRayHit records at `d_hits`
+        (e.g. torch tensors' data_ptr()), asynchronously on `stream` (see _stream_arg); no host synchronisation."""
+        _check_range(0, n)
+        flags = _check_rays_flags(flags)
+        if int(n):
+            d_rays, d_hits = _check_address("d_rays", d_rays), _check_address("d_hits", d_hits)
+        check(lib().mirt_ctx_trace_rays_device(self._h, C.c_void_p(d_rays) if int(n) else None, int(n), flags,
+                                               C.c_void_p(d_hits) if int(n) else None, _stream_arg(stream)))
+
+    def trace_stats(self) -> dict:
+        """mirt_ctx_trace_stats: waits for the last trace call -> {"kernel_ms", "rays", "sphere_tests", "roots", "hits", "nodes",
+        "wave_nodes"}; the counters are 0 unless that call had MIRT_RAYS_COUNT."""
+        st = _abi.MirtRayStats()
+        check(lib().mirt_ctx_trace_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def bvh_refits(self) -> int:
         """mirt_ctx_bvh_refits: successful updates since the scene was set (0 after every set_scene)."""

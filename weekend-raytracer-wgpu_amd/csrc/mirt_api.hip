@@ -483,6 +483,16 @@ struct MirtContext {
     mirt::BvhRefit bvh_refit;
     mirt::BvhDeviceScratch bvh_stage;        // the records of a host update on their way to the scatter: grows with the largest count
     uint32_t       bvh_refits = 0;
+
+    // mirt_ctx_trace_rays* (DESIGN.md 10.7): state of its own, so that a trace touches neither the launch ring nor MirtStats
+    hipEvent_t          ev_trace_begin = nullptr, ev_trace_end = nullptr;   // around the last trace kernel, on its stream
+    bool                trace_pending = false;     // ev_trace_end is recorded and nobody has waited for it yet
+    bool                trace_timed = false, trace_counted = false;
+    unsigned long long* d_trace_counters = nullptr;   // [kNumCounters] of the last counting trace
+    unsigned char*      d_trace_rays = nullptr;    // staging of the host path: [n] MirtRay, [n] MirtRayHit
+    unsigned char*      d_trace_hits = nullptr;
+    size_t              cap_trace_rays = 0, cap_trace_hits = 0;
+    MirtRayStats        trace_stats{};
 };
 
 extern "C" {
@@ -661,6 +671,9 @@ int mirt_ctx_create(int device, MirtContext** out)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->zero_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreate(&c->ev_trace_begin);
+    if (e == hipSuccess) e = hipEventCreate(&c->ev_trace_end);
+    if (e == hipSuccess) e = hipMalloc(&c->d_trace_counters, sizeof(unsigned long long) * mirt::kNumCounters);
     if (e == hipSuccess) e = hipMalloc(&c->d_sky, sizeof(MirtSkyState));
     if (e == hipSuccess) e = hipMalloc(&c->d_counters, sizeof(unsigned long long) * mirt::kNumCounters * kEventPool);
     if (e == hipSuccess) e = hipMalloc(&c->d_work_counter, sizeof(uint32_t) * kEventPool * kDispenserWords);
@@ -687,6 +700,10 @@ void mirt_ctx_destroy(MirtContext* c)
     if (c->zero_stream) (void)hipStreamSynchronize(c->zero_stream);
     if (c->frame_stream_b) (void)hipStreamSynchronize(c->frame_stream_b);
     if (!c->untimed_streams.empty()) (void)hipDeviceSynchronize();      // launches without an event may still read the tables freed below
+    if (c->trace_pending) (void)hipEventSynchronize(c->ev_trace_end);    // a trace on a caller stream reads them too
+    (void)hipFree(c->d_trace_counters); (void)hipFree(c->d_trace_rays); (void)hipFree(c->d_trace_hits);
+    if (c->ev_trace_begin) (void)hipEventDestroy(c->ev_trace_begin);
+    if (c->ev_trace_end) (void)hipEventDestroy(c->ev_trace_end);
     (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_bvh); (void)hipFree(c->bvh_scratch.d); (void)hipFree(c->bvh_stage.d); (void)hipFree(c->d_texels);
     (void)hipFree(c->d_sky); (void)hipFree(c->d_counters); (void)hipFree(c->d_work_counter); (void)hipFree(c->d_out); (void)hipFree(c->d_accum);
     for (hipEvent_t ev : c->ev_begin) (void)hipEventDestroy(ev);
@@ -1205,6 +1222,21 @@ static void poison_slot(MirtContext* c, size_t i, hipStream_t stream)
     c->slot_dirty[i] = 0;
 }
 
+// The tree of a MIRT_SCENE_HBM scene as nearest_hit_bvh reads it from a launch's kernel arguments: one function for the render launches and
+// the ray queries (launch_trace).  stack_entries: node references per lane of the launch's traversal stacks (0: MIRT_BVH_MAX_DEPTH, the strip kernels).
+static void fill_bvh_args(const MirtContext* c, mirt::RenderArgs* a, uint32_t stack_entries)
+{
+    a->bvh_nodes = reinterpret_cast<const float4*>(c->d_bvh);
+    a->bvh_recs = reinterpret_cast<const float4*>(c->d_bvh + c->bvh_off_recs);
+    a->bvh_ids = reinterpret_cast<const uint32_t*>(c->d_bvh + c->bvh_off_ids);
+    a->bvh_root = c->bvh_root;
+    a->bvh_n_always = c->bvh_n_always;
+    for (int k = 0; k < 3; ++k) a->bvh_centre[k] = c->bvh_centre[k];
+    a->bvh_radius = c->bvh_radius;
+    a->bvh_rmax = c->bvh_rmax;
+    a->bvh_stack_entries = stack_entries;
+}
+
 static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, hipStream_t stream,
                          unsigned long long* d_accum = nullptr)
 {
@@ -1372,17 +1404,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     // (the strip kernel's grid build keeps a camera-ray candidate list per wave behind the blob: 4 waves x 48 bytes)
     a.lds_bytes = use_grid ? (uint32_t)(scene_lds_g + a.grid_bytes + (pool ? pcu.lds_bytes : 4u * 48u)) : (uint32_t)(scene_lds + (pool ? pcu.lds_bytes : 0));
     if (pool_hbm) a.lds_bytes = hbm_plan.lds_bytes_per_block;     // camera (+ sky), the block's pools, its waves' traversal stacks
-    if (hbm) {
-        a.bvh_nodes = reinterpret_cast<const float4*>(c->d_bvh);
-        a.bvh_recs = reinterpret_cast<const float4*>(c->d_bvh + c->bvh_off_recs);
-        a.bvh_ids = reinterpret_cast<const uint32_t*>(c->d_bvh + c->bvh_off_ids);
-        a.bvh_root = c->bvh_root;
-        a.bvh_n_always = c->bvh_n_always;
-        for (int k = 0; k < 3; ++k) a.bvh_centre[k] = c->bvh_centre[k];
-        a.bvh_radius = c->bvh_radius;
-        a.bvh_rmax = c->bvh_rmax;
-        a.bvh_stack_entries = pool_hbm ? hbm_plan.stack_entries : 0u;
-    }
+    if (hbm) fill_bvh_args(c, &a, pool_hbm ? hbm_plan.stack_entries : 0u);
     if (!use_grid && !c->fits_flat && !hbm)
         return fail(MIRT_ERR_SCENE_TOO_LARGE, "this scene only fits LDS in the grid build of the path-traced mode "
                     "(no parity mode, no MIRT_FLAG_COUNT_WORK / MIRT_FLAG_NO_GRID / MIRT_FLAG_KERNEL_POOL)");
@@ -1614,6 +1636,7 @@ int mirt_ctx_synchronize(MirtContext* c)
     if (c->frame_stream_b) HIP_TRY(hipStreamSynchronize(c->frame_stream_b));
     for (hipStream_t st : c->untimed_streams) HIP_TRY(hipStreamSynchronize(st));      // launches that carried no event (mirt_ctx_set_timing(0))
     c->untimed_streams.clear();
+    if (c->trace_pending) HIP_TRY(hipEventSynchronize(c->ev_trace_end));              // a ray query on a caller stream (mirt_ctx_trace_stats folds it)
     return MIRT_OK;
 }
 
@@ -1694,6 +1717,99 @@ int mirt_ctx_get_stats(MirtContext* c, MirtStats* out)
         c->stats_counted = false;
     }
     *out = c->stats;
+    return MIRT_OK;
+}
+
+// ---- ray queries against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+// What both entry points check, in the header's order; MIRT_OK with *go = false: nothing to do (n_rays == 0).
+static int check_trace(const MirtContext* c, const void* rays, uint32_t n, uint32_t flags, const void* hits, bool* go)
+{
+    *go = false;
+    if (!c) return fail(MIRT_ERR_NULL_POINTER, "ctx is null");
+    if (flags & ~(uint32_t)(MIRT_RAYS_FLAT | MIRT_RAYS_ANY_HIT | MIRT_RAYS_COUNT)) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RAYS_* bits 0x%x", flags);
+    if (n && (!rays || !hits)) return fail(MIRT_ERR_NULL_POINTER, "rays/hits is null");
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    *go = n != 0u;
+    return MIRT_OK;
+}
+
+// Queue trace_rays_kernel<bvh, any, count> for n > 0 rays in device memory on `st`.  No host synchronisation.
+static int launch_trace(MirtContext* c, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, hipStream_t st)
+{
+    const bool bvh = !(flags & MIRT_RAYS_FLAT), any = (flags & MIRT_RAYS_ANY_HIT) != 0, count = (flags & MIRT_RAYS_COUNT) != 0;
+    mirt::RenderArgs a{};
+    a.spheres = c->d_spheres;
+    a.n_spheres = c->n_spheres;
+    a.counters = c->d_trace_counters;
+    // the traversal stacks hold as many node references per lane as the resident tree is deep (a push happens at inner nodes only, at
+    // most one per level): 256 x depth bytes per wave, as in the pooled kernel -- at most 32 KB per block (MIRT_BVH_MAX_DEPTH)
+    const uint32_t entries = bvh ? (c->bvh_plan.max_depth ? c->bvh_plan.max_depth : 1u) : 0u;
+    fill_bvh_args(c, &a, entries);
+    a.lds_bytes = (mirt::kBlockThreads / 64u) * 64u * 4u * entries;
+    if (count) HIP_TRY(hipMemsetAsync(c->d_trace_counters, 0, sizeof(unsigned long long) * mirt::kNumCounters, st));
+    const bool timed = c->timing;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    HIP_TRY(kx::launch_trace_rays(a, d_rays, d_hits, n, bvh, any, count, st));
+    const char* tf[2] = { "false", "true" };
+    snprintf(c->last_kernel, sizeof c->last_kernel, "trace_rays_kernel<%s,%s,%s>", tf[bvh], tf[any], tf[count]);
+    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
+    c->trace_pending = true;
+    c->trace_timed = timed;
+    c->trace_counted = count;
+    c->trace_stats = MirtRayStats{};
+    return MIRT_OK;
+}
+
+int mirt_ctx_trace_rays_device(MirtContext* c, const void* d_rays, uint32_t n_rays, uint32_t flags, void* d_hits, void* hip_stream)
+{
+    bool go;
+    const int rc = check_trace(c, d_rays, n_rays, flags, d_hits, &go);
+    if (rc != MIRT_OK || !go) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return launch_trace(c, d_rays, n_rays, flags, d_hits, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int mirt_ctx_trace_rays(MirtContext* c, const MirtRay* rays, uint32_t n_rays, uint32_t flags, MirtRayHit* hits)
+{
+    bool go;
+    int rc = check_trace(c, rays, n_rays, flags, hits, &go);
+    if (rc != MIRT_OK || !go) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)n_rays * sizeof(MirtRay);
+    static_assert(sizeof(MirtRay) == sizeof(MirtRayHit), "one size for both staging buffers");
+    if ((rc = ensure_capacity(&c->d_trace_rays, &c->cap_trace_rays, bytes)) != MIRT_OK) return rc;
+    if ((rc = ensure_capacity(&c->d_trace_hits, &c->cap_trace_hits, bytes)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_trace_rays, rays, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_trace(c, c->d_trace_rays, n_rays, flags, c->d_trace_hits, c->stream)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(hits, c->d_trace_hits, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_ctx_trace_stats(MirtContext* c, MirtRayStats* out)
+{
+    if (!c || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/out is null");
+    if (c->trace_pending) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipEventSynchronize(c->ev_trace_end));
+        c->trace_pending = false;
+        if (c->trace_timed) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace_begin, c->ev_trace_end));
+            c->trace_stats.kernel_ms = ms;
+        }
+        if (c->trace_counted) {
+            unsigned long long h[mirt::kNumCounters];
+            HIP_TRY(hipMemcpy(h, c->d_trace_counters, sizeof h, hipMemcpyDeviceToHost));
+            c->trace_stats.rays = h[mirt::kCntRays];
+            c->trace_stats.sphere_tests = h[mirt::kCntTests];
+            c->trace_stats.roots = h[mirt::kCntRoots];
+            c->trace_stats.hits = h[mirt::kCntHits];
+            c->trace_stats.nodes = h[mirt::kCntCells];
+            c->trace_stats.wave_nodes = h[mirt::kCntWaveCells];
+        }
+    }
+    *out = c->trace_stats;
     return MIRT_OK;
 }
 

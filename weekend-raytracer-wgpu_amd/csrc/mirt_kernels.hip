@@ -1647,20 +1647,34 @@ MIRT_DEV void bvh_slab(float4 lo_hi_a, float4 lo_hi_b, float4 lo_hi_c, int first
     tf = __builtin_fminf(__builtin_fminf(fx, fy), fz);
 }
 
-template <bool COUNT>
+//
+// Ray queries (mirt_trace_kernel.inc) start the walk at a caller's bound, `closest0` = the ray's t_max, instead of kMaxT, and may ask
+// for ANY hit.  The argument above does not use the value closest starts from: a sphere can win only with a computed f < closest, at
+// every moment of the walk, so "a sphere that can still win" has L <= closest |d| + 2 r_max for the CURRENT closest whatever it started
+// as -- a smaller start only tightens the cone bound and prunes more boxes, none of which holds a sphere the flat scan (started at the
+// same t_max) would take.  A start ABOVE kMaxT is covered too: the bound is min(cone, world, box), and a cone term that overflows to
+// +inf (t_max = +inf, or huge) or is NaN (inf x 0 for a zero direction) loses the `e < e_world` comparison, which leaves the world
+// bound.  t_max = +inf: lim = +inf and no box is cut by it; test_sphere takes every finite f.  t_max = NaN: test_sphere's `f < closest`
+// and `f == closest` are false for every f, the flat scan reports a miss, and so does the walk whatever it visits (lim = NaN makes
+// the negated comparisons visit everything: slow, not wrong).  t_max <= MIN_T (0, negative, -inf): no f > MIN_T is below it -- a miss
+// in both; the cone term may then be negative and shrink boxes, which can only drop spheres that cannot win.
+// ANY: a lane leaves the walk at its first take (best >= 0).  Until that take its walk is the nearest-hit walk step for step
+// (closest is still t_max), so it performs a prefix of that walk's tests, and it finds a sphere iff the nearest-hit walk does.
+// The defaults are the render kernels' walk, instruction for instruction.
+template <bool COUNT, bool ANY = false>
 MIRT_DEV int nearest_hit_bvh(f3 ro, f3 rd, bool alive, float& closest_out, Work<COUNT>& work, uint32_t lane, uint32_t* stack,
-                             uint32_t stack_cap = kBvhStack)
+                             uint32_t stack_cap = kBvhStack, float closest0 = kMaxT)
 {
     const RenderArgs& A = per_strip_args();          // the tree's pointers and bounds: read where they are used, not held across the path
     const float a = dot(rd, rd);
     const float inv_a = rcp_(a);
-    float closest = kMaxT;
+    float closest = closest0;
     int best = -1;
     if (alive) work.add(kCntRays);
     const float4* recs = A.bvh_recs;
     const uint32_t* ids = A.bvh_ids;
     const uint32_t n_always = A.bvh_n_always;
-    for (uint32_t j = 0; j < n_always; ++j) test_sphere<COUNT>(recs[j], ids[j], ro, rd, a, inv_a, alive, closest, best, work);
+    for (uint32_t j = 0; j < n_always; ++j) test_sphere<COUNT>(recs[j], ids[j], ro, rd, a, inv_a, ANY ? (alive && best < 0) : alive, closest, best, work);
 
     const f3 inv = mk(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
     const bool sx = inv.x >= 0.0f, sy = inv.y >= 0.0f, sz = inv.z >= 0.0f;
@@ -1675,14 +1689,14 @@ MIRT_DEV int nearest_hit_bvh(f3 ro, f3 rd, bool alive, float& closest_out, Work<
     };
     grow();
     uint32_t ref = A.bvh_root, sp = 0;
-    bool go = alive;
+    bool go = ANY ? (alive && best < 0) : alive;
     while (ballot_(go)) {
         if constexpr (COUNT) { if (go) work.add(kCntCells); if (lane == 0) work.add(kCntWaveCells); }
         if (go) {
             bool pop = false;
             if (ref & kBvhLeafRef) {
                 const uint32_t first = ref & 0xffffffu, cnt = (ref >> 24) & 0x7fu;
-                for (uint32_t k = 0; k < cnt; ++k) test_sphere<COUNT>(recs[first + k], ids[first + k], ro, rd, a, inv_a, true, closest, best, work);
+                for (uint32_t k = 0; k < cnt; ++k) test_sphere<COUNT>(recs[first + k], ids[first + k], ro, rd, a, inv_a, ANY ? best < 0 : true, closest, best, work);
                 grow();
                 pop = true;
             } else {
@@ -1709,6 +1723,7 @@ MIRT_DEV int nearest_hit_bvh(f3 ro, f3 rd, bool alive, float& closest_out, Work<
                 if (sp == 0u) go = false;
                 else { --sp; ref = stack[sp * 64u + lane]; }
             }
+            if constexpr (ANY) go = go && best < 0;
         }
     }
     closest_out = closest;
@@ -2165,7 +2180,9 @@ struct PoolHbmState {
 #include "mirt_isa_probes.inc"       // tools/isa_mix.py; never part of libmirt.so
 #endif
 
-#ifndef MIRT_FAST_MATH       // self-test, resolve and frame assembly live in the exact build only
+#ifndef MIRT_FAST_MATH       // ray queries, self-test, resolve and frame assembly live in the exact build only
+#include "mirt_trace_kernel.inc"
+
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns
 // ------------------------------------------------------------------------------------------

@@ -71,6 +71,37 @@ inline void set_spheres_device(MirtContext* ctx, const void* d_spheres, uint32_t
 {
     check(mirt_ctx_set_spheres_device(ctx, d_spheres, n_spheres));
 }
+// mirt_ctx_trace_rays: the flat scan's answer for every ray against the context's MIRT_SCENE_HBM scene, in the caller's order
+// (flags = MIRT_RAYS_*; hit.sphere == MIRT_RAY_MISS: nothing hit).  Blocking.
+inline MirtRay make_ray(Vec3 origin, Vec3 direction, float t_max = 1000.0f)
+{
+    return MirtRay{ { origin.x, origin.y, origin.z }, t_max, { direction.x, direction.y, direction.z }, 0.0f };
+}
+inline std::vector<MirtRayHit> trace_rays(MirtContext* ctx, const std::vector<MirtRay>& rays, uint32_t flags = 0)
+{
+    std::vector<MirtRayHit> hits(rays.size());
+    check(mirt_ctx_trace_rays(ctx, rays.data(), (uint32_t)rays.size(), flags, hits.data()));
+    return hits;
+}
+// the same between buffers in memory of the context's device, asynchronously on `hip_stream` (nullptr: the context's stream)
+inline void trace_rays_device(MirtContext* ctx, const void* d_rays, uint32_t n_rays, void* d_hits, uint32_t flags = 0, void* hip_stream = nullptr)
+{
+    check(mirt_ctx_trace_rays_device(ctx, d_rays, n_rays, flags, d_hits, hip_stream));
+}
+inline MirtRayStats trace_stats(MirtContext* ctx) { MirtRayStats st; check(mirt_ctx_trace_stats(ctx, &st)); return st; }
+// the pinhole ray through the centre of pixel (x, y), row 0 on top: cameraMakeRay with a zero lens
+inline MirtRay pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float t_max = 1000.0f)
+{
+    const float u = ((float)x + 0.5f) / (float)width, v = 1.0f - ((float)y + 0.5f) / (float)height;
+    MirtRay r{};
+    for (int k = 0; k < 3; ++k) {
+        r.origin[k] = cam.eye[k];
+        r.direction[k] = (cam.lower_left_corner[k] + u * cam.horizontal[k] + v * cam.vertical[k]) - cam.eye[k];
+    }
+    r.t_max = t_max;
+    return r;
+}
+
 // move_spheres of Layer / Raytracer: held[first ..] take centre and radius of `spheres` and keep their material
 inline void move_held_spheres(std::vector<MirtSphere>& held, uint32_t first, const std::vector<MirtSphere>& spheres)
 {

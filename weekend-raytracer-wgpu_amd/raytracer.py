@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import MirtError, check, lib
-from .context import Context, SceneData, make_params, set_scene_any_size
+from .context import Context, SceneData, make_params, make_rays, set_scene_any_size
 from .node import Node
 
 f32 = np.float32
@@ -412,6 +412,35 @@ def _set_world_resident(owner, target, world: Sequence[Sphere], scene_data) -> N
         raise
 
 
+def pixel_ray(camera: _abi.MirtGpuCamera, width: int, height: int, x: int, y: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The pinhole ray through the CENTRE of pixel (x, y), row 0 on top: `cameraMakeRay` (wgsl:345-362) with a zero lens at
+    u = (x + 0.5) / width, v = 1 - (y + 0.5) / height, in float32 on the host -> (origin [3], direction [3], not normalised)."""
+    if not (0 <= int(x) < int(width) and 0 <= int(y) < int(height)):
+        raise ValueError(f"pixel ({x}, {y}) lies outside the {width} x {height} viewport")
+    u = f32(f32(x) + f32(0.5)) / f32(width)
+    v = f32(1.0) - f32(f32(y) + f32(0.5)) / f32(height)
+    eye, hor, ver, llc = (np.asarray(a[:3], f32) for a in (camera.eye, camera.horizontal, camera.vertical, camera.lower_left_corner))
+    d = (llc.astype(np.float64) + np.float64(u) * hor + np.float64(v) * ver).astype(f32) - eye
+    return eye, d.astype(f32)
+
+
+def _pick(owner, x: int, y: int, width: int, height: int, camera: _abi.MirtGpuCamera, scene_data) -> Optional[dict]:
+    """Layer.pick / Raytracer.pick: the sphere under pixel (x, y) by Context.trace_rays with t_max = 1000 (what a path of the renderer
+    would hit first).  Ray queries need the world in device memory: a resident LDS scene -- or none yet -- is set again as a
+    MIRT_SCENE_HBM scene first (the images do not change; owner._hbm is True afterwards).  On a node the query runs on member 0's
+    context."""
+    o, d = pixel_ray(camera, width, height, x, y)              # refuses a pixel outside the viewport before anything is set
+    target = owner._pick_target()
+    if not owner._hbm:
+        target.set_scene(scene_data(), hbm=True)
+        owner._hbm = True
+    ctx = target.context(0) if hasattr(target, "context") else target
+    hit = ctx.trace_rays(make_rays(o, d[None, :], 1000.0))[0]
+    if int(hit["sphere"]) == _abi.MIRT_RAY_MISS:
+        return None
+    return {"sphere": int(hit["sphere"]), "t": float(hit["t"]), "point": hit["point"].copy(), "normal": hit["normal"].copy()}
+
+
 def _jpeg_check(rc: int) -> None:
     if rc != 0:
         raise MirtError(rc, (lib().mirt_jpeg_last_error() or b"").decode())
@@ -549,6 +578,24 @@ class Layer:
             w, h = int(self.vp_size[0]), int(self.vp_size[1])
             self._rgba = target.render(make_params(w, h, render_params.sampling.num_samples_per_pixel, mode=_abi.MIRT_MODE_PARITY))
             self.last_stats = target.stats()
+
+    def _pick_target(self):
+        if self._devices is not None:
+            if self._node is None:
+                self._node = Node(self._devices)
+            return self._node
+        if self._ctx is None:
+            self._ctx = Context(self._device)
+        return self._ctx
+
+    def pick(self, x: int, y: int) -> Optional[dict]:
+        """The sphere of `world` under pixel (x, y) of the viewport (row 0 on top): {"sphere": index into `world`, "t", "point",
+        "normal"} -- exactly the record Context.trace_rays returns for the pinhole ray through the pixel's centre (pixel_ray) with
+        t_max = 1000 -- or None where the ray leaves the scene.  Ray queries need the world in device memory: if the resident scene is
+        not a MIRT_SCENE_HBM one (or nothing is resident yet, before the first set_data) the world is set as one first, and
+        move_spheres / set_world then work on it in place; the next set_data sets the scene by its own rule again (a small world goes
+        back to LDS), so a pick after it pays for one more set_scene."""
+        return _pick(self, x, y, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data)
 
     def register_texture(self) -> np.ndarray:         # layer.rs:150-176: the RGBA8 bytes imgui would receive
         if self._rgba is None:
@@ -711,6 +758,16 @@ class Raytracer:
         self.spheres = new
         self._accumulated = None
 
+    def _pick_target(self):
+        return self._ctx
+
+    def pick(self, x: int, y: int) -> Optional[dict]:
+        """The sphere of the scene under pixel (x, y) of the viewport, as Layer.pick: {"sphere", "t", "point", "normal"} of the pinhole
+        ray through the pixel's centre (the lens is ignored), or None.  A scene held in LDS is set again as a MIRT_SCENE_HBM scene
+        first and stays one; the accumulation is not touched (the images are the same either way)."""
+        w, h = self.render_params.viewport_size
+        return _pick(self, x, y, int(w), int(h), self.camera.c, self.scene_data)
+
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
         """All `max_samples_per_pixel` samples in one launch -> RGBA8 [h][w][4].
 
@@ -731,4 +788,4 @@ class Raytracer:
 __all__ = ["Angle", "Camera", "GpuCamera", "SamplingParams", "SkyParams", "RenderParams",
            "RenderParamsValidationError", "FlyCameraController", "Sphere", "Texture", "Material",
            "TextureDescriptor", "GpuMaterial", "Scene", "Layer", "Raytracer", "flatten_materials",
-           "asset_path", "MirtError", "decode_jpeg", "jpeg_info"]
+           "asset_path", "MirtError", "decode_jpeg", "jpeg_info", "pixel_ray"]
