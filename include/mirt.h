@@ -486,6 +486,51 @@ int mirt_ctx_trace_rays_device(MirtContext* ctx, const void* d_rays, uint32_t n_
 /* Waits for the last trace call and reports its statistics (all 0 before the first). */
 int mirt_ctx_trace_stats(MirtContext* ctx, MirtRayStats* out);
 
+/* ---- first-hit feature frames of a MIRT_SCENE_HBM scene: albedo, normal, depth and id per pixel ----
+ * What the context's camera sees FIRST at every pixel, for denoiser guides (albedo, normal) and for picking, outlines and snapping
+ * (sphere, t).  One MirtFeaturePixel per pixel of the rows `params` selects, compact and row-major exactly like mirt_ctx_render
+ * (row_begin / row_end / tile_rows / n_parts / part; mirt_params_out_rows gives the row count).  Of MirtParams the call reads width,
+ * height, the row fields, spp, sample_begin and seed; it does NOT read mode, num_bounces, flags and frame_begin.  frame_spp must be 0
+ * (MIRT_ERR_FRAME_SPP otherwise): the reference's per-frame stream threads a pixel's later primary rays through the bounces of its
+ * earlier paths, and a feature pass has no paths -- a guide needs the same pixel filter, not the same draws.
+ *   the centre ray   u = (x + 0.5f) * inv_w, v = 1 - (y + 0.5f) * inv_h with inv_w = 1.0f / (float)width, inv_h = 1.0f / (float)height;
+ *                    origin = eye (the lens is ignored, no random draw), direction = fma(v, vertical, fma(u, horizontal,
+ *                    lower_left_corner)) - eye per component: the renderer's primary ray with both jitter draws replaced by 0.5 and a
+ *                    zero lens.  mirt_camera_pixel_ray restates it on the host bit for bit.
+ *   sphere, t        the nearest hit of the centre ray from t_max = 1000, the `sphere` and `t` of mirt_ctx_trace_rays: the original
+ *                    index and the computed root, or MIRT_RAY_MISS and 0.
+ *   the sample set   spp == 0 (legal here): the centre ray alone.  spp >= 1: the renderer's own primary rays of samples
+ *                    sample_begin .. sample_begin + spp - 1, the RNG seeded from `seed` as a render call seeds it -- jitter, lens,
+ *                    the two lens draws: the guides carry the pixel filter and the depth of field of the beauty pass.  A pixel costs
+ *                    1 ray at spp == 0 and spp + 1 rays otherwise.
+ *   albedo, normal   float sums from +0 over the samples in order; a sample that hits adds its normal inv_r * (point - centre) (NOT
+ *                    turned towards the ray, as in MirtRayHit) and its albedo, a sample that misses adds nothing; the record holds
+ *                    sum / (float)max(spp, 1).  A NaN stays a NaN (a zero-radius winner: inf x 0).  The albedo of a hit is the
+ *                    attenuation the renderer's scatter routine of its material applies, without the lambertian's grazing factor:
+ *                    routines 0 and 1 the first texture at the hit, 2 (1, 1, 1), 3 the checkerboard's texture of the hit point,
+ *                    any other id (0.9921, 0.24705, 0.57254).  No scatter direction is computed and no further draw is taken.
+ * flags: 0 = the BVH walk of the render kernels (feature_frame_kernel<true>); MIRT_FEATURES_FLAT = the flat scan of the resident table
+ * in original index order, the comparison build as MIRT_RAYS_FLAT is; any other bit: MIRT_ERR_BAD_MODE.
+ * MIRT_ERR_NULL_POINTER: ctx, params or the output is null;  MIRT_ERR_NO_SCENE: no scene, or not a MIRT_SCENE_HBM one;  zero width or
+ * height and bad rows: the codes mirt_ctx_render gives;  MIRT_ERR_SPP_RANGE: spp > MIRT_MAX_SPP_PER_CALL or sample_begin + spp reaches
+ * 2^32;  MIRT_ERR_OUT_BUFFER: out_len < rows * width * 32;  MIRT_ERR_MATERIAL_INDEX / MIRT_ERR_TEXEL_RANGE: exactly as a path-traced
+ * render call on that scene answers -- this call reads materials, unlike ray queries.  A refused call queues nothing; neither does a
+ * call whose part of a tile partition owns no row (MIRT_OK).
+ *   mirt_ctx_render_features          `out` in HOST memory: kernel and copy on the context's stream; blocking.
+ *   mirt_ctx_render_features_device   `d_out` in memory of the context's device (4-byte aligned): ONE kernel queued on `hip_stream` (NULL =
+ *                                     the context's stream; hipStreamLegacy for the default stream), no host synchronisation.
+ * State is kept the way the ray queries keep it: neither the launch ring, MirtStats nor the accumulation is touched; mirt_ctx_last_kernel
+ * names the feature kernel; mirt_ctx_synchronize and mirt_ctx_destroy wait for it; its time is mirt_ctx_trace_stats().kernel_ms (the
+ * counters are 0).
+ *   mirt_camera_pixel_ray             HOST ONLY, no device: the centre ray of pixel (x, y) of a width x height viewport (row 0 on top) in
+ *                                     float32 with fmaf, t_max = 1000.0f.  MIRT_ERR_NULL_POINTER for a null pointer,
+ *                                     MIRT_ERR_VIEWPORT_SIZE for a zero size, MIRT_ERR_BAD_ROWS for a pixel outside the viewport. */
+typedef struct MirtFeaturePixel { float albedo[3]; float t; float normal[3]; uint32_t sphere; } MirtFeaturePixel;   /* 32 B */
+enum { MIRT_FEATURES_FLAT = 1u << 0 };
+int mirt_ctx_render_features(MirtContext* ctx, const MirtParams* params, uint32_t flags, MirtFeaturePixel* out, size_t out_len);
+int mirt_ctx_render_features_device(MirtContext* ctx, const MirtParams* params, uint32_t flags, void* d_out, size_t out_len, void* hip_stream);
+int mirt_camera_pixel_ray(const MirtGpuCamera* camera, uint32_t width, uint32_t height, uint32_t x, uint32_t y, MirtRay* out);
+
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by
  * value with each launch, so this neither copies to the device nor synchronises; launches already
@@ -706,6 +751,7 @@ static_assert(sizeof(MirtCamera) == 48, "Camera is 12 f32 (mod.rs:489-499)");
 static_assert(sizeof(MirtRay) == 32, "MirtRay is two 16-byte loads");
 static_assert(sizeof(MirtRayHit) == 32, "MirtRayHit is two 16-byte stores");
 static_assert(sizeof(MirtRayStats) == 56, "MirtRayStats is a double and six u64");
+static_assert(sizeof(MirtFeaturePixel) == 32, "MirtFeaturePixel is two 16-byte stores");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -716,6 +762,7 @@ _Static_assert(sizeof(MirtCamera) == 48, "Camera is 12 f32 (mod.rs:489-499)");
 _Static_assert(sizeof(MirtRay) == 32, "MirtRay is two 16-byte loads");
 _Static_assert(sizeof(MirtRayHit) == 32, "MirtRayHit is two 16-byte stores");
 _Static_assert(sizeof(MirtRayStats) == 56, "MirtRayStats is a double and six u64");
+_Static_assert(sizeof(MirtFeaturePixel) == 32, "MirtFeaturePixel is two 16-byte stores");
 #endif
 
 #endif /* MIRT_H */

@@ -230,6 +230,20 @@ pub struct MirtRayStats {
     pub wave_nodes: u64,
 }
 
+/// One pixel of `mirt_ctx_render_features*`: what the camera sees first there.  `sphere == MIRT_RAY_MISS` and `t == 0` where the centre
+/// ray leaves the scene; `albedo` and `normal` are means over the sample set (the centre ray alone for `spp == 0`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtFeaturePixel {
+    pub albedo: [f32; 3],
+    pub t: f32,
+    pub normal: [f32; 3],
+    pub sphere: u32,
+}
+
+/// `mirt_ctx_render_features*` flag: the flat scan instead of the tree (the comparison build).
+pub const MIRT_FEATURES_FLAT: u32 = 1 << 0;
+
 pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
 /// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.
 pub const MIRT_RAYS_FLAT: u32 = 1 << 0;
@@ -319,6 +333,9 @@ extern "C" {
     pub fn mirt_ctx_trace_rays(ctx: *mut MirtContext, rays: *const MirtRay, n_rays: u32, flags: u32, hits: *mut MirtRayHit) -> c_int;
     pub fn mirt_ctx_trace_rays_device(ctx: *mut MirtContext, d_rays: *const c_void, n_rays: u32, flags: u32, d_hits: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_ctx_trace_stats(ctx: *mut MirtContext, out: *mut MirtRayStats) -> c_int;
+    pub fn mirt_ctx_render_features(ctx: *mut MirtContext, params: *const MirtParams, flags: u32, out: *mut MirtFeaturePixel, out_len: usize) -> c_int;
+    pub fn mirt_ctx_render_features_device(ctx: *mut MirtContext, params: *const MirtParams, flags: u32, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_camera_pixel_ray(camera: *const MirtGpuCamera, width: u32, height: u32, x: u32, y: u32, out: *mut MirtRay) -> c_int;
     pub fn mirt_ctx_set_camera(ctx: *mut MirtContext, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_ctx_render(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;

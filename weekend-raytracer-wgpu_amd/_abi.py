@@ -37,6 +37,9 @@ MIRT_RAYS_ANY_HIT = 1 << 1
 MIRT_RAYS_COUNT = 1 << 2
 MIRT_RAY_MISS = 0xFFFFFFFF
 
+# mirt_ctx_render_features* flags
+MIRT_FEATURES_FLAT = 1 << 0
+
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
 MIRT_NODE_RCCL = 1 << 0
@@ -181,6 +184,10 @@ class MirtRayHit(C.Structure):
     _fields_ = [("t", C.c_float), ("sphere", C.c_uint32), ("point", C.c_float * 3), ("normal", C.c_float * 3)]
 
 
+class MirtFeaturePixel(C.Structure):
+    _fields_ = [("albedo", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("sphere", C.c_uint32)]
+
+
 class MirtRayStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("rays", C.c_uint64), ("sphere_tests", C.c_uint64), ("roots", C.c_uint64),
                 ("hits", C.c_uint64), ("nodes", C.c_uint64), ("wave_nodes", C.c_uint64)]
@@ -228,6 +235,9 @@ SYMBOLS = {
     "mirt_ctx_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "mirt_ctx_trace_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mirt_ctx_trace_stats": (C.c_int, [C.c_void_p, _P(MirtRayStats)]),
+    "mirt_ctx_render_features": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_uint32, C.c_void_p, C.c_size_t]),
+    "mirt_ctx_render_features_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mirt_camera_pixel_ray": (C.c_int, [_P(MirtGpuCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(MirtRay)]),
     "mirt_ctx_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_ctx_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),

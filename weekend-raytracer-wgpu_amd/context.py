@@ -168,6 +168,30 @@ def _check_address(name, v) -> int:
     return int(v)
 
 
+# MirtFeaturePixel as a numpy record (32 bytes): what render_features returns per pixel
+FEATURE_DTYPE = np.dtype([("albedo", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)), ("sphere", "<u4")])
+
+
+def _check_params(params) -> _abi.MirtParams:
+    if not isinstance(params, _abi.MirtParams):
+        raise ValueError(f"params must be a MirtParams (make_params builds one), not {type(params).__name__}")
+    return params
+
+
+def camera_pixel_ray(camera: _abi.MirtGpuCamera, w: int, h: int, x: int, y: int) -> np.ndarray:
+    """mirt_camera_pixel_ray: the CENTRE ray of pixel (x, y) of a w x h viewport (row 0 on top) exactly as the feature kernel traces
+    it -- float32 with fmaf, origin = eye, the lens ignored, t_max = 1000 -> one RAY_DTYPE record (a [1] array: what trace_rays takes).
+    Needs no device.  A zero size or a pixel outside the viewport: MirtError."""
+    if not isinstance(camera, _abi.MirtGpuCamera):
+        raise ValueError(f"camera must be a MirtGpuCamera, not {type(camera).__name__}")
+    for name, v in (("w", w), ("h", h), ("x", x), ("y", y)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    ray = np.zeros(1, RAY_DTYPE)
+    check(lib().mirt_camera_pixel_ray(C.byref(camera), int(w), int(h), int(x), int(y), C.cast(C.c_void_p(ray.ctypes.data), C.POINTER(_abi.MirtRay))))
+    return ray
+
+
 def _check_range(first, count) -> None:
     for name, v in (("first", first), ("count", count)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
@@ -316,6 +340,33 @@ class Context:
         st = _abi.MirtRayStats()
         check(lib().mirt_ctx_trace_stats(self._h, C.byref(st)))
         return st.as_dict()
+
+    # ---- first-hit feature frames of the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+    def render_features(self, params: _abi.MirtParams, flat: bool = False) -> np.ndarray:
+        """mirt_ctx_render_features: what the camera sees first at every pixel of the rows `params` selects -> a FEATURE_DTYPE array
+        [rows, width] {"albedo", "t", "normal", "sphere"}; `sphere` == MIRT_RAY_MISS and `t` == 0 where the centre ray leaves the scene.
+        params.spp == 0: the centre ray alone; spp >= 1: albedo and normal are means over the renderer's own primary rays of those
+        samples.  flat=True runs the flat scan instead of the tree (the comparison build).  Needs a scene set with hbm=True.  Blocking."""
+        params = _check_params(params)
+        if not isinstance(flat, (bool, np.bool_)):
+            raise ValueError(f"flat must be a bool, not {flat!r}")
+        rows, width = max(params_out_rows(params), 0), int(params.width)
+        buf = np.zeros(max(rows * width, 1), FEATURE_DTYPE)              # (never a null pointer: a part may own no row)
+        check(lib().mirt_ctx_render_features(self._h, C.byref(params), _abi.MIRT_FEATURES_FLAT if flat else 0,
+                                             C.c_void_p(buf.ctypes.data), rows * width * FEATURE_DTYPE.itemsize))
+        return buf[:rows * width].reshape(rows, width)
+
+    def render_features_device(self, params: _abi.MirtParams, d_ptr: int, nbytes: int, flat: bool = False, stream: Optional[int] = None) -> None:
+        """mirt_ctx_render_features_device: the same records into `nbytes` of device memory at `d_ptr` (4-byte aligned, e.g. a torch
+        tensor's data_ptr()), one kernel queued on `stream` (see _stream_arg); no host synchronisation."""
+        params = _check_params(params)
+        if not isinstance(flat, (bool, np.bool_)):
+            raise ValueError(f"flat must be a bool, not {flat!r}")
+        d_ptr = _check_address("d_ptr", d_ptr)
+        if not isinstance(nbytes, (int, np.integer)) or isinstance(nbytes, bool) or int(nbytes) < 0:
+            raise ValueError(f"nbytes must be a byte count, not {nbytes!r}")
+        check(lib().mirt_ctx_render_features_device(self._h, C.byref(params), _abi.MIRT_FEATURES_FLAT if flat else 0, C.c_void_p(d_ptr),
+                                                    int(nbytes), _stream_arg(stream)))
 
     def bvh_refits(self) -> int:
         """mirt_ctx_bvh_refits: successful updates since the scene was set (0 after every set_scene)."""

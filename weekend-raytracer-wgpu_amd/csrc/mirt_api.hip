@@ -1813,6 +1813,101 @@ int mirt_ctx_trace_stats(MirtContext* c, MirtRayStats* out)
     return MIRT_OK;
 }
 
+// ---- first-hit feature frames of the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+// What both entry points check, in the header's order.  Nothing is queued before the last of them has passed.
+static int check_features(const MirtContext* c, const MirtParams* p, uint32_t flags, const void* out, size_t out_len)
+{
+    if (!c || !p || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/out is null");
+    if (flags & ~(uint32_t)MIRT_FEATURES_FLAT) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_FEATURES_* bits 0x%x", flags);
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (p->width == 0 || p->height == 0)
+        return fail(MIRT_ERR_VIEWPORT_SIZE, "viewport_size elements cannot be zero: (%u, %u)", p->width, p->height);
+    uint32_t rb, re;
+    if (!rows_valid(p, &rb, &re)) return fail(MIRT_ERR_BAD_ROWS, "invalid row selection [%u,%u) of %u, part %u/%u", p->row_begin, p->row_end, p->height, p->part, p->n_parts);
+    if ((uint64_t)out_rows(p) * p->width > 0xffffffffull) return fail(MIRT_ERR_BAD_ROWS, "more than 2^32 pixels in one call");
+    if (p->spp > MIRT_MAX_SPP_PER_CALL || (uint64_t)p->sample_begin + p->spp > 0xffffffffull)
+        return fail(MIRT_ERR_SPP_RANGE, "spp %u (from sample %u) is out of range: at most %u samples per pixel in one call, sample indices below 2^32",
+                    p->spp, p->sample_begin, (unsigned)MIRT_MAX_SPP_PER_CALL);
+    if (p->frame_spp != 0) return fail(MIRT_ERR_FRAME_SPP, "frame_spp %u: a feature frame has no per-frame RNG stream, pass 0", p->frame_spp);
+    const size_t need = (size_t)out_rows(p) * p->width * sizeof(MirtFeaturePixel);
+    if (out_len < need) return fail(MIRT_ERR_OUT_BUFFER, "output buffer holds %zu bytes, %zu needed", out_len, need);
+    if (c->pt_scene_status != MIRT_OK) return fail(c->pt_scene_status, "scene tables are inconsistent: %s", mirt_status_string(c->pt_scene_status));
+    return MIRT_OK;
+}
+
+// Queue feature_frame_kernel<bvh> for the pixels `p` selects on `st`.  No host synchronisation.  The launch ring, MirtStats and the
+// accumulation stay as they are; the event pair and the pending flag are the ray queries' (mirt_ctx_trace_stats folds the time).
+static int launch_features(MirtContext* c, const MirtParams* p, uint32_t flags, void* d_out, hipStream_t st)
+{
+    const bool bvh = !(flags & MIRT_FEATURES_FLAT);
+    mirt::RenderArgs a{};
+    a.cam = c->cam;
+    // generate_primary's pinhole shortcut: the flag travels in the padding word of THIS launch's copy of the camera, as in launch_render
+    { const uint32_t flag = (c->tuning.pinhole != 0 && camera_is_pinhole(c->cam)) ? 1u : 0u; std::memcpy(&a.cam._padding5, &flag, 4); }
+    a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels;
+    a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
+    a.width = p->width; a.height = p->height; a.spp = p->spp;
+    a.seed_mix = jenkins_hash((uint32_t)p->seed ^ jenkins_hash((uint32_t)(p->seed >> 32)));
+    a.sample_begin = p->sample_begin;
+    a.row_begin = p->row_begin; a.tile_rows = p->tile_rows; a.n_parts = p->n_parts; a.part = p->part;
+    a.out_rows = out_rows(p);
+    // traversal stacks as for ray queries: as many node references per lane as the resident tree is deep, 256 x depth bytes per wave
+    const uint32_t entries = bvh ? (c->bvh_plan.max_depth ? c->bvh_plan.max_depth : 1u) : 0u;
+    fill_bvh_args(c, &a, entries);
+    a.lds_bytes = (mirt::kBlockThreads / 64u) * 64u * 4u * entries;
+    const bool timed = c->timing;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    HIP_TRY(kx::launch_features(a, d_out, bvh, st));
+    snprintf(c->last_kernel, sizeof c->last_kernel, "feature_frame_kernel<%s>", bvh ? "true" : "false");
+    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
+    c->trace_pending = true;
+    c->trace_timed = timed;
+    c->trace_counted = false;
+    c->trace_stats = MirtRayStats{};
+    return MIRT_OK;
+}
+
+int mirt_ctx_render_features_device(MirtContext* c, const MirtParams* p, uint32_t flags, void* d_out, size_t out_len, void* hip_stream)
+{
+    const int rc = check_features(c, p, flags, d_out, out_len);
+    if (rc != MIRT_OK || out_rows(p) == 0u) return rc;                 // (a part of a tile partition may own no row: nothing to do)
+    HIP_TRY(hipSetDevice(c->device));
+    return launch_features(c, p, flags, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int mirt_ctx_render_features(MirtContext* c, const MirtParams* p, uint32_t flags, MirtFeaturePixel* out, size_t out_len)
+{
+    int rc = check_features(c, p, flags, out, out_len);
+    if (rc != MIRT_OK || out_rows(p) == 0u) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    static_assert(sizeof(MirtFeaturePixel) == sizeof(MirtRayHit), "the host path stages its records where a host trace stages its hits");
+    const size_t bytes = (size_t)out_rows(p) * p->width * sizeof(MirtFeaturePixel);
+    if ((rc = ensure_capacity(&c->d_trace_hits, &c->cap_trace_hits, bytes)) != MIRT_OK) return rc;
+    if ((rc = launch_features(c, p, flags, c->d_trace_hits, c->stream)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_trace_hits, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_camera_pixel_ray(const MirtGpuCamera* cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, MirtRay* out)
+{
+    if (!cam || !out) return fail(MIRT_ERR_NULL_POINTER, "camera/out is null");
+    if (width == 0 || height == 0) return fail(MIRT_ERR_VIEWPORT_SIZE, "viewport_size elements cannot be zero: (%u, %u)", width, height);
+    if (x >= width || y >= height) return fail(MIRT_ERR_BAD_ROWS, "pixel (%u, %u) lies outside the %u x %u viewport", x, y, width, height);
+    // feature_frame_kernel's centre ray, operation for operation (this file is compiled with -ffp-contract=off: the only fused
+    // operations are the two fmaf per component)
+    const float inv_w = 1.0f / (float)width, inv_h = 1.0f / (float)height;
+    const float u = ((float)x + 0.5f) * inv_w;
+    const float v = 1.0f - ((float)y + 0.5f) * inv_h;
+    for (int k = 0; k < 3; ++k) {
+        out->origin[k] = cam->eye[k];
+        out->direction[k] = std::fmaf(v, cam->vertical[k], std::fmaf(u, cam->horizontal[k], cam->lower_left_corner[k])) - cam->eye[k];
+    }
+    out->t_max = 1000.0f;
+    out->_pad = 0.0f;
+    return MIRT_OK;
+}
+
 int mirt_ctx_accum_reset(MirtContext* c, const MirtParams* p)
 {
     int rc = check_params(c, p);

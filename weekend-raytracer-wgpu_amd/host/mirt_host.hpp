@@ -89,6 +89,22 @@ inline void trace_rays_device(MirtContext* ctx, const void* d_rays, uint32_t n_r
     check(mirt_ctx_trace_rays_device(ctx, d_rays, n_rays, flags, d_hits, hip_stream));
 }
 inline MirtRayStats trace_stats(MirtContext* ctx) { MirtRayStats st; check(mirt_ctx_trace_stats(ctx, &st)); return st; }
+// mirt_ctx_render_features: what the context's camera sees first at every pixel of the rows `params` selects -- albedo, depth, normal
+// and sphere id, compact and row-major like a render; params.spp == 0 traces the centre rays alone, flags = MIRT_FEATURES_*.  Blocking.
+inline std::vector<MirtFeaturePixel> render_features(MirtContext* ctx, const MirtParams& params, uint32_t flags = 0)
+{
+    std::vector<MirtFeaturePixel> out((size_t)mirt_params_out_rows(&params) * params.width);
+    MirtFeaturePixel none{};
+    check(mirt_ctx_render_features(ctx, &params, flags, out.empty() ? &none : out.data(), out.size() * sizeof(MirtFeaturePixel)));
+    return out;
+}
+// the centre ray of pixel (x, y) exactly as the feature kernel traces it (mirt_camera_pixel_ray: float32 with fmaf, t_max = 1000)
+inline MirtRay camera_pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y)
+{
+    MirtRay r{};
+    check(mirt_camera_pixel_ray(&cam, width, height, x, y, &r));
+    return r;
+}
 // the pinhole ray through the centre of pixel (x, y), row 0 on top: cameraMakeRay with a zero lens
 inline MirtRay pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float t_max = 1000.0f)
 {

@@ -441,6 +441,22 @@ def _pick(owner, x: int, y: int, width: int, height: int, camera: _abi.MirtGpuCa
     return {"sphere": int(hit["sphere"]), "t": float(hit["t"]), "point": hit["point"].copy(), "normal": hit["normal"].copy()}
 
 
+def _features(owner, spp: int, seed: int, width: int, height: int, camera: _abi.MirtGpuCamera, scene_data) -> dict:
+    """Layer.features / Raytracer.features: Context.render_features of the whole viewport with `camera` -> the planes {"albedo"
+    [h, w, 3], "normal" [h, w, 3], "t" [h, w], "sphere" [h, w]}.  Like _pick: a resident LDS scene -- or none yet -- is set again as a
+    MIRT_SCENE_HBM scene first, and on a node member 0's context renders the whole band."""
+    if not isinstance(spp, (int, np.integer)) or isinstance(spp, bool) or int(spp) < 0:
+        raise ValueError(f"spp must be a sample count >= 0, not {spp!r}")
+    target = owner._pick_target()
+    if not owner._hbm:
+        target.set_scene(scene_data(), hbm=True)
+        owner._hbm = True
+    ctx = target.context(0) if hasattr(target, "context") else target
+    ctx.set_camera(camera)                                     # Layer.update_camera changes the camera without a device call
+    rec = ctx.render_features(make_params(width, height, int(spp), mode=_abi.MIRT_MODE_PT, seed=seed))
+    return {k: rec[k].copy() for k in ("albedo", "normal", "t", "sphere")}
+
+
 def _jpeg_check(rc: int) -> None:
     if rc != 0:
         raise MirtError(rc, (lib().mirt_jpeg_last_error() or b"").decode())
@@ -596,6 +612,14 @@ class Layer:
         move_spheres / set_world then work on it in place; the next set_data sets the scene by its own rule again (a small world goes
         back to LDS), so a pick after it pays for one more set_scene."""
         return _pick(self, x, y, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data)
+
+    def features(self, spp: int = 0, *, seed: int = 0) -> dict:
+        """What the camera sees first at every pixel of the viewport: {"albedo" [h, w, 3], "normal" [h, w, 3], "t" [h, w], "sphere"
+        [h, w] (index into `world`, MIRT_RAY_MISS where the pixel's centre ray leaves the scene)} by Context.render_features with the
+        layer's current camera.  spp = 0: the centre rays alone (an id and depth buffer for picking, exact guides); spp >= 1: albedo
+        and normal are means over the path tracer's own primary rays of samples 0 .. spp - 1 (its pixel filter and depth of field).
+        Like pick, it needs the world in device memory and sets it as a MIRT_SCENE_HBM scene first where it is not."""
+        return _features(self, spp, seed, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data)
 
     def register_texture(self) -> np.ndarray:         # layer.rs:150-176: the RGBA8 bytes imgui would receive
         if self._rgba is None:
@@ -767,6 +791,16 @@ class Raytracer:
         first and stays one; the accumulation is not touched (the images are the same either way)."""
         w, h = self.render_params.viewport_size
         return _pick(self, x, y, int(w), int(h), self.camera.c, self.scene_data)
+
+    def features(self, spp: Optional[int] = None, *, seed: int = 0) -> dict:
+        """First-hit guides of the current viewport and camera, as Layer.features: {"albedo", "normal", "t", "sphere"} planes.
+        spp = None takes `sampling.num_samples_per_pixel`, the samples of one displayed frame (samples 0 .. spp - 1 of `seed`, one RNG
+        stream per sample whatever `reference_stream` says: a guide needs the frame's pixel filter, not its draws); spp = 0 the centre
+        rays alone.  A scene held in LDS is set again as a MIRT_SCENE_HBM scene first and stays one; the accumulation is not touched."""
+        w, h = self.render_params.viewport_size
+        if spp is None:
+            spp = self.render_params.sampling.num_samples_per_pixel
+        return _features(self, spp, seed, int(w), int(h), self.camera.c, self.scene_data)
 
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
         """All `max_samples_per_pixel` samples in one launch -> RGBA8 [h][w][4].
