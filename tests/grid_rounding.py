@@ -288,8 +288,9 @@ def binning(cen, rad, cell_factor=2.5, big_factor=4.0, disc_slack=True):
             e_walk = 1e-3 * cell + 2.0 ** -22 * coord_max + 2.0 ** -23 * (steps + 16.0) * l_safe
             eps = e_walk + e_disc
             glo, ghi = lo - eps, hi + eps
-            dims = np.maximum(1.0, np.ceil((ghi - glo) / cell + 1e-6)).astype(np.int64)
+            dims = np.maximum(1.0, np.ceil((ghi - glo) / cell + 1e-6))        # counted in float64: an extent of 2^83 cells is no integer
         if dims.prod() <= GRID_MAX_CELLS:
+            dims = dims.astype(np.int64)
             break
         cell *= 1.26
     enl = eps if disc_slack else e_walk
@@ -321,6 +322,13 @@ def dot32(ax, ay, az, bx, by, bz):
 
 def first_roots(o, d, cen, rad):
     """test_sphere for rays [n, 3] x spheres [k]: the first root above MIN_T each pair computes, +inf where it computes none."""
+    with np.errstate(all="ignore"):
+        rr = (rad.astype(f32) * rad.astype(f32)).astype(f32)
+    return first_roots_rr(o, d, cen, rr)
+
+
+def first_roots_rr(o, d, cen, rr):
+    """first_roots from test records {centre, r * r} (the float32 product PreparedSphere.rr / a BVH record holds)."""
     o, d = o.astype(f32), d.astype(f32)
     a = dot32(d[:, 0], d[:, 1], d[:, 2], d[:, 0], d[:, 1], d[:, 2])[:, None]
     inv_a = (f32(1.0) / a).astype(f32)
@@ -328,7 +336,7 @@ def first_roots(o, d, cen, rad):
         oc = [(o[:, k, None] - cen[None, :, k].astype(f32)).astype(f32) for k in range(3)]
         dd = [np.broadcast_to(d[:, k, None], oc[0].shape) for k in range(3)]
         b = dot32(oc[0], oc[1], oc[2], dd[0], dd[1], dd[2])
-        rr = (rad.astype(f32) * rad.astype(f32)).astype(f32)
+        rr = np.asarray(rr, f32)
         cq = (dot32(oc[0], oc[1], oc[2], oc[0], oc[1], oc[2]) - rr[None, :]).astype(f32)
         disc = fma32(b, b, -(a * cq).astype(f32))
         pos = disc > 0

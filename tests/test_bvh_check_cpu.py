@@ -2,52 +2,7 @@
 import numpy as np
 import pytest
 
-from bvh_check import LEAF, NODE_DTYPE, BvhError, always_list, check_bvh, sphere_boxes
-
-
-def assemble(topology, centres, radii, always=()):
-    """(nodes, recs, ids, info) of a tree given as nested pairs whose leaves are lists of sphere indices; boxes by the validator's own
-    per-sphere formula, so that a test changes exactly one thing afterwards."""
-    centres = np.asarray(centres, np.float32)
-    radii = np.asarray(radii, np.float32)
-    lo, hi = sphere_boxes(centres, radii)
-    ids = [int(i) for i in always]
-    nodes = []
-    stat = {"n_leaves": 0, "max_depth": 0, "max_leaf": 0}
-
-    def build(t, depth):
-        """-> (reference, lo, hi)"""
-        if isinstance(t, list):
-            ref = LEAF | (len(t) << 24) | len(ids)
-            ids.extend(t)
-            if t:
-                stat["n_leaves"] += 1
-                stat["max_depth"] = max(stat["max_depth"], depth)
-                stat["max_leaf"] = max(stat["max_leaf"], len(t))
-            if not t:
-                return ref, np.full(3, np.inf, np.float32), np.full(3, -np.inf, np.float32)
-            return ref, lo[t].min(axis=0), hi[t].max(axis=0)
-        me = len(nodes)
-        nodes.append(None)
-        l, r = build(t[0], depth + 1), build(t[1], depth + 1)
-        nd = np.zeros((), NODE_DTYPE)
-        nd["left"], nd["lmin"], nd["lmax"] = l
-        nd["right"], nd["rmin"], nd["rmax"] = r
-        nodes[me] = nd
-        return me, np.minimum(l[1], r[1]), np.maximum(l[2], r[2])
-
-    root, blo, bhi = build(topology, 0)
-    ids = np.array(ids, np.uint32)
-    recs = np.concatenate([centres[ids], (radii[ids] * radii[ids])[:, None]], axis=1).astype(np.float32)
-    if not len(ids) - len(always):                       # an empty tree: there is nothing to bound
-        blo, bhi = np.zeros(3, np.float32), np.zeros(3, np.float32)
-    cen = (0.5 * (blo.astype(np.float64) + bhi)).astype(np.float32)
-    far = np.sqrt((np.maximum(np.abs(blo - cen.astype(np.float64)), np.abs(bhi - cen.astype(np.float64))) ** 2).sum())
-    info = {"plan": {"n_nodes": len(nodes), "n_leaves": stat["n_leaves"], "n_leaf_spheres": len(ids) - len(always), "n_always": len(always),
-                     "max_depth": stat["max_depth"], "max_leaf": stat["max_leaf"], "device_bytes": 64 * len(nodes) + 20 * len(ids)},
-            "root": root, "built_on_device": 0, "centre": cen.tolist(), "radius": float(np.float32(far * 1.001)),
-            "r_max": float(np.float32(np.nanmax(np.abs(radii[ids[len(always):]]), initial=0.0) * 1.001))}
-    return np.array(nodes, NODE_DTYPE) if nodes else np.zeros(0, NODE_DTYPE), recs, ids, info
+from bvh_check import LEAF, NODE_DTYPE, BvhError, always_list, assemble, check_bvh, sphere_boxes
 
 
 def _world(n, seed=0):

@@ -8,6 +8,7 @@ import pytest
 import weekend_raytracer_wgpu_amd as m
 from weekend_raytracer_wgpu_amd import _abi
 from hbm_worlds import c_spheres, clustered_soup, rtiow_field, sphere_array
+import deep_worlds
 
 
 def _plan(arr):
@@ -45,6 +46,8 @@ def _inputs():
     yield "nonfinite", bad
     yield "field", rtiow_field(20000)[0]
     yield "clustered", clustered_soup(20000)[0]
+    yield "line26", deep_worlds.line("line26")
+    yield "line32", deep_worlds.line("line32")
 
 
 INPUTS = list(_inputs())

@@ -160,17 +160,23 @@ std::vector<unsigned char> build_grid(const MirtSphere* sph, uint32_t n, double 
             e_disc = 0.25 * cell;
             l_safe = std::sqrt(((r_min + e_disc) * (r_min + e_disc) - r_min * r_min) / kDiscErr);
         }
-        uint64_t total = 1;
+        // The dims are counted in double and converted only once they are known to be small: a world whose extent is 2^32 cells or
+        // more (spheres of radius 2^-29 along 80 octaves) made the conversion itself undefined -- dims of 0, a grid of no cells that
+        // "fits", and a write into its first list.
+        double ddims[3] = { 16.0, 16.0, 16.0 }, total = 1.0;
         for (int pass = 0; pass < 2; ++pass) {                    // the step count of e_walk comes from the dims: settle them in two passes
-            const double steps = pass ? (double)dims[0] + dims[1] + dims[2] : 3.0 * 16.0;
+            const double steps = ddims[0] + ddims[1] + ddims[2];
             eps = 1e-3 * cell + 0x1p-22 * coord_max + 0x1p-23 * (steps + 16.0) * l_safe + e_disc;
-            total = 1;
+            total = 1.0;
             for (int k = 0; k < 3; ++k) {
                 glo[k] = lo[k] - eps; ghi[k] = hi[k] + eps;
-                dims[k] = (uint32_t)std::max(1.0, std::ceil((ghi[k] - glo[k]) / cell + 1e-6)); total *= dims[k];
+                ddims[k] = std::max(1.0, std::ceil((ghi[k] - glo[k]) / cell + 1e-6)); total *= ddims[k];
             }
         }
-        if (total <= mirt::kGridMaxCells) break;
+        if (total <= (double)mirt::kGridMaxCells) {
+            for (int k = 0; k < 3; ++k) dims[k] = (uint32_t)ddims[k];
+            break;
+        }
         cell *= 1.26;
     }
     for (int k = 0; k < 3; ++k) lo[k] = glo[k];                   // the grid's lower corner: the spheres' box grown by eps

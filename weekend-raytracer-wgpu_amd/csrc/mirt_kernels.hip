@@ -1619,10 +1619,12 @@ MIRT_DEV uint32_t strip_candidates(const RenderArgs& AP, const SceneLds& S, uint
 // lattices whose boxes share faces, axis-aligned cameras, a camera inside a sphere, grazing rays at r = 10^-3 / distance 10^3,
 // zero-radius and non-finite spheres -- all byte-equal to the flat scan.
 //
-// Traversal: near child first, the far one on a per-lane stack in LDS of MIRT_BVH_MAX_DEPTH entries.  An entry is pushed only at an
-// inner node, at most one per level of the path from the root, and the builder bounds the depth (mirt_bvh.cpp): the stack cannot
-// fill; a push past its end is not written in any case.  `stack_cap` = the entries the caller's stack holds: MIRT_BVH_MAX_DEPTH in the
-// strip kernels; the pooled kernel sizes its stacks by the resident tree's depth (RenderArgs.bvh_stack_entries).
+// Traversal: near child first, the far one on a per-lane stack in LDS of `stack_cap` entries.  An entry is pushed only at an inner
+// node, at most one per level of the path from the root, so a stack of as many entries as the tree is deep can FILL EXACTLY (a ray
+// that visits both children at every level of the deepest path: tests/test_gpu_deep_trees.py) and cannot overflow; a push past its end
+// is not written in any case -- a stack one entry short loses a subtree without a trace.  `stack_cap` = the entries the caller's stack
+// holds: MIRT_BVH_MAX_DEPTH, which bounds the depth of both builders' trees, in the strip kernels; the pooled, ray-query and feature
+// kernels size their stacks by the resident tree's depth (RenderArgs.bvh_stack_entries = plan.max_depth).
 constexpr uint32_t kBvhLeafRef = 0x80000000u;      // mirt_bvh.h: kBvhLeaf -- count in bits 24..30, first record in bits 0..23
 constexpr uint32_t kBvhStack = MIRT_BVH_MAX_DEPTH;
 constexpr float    kBvhSlack = 1.0f + 0x1p-9f;
