@@ -531,6 +531,46 @@ int mirt_ctx_render_features(MirtContext* ctx, const MirtParams* params, uint32_
 int mirt_ctx_render_features_device(MirtContext* ctx, const MirtParams* params, uint32_t flags, void* d_out, size_t out_len, void* hip_stream);
 int mirt_camera_pixel_ray(const MirtGpuCamera* camera, uint32_t width, uint32_t height, uint32_t x, uint32_t y, MirtRay* out);
 
+/* ---- path-traced radiance for a caller's rays against a MIRT_SCENE_HBM scene ----
+ * The path tracer for rays the HOST chooses: panorama, fisheye, cube-map and stereo cameras, light and reflection probes, irradiance
+ * at points of a simulation, batches of training rays held in device memory.  One MirtRadiance per MirtRadianceRay, in the caller's order.
+ *   a sample         is the renderer's sample from its primary ray on.  For sample s in sample_begin .. sample_begin + spp - 1 the ray's
+ *                    lane seeds rng.state = jenkins_hash((ray.stream ^ jenkins_hash(s + 1)) ^ seed_mix), seed_mix derived from `seed`
+ *                    exactly as a render call derives it: `stream` takes the place the pixel index (x + y * width) has in a render.  The
+ *                    lane then advances the stream by the four draws a primary ray consumes (two jitter, two lens) and runs the renderer's
+ *                    bounce loop from (origin, direction) with num_bounces.  So a ray equal to a renderer's primary ray, with `stream`
+ *                    equal to that pixel's index, continues that sample's path bit for bit.
+ *   the ray          `direction` is used as given, NOT normalised, as a primary ray's is; every segment of the path has the renderer's
+ *                    t_max = 1000; `_pad` is not read.
+ *   the record       sum[k] = the sum over the samples, in order, of to_fixed(radiance[k]): the units of the context's accumulation
+ *                    buffer, 2^-20, each sample clamped to [0, 4096).  Without MIRT_RADIANCE_ACCUMULATE the record is overwritten:
+ *                    samples = spp, _pad = 0.  With it the lane adds to the sums already in the record and adds spp to `samples`
+ *                    (mod 2^32; _pad = 0); a progressive probe passes sample_begin = the samples so far, as mirt_ctx_accum_add does
+ *                    internally.  The mean is sum / 2^20 / samples; it is left to the host, because the integer sums are what is exact
+ *                    and additive.  A record depends only on its ray, the params and the scene: not on the ray's place in the batch, not
+ *                    on n_rays.
+ * flags: 0 = the BVH walk of the render kernels (radiance_rays_kernel<.., true>); MIRT_RADIANCE_FLAT = the flat scan of the resident table,
+ * the comparison build as MIRT_RAYS_FLAT is; MIRT_RADIANCE_SKY_HOSEK = the scene's Hosek blob, as MIRT_FLAG_SKY_HOSEK (MIRT_ERR_SKY
+ * without a blob); any other bit: MIRT_ERR_BAD_MODE.
+ * MIRT_ERR_NULL_POINTER: ctx or params is null, or rays or the output is null with n_rays > 0;  MIRT_ERR_NO_SCENE: no scene, or not a
+ * MIRT_SCENE_HBM one;  MIRT_ERR_SPP_ZERO, MIRT_ERR_SPP_RANGE: the rules of mirt_ctx_render;  MIRT_ERR_MATERIAL_INDEX / MIRT_ERR_TEXEL_RANGE:
+ * exactly as a path-traced render call on that scene answers.  n_rays == 0 (after these checks): MIRT_OK without device work.  A refused
+ * call queues nothing and writes nothing.
+ *   mirt_ctx_trace_radiance          rays and records in HOST memory: copy, kernel, copy on the context's stream; blocking.  With
+ *                                    MIRT_RADIANCE_ACCUMULATE it copies `out` to the device first.
+ *   mirt_ctx_trace_radiance_device   pointers are memory of the context's device, 4-byte aligned: ONE kernel queued on `hip_stream` (NULL =
+ *                                    the context's stream; hipStreamLegacy for the default stream), no host synchronisation; ordered
+ *                                    against set_scene*, update_spheres* and set_spheres* the way ray queries are.
+ * State is kept the way the ray queries keep it: neither the launch ring, MirtStats nor the accumulation is touched; mirt_ctx_last_kernel
+ * names the kernel; mirt_ctx_synchronize and mirt_ctx_destroy wait for it; its time is mirt_ctx_trace_stats().kernel_ms (the counters
+ * are 0). */
+typedef struct MirtRadianceRay { float origin[3]; uint32_t stream; float direction[3]; uint32_t _pad; } MirtRadianceRay;   /* 32 B */
+typedef struct MirtRadiance { uint64_t sum[3]; uint32_t samples; uint32_t _pad; } MirtRadiance;   /* 32 B */
+typedef struct MirtRadianceParams { uint32_t spp, sample_begin, num_bounces, flags; uint64_t seed; } MirtRadianceParams;   /* 24 B */
+enum { MIRT_RADIANCE_FLAT = 1u << 0, MIRT_RADIANCE_ACCUMULATE = 1u << 1, MIRT_RADIANCE_SKY_HOSEK = 1u << 2 };
+int mirt_ctx_trace_radiance(MirtContext* ctx, const MirtRadianceRay* rays, uint32_t n_rays, const MirtRadianceParams* params, MirtRadiance* out);
+int mirt_ctx_trace_radiance_device(MirtContext* ctx, const void* d_rays, uint32_t n_rays, const MirtRadianceParams* params, void* d_out, void* hip_stream);
+
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by
  * value with each launch, so this neither copies to the device nor synchronises; launches already
@@ -752,6 +792,9 @@ static_assert(sizeof(MirtRay) == 32, "MirtRay is two 16-byte loads");
 static_assert(sizeof(MirtRayHit) == 32, "MirtRayHit is two 16-byte stores");
 static_assert(sizeof(MirtRayStats) == 56, "MirtRayStats is a double and six u64");
 static_assert(sizeof(MirtFeaturePixel) == 32, "MirtFeaturePixel is two 16-byte stores");
+static_assert(sizeof(MirtRadianceRay) == 32, "MirtRadianceRay is two 16-byte loads");
+static_assert(sizeof(MirtRadiance) == 32, "MirtRadiance is two 16-byte stores");
+static_assert(sizeof(MirtRadianceParams) == 24, "MirtRadianceParams is four u32 and a u64");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -763,6 +806,9 @@ _Static_assert(sizeof(MirtRay) == 32, "MirtRay is two 16-byte loads");
 _Static_assert(sizeof(MirtRayHit) == 32, "MirtRayHit is two 16-byte stores");
 _Static_assert(sizeof(MirtRayStats) == 56, "MirtRayStats is a double and six u64");
 _Static_assert(sizeof(MirtFeaturePixel) == 32, "MirtFeaturePixel is two 16-byte stores");
+_Static_assert(sizeof(MirtRadianceRay) == 32, "MirtRadianceRay is two 16-byte loads");
+_Static_assert(sizeof(MirtRadiance) == 32, "MirtRadiance is two 16-byte stores");
+_Static_assert(sizeof(MirtRadianceParams) == 24, "MirtRadianceParams is four u32 and a u64");
 #endif
 
 #endif /* MIRT_H */

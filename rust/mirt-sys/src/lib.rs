@@ -244,6 +244,43 @@ pub struct MirtFeaturePixel {
 /// `mirt_ctx_render_features*` flag: the flat scan instead of the tree (the comparison build).
 pub const MIRT_FEATURES_FLAT: u32 = 1 << 0;
 
+/// One ray of `mirt_ctx_trace_radiance*`.  `direction` is used as given (not normalised); `stream` selects the ray's RNG stream and
+/// takes the place a pixel's index has in a render; `_pad` is not read.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtRadianceRay {
+    pub origin: [f32; 3],
+    pub stream: u32,
+    pub direction: [f32; 3],
+    pub _pad: u32,
+}
+
+/// One record of `mirt_ctx_trace_radiance*`: the exact sums of `samples` path-traced samples in units of 2^-20 (the mean is
+/// `sum / 2^20 / samples`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtRadiance {
+    pub sum: [u64; 3],
+    pub samples: u32,
+    pub _pad: u32,
+}
+
+/// What a `mirt_ctx_trace_radiance*` call traces: samples `sample_begin .. sample_begin + spp - 1` of every ray's stream.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtRadianceParams {
+    pub spp: u32,
+    pub sample_begin: u32,
+    pub num_bounces: u32,
+    pub flags: u32,
+    pub seed: u64,
+}
+
+/// `MirtRadianceParams.flags`: the flat scan instead of the tree; add to the records instead of overwriting them; the scene's Hosek sky.
+pub const MIRT_RADIANCE_FLAT: u32 = 1 << 0;
+pub const MIRT_RADIANCE_ACCUMULATE: u32 = 1 << 1;
+pub const MIRT_RADIANCE_SKY_HOSEK: u32 = 1 << 2;
+
 pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
 /// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.
 pub const MIRT_RAYS_FLAT: u32 = 1 << 0;
@@ -336,6 +373,8 @@ extern "C" {
     pub fn mirt_ctx_render_features(ctx: *mut MirtContext, params: *const MirtParams, flags: u32, out: *mut MirtFeaturePixel, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_features_device(ctx: *mut MirtContext, params: *const MirtParams, flags: u32, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_camera_pixel_ray(camera: *const MirtGpuCamera, width: u32, height: u32, x: u32, y: u32, out: *mut MirtRay) -> c_int;
+    pub fn mirt_ctx_trace_radiance(ctx: *mut MirtContext, rays: *const MirtRadianceRay, n_rays: u32, params: *const MirtRadianceParams, out: *mut MirtRadiance) -> c_int;
+    pub fn mirt_ctx_trace_radiance_device(ctx: *mut MirtContext, d_rays: *const c_void, n_rays: u32, params: *const MirtRadianceParams, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_ctx_set_camera(ctx: *mut MirtContext, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_ctx_render(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;

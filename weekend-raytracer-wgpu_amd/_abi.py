@@ -40,6 +40,11 @@ MIRT_RAY_MISS = 0xFFFFFFFF
 # mirt_ctx_render_features* flags
 MIRT_FEATURES_FLAT = 1 << 0
 
+# mirt_ctx_trace_radiance* flags (MirtRadianceParams.flags)
+MIRT_RADIANCE_FLAT = 1 << 0
+MIRT_RADIANCE_ACCUMULATE = 1 << 1
+MIRT_RADIANCE_SKY_HOSEK = 1 << 2
+
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
 MIRT_NODE_RCCL = 1 << 0
@@ -188,6 +193,18 @@ class MirtFeaturePixel(C.Structure):
     _fields_ = [("albedo", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("sphere", C.c_uint32)]
 
 
+class MirtRadianceRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("stream", C.c_uint32), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
+class MirtRadiance(C.Structure):
+    _fields_ = [("sum", C.c_uint64 * 3), ("samples", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class MirtRadianceParams(C.Structure):
+    _fields_ = [("spp", C.c_uint32), ("sample_begin", C.c_uint32), ("num_bounces", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class MirtRayStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("rays", C.c_uint64), ("sphere_tests", C.c_uint64), ("roots", C.c_uint64),
                 ("hits", C.c_uint64), ("nodes", C.c_uint64), ("wave_nodes", C.c_uint64)]
@@ -238,6 +255,8 @@ SYMBOLS = {
     "mirt_ctx_render_features": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_uint32, C.c_void_p, C.c_size_t]),
     "mirt_ctx_render_features_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mirt_camera_pixel_ray": (C.c_int, [_P(MirtGpuCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(MirtRay)]),
+    "mirt_ctx_trace_radiance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, _P(MirtRadianceParams), C.c_void_p]),
+    "mirt_ctx_trace_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, _P(MirtRadianceParams), C.c_void_p, C.c_void_p]),
     "mirt_ctx_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_ctx_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),

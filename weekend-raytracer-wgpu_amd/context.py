@@ -192,6 +192,56 @@ def camera_pixel_ray(camera: _abi.MirtGpuCamera, w: int, h: int, x: int, y: int)
     return ray
 
 
+# MirtRadianceRay / MirtRadiance as numpy records (32 bytes each): what trace_radiance takes and returns
+RADIANCE_RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("stream", "<u4"), ("direction", "<f4", (3,)), ("_pad", "<u4")])
+RADIANCE_DTYPE = np.dtype([("sum", "<u8", (3,)), ("samples", "<u4"), ("_pad", "<u4")])
+
+
+def make_radiance_rays(origins, directions, streams=None) -> np.ndarray:
+    """A RADIANCE_RAY_DTYPE array from origins [n, 3] (or one origin), directions [n, 3] (used as given, not normalised) and the
+    rays' RNG streams (a scalar or [n] of u32; default: the ray's index, the place a pixel's index has in a render)."""
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(d), RADIANCE_RAY_DTYPE)
+    rays["origin"] = np.asarray(origins, np.float32)
+    rays["direction"] = d
+    st = np.arange(len(d), dtype=np.uint64) if streams is None else np.asarray(streams)
+    if st.dtype.kind not in "iu" or (st.size and (int(st.min()) < 0 or int(st.max()) > 0xffffffff)):
+        raise ValueError("streams must be integers in [0, 2^32)")
+    rays["stream"] = st.astype(np.uint32)
+    return rays
+
+
+def radiance_ray_records(rays) -> np.ndarray:
+    """`rays` for trace_radiance -> a contiguous one-dimensional RADIANCE_RAY_DTYPE array (a view where possible): a RADIANCE_RAY_DTYPE
+    array, or a uint32 array [n, 8] of the records' bit patterns.  Anything else: ValueError, before the library is called."""
+    if not isinstance(rays, np.ndarray):
+        raise ValueError(f"rays must be a numpy array of RADIANCE_RAY_DTYPE or uint32 [n, 8], not {type(rays).__name__}")
+    if rays.dtype == RADIANCE_RAY_DTYPE and rays.ndim == 1:
+        return np.ascontiguousarray(rays)
+    if rays.dtype == np.uint32 and rays.ndim == 2 and rays.shape[1] == 8:
+        return np.ascontiguousarray(rays).view(RADIANCE_RAY_DTYPE).reshape(-1)
+    raise ValueError(f"rays must be a one-dimensional RADIANCE_RAY_DTYPE array or uint32 [n, 8], not {rays.dtype} of shape {rays.shape}")
+
+
+def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate) -> _abi.MirtRadianceParams:
+    for name, v in (("spp", spp), ("sample_begin", sample_begin), ("num_bounces", num_bounces)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), not {seed!r}")
+    for name, v in (("flat", flat), ("hosek", hosek), ("accumulate", accumulate)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, not {v!r}")
+    flags = (_abi.MIRT_RADIANCE_FLAT if flat else 0) | (_abi.MIRT_RADIANCE_SKY_HOSEK if hosek else 0) | (_abi.MIRT_RADIANCE_ACCUMULATE if accumulate else 0)
+    return _abi.MirtRadianceParams(int(spp), int(sample_begin), int(num_bounces), flags, int(seed))
+
+
+def radiance_mean(records: np.ndarray) -> np.ndarray:
+    """RADIANCE_DTYPE records -> float64 means [n, 3]: sum / 2^20 / samples (0 where a record holds no sample)."""
+    n = np.maximum(records["samples"].astype(np.float64), 1.0)[:, None]
+    return records["sum"].astype(np.float64) / float(1 << 20) / n
+
+
 def _check_range(first, count) -> None:
     for name, v in (("first", first), ("count", count)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
@@ -340,6 +390,39 @@ class Context:
         st = _abi.MirtRayStats()
         check(lib().mirt_ctx_trace_stats(self._h, C.byref(st)))
         return st.as_dict()
+
+    # ---- path-traced radiance for a caller's rays against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+    def trace_radiance(self, rays, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0, flat: bool = False,
+                       hosek: bool = False, into: Optional[np.ndarray] = None) -> np.ndarray:
+        """mirt_ctx_trace_radiance: `spp` samples of the path tracer for every ray -> a RADIANCE_DTYPE array {"sum" [3] in 2^-20 units,
+        "samples"}, one record per ray in the caller's order (radiance_mean gives the means).  A sample is the renderer's from its
+        primary ray on: samples sample_begin .. sample_begin + spp - 1 of the RNG stream a pixel of index `stream` has under `seed`.
+        `rays`: see radiance_ray_records (make_radiance_rays builds them).  flat=True: the flat scan instead of the tree; hosek=True:
+        the scene's Hosek sky.  into: a RADIANCE_DTYPE array [n] to ADD to (MIRT_RADIANCE_ACCUMULATE), changed in place and
+        returned -- a progressive probe passes sample_begin = the samples it holds.  Needs a scene set with hbm=True.  Blocking."""
+        recs = radiance_ray_records(rays)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, into is not None)
+        if into is None:
+            out = np.zeros(len(recs), RADIANCE_DTYPE)
+        else:
+            if not isinstance(into, np.ndarray) or into.dtype != RADIANCE_DTYPE or into.shape != (len(recs),) or not into.flags.c_contiguous or not into.flags.writeable:
+                raise ValueError("into must be a writable contiguous RADIANCE_DTYPE array with one record per ray")
+            out = into
+        check(lib().mirt_ctx_trace_radiance(self._h, C.c_void_p(recs.ctypes.data) if len(recs) else None, len(recs), C.byref(params),
+                                            C.c_void_p(out.ctypes.data) if len(recs) else None))
+        return out
+
+    def trace_radiance_device(self, d_rays: int, n: int, d_out: int, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0,
+                              flat: bool = False, hosek: bool = False, accumulate: bool = False, stream: Optional[int] = None) -> None:
+        """mirt_ctx_trace_radiance_device: `n` 32-byte MirtRadianceRay records at device address `d_rays` -> `n` MirtRadiance records at
+        `d_out` (e.g. torch tensors' data_ptr()), one kernel queued on `stream` (see _stream_arg); no host synchronisation.
+        accumulate=True adds to the records already at `d_out`."""
+        _check_range(0, n)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate)
+        if int(n):
+            d_rays, d_out = _check_address("d_rays", d_rays), _check_address("d_out", d_out)
+        check(lib().mirt_ctx_trace_radiance_device(self._h, C.c_void_p(d_rays) if int(n) else None, int(n), C.byref(params),
+                                                   C.c_void_p(d_out) if int(n) else None, _stream_arg(stream)))
 
     # ---- first-hit feature frames of the resident MIRT_SCENE_HBM scene (include/mirt.h; DESIGN.md 10.8) ----
     def render_features(self, params: _abi.MirtParams, flat: bool = False) -> np.ndarray:

@@ -1914,6 +1914,81 @@ int mirt_camera_pixel_ray(const MirtGpuCamera* cam, uint32_t width, uint32_t hei
     return MIRT_OK;
 }
 
+// ---- path-traced radiance for a caller's rays against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+// What both entry points check, in the header's order; MIRT_OK with *go = false: nothing to do (n_rays == 0).
+static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, const MirtRadianceParams* p, const void* out, bool* go)
+{
+    *go = false;
+    if (!c || !p) return fail(MIRT_ERR_NULL_POINTER, "ctx/params is null");
+    if (n && (!rays || !out)) return fail(MIRT_ERR_NULL_POINTER, "rays/out is null");
+    if (p->flags & ~(uint32_t)(MIRT_RADIANCE_FLAT | MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_SKY_HOSEK))
+        return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RADIANCE_* bits 0x%x", p->flags);
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (p->spp == 0) return fail(MIRT_ERR_SPP_ZERO, "spp is zero");
+    if (p->spp > MIRT_MAX_SPP_PER_CALL || (uint64_t)p->sample_begin + p->spp > 0xffffffffull)
+        return fail(MIRT_ERR_SPP_RANGE, "spp %u (from sample %u) is out of range: at most %u samples per ray in one call, sample indices below 2^32",
+                    p->spp, p->sample_begin, (unsigned)MIRT_MAX_SPP_PER_CALL);
+    if (c->pt_scene_status != MIRT_OK) return fail(c->pt_scene_status, "scene tables are inconsistent: %s", mirt_status_string(c->pt_scene_status));
+    if ((p->flags & MIRT_RADIANCE_SKY_HOSEK) && !c->have_sky) return fail(MIRT_ERR_SKY, "MIRT_RADIANCE_SKY_HOSEK needs scene.sky");
+    *go = n != 0u;
+    return MIRT_OK;
+}
+
+// Queue radiance_rays_kernel<hosek, bvh> for n > 0 rays in device memory on `st`.  No host synchronisation.  The launch ring, MirtStats and
+// the accumulation stay as they are; the event pair and the pending flag are the ray queries' (mirt_ctx_trace_stats folds the time).
+static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const MirtRadianceParams* p, void* d_out, hipStream_t st)
+{
+    const bool bvh = !(p->flags & MIRT_RADIANCE_FLAT), hosek = (p->flags & MIRT_RADIANCE_SKY_HOSEK) != 0;
+    mirt::RenderArgs a{};                                 // (the camera stays zero: a query has none)
+    a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
+    a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
+    a.spp = p->spp; a.num_bounces = p->num_bounces; a.flags = p->flags;
+    a.seed_mix = jenkins_hash((uint32_t)p->seed ^ jenkins_hash((uint32_t)(p->seed >> 32)));      // as launch_render derives it
+    a.sample_begin = p->sample_begin;
+    a.n_units = n;
+    // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
+    fill_bvh_args(c, &a, 0u);
+    a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
+    const bool timed = c->timing;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    HIP_TRY(kx::launch_radiance(a, d_rays, d_out, hosek, bvh, st));
+    const char* tf[2] = { "false", "true" };
+    snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays_kernel<%s,%s>", tf[hosek], tf[bvh]);
+    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
+    c->trace_pending = true;
+    c->trace_timed = timed;
+    c->trace_counted = false;
+    c->trace_stats = MirtRayStats{};
+    return MIRT_OK;
+}
+
+int mirt_ctx_trace_radiance_device(MirtContext* c, const void* d_rays, uint32_t n_rays, const MirtRadianceParams* p, void* d_out, void* hip_stream)
+{
+    bool go;
+    const int rc = check_radiance(c, d_rays, n_rays, p, d_out, &go);
+    if (rc != MIRT_OK || !go) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return launch_radiance(c, d_rays, n_rays, p, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int mirt_ctx_trace_radiance(MirtContext* c, const MirtRadianceRay* rays, uint32_t n_rays, const MirtRadianceParams* p, MirtRadiance* out)
+{
+    bool go;
+    int rc = check_radiance(c, rays, n_rays, p, out, &go);
+    if (rc != MIRT_OK || !go) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    static_assert(sizeof(MirtRadianceRay) == sizeof(MirtRay) && sizeof(MirtRadiance) == sizeof(MirtRayHit), "the host path stages where a host trace stages");
+    const size_t bytes = (size_t)n_rays * sizeof(MirtRadianceRay);
+    if ((rc = ensure_capacity(&c->d_trace_rays, &c->cap_trace_rays, bytes)) != MIRT_OK) return rc;
+    if ((rc = ensure_capacity(&c->d_trace_hits, &c->cap_trace_hits, bytes)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_trace_rays, rays, bytes, hipMemcpyHostToDevice, c->stream));
+    if (p->flags & MIRT_RADIANCE_ACCUMULATE) HIP_TRY(hipMemcpyAsync(c->d_trace_hits, out, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_radiance(c, c->d_trace_rays, n_rays, p, c->d_trace_hits, c->stream)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_trace_hits, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
 int mirt_ctx_accum_reset(MirtContext* c, const MirtParams* p)
 {
     int rc = check_params(c, p);

@@ -301,6 +301,11 @@ hipError_t launch_trace_rays(const RenderArgs& a, const void* d_rays, void* d_hi
 // camera (with the pinhole word set), the tables, the tree, seed_mix, spp, sample_begin and the row fields as a render launch's does,
 // bvh_stack_entries and lds_bytes as launch_trace_rays wants them; d_out: [out_rows x width] MirtFeaturePixel in device memory, 4-byte aligned.
 hipError_t launch_features(const RenderArgs& a, void* d_out, bool bvh, hipStream_t stream);
+// mirt_ctx_trace_radiance*: radiance_rays_kernel<hosek, bvh> (mirt_radiance_kernel.inc), one thread per ray, one wave per block.  `a` carries the tables, the sky and
+// the tree as a render launch's does, spp, sample_begin, num_bounces and seed_mix, n_units = the number of rays, flags = the caller's
+// MIRT_RADIANCE_* bits, lds_bytes = scene_lds_bytes_grid(n_spheres, hosek) + kBvhStackBytesPerWave (BVH build);
+// d_rays / d_out: [n_units] MirtRadianceRay / MirtRadiance in device memory, 4-byte aligned.
+hipError_t launch_radiance(const RenderArgs& a, const void* d_rays, void* d_out, bool hosek, bool bvh, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);
 size_t     scene_lds_bytes(uint32_t n_spheres, uint32_t n_mats, bool pt, bool hosek);
 size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);

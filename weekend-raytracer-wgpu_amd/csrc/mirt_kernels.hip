@@ -2182,9 +2182,10 @@ struct PoolHbmState {
 #include "mirt_isa_probes.inc"       // tools/isa_mix.py; never part of libmirt.so
 #endif
 
-#ifndef MIRT_FAST_MATH       // ray queries, feature frames, self-test, resolve and frame assembly live in the exact build only
+#ifndef MIRT_FAST_MATH       // ray queries, feature frames, radiance queries, self-test, resolve and frame assembly live in the exact build only
 #include "mirt_trace_kernel.inc"
 #include "mirt_feature_kernel.inc"
+#include "mirt_radiance_kernel.inc"
 
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns

@@ -1,0 +1,86 @@
+// mirt_radiance_kernel.inc -- path-traced radiance for a caller's rays against a resident MIRT_SCENE_HBM scene
+// (mirt_ctx_trace_radiance*; DESIGN.md 10.9).  Included once by mirt_kernels.hip behind mirt_feature_kernel.inc (it shares
+// mirt_trace_kernel.inc's vector types), exact build only: there is no fast_build:: copy, no counting build and no dispenser.
+//
+// radiance_rays_kernel<HOSEK, BVH>: lane = ray, 64 consecutive rays per wave, ONE wave per block (kRadianceThreads), one ray per thread and no
+// loop over rays: the caller's order is the wave's order.  RenderArgs.n_units is the number of rays; lanes of the last wave beyond it are
+// not alive: they load nothing, take part in the wave's loops with their tests masked off and store nothing.  A ray (MirtRadianceRay,
+// 32 bytes: {origin, stream} {direction, _pad}) is two 16-byte loads through a 4-byte-aligned vector type.
+//   A sample is the renderer's sample from its primary ray on.  For s in sample_begin .. sample_begin + spp - 1 (the same trip count in
+// every lane) the lane seeds the stream generate_primary would seed for a pixel whose index is the ray's `stream`, skips the four draws
+// a primary ray consumes (two jitter, two lens) and calls path_radiance -- the function the render kernels call, with the source
+// render_pt_hbm_kernel gives it -- from (origin, direction).  The three sums of to_fixed(radiance) are kept per lane as 64-bit
+// integers; there is no reduction: a record depends on its ray alone.
+//   BVH = true : kSrcBvh, nearest_hit_bvh through per_strip_args(), which is why RenderArgs is the FIRST kernel argument.  path_radiance
+//                walks with the strip kernels' stack capacity, so every wave keeps kBvhStackBytesPerWave of traversal stacks in LDS.
+//   BVH = false: kSrcHbmFlat, the flat scan of the sphere table in device memory (MIRT_RADIANCE_FLAT, the comparison build).
+//   HOSEK      : the scene's sky blob, staged into LDS by stage_scene as in the render kernels.
+// LDS of a block: stage_scene's image without the tables (the launch's camera words, which nothing reads, and the sky blob) | the wave's
+// stacks, 8 KB.  Block size, measured (tools/radiance_rates.py, 1080p centre rays, 64- against 256-thread blocks, alternating runs;
+// DESIGN.md 10.9): 484 spheres 2 / 16 spp 0.92 / 7.12 ms against 1.06 / 8.03, 1 M spheres 8.98 / 64.8 against 9.16 / 65.8, the same rays
+// shuffled 18.8 / 147.6 against 28.0 / 222.1 -- a block leaves when its slowest wave is done and holds all its stacks until then, and
+// with one wave per block LDS keeps 19 waves on a CU (160 KB / 8.1 KB) instead of 16 (four blocks of 32.1 KB), the residency of the
+// render kernel's one-unit-per-wave launches.  The launch bounds ask for the 5 waves per SIMD that covers: 96 VGPRs allowed, 80 used.
+//   A record (MirtRadiance, 32 bytes: three u64 sums, samples, _pad) leaves as two 16-byte stores; with MIRT_RADIANCE_ACCUMULATE
+// (RenderArgs.flags, wave-uniform) two 16-byte loads precede them and the lane adds.
+
+constexpr uint32_t kRadianceThreads = 64;
+constexpr uint32_t kRadianceFlat = 1u << 0, kRadianceAccumulate = 1u << 1, kRadianceHosek = 1u << 2;     // MIRT_RADIANCE_* (include/mirt.h)
+static_assert(kRadianceFlat == MIRT_RADIANCE_FLAT && kRadianceAccumulate == MIRT_RADIANCE_ACCUMULATE && kRadianceHosek == MIRT_RADIANCE_SKY_HOSEK,
+              "RenderArgs.flags of a radiance launch are the caller's MIRT_RADIANCE_* bits");
+
+template <bool HOSEK, bool BVH>
+__global__ __launch_bounds__(kRadianceThreads, 5) void radiance_rays_kernel(RenderArgs A, const trace_u4* rays, trace_u4* out)
+{
+    constexpr uint32_t SRC = BVH ? kSrcBvh : kSrcHbmFlat;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const SceneLds S = stage_scene<true, false>(A, smem, HOSEK);
+    const GridLds G{};
+    uint32_t* bvh_stack = nullptr;
+    if constexpr (BVH)
+        bvh_stack = reinterpret_cast<uint32_t*>(smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, HOSEK, false)) + (threadIdx.x >> 6) * (kBvhStackBytesPerWave / 4u);      // (one wave per block today: + 0)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t i = (uint64_t)blockIdx.x * kRadianceThreads + threadIdx.x;
+    const bool alive = i < A.n_units;
+    trace_u4 r0 = { 0u, 0u, 0u, 0u }, r1 = { 0u, 0u, 0u, 0u };
+    if (alive) { r0 = rays[2u * i]; r1 = rays[2u * i + 1u]; }          // {origin, stream} {direction, _pad}
+    const f3 ro = mk(from_bits(r0.x), from_bits(r0.y), from_bits(r0.z));
+    const f3 rd = mk(from_bits(r1.x), from_bits(r1.y), from_bits(r1.z));
+    const uint32_t stream = r0.w;
+
+    Work<false> work;
+    work.clear();
+    unsigned long long acc_r = 0, acc_g = 0, acc_b = 0;
+    for (uint32_t s = 0; s < A.spp; ++s) {
+        Rng rng;
+        // generate_primary's seed with `stream` for the pixel index, then the two jitter and the two lens draws of a primary ray
+        rng.state = jenkins_hash((stream ^ jenkins_hash(A.sample_begin + s + 1u)) ^ A.seed_mix);
+        rng.skip(); rng.skip(); rng.skip(); rng.skip();
+        const f3 c = path_radiance<false, HOSEK, false, SRC>(A, S, G, alive, rng, ro, rd, work, lane, nullptr, kNoCand, bvh_stack);
+        acc_r += to_fixed(c.x);
+        acc_g += to_fixed(c.y);
+        acc_b += to_fixed(c.z);
+    }
+    if (alive) {
+        uint32_t samples = A.spp;
+        if (A.flags & kRadianceAccumulate) {
+            const trace_u4 o0 = out[2u * i], o1 = out[2u * i + 1u];
+            acc_r += (unsigned long long)o0.x | ((unsigned long long)o0.y << 32);
+            acc_g += (unsigned long long)o0.z | ((unsigned long long)o0.w << 32);
+            acc_b += (unsigned long long)o1.x | ((unsigned long long)o1.y << 32);
+            samples += o1.z;
+        }
+        out[2u * i] = trace_u4{ (uint32_t)acc_r, (uint32_t)(acc_r >> 32), (uint32_t)acc_g, (uint32_t)(acc_g >> 32) };
+        out[2u * i + 1u] = trace_u4{ (uint32_t)acc_b, (uint32_t)(acc_b >> 32), samples, 0u };
+    }
+}
+
+// one thread per ray (a.n_units of them), one wave per block; a.lds_bytes = stage_scene's image without the tables + the wave's traversal stacks (BVH build)
+hipError_t launch_radiance(const RenderArgs& a, const void* d_rays, void* d_out, bool hosek, bool bvh, hipStream_t stream)
+{
+    const uint32_t blocks = (uint32_t)(((uint64_t)a.n_units + kRadianceThreads - 1u) / kRadianceThreads);
+    auto k = hosek ? (bvh ? radiance_rays_kernel<true, true> : radiance_rays_kernel<true, false>)
+                   : (bvh ? radiance_rays_kernel<false, true> : radiance_rays_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(kRadianceThreads), a.lds_bytes, stream, a, static_cast<const trace_u4*>(d_rays), static_cast<trace_u4*>(d_out));
+    return hipGetLastError();
+}

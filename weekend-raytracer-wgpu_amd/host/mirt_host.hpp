@@ -105,6 +105,14 @@ inline MirtRay camera_pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32
     check(mirt_camera_pixel_ray(&cam, width, height, x, y, &r));
     return r;
 }
+// mirt_ctx_trace_radiance: params.spp samples of the path tracer for every ray (the renderer's samples from the primary ray on; `stream`
+// of a ray takes the place of a pixel's index) -> one record of exact sums per ray; params.flags = MIRT_RADIANCE_* (the records start at zero, so _ACCUMULATE changes nothing here).  Blocking.
+inline std::vector<MirtRadiance> trace_radiance(MirtContext* ctx, const std::vector<MirtRadianceRay>& rays, const MirtRadianceParams& params)
+{
+    std::vector<MirtRadiance> out(rays.size());
+    check(mirt_ctx_trace_radiance(ctx, rays.data(), (uint32_t)rays.size(), &params, out.data()));
+    return out;
+}
 // the pinhole ray through the centre of pixel (x, y), row 0 on top: cameraMakeRay with a zero lens
 inline MirtRay pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float t_max = 1000.0f)
 {
