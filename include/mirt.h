@@ -463,6 +463,8 @@ int      mirt_ctx_set_spheres_device(MirtContext* ctx, const void* d_spheres, ui
  *   MIRT_RAYS_ANY_HIT   occlusion query: a ray stops at the first sphere it finds with f < t_max and writes sphere = 0 ("something is
  *                       hit") or MIRT_RAY_MISS, every other field 0; hit or miss is exactly that of the nearest-hit query.  Valid with _FLAT;
  *   MIRT_RAYS_COUNT     the counting build: fills the counters of MirtRayStats (otherwise 0).  Same results.
+ *   MIRT_RAYS_SORT      the batch is traced in an order the library derives on the device (trace_rays_sorted_kernel<...>; "sorted ray
+ *                       batches" below).  Same bytes in the same places.  Valid with every other flag.  Bit 3 is not assigned.
  *   any other bit: MIRT_ERR_BAD_MODE.
  * MIRT_ERR_NULL_POINTER: ctx is null, or rays / hits is with n_rays > 0;  MIRT_ERR_NO_SCENE: no scene, or not a MIRT_SCENE_HBM one (the LDS
  * layouts keep no record table and no tree to query);  n_rays == 0: MIRT_OK without device work.
@@ -476,7 +478,7 @@ int      mirt_ctx_set_spheres_device(MirtContext* ctx, const void* d_spheres, ui
 typedef struct MirtRay    { float origin[3]; float t_max; float direction[3]; float _pad; } MirtRay;      /* 32 B */
 typedef struct MirtRayHit { float t; uint32_t sphere; float point[3]; float normal[3]; }   MirtRayHit;    /* 32 B */
 #define MIRT_RAY_MISS 0xffffffffu
-enum { MIRT_RAYS_FLAT = 1u << 0, MIRT_RAYS_ANY_HIT = 1u << 1, MIRT_RAYS_COUNT = 1u << 2 };
+enum { MIRT_RAYS_FLAT = 1u << 0, MIRT_RAYS_ANY_HIT = 1u << 1, MIRT_RAYS_COUNT = 1u << 2, MIRT_RAYS_SORT = 1u << 4 };     /* bit 3: unassigned */
 /* Of the LAST trace call.  kernel_ms: hipEvent time of its kernel, 0 with mirt_ctx_set_timing(ctx, 0).  The counters are filled by
  * MIRT_RAYS_COUNT only: rays traced, sphere tests the lanes really performed, roots evaluated, rays with a hit, BVH nodes visited summed
  * over lanes (leaves included) and BVH loop iterations summed over waves (x 64 = lane slots) -- both 0 for the flat scan. */
@@ -551,7 +553,9 @@ int mirt_camera_pixel_ray(const MirtGpuCamera* camera, uint32_t width, uint32_t 
  *                    on n_rays.
  * flags: 0 = the BVH walk of the render kernels (radiance_rays_kernel<.., true>); MIRT_RADIANCE_FLAT = the flat scan of the resident table,
  * the comparison build as MIRT_RAYS_FLAT is; MIRT_RADIANCE_SKY_HOSEK = the scene's Hosek blob, as MIRT_FLAG_SKY_HOSEK (MIRT_ERR_SKY
- * without a blob); any other bit: MIRT_ERR_BAD_MODE.
+ * without a blob); MIRT_RADIANCE_SORT = the batch runs in an order the library derives on the device (radiance_rays_sorted_kernel<..>;
+ * "sorted ray batches" below), same bytes in the same places, valid with every other flag; bit 3 is not assigned; any other bit:
+ * MIRT_ERR_BAD_MODE.
  * MIRT_ERR_NULL_POINTER: ctx or params is null, or rays or the output is null with n_rays > 0;  MIRT_ERR_NO_SCENE: no scene, or not a
  * MIRT_SCENE_HBM one;  MIRT_ERR_SPP_ZERO, MIRT_ERR_SPP_RANGE: the rules of mirt_ctx_render;  MIRT_ERR_MATERIAL_INDEX / MIRT_ERR_TEXEL_RANGE:
  * exactly as a path-traced render call on that scene answers.  n_rays == 0 (after these checks): MIRT_OK without device work.  A refused
@@ -567,9 +571,40 @@ int mirt_camera_pixel_ray(const MirtGpuCamera* camera, uint32_t width, uint32_t 
 typedef struct MirtRadianceRay { float origin[3]; uint32_t stream; float direction[3]; uint32_t _pad; } MirtRadianceRay;   /* 32 B */
 typedef struct MirtRadiance { uint64_t sum[3]; uint32_t samples; uint32_t _pad; } MirtRadiance;   /* 32 B */
 typedef struct MirtRadianceParams { uint32_t spp, sample_begin, num_bounces, flags; uint64_t seed; } MirtRadianceParams;   /* 24 B */
-enum { MIRT_RADIANCE_FLAT = 1u << 0, MIRT_RADIANCE_ACCUMULATE = 1u << 1, MIRT_RADIANCE_SKY_HOSEK = 1u << 2 };
+enum { MIRT_RADIANCE_FLAT = 1u << 0, MIRT_RADIANCE_ACCUMULATE = 1u << 1, MIRT_RADIANCE_SKY_HOSEK = 1u << 2, MIRT_RADIANCE_SORT = 1u << 4 };   /* bit 3: unassigned */
 int mirt_ctx_trace_radiance(MirtContext* ctx, const MirtRadianceRay* rays, uint32_t n_rays, const MirtRadianceParams* params, MirtRadiance* out);
 int mirt_ctx_trace_radiance_device(MirtContext* ctx, const void* d_rays, uint32_t n_rays, const MirtRadianceParams* params, void* d_out, void* hip_stream);
+
+/* ---- sorted ray batches: MIRT_RAYS_SORT, MIRT_RADIANCE_SORT ----
+ * Lane = ray and 64 consecutive records form a wave, so a batch that is not in a coherent order (probe grids, shuffled training rays)
+ * walks the tree with waves whose lanes disagree.  With the flag the library computes a 31-bit code per ray on the device, sorts
+ * (code, caller's index) with a stable radix sort and runs slot k of the query kernel on record order[k]; the records are neither moved
+ * nor copied, every result lands at its ray's own position, and since a record depends on its ray alone the bytes are those of the call
+ * without the flag, for every float bit pattern in a ray.  Errors, the n_rays == 0 rule and "a refused call queues and writes nothing"
+ * are unchanged.  The order is ascending (code, caller's index) and depends on the rays and the resident tree's bounds alone.
+ *   the code, float32, one IEEE operation at a time, no contraction (centre, radius: those of MirtBvhInfo):
+ *     q(f, n)    = 0 if !(f > 0) (NaN included), n - 1 if f >= n, else (uint32_t)f (truncated)
+ *     origin     inv = 16.0f / radius;  c[k] = q((o[k] - (centre[k] - radius)) * inv, 32): MIRT_RAY_SORT_ORIGIN_BITS = 5 bits per axis
+ *     direction  octahedral: s = (|dx| + |dy|) + |dz|;  r = 1.0f / s;  u = dx * r;  v = dy * r;  if dz < 0, both from the old u, v:
+ *                u' = (1 - |v|) * (u >= 0 ? 1 : -1), v' = (1 - |u|) * (v >= 0 ? 1 : -1);
+ *                a = q(u * 128.0f + 128.0f, 256), b likewise from v: MIRT_RAY_SORT_DIRECTION_BITS = 8 bits per axis
+ *     code       = morton3(c) << 16 | morton2(a, b);  bits 3j + 2, 3j + 1, 3j of morton3 = bit j of c[0], c[1], c[2];  bits 2j + 1, 2j of
+ *                morton2 = bit j of a, b.  Every bit pattern has a code: an empty tree, a zero, infinite or NaN radius, a zero direction.
+ *   Origin bits come first: probes differ by origin; a camera's rays share them and are ordered by direction.
+ *   scratch      codes, order and the sort's storage belong to the context and only grow.  A call that must grow them waits for the
+ *                device first; otherwise the device forms stay free of host synchronisation (code kernel, sort and query kernel are
+ *                queued on `hip_stream`).  A failed allocation: MIRT_ERR_ALLOC, nothing queued, nothing written.  ALL sorted launches of a
+ *                context share that scratch: the caller keeps them in order among themselves (one stream, or its own events), as for
+ *                counting traces.  mirt_ctx_trace_stats().kernel_ms spans the code kernel through the query kernel.
+ *   mirt_ray_sort_code          HOST ONLY, no device, no context: the code of one 32-byte record (MirtRay and MirtRadianceRay share what
+ *                               it reads: origin at byte 0, direction at byte 16).  MIRT_ERR_NULL_POINTER for a null pointer.
+ *   mirt_ctx_trace_order_read   blocking, for tests, like mirt_ctx_bvh_read: the permutation of the LAST sorted launch on the context,
+ *                               order[k] = the caller's index of the ray that ran in slot k.  MIRT_ERR_NO_SCENE before the first sorted
+ *                               launch, MIRT_ERR_OUT_BUFFER if len < its n_rays. */
+#define MIRT_RAY_SORT_ORIGIN_BITS    5u
+#define MIRT_RAY_SORT_DIRECTION_BITS 8u
+int mirt_ray_sort_code(const float centre[3], float radius, const void* ray32, uint32_t* out_code);
+int mirt_ctx_trace_order_read(MirtContext* ctx, uint32_t* order, size_t len);
 
 /* Replace only the camera (`Layer::update_camera`, layer.rs:188-193; `Raytracer::set_render_params`,
  * mod.rs:353-388 — every interactive frame in the reference).  Host-side only: the camera travels by

@@ -280,12 +280,19 @@ pub struct MirtRadianceParams {
 pub const MIRT_RADIANCE_FLAT: u32 = 1 << 0;
 pub const MIRT_RADIANCE_ACCUMULATE: u32 = 1 << 1;
 pub const MIRT_RADIANCE_SKY_HOSEK: u32 = 1 << 2;
+/// The batch runs in an order the library derives on the device; same records.  Bit 3 is unassigned.
+pub const MIRT_RADIANCE_SORT: u32 = 1 << 4;
 
 pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
 /// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.
 pub const MIRT_RAYS_FLAT: u32 = 1 << 0;
 pub const MIRT_RAYS_ANY_HIT: u32 = 1 << 1;
 pub const MIRT_RAYS_COUNT: u32 = 1 << 2;
+/// The batch is traced in an order the library derives on the device; same hits.  Bit 3 is unassigned.
+pub const MIRT_RAYS_SORT: u32 = 1 << 4;
+/// Bits per origin axis / per octahedral direction axis of `mirt_ray_sort_code`.
+pub const MIRT_RAY_SORT_ORIGIN_BITS: u32 = 5;
+pub const MIRT_RAY_SORT_DIRECTION_BITS: u32 = 8;
 
 /// `mirt_ctx_set_scene_ex` / `mirt_node_set_scene_ex` flags: the scene's tables in device memory, nearest hit through a BVH
 /// (worlds beyond the LDS budget, up to `MIRT_SCENE_HBM_MAX_SPHERES`).
@@ -375,6 +382,8 @@ extern "C" {
     pub fn mirt_camera_pixel_ray(camera: *const MirtGpuCamera, width: u32, height: u32, x: u32, y: u32, out: *mut MirtRay) -> c_int;
     pub fn mirt_ctx_trace_radiance(ctx: *mut MirtContext, rays: *const MirtRadianceRay, n_rays: u32, params: *const MirtRadianceParams, out: *mut MirtRadiance) -> c_int;
     pub fn mirt_ctx_trace_radiance_device(ctx: *mut MirtContext, d_rays: *const c_void, n_rays: u32, params: *const MirtRadianceParams, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ray_sort_code(centre: *const f32, radius: f32, ray32: *const c_void, out_code: *mut u32) -> c_int;
+    pub fn mirt_ctx_trace_order_read(ctx: *mut MirtContext, order: *mut u32, len: usize) -> c_int;
     pub fn mirt_ctx_set_camera(ctx: *mut MirtContext, camera: *const MirtGpuCamera) -> c_int;
     pub fn mirt_ctx_render(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_ctx_render_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;

@@ -35,6 +35,7 @@ MIRT_BVH_BIG_RADII = 4
 MIRT_RAYS_FLAT = 1 << 0
 MIRT_RAYS_ANY_HIT = 1 << 1
 MIRT_RAYS_COUNT = 1 << 2
+MIRT_RAYS_SORT = 1 << 4                 # bit 3 is unassigned
 MIRT_RAY_MISS = 0xFFFFFFFF
 
 # mirt_ctx_render_features* flags
@@ -44,6 +45,10 @@ MIRT_FEATURES_FLAT = 1 << 0
 MIRT_RADIANCE_FLAT = 1 << 0
 MIRT_RADIANCE_ACCUMULATE = 1 << 1
 MIRT_RADIANCE_SKY_HOSEK = 1 << 2
+MIRT_RADIANCE_SORT = 1 << 4             # bit 3 is unassigned
+# the sort code of MIRT_RAYS_SORT / MIRT_RADIANCE_SORT: bits per origin axis / per octahedral direction axis
+MIRT_RAY_SORT_ORIGIN_BITS = 5
+MIRT_RAY_SORT_DIRECTION_BITS = 8
 
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
@@ -257,6 +262,8 @@ SYMBOLS = {
     "mirt_camera_pixel_ray": (C.c_int, [_P(MirtGpuCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(MirtRay)]),
     "mirt_ctx_trace_radiance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, _P(MirtRadianceParams), C.c_void_p]),
     "mirt_ctx_trace_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, _P(MirtRadianceParams), C.c_void_p, C.c_void_p]),
+    "mirt_ray_sort_code": (C.c_int, [_P(C.c_float), C.c_float, C.c_void_p, _P(C.c_uint32)]),
+    "mirt_ctx_trace_order_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mirt_ctx_set_camera": (C.c_int, [C.c_void_p, _P(MirtGpuCamera)]),
     "mirt_ctx_render": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
     "mirt_ctx_render_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -130,7 +130,7 @@ def sphere_records(spheres) -> tuple:
 # MirtRay / MirtRayHit as numpy records (32 bytes each): what trace_rays takes and returns
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("direction", "<f4", (3,)), ("_pad", "<f4")])
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("sphere", "<u4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,))])
-RAYS_FLAGS = _abi.MIRT_RAYS_FLAT | _abi.MIRT_RAYS_ANY_HIT | _abi.MIRT_RAYS_COUNT
+RAYS_FLAGS = _abi.MIRT_RAYS_FLAT | _abi.MIRT_RAYS_ANY_HIT | _abi.MIRT_RAYS_COUNT | _abi.MIRT_RAYS_SORT
 
 
 def make_rays(origins, directions, t_max=1000.0) -> np.ndarray:
@@ -156,10 +156,34 @@ def ray_records(rays) -> np.ndarray:
     raise ValueError(f"rays must be a one-dimensional RAY_DTYPE array or float32 [n, 8], not {rays.dtype} of shape {rays.shape}")
 
 
-def _check_rays_flags(flags) -> int:
+def _check_rays_flags(flags, sort=False) -> int:
     if not isinstance(flags, (int, np.integer)) or isinstance(flags, bool) or int(flags) & ~RAYS_FLAGS or int(flags) < 0:
-        raise ValueError(f"flags must be a combination of MIRT_RAYS_FLAT, MIRT_RAYS_ANY_HIT and MIRT_RAYS_COUNT, not {flags!r}")
-    return int(flags)
+        raise ValueError(f"flags must be a combination of MIRT_RAYS_FLAT, MIRT_RAYS_ANY_HIT, MIRT_RAYS_COUNT and MIRT_RAYS_SORT, not {flags!r}")
+    if not isinstance(sort, (bool, np.bool_)):
+        raise ValueError(f"sort must be a bool, not {sort!r}")
+    return int(flags) | (_abi.MIRT_RAYS_SORT if sort else 0)
+
+
+def ray_sort_codes(centre, radius, rays) -> np.ndarray:
+    """mirt_ray_sort_code for every record of `rays` (a RAY_DTYPE or RADIANCE_RAY_DTYPE array: both keep the origin at byte 0 and the
+    direction at byte 16) -> uint32 [n], the 31-bit codes a sorted launch orders by; centre, radius: those of Context.bvh_info().
+    Needs no device."""
+    if not isinstance(rays, np.ndarray) or rays.dtype not in (RAY_DTYPE, RADIANCE_RAY_DTYPE) or rays.ndim != 1:
+        raise ValueError("rays must be a one-dimensional RAY_DTYPE or RADIANCE_RAY_DTYPE array")
+    cen = np.asarray(centre, np.float32)
+    if cen.shape != (3,):
+        raise ValueError(f"centre must hold three floats, not shape {cen.shape}")
+    if not isinstance(radius, (int, float, np.integer, np.floating)) or isinstance(radius, bool):
+        raise ValueError(f"radius must be a number, not {radius!r}")
+    recs = np.ascontiguousarray(rays)
+    cen = np.ascontiguousarray(cen)
+    codes = np.zeros(len(recs), np.uint32)
+    f, code = lib().mirt_ray_sort_code, C.c_uint32()
+    c_cen, c_rad = cen.ctypes.data_as(C.POINTER(C.c_float)), C.c_float(float(np.float32(radius)))
+    for i in range(len(recs)):
+        check(f(c_cen, c_rad, C.c_void_p(recs.ctypes.data + 32 * i), C.byref(code)))
+        codes[i] = code.value
+    return codes
 
 
 def _check_address(name, v) -> int:
@@ -223,16 +247,17 @@ def radiance_ray_records(rays) -> np.ndarray:
     raise ValueError(f"rays must be a one-dimensional RADIANCE_RAY_DTYPE array or uint32 [n, 8], not {rays.dtype} of shape {rays.shape}")
 
 
-def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate) -> _abi.MirtRadianceParams:
+def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort=False) -> _abi.MirtRadianceParams:
     for name, v in (("spp", spp), ("sample_begin", sample_begin), ("num_bounces", num_bounces)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
             raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
     if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= int(seed) < 1 << 64:
         raise ValueError(f"seed must be an integer in [0, 2^64), not {seed!r}")
-    for name, v in (("flat", flat), ("hosek", hosek), ("accumulate", accumulate)):
+    for name, v in (("flat", flat), ("hosek", hosek), ("accumulate", accumulate), ("sort", sort)):
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError(f"{name} must be a bool, not {v!r}")
-    flags = (_abi.MIRT_RADIANCE_FLAT if flat else 0) | (_abi.MIRT_RADIANCE_SKY_HOSEK if hosek else 0) | (_abi.MIRT_RADIANCE_ACCUMULATE if accumulate else 0)
+    flags = (_abi.MIRT_RADIANCE_FLAT if flat else 0) | (_abi.MIRT_RADIANCE_SKY_HOSEK if hosek else 0) | (_abi.MIRT_RADIANCE_ACCUMULATE if accumulate else 0) \
+        | (_abi.MIRT_RADIANCE_SORT if sort else 0)
     return _abi.MirtRadianceParams(int(spp), int(sample_begin), int(num_bounces), flags, int(seed))
 
 
@@ -363,26 +388,30 @@ class Context:
         check(lib().mirt_ctx_set_spheres_device(self._h, C.c_void_p(int(d_ptr)) if int(count) else None, int(count)))
 
     # ---- ray queries against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
-    def trace_rays(self, rays, flags: int = 0) -> np.ndarray:
+    def trace_rays(self, rays, flags: int = 0, sort: bool = False) -> np.ndarray:
         """mirt_ctx_trace_rays: the flat scan's answer for every ray, by the renderer's own arithmetic -> a RAY_HIT_DTYPE array, one
         record per ray in the caller's order; `sphere` == MIRT_RAY_MISS (and everything else 0) for a miss.  `rays`: see ray_records
-        (make_rays builds them); flags: MIRT_RAYS_FLAT / _ANY_HIT / _COUNT.  Needs a scene set with hbm=True.  Blocking."""
+        (make_rays builds them); flags: MIRT_RAYS_FLAT / _ANY_HIT / _COUNT / _SORT; sort=True sets MIRT_RAYS_SORT: the batch is traced
+        in an order derived on the device, the records are the same.  Needs a scene set with hbm=True.  Blocking."""
         recs = ray_records(rays)
-        flags = _check_rays_flags(flags)
+        flags = _check_rays_flags(flags, sort)
         hits = np.zeros(len(recs), RAY_HIT_DTYPE)
         check(lib().mirt_ctx_trace_rays(self._h, C.c_void_p(recs.ctypes.data) if len(recs) else None, len(recs), flags,
                                         C.c_void_p(hits.ctypes.data) if len(recs) else None))
+        self._note_sorted(flags & _abi.MIRT_RAYS_SORT, len(recs))
         return hits
 
-    def trace_rays_device(self, d_rays: int, n: int, d_hits: int, flags: int = 0, stream: Optional[int] = None) -> None:
+    def trace_rays_device(self, d_rays: int, n: int, d_hits: int, flags: int = 0, stream: Optional[int] = None, sort: bool = False) -> None:
         """mirt_ctx_trace_rays_device: `n` 32-byte MirtRay records at device address `d_rays` -> `n` MirtRayHit records at `d_hits`
-        (e.g. torch tensors' data_ptr()), asynchronously on `stream` (see _stream_arg); no host synchronisation."""
+        (e.g. torch tensors' data_ptr()), asynchronously on `stream` (see _stream_arg); no host synchronisation (sort=True: unless the
+        context's sort scratch must grow; sorted launches of one context are kept in order by the caller)."""
         _check_range(0, n)
-        flags = _check_rays_flags(flags)
+        flags = _check_rays_flags(flags, sort)
         if int(n):
             d_rays, d_hits = _check_address("d_rays", d_rays), _check_address("d_hits", d_hits)
         check(lib().mirt_ctx_trace_rays_device(self._h, C.c_void_p(d_rays) if int(n) else None, int(n), flags,
                                                C.c_void_p(d_hits) if int(n) else None, _stream_arg(stream)))
+        self._note_sorted(flags & _abi.MIRT_RAYS_SORT, int(n))
 
     def trace_stats(self) -> dict:
         """mirt_ctx_trace_stats: waits for the last trace call -> {"kernel_ms", "rays", "sphere_tests", "roots", "hits", "nodes",
@@ -391,17 +420,31 @@ class Context:
         check(lib().mirt_ctx_trace_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def _note_sorted(self, sort, n: int) -> None:
+        if sort and n:       # the length trace_order reads: that of the last sorted launch the library accepted
+            self._sorted_n = n
+
+    def trace_order(self) -> np.ndarray:
+        """mirt_ctx_trace_order_read: the permutation of the last sorted launch (trace_rays / trace_radiance with sort=True) on this
+        context -> uint32 [n_rays]; order[k] = the caller's index of the ray that ran in slot k, ascending (ray_sort_codes, index).
+        Blocking; MirtError before the first sorted launch."""
+        order = np.zeros(max(getattr(self, "_sorted_n", 0), 1), np.uint32)
+        check(lib().mirt_ctx_trace_order_read(self._h, C.c_void_p(order.ctypes.data), order.size))
+        return order[:getattr(self, "_sorted_n", 0)]
+
     # ---- path-traced radiance for a caller's rays against the resident MIRT_SCENE_HBM scene (include/mirt.h; DESIGN.md 10.9) ----
     def trace_radiance(self, rays, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0, flat: bool = False,
-                       hosek: bool = False, into: Optional[np.ndarray] = None) -> np.ndarray:
+                       hosek: bool = False, into: Optional[np.ndarray] = None, sort: bool = False) -> np.ndarray:
         """mirt_ctx_trace_radiance: `spp` samples of the path tracer for every ray -> a RADIANCE_DTYPE array {"sum" [3] in 2^-20 units,
         "samples"}, one record per ray in the caller's order (radiance_mean gives the means).  A sample is the renderer's from its
         primary ray on: samples sample_begin .. sample_begin + spp - 1 of the RNG stream a pixel of index `stream` has under `seed`.
         `rays`: see radiance_ray_records (make_radiance_rays builds them).  flat=True: the flat scan instead of the tree; hosek=True:
         the scene's Hosek sky.  into: a RADIANCE_DTYPE array [n] to ADD to (MIRT_RADIANCE_ACCUMULATE), changed in place and
-        returned -- a progressive probe passes sample_begin = the samples it holds.  Needs a scene set with hbm=True.  Blocking."""
+        returned -- a progressive probe passes sample_begin = the samples it holds.  sort=True (MIRT_RADIANCE_SORT): the batch runs in
+        an order derived on the device, for batches that are not in a coherent order; the records are the same.  Needs a scene set
+        with hbm=True.  Blocking."""
         recs = radiance_ray_records(rays)
-        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, into is not None)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, into is not None, sort)
         if into is None:
             out = np.zeros(len(recs), RADIANCE_DTYPE)
         else:
@@ -410,19 +453,23 @@ class Context:
             out = into
         check(lib().mirt_ctx_trace_radiance(self._h, C.c_void_p(recs.ctypes.data) if len(recs) else None, len(recs), C.byref(params),
                                             C.c_void_p(out.ctypes.data) if len(recs) else None))
+        self._note_sorted(sort, len(recs))
         return out
 
     def trace_radiance_device(self, d_rays: int, n: int, d_out: int, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0,
-                              flat: bool = False, hosek: bool = False, accumulate: bool = False, stream: Optional[int] = None) -> None:
+                              flat: bool = False, hosek: bool = False, accumulate: bool = False, stream: Optional[int] = None,
+                              sort: bool = False) -> None:
         """mirt_ctx_trace_radiance_device: `n` 32-byte MirtRadianceRay records at device address `d_rays` -> `n` MirtRadiance records at
         `d_out` (e.g. torch tensors' data_ptr()), one kernel queued on `stream` (see _stream_arg); no host synchronisation.
-        accumulate=True adds to the records already at `d_out`."""
+        accumulate=True adds to the records already at `d_out`.  sort=True: the code kernel and the sort are queued in front of it (sorted
+        launches of one context are kept in order by the caller)."""
         _check_range(0, n)
-        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort)
         if int(n):
             d_rays, d_out = _check_address("d_rays", d_rays), _check_address("d_out", d_out)
         check(lib().mirt_ctx_trace_radiance_device(self._h, C.c_void_p(d_rays) if int(n) else None, int(n), C.byref(params),
                                                    C.c_void_p(d_out) if int(n) else None, _stream_arg(stream)))
+        self._note_sorted(sort, int(n))
 
     # ---- first-hit feature frames of the resident MIRT_SCENE_HBM scene (include/mirt.h; DESIGN.md 10.8) ----
     def render_features(self, params: _abi.MirtParams, flat: bool = False) -> np.ndarray:

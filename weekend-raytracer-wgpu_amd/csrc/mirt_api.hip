@@ -499,6 +499,11 @@ struct MirtContext {
     unsigned char*      d_trace_hits = nullptr;
     size_t              cap_trace_rays = 0, cap_trace_hits = 0;
     MirtRayStats        trace_stats{};
+    // MIRT_RAYS_SORT / MIRT_RADIANCE_SORT: codes, order and the sort's storage; grows, never shrinks; shared by all sorted launches
+    mirt::BvhDeviceScratch ray_sort;
+    size_t              ray_sort_off_order = 0;    // of the last sorted launch: its permutation in ray_sort.d, [ray_sort_n] uint32
+    uint32_t            ray_sort_n = 0;
+    bool                ray_sort_any = false;      // a sorted launch has been queued on this context
 };
 
 extern "C" {
@@ -707,7 +712,7 @@ void mirt_ctx_destroy(MirtContext* c)
     if (c->frame_stream_b) (void)hipStreamSynchronize(c->frame_stream_b);
     if (!c->untimed_streams.empty()) (void)hipDeviceSynchronize();      // launches without an event may still read the tables freed below
     if (c->trace_pending) (void)hipEventSynchronize(c->ev_trace_end);    // a trace on a caller stream reads them too
-    (void)hipFree(c->d_trace_counters); (void)hipFree(c->d_trace_rays); (void)hipFree(c->d_trace_hits);
+    (void)hipFree(c->d_trace_counters); (void)hipFree(c->d_trace_rays); (void)hipFree(c->d_trace_hits); (void)hipFree(c->ray_sort.d);
     if (c->ev_trace_begin) (void)hipEventDestroy(c->ev_trace_begin);
     if (c->ev_trace_end) (void)hipEventDestroy(c->ev_trace_end);
     (void)hipFree(c->d_spheres); (void)hipFree(c->d_mats); (void)hipFree(c->d_pmats); (void)hipFree(c->d_grid); (void)hipFree(c->d_shade); (void)hipFree(c->d_bvh); (void)hipFree(c->bvh_scratch.d); (void)hipFree(c->bvh_stage.d); (void)hipFree(c->d_texels);
@@ -1732,17 +1737,32 @@ static int check_trace(const MirtContext* c, const void* rays, uint32_t n, uint3
 {
     *go = false;
     if (!c) return fail(MIRT_ERR_NULL_POINTER, "ctx is null");
-    if (flags & ~(uint32_t)(MIRT_RAYS_FLAT | MIRT_RAYS_ANY_HIT | MIRT_RAYS_COUNT)) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RAYS_* bits 0x%x", flags);
+    if (flags & ~(uint32_t)(MIRT_RAYS_FLAT | MIRT_RAYS_ANY_HIT | MIRT_RAYS_COUNT | MIRT_RAYS_SORT)) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RAYS_* bits 0x%x", flags);
     if (n && (!rays || !hits)) return fail(MIRT_ERR_NULL_POINTER, "rays/hits is null");
     if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
     *go = n != 0u;
     return MIRT_OK;
 }
 
-// Queue trace_rays_kernel<bvh, any, count> for n > 0 rays in device memory on `st`.  No host synchronisation.
+// MIRT_RAYS_SORT / MIRT_RADIANCE_SORT: queue the codes of n > 0 rays and their sort on `st` (after the caller has recorded the begin event, so
+// that kernel_ms spans them); *d_order = the permutation for the query kernel that follows on the same stream.  No host synchronisation
+// unless the context's scratch must grow.  The bounds are the resident tree's, those of mirt_ctx_bvh_info.
+static int queue_ray_sort(MirtContext* c, const void* d_rays, uint32_t n, hipStream_t st, const uint32_t** d_order)
+{
+    const int rc = mirt::ray_sort_order(d_rays, n, c->bvh_centre, c->bvh_radius, st, &c->ray_sort, &c->ray_sort_off_order);
+    if (rc != MIRT_OK) return rc;
+    c->ray_sort_n = n;
+    c->ray_sort_any = true;
+    *d_order = reinterpret_cast<const uint32_t*>(c->ray_sort.d + c->ray_sort_off_order);
+    return MIRT_OK;
+}
+
+// Queue trace_rays_kernel<bvh, any, count> (trace_rays_sorted_kernel behind the code kernel and the sort with MIRT_RAYS_SORT) for n > 0 rays in
+// device memory on `st`.  No host synchronisation.
 static int launch_trace(MirtContext* c, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, hipStream_t st)
 {
     const bool bvh = !(flags & MIRT_RAYS_FLAT), any = (flags & MIRT_RAYS_ANY_HIT) != 0, count = (flags & MIRT_RAYS_COUNT) != 0;
+    const bool sort = (flags & MIRT_RAYS_SORT) != 0;
     mirt::RenderArgs a{};
     a.spheres = c->d_spheres;
     a.n_spheres = c->n_spheres;
@@ -1752,12 +1772,19 @@ static int launch_trace(MirtContext* c, const void* d_rays, uint32_t n, uint32_t
     const uint32_t entries = bvh ? (c->bvh_plan.max_depth ? c->bvh_plan.max_depth : 1u) : 0u;
     fill_bvh_args(c, &a, entries);
     a.lds_bytes = (mirt::kBlockThreads / 64u) * 64u * 4u * entries;
-    if (count) HIP_TRY(hipMemsetAsync(c->d_trace_counters, 0, sizeof(unsigned long long) * mirt::kNumCounters, st));
     const bool timed = c->timing;
-    if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
-    HIP_TRY(kx::launch_trace_rays(a, d_rays, d_hits, n, bvh, any, count, st));
+    const uint32_t* d_order = nullptr;
+    if (sort) {           // first: a failed allocation leaves nothing queued
+        if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+        const int rc = queue_ray_sort(c, d_rays, n, st, &d_order);
+        if (rc != MIRT_OK) return rc;
+    }
+    if (count) HIP_TRY(hipMemsetAsync(c->d_trace_counters, 0, sizeof(unsigned long long) * mirt::kNumCounters, st));
+    if (timed && !sort) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    if (sort) HIP_TRY(kx::launch_trace_rays_sorted(a, d_rays, d_hits, n, d_order, bvh, any, count, st));
+    else HIP_TRY(kx::launch_trace_rays(a, d_rays, d_hits, n, bvh, any, count, st));
     const char* tf[2] = { "false", "true" };
-    snprintf(c->last_kernel, sizeof c->last_kernel, "trace_rays_kernel<%s,%s,%s>", tf[bvh], tf[any], tf[count]);
+    snprintf(c->last_kernel, sizeof c->last_kernel, "trace_rays%s_kernel<%s,%s,%s>", sort ? "_sorted" : "", tf[bvh], tf[any], tf[count]);
     HIP_TRY(hipEventRecord(c->ev_trace_end, st));
     c->trace_pending = true;
     c->trace_timed = timed;
@@ -1789,6 +1816,25 @@ int mirt_ctx_trace_rays(MirtContext* c, const MirtRay* rays, uint32_t n_rays, ui
     if ((rc = launch_trace(c, c->d_trace_rays, n_rays, flags, c->d_trace_hits, c->stream)) != MIRT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(hits, c->d_trace_hits, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_ray_sort_code(const float centre[3], float radius, const void* ray32, uint32_t* out_code)
+{
+    if (!centre || !ray32 || !out_code) return fail(MIRT_ERR_NULL_POINTER, "centre/ray/out_code is null");
+    *out_code = mirt::ray_sort_code(centre, radius, ray32);
+    return MIRT_OK;
+}
+
+int mirt_ctx_trace_order_read(MirtContext* c, uint32_t* order, size_t len)
+{
+    if (!c) return fail(MIRT_ERR_NULL_POINTER, "ctx is null");
+    if (!c->ray_sort_any) return fail(MIRT_ERR_NO_SCENE, "no sorted launch has run on this context");
+    if (len < c->ray_sort_n) return fail(MIRT_ERR_OUT_BUFFER, "the order holds %u indices, room for %zu", c->ray_sort_n, len);
+    if (!order) return fail(MIRT_ERR_NULL_POINTER, "order is null");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());      // the sort may be in flight on a caller's stream
+    HIP_TRY(hipMemcpy(order, c->ray_sort.d + c->ray_sort_off_order, sizeof(uint32_t) * (size_t)c->ray_sort_n, hipMemcpyDeviceToHost));
     return MIRT_OK;
 }
 
@@ -1921,7 +1967,7 @@ static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, co
     *go = false;
     if (!c || !p) return fail(MIRT_ERR_NULL_POINTER, "ctx/params is null");
     if (n && (!rays || !out)) return fail(MIRT_ERR_NULL_POINTER, "rays/out is null");
-    if (p->flags & ~(uint32_t)(MIRT_RADIANCE_FLAT | MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_SKY_HOSEK))
+    if (p->flags & ~(uint32_t)(MIRT_RADIANCE_FLAT | MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_SKY_HOSEK | MIRT_RADIANCE_SORT))
         return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RADIANCE_* bits 0x%x", p->flags);
     if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
     if (p->spp == 0) return fail(MIRT_ERR_SPP_ZERO, "spp is zero");
@@ -1934,11 +1980,12 @@ static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, co
     return MIRT_OK;
 }
 
-// Queue radiance_rays_kernel<hosek, bvh> for n > 0 rays in device memory on `st`.  No host synchronisation.  The launch ring, MirtStats and
+// Queue radiance_rays_kernel<hosek, bvh> (radiance_rays_sorted_kernel behind the code kernel and the sort with MIRT_RADIANCE_SORT) for n > 0 rays in
+// device memory on `st`.  No host synchronisation.  The launch ring, MirtStats and
 // the accumulation stay as they are; the event pair and the pending flag are the ray queries' (mirt_ctx_trace_stats folds the time).
 static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const MirtRadianceParams* p, void* d_out, hipStream_t st)
 {
-    const bool bvh = !(p->flags & MIRT_RADIANCE_FLAT), hosek = (p->flags & MIRT_RADIANCE_SKY_HOSEK) != 0;
+    const bool bvh = !(p->flags & MIRT_RADIANCE_FLAT), hosek = (p->flags & MIRT_RADIANCE_SKY_HOSEK) != 0, sort = (p->flags & MIRT_RADIANCE_SORT) != 0;
     mirt::RenderArgs a{};                                 // (the camera stays zero: a query has none)
     a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
     a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
@@ -1951,9 +1998,16 @@ static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const
     a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
-    HIP_TRY(kx::launch_radiance(a, d_rays, d_out, hosek, bvh, st));
+    if (sort) {
+        const uint32_t* d_order = nullptr;
+        const int rc = queue_ray_sort(c, d_rays, n, st, &d_order);
+        if (rc != MIRT_OK) return rc;
+        HIP_TRY(kx::launch_radiance_sorted(a, d_rays, d_out, d_order, hosek, bvh, st));
+    } else {
+        HIP_TRY(kx::launch_radiance(a, d_rays, d_out, hosek, bvh, st));
+    }
     const char* tf[2] = { "false", "true" };
-    snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays_kernel<%s,%s>", tf[hosek], tf[bvh]);
+    snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays%s_kernel<%s,%s>", sort ? "_sorted" : "", tf[hosek], tf[bvh]);
     HIP_TRY(hipEventRecord(c->ev_trace_end, st));
     c->trace_pending = true;
     c->trace_timed = timed;

@@ -128,4 +128,14 @@ int census_spheres_device(const void* d_wire, uint32_t n, const void* d_mats, ui
 int prepare_spheres_device(const void* d_wire, uint32_t n, const void* d_mats, uint32_t n_mats, const uint32_t routine_queue[5], void* d_prepared,
                            void* hip_stream, float* ms);
 
+// ---- the schedule of a sorted ray batch (mirt_bvh_device.hip): MIRT_RAYS_SORT, MIRT_RADIANCE_SORT ----
+// mirt_ray_sort_code of include/mirt.h for one 32-byte record (origin at byte 0, direction at byte 16).  Host only.
+uint32_t ray_sort_code(const float centre[3], float radius, const void* ray32);
+
+// Queues, on the stream, the codes of [n] 32-byte ray records in device memory (4-byte aligned) and their stable sort: afterwards
+// scratch->d + *off_order holds [n] uint32, the caller's index of the ray in every slot, ascending (code, index).  No host
+// synchronisation unless the scratch must grow: then the device is waited for first (launches in flight may read the old one).
+// MIRT_OK, MIRT_ERR_ALLOC (nothing queued) or MIRT_ERR_HIP.
+int ray_sort_order(const void* d_rays, uint32_t n, const float centre[3], float radius, void* hip_stream, BvhDeviceScratch* scratch, size_t* off_order);
+
 }  // namespace mirt

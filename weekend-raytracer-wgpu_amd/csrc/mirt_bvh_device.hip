@@ -928,3 +928,106 @@ int mirt::prepare_spheres_device(const void* d_wire, uint32_t n, const void* d_m
     }
     return MIRT_OK;
 }
+
+// ---- the schedule of a sorted ray batch (MIRT_RAYS_SORT, MIRT_RADIANCE_SORT; include/mirt.h) ----
+namespace {
+
+typedef uint32_t trace_u4 __attribute__((ext_vector_type(4), aligned(4)));      // mirt_trace_kernel.inc: a caller's records are 4-byte aligned
+
+// q(f, n) of the header: 0 for anything that is not above 0 (NaN included), n - 1 from n on, truncation between
+__host__ __device__ inline uint32_t sort_q(float f, uint32_t n)
+{
+    if (!(f > 0.0f)) return 0u;
+    if (f >= (float)n) return n - 1u;
+    return (uint32_t)f;
+}
+
+// The 31-bit code of the header, one IEEE operation per line of its text (this file is compiled with -ffp-contract=off and correctly
+// rounded division on both sides, so the host and the device agree bit for bit).  lo[k] = centre[k] - radius, inv = 16.0f / radius.
+__host__ __device__ inline uint32_t ray_code(const float o[3], const float d[3], const float lo[3], float inv)
+{
+    uint32_t c[3];
+    for (int k = 0; k < 3; ++k) c[k] = sort_q((o[k] - lo[k]) * inv, 1u << MIRT_RAY_SORT_ORIGIN_BITS);
+    const float s = (__builtin_fabsf(d[0]) + __builtin_fabsf(d[1])) + __builtin_fabsf(d[2]);
+    const float r = 1.0f / s;
+    float u = d[0] * r, v = d[1] * r;
+    if (d[2] < 0.0f) {
+        const float fu = (1.0f - __builtin_fabsf(v)) * (u >= 0.0f ? 1.0f : -1.0f);
+        const float fv = (1.0f - __builtin_fabsf(u)) * (v >= 0.0f ? 1.0f : -1.0f);
+        u = fu;
+        v = fv;
+    }
+    const float half = (float)(1u << (MIRT_RAY_SORT_DIRECTION_BITS - 1u));
+    const uint32_t a = sort_q(u * half + half, 1u << MIRT_RAY_SORT_DIRECTION_BITS);
+    const uint32_t b = sort_q(v * half + half, 1u << MIRT_RAY_SORT_DIRECTION_BITS);
+    uint32_t m3 = 0u, m2 = 0u;
+    for (uint32_t j = 0; j < MIRT_RAY_SORT_ORIGIN_BITS; ++j)
+        m3 |= (((c[0] >> j) & 1u) << (3u * j + 2u)) | (((c[1] >> j) & 1u) << (3u * j + 1u)) | (((c[2] >> j) & 1u) << (3u * j));
+    for (uint32_t j = 0; j < MIRT_RAY_SORT_DIRECTION_BITS; ++j)
+        m2 |= (((a >> j) & 1u) << (2u * j + 1u)) | (((b >> j) & 1u) << (2u * j));
+    return (m3 << (2u * MIRT_RAY_SORT_DIRECTION_BITS)) | m2;
+}
+static_assert(3u * MIRT_RAY_SORT_ORIGIN_BITS + 2u * MIRT_RAY_SORT_DIRECTION_BITS == 31u, "the sort runs over 31 key bits");
+
+struct SortBounds { float lo[3]; float inv; };
+
+// lane = ray: two 16-byte loads, the code and the ray's own index out
+__global__ __launch_bounds__(kBlock) void ray_codes_kernel(const trace_u4* rays, uint32_t n_rays, SortBounds B, uint32_t* codes, uint32_t* index)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_rays) return;
+    const trace_u4 r0 = rays[2u * i], r1 = rays[2u * i + 1u];          // {origin, t_max | stream} {direction, _pad}
+    const float o[3] = { __uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z) };
+    const float d[3] = { __uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z) };
+    codes[i] = ray_code(o, d, B.lo, B.inv);
+    index[i] = (uint32_t)i;
+}
+
+SortBounds sort_bounds(const float centre[3], float radius)
+{
+    SortBounds b;
+    for (int k = 0; k < 3; ++k) b.lo[k] = centre[k] - radius;
+    b.inv = 16.0f / radius;
+    return b;
+}
+
+}  // namespace
+
+uint32_t mirt::ray_sort_code(const float centre[3], float radius, const void* ray32)
+{
+    float f[8];
+    std::memcpy(f, ray32, sizeof f);
+    const SortBounds b = sort_bounds(centre, radius);
+    return ray_code(f, f + 4, b.lo, b.inv);
+}
+
+int mirt::ray_sort_order(const void* d_rays, uint32_t n, const float centre[3], float radius, void* hip_stream, BvhDeviceScratch* scratch, size_t* off_order)
+{
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    constexpr unsigned kKeyBits = 3u * MIRT_RAY_SORT_ORIGIN_BITS + 2u * MIRT_RAY_SORT_DIRECTION_BITS;
+    size_t sort_bytes = 0;
+    BVH_HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u,
+                                          kKeyBits, stream));
+    // scratch: the order | codes (in, sorted) | indices in | the sort's storage
+    size_t off = 0;
+    const size_t o_order = off;    off += align256(4ull * n);
+    const size_t o_codes_in = off; off += align256(4ull * n);
+    const size_t o_codes = off;    off += align256(4ull * n);
+    const size_t o_index = off;    off += align256(4ull * n);
+    const size_t o_sort = off;     off += align256(sort_bytes);
+    if (off > scratch->cap || !scratch->d) {
+        BVH_HIP_TRY(hipDeviceSynchronize());      // sorted launches may still read the old scratch, on any stream
+        int rc;
+        if ((rc = grow(&scratch->d, &scratch->cap, off)) != MIRT_OK) return rc;
+    }
+    unsigned char* S = scratch->d;
+    uint32_t* codes_in = reinterpret_cast<uint32_t*>(S + o_codes_in);
+    uint32_t* index = reinterpret_cast<uint32_t*>(S + o_index);
+    ray_codes_kernel<<<(uint32_t)(((uint64_t)n + kBlock - 1u) / kBlock), kBlock, 0, stream>>>(static_cast<const trace_u4*>(d_rays), n, sort_bounds(centre, radius), codes_in, index);
+    BVH_HIP_TRY(hipGetLastError());
+    // stable: equal codes keep the caller's order
+    BVH_HIP_TRY(rocprim::radix_sort_pairs(S + o_sort, sort_bytes, codes_in, reinterpret_cast<uint32_t*>(S + o_codes), index, reinterpret_cast<uint32_t*>(S + o_order),
+                                          (size_t)n, 0u, kKeyBits, stream));
+    *off_order = o_order;
+    return MIRT_OK;
+}

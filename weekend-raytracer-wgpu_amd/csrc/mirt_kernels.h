@@ -297,6 +297,9 @@ hipError_t launch_selftest_math(unsigned long long* d_mismatches, hipStream_t st
 // launch's does, bvh_stack_entries = the stack entries per lane, lds_bytes = 256 x that per wave of the block (0 for the flat scan), and
 // `counters`; d_rays / d_hits: [n_rays] MirtRay / MirtRayHit in device memory, 4-byte aligned.
 hipError_t launch_trace_rays(const RenderArgs& a, const void* d_rays, void* d_hits, uint32_t n_rays, bool bvh, bool any, bool count, hipStream_t stream);
+// MIRT_RAYS_SORT: trace_rays_sorted_kernel<bvh, any, count>, the same launch with slot k working on record d_order[k] ([n_rays] uint32 in device memory)
+hipError_t launch_trace_rays_sorted(const RenderArgs& a, const void* d_rays, void* d_hits, uint32_t n_rays, const uint32_t* d_order, bool bvh, bool any, bool count,
+                                    hipStream_t stream);
 // mirt_ctx_render_features*: feature_frame_kernel<bvh> (mirt_feature_kernel.inc), one thread per pixel of a.out_rows x a.width.  `a` carries the
 // camera (with the pinhole word set), the tables, the tree, seed_mix, spp, sample_begin and the row fields as a render launch's does,
 // bvh_stack_entries and lds_bytes as launch_trace_rays wants them; d_out: [out_rows x width] MirtFeaturePixel in device memory, 4-byte aligned.
@@ -306,6 +309,8 @@ hipError_t launch_features(const RenderArgs& a, void* d_out, bool bvh, hipStream
 // MIRT_RADIANCE_* bits, lds_bytes = scene_lds_bytes_grid(n_spheres, hosek) + kBvhStackBytesPerWave (BVH build);
 // d_rays / d_out: [n_units] MirtRadianceRay / MirtRadiance in device memory, 4-byte aligned.
 hipError_t launch_radiance(const RenderArgs& a, const void* d_rays, void* d_out, bool hosek, bool bvh, hipStream_t stream);
+// MIRT_RADIANCE_SORT: radiance_rays_sorted_kernel<hosek, bvh>, slot k working on record d_order[k] ([n_units] uint32 in device memory)
+hipError_t launch_radiance_sorted(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, bool hosek, bool bvh, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);
 size_t     scene_lds_bytes(uint32_t n_spheres, uint32_t n_mats, bool pt, bool hosek);
 size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);

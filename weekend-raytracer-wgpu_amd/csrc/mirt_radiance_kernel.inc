@@ -3,7 +3,8 @@
 // mirt_trace_kernel.inc's vector types), exact build only: there is no fast_build:: copy, no counting build and no dispenser.
 //
 // radiance_rays_kernel<HOSEK, BVH>: lane = ray, 64 consecutive rays per wave, ONE wave per block (kRadianceThreads), one ray per thread and no
-// loop over rays: the caller's order is the wave's order.  RenderArgs.n_units is the number of rays; lanes of the last wave beyond it are
+// loop over rays: the caller's order is the wave's order (radiance_rays_sorted_kernel, MIRT_RADIANCE_SORT: the order of a permutation in
+// device memory; the body of both is mirt_radiance_ray_body.inc).  RenderArgs.n_units is the number of rays; lanes of the last wave beyond it are
 // not alive: they load nothing, take part in the wave's loops with their tests masked off and store nothing.  A ray (MirtRadianceRay,
 // 32 bytes: {origin, stream} {direction, _pad}) is two 16-byte loads through a 4-byte-aligned vector type.
 //   A sample is the renderer's sample from its primary ray on.  For s in sample_begin .. sample_begin + spp - 1 (the same trip count in
@@ -32,47 +33,23 @@ static_assert(kRadianceFlat == MIRT_RADIANCE_FLAT && kRadianceAccumulate == MIRT
 template <bool HOSEK, bool BVH>
 __global__ __launch_bounds__(kRadianceThreads, 5) void radiance_rays_kernel(RenderArgs A, const trace_u4* rays, trace_u4* out)
 {
-    constexpr uint32_t SRC = BVH ? kSrcBvh : kSrcHbmFlat;
-    extern __shared__ __align__(16) unsigned char smem[];
-    const SceneLds S = stage_scene<true, false>(A, smem, HOSEK);
-    const GridLds G{};
-    uint32_t* bvh_stack = nullptr;
-    if constexpr (BVH)
-        bvh_stack = reinterpret_cast<uint32_t*>(smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, HOSEK, false)) + (threadIdx.x >> 6) * (kBvhStackBytesPerWave / 4u);      // (one wave per block today: + 0)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t i = (uint64_t)blockIdx.x * kRadianceThreads + threadIdx.x;
-    const bool alive = i < A.n_units;
-    trace_u4 r0 = { 0u, 0u, 0u, 0u }, r1 = { 0u, 0u, 0u, 0u };
-    if (alive) { r0 = rays[2u * i]; r1 = rays[2u * i + 1u]; }          // {origin, stream} {direction, _pad}
-    const f3 ro = mk(from_bits(r0.x), from_bits(r0.y), from_bits(r0.z));
-    const f3 rd = mk(from_bits(r1.x), from_bits(r1.y), from_bits(r1.z));
-    const uint32_t stream = r0.w;
+#define MIRT_RAY_SLOT i
+#define MIRT_RAY_OF_SLOT
+#include "mirt_radiance_ray_body.inc"
+#undef MIRT_RAY_SLOT
+#undef MIRT_RAY_OF_SLOT
+}
 
-    Work<false> work;
-    work.clear();
-    unsigned long long acc_r = 0, acc_g = 0, acc_b = 0;
-    for (uint32_t s = 0; s < A.spp; ++s) {
-        Rng rng;
-        // generate_primary's seed with `stream` for the pixel index, then the two jitter and the two lens draws of a primary ray
-        rng.state = jenkins_hash((stream ^ jenkins_hash(A.sample_begin + s + 1u)) ^ A.seed_mix);
-        rng.skip(); rng.skip(); rng.skip(); rng.skip();
-        const f3 c = path_radiance<false, HOSEK, false, SRC>(A, S, G, alive, rng, ro, rd, work, lane, nullptr, kNoCand, bvh_stack);
-        acc_r += to_fixed(c.x);
-        acc_g += to_fixed(c.y);
-        acc_b += to_fixed(c.z);
-    }
-    if (alive) {
-        uint32_t samples = A.spp;
-        if (A.flags & kRadianceAccumulate) {
-            const trace_u4 o0 = out[2u * i], o1 = out[2u * i + 1u];
-            acc_r += (unsigned long long)o0.x | ((unsigned long long)o0.y << 32);
-            acc_g += (unsigned long long)o0.z | ((unsigned long long)o0.w << 32);
-            acc_b += (unsigned long long)o1.x | ((unsigned long long)o1.y << 32);
-            samples += o1.z;
-        }
-        out[2u * i] = trace_u4{ (uint32_t)acc_r, (uint32_t)(acc_r >> 32), (uint32_t)acc_g, (uint32_t)(acc_g >> 32) };
-        out[2u * i + 1u] = trace_u4{ (uint32_t)acc_b, (uint32_t)(acc_b >> 32), samples, 0u };
-    }
+// MIRT_RADIANCE_SORT (DESIGN.md 10.10): slot k of the launch loads and stores record order[k], the MIRT_RADIANCE_ACCUMULATE loads
+// included -- the permutation ray_sort_order left in device memory.  The records stay where the caller put them.
+template <bool HOSEK, bool BVH>
+__global__ __launch_bounds__(kRadianceThreads, 5) void radiance_rays_sorted_kernel(RenderArgs A, const trace_u4* rays, trace_u4* out, const uint32_t* order)
+{
+#define MIRT_RAY_SLOT slot
+#define MIRT_RAY_OF_SLOT const uint64_t i = alive ? order[slot] : 0u;
+#include "mirt_radiance_ray_body.inc"
+#undef MIRT_RAY_SLOT
+#undef MIRT_RAY_OF_SLOT
 }
 
 // one thread per ray (a.n_units of them), one wave per block; a.lds_bytes = stage_scene's image without the tables + the wave's traversal stacks (BVH build)
@@ -82,5 +59,15 @@ hipError_t launch_radiance(const RenderArgs& a, const void* d_rays, void* d_out,
     auto k = hosek ? (bvh ? radiance_rays_kernel<true, true> : radiance_rays_kernel<true, false>)
                    : (bvh ? radiance_rays_kernel<false, true> : radiance_rays_kernel<false, false>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(kRadianceThreads), a.lds_bytes, stream, a, static_cast<const trace_u4*>(d_rays), static_cast<trace_u4*>(d_out));
+    return hipGetLastError();
+}
+
+// the same launch in the order d_order gives ([a.n_units] uint32 in device memory, a permutation)
+hipError_t launch_radiance_sorted(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, bool hosek, bool bvh, hipStream_t stream)
+{
+    const uint32_t blocks = (uint32_t)(((uint64_t)a.n_units + kRadianceThreads - 1u) / kRadianceThreads);
+    auto k = hosek ? (bvh ? radiance_rays_sorted_kernel<true, true> : radiance_rays_sorted_kernel<true, false>)
+                   : (bvh ? radiance_rays_sorted_kernel<false, true> : radiance_rays_sorted_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(kRadianceThreads), a.lds_bytes, stream, a, static_cast<const trace_u4*>(d_rays), static_cast<trace_u4*>(d_out), d_order);
     return hipGetLastError();
 }

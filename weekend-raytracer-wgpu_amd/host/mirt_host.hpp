@@ -113,6 +113,22 @@ inline std::vector<MirtRadiance> trace_radiance(MirtContext* ctx, const std::vec
     check(mirt_ctx_trace_radiance(ctx, rays.data(), (uint32_t)rays.size(), &params, out.data()));
     return out;
 }
+// mirt_ray_sort_code: the 31-bit code MIRT_RAYS_SORT / MIRT_RADIANCE_SORT order a batch by, for one 32-byte record (MirtRay or
+// MirtRadianceRay); centre, radius: those of mirt_ctx_bvh_info.  Host only.
+inline uint32_t ray_sort_code(const float centre[3], float radius, const void* ray32)
+{
+    uint32_t code = 0;
+    check(mirt_ray_sort_code(centre, radius, ray32, &code));
+    return code;
+}
+// mirt_ctx_trace_order_read: the permutation of the last sorted launch of `n_rays` rays; order[k] = the caller's index of the ray in slot k
+inline std::vector<uint32_t> trace_order(MirtContext* ctx, uint32_t n_rays)
+{
+    std::vector<uint32_t> order(n_rays ? n_rays : 1u);
+    check(mirt_ctx_trace_order_read(ctx, order.data(), order.size()));
+    order.resize(n_rays);
+    return order;
+}
 // the pinhole ray through the centre of pixel (x, y), row 0 on top: cameraMakeRay with a zero lens
 inline MirtRay pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float t_max = 1000.0f)
 {
