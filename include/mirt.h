@@ -554,8 +554,9 @@ int mirt_camera_pixel_ray(const MirtGpuCamera* camera, uint32_t width, uint32_t 
  * flags: 0 = the BVH walk of the render kernels (radiance_rays_kernel<.., true>); MIRT_RADIANCE_FLAT = the flat scan of the resident table,
  * the comparison build as MIRT_RAYS_FLAT is; MIRT_RADIANCE_SKY_HOSEK = the scene's Hosek blob, as MIRT_FLAG_SKY_HOSEK (MIRT_ERR_SKY
  * without a blob); MIRT_RADIANCE_SORT = the batch runs in an order the library derives on the device (radiance_rays_sorted_kernel<..>;
- * "sorted ray batches" below), same bytes in the same places, valid with every other flag; bit 3 is not assigned; any other bit:
- * MIRT_ERR_BAD_MODE.
+ * "sorted ray batches" below), same bytes in the same places, valid with every other flag; MIRT_RADIANCE_POOL = the pooled schedule
+ * ("pooled radiance queries" below), a hint, same bytes in the same places, valid with every other flag; bits 3 and 5 are not assigned;
+ * any other bit: MIRT_ERR_BAD_MODE.
  * MIRT_ERR_NULL_POINTER: ctx or params is null, or rays or the output is null with n_rays > 0;  MIRT_ERR_NO_SCENE: no scene, or not a
  * MIRT_SCENE_HBM one;  MIRT_ERR_SPP_ZERO, MIRT_ERR_SPP_RANGE: the rules of mirt_ctx_render;  MIRT_ERR_MATERIAL_INDEX / MIRT_ERR_TEXEL_RANGE:
  * exactly as a path-traced render call on that scene answers.  n_rays == 0 (after these checks): MIRT_OK without device work.  A refused
@@ -572,8 +573,28 @@ typedef struct MirtRadianceRay { float origin[3]; uint32_t stream; float directi
 typedef struct MirtRadiance { uint64_t sum[3]; uint32_t samples; uint32_t _pad; } MirtRadiance;   /* 32 B */
 typedef struct MirtRadianceParams { uint32_t spp, sample_begin, num_bounces, flags; uint64_t seed; } MirtRadianceParams;   /* 24 B */
 enum { MIRT_RADIANCE_FLAT = 1u << 0, MIRT_RADIANCE_ACCUMULATE = 1u << 1, MIRT_RADIANCE_SKY_HOSEK = 1u << 2, MIRT_RADIANCE_SORT = 1u << 4 };   /* bit 3: unassigned */
+enum { MIRT_RADIANCE_POOL = 1u << 6 };   /* bit 5: unassigned */
 int mirt_ctx_trace_radiance(MirtContext* ctx, const MirtRadianceRay* rays, uint32_t n_rays, const MirtRadianceParams* params, MirtRadiance* out);
 int mirt_ctx_trace_radiance_device(MirtContext* ctx, const void* d_rays, uint32_t n_rays, const MirtRadianceParams* params, void* d_out, void* hip_stream);
+
+/* ---- pooled radiance queries: MIRT_RADIANCE_POOL ----
+ * Without the flag lane = ray: a lane walks its ray's spp samples one after the other and in every sample the wave waits for its longest
+ * path.  With it a wave owns 16 consecutive slots of the batch (slot k = ray k, or the k-th ray of the sorted order under
+ * MIRT_RADIANCE_SORT) and keeps their 16 x spp (ray, sample) items in a wave-private pool of paths, as the pooled render of a
+ * MIRT_SCENE_HBM scene (MIRT_FLAG_KERNEL_POOL) does with 16 pixels: a finished path's slot takes the next item at once.
+ *   same bytes in the same places   the sums are exact integers, so the order in which the items are served cannot change them: the
+ *                    records are those of the call without the flag, for every float bit pattern in a ray, and with every other flag
+ *                    (_ACCUMULATE, _SKY_HOSEK, _SORT).  Errors, the n_rays == 0 rule and "a refused call queues and writes nothing" are
+ *                    unchanged.  A record still depends on its ray, the params and the scene alone.
+ *   a hint           like MIRT_FLAG_KERNEL_POOL.  The pooled kernel runs on the BVH build.  It does not run, and the call runs exactly as
+ *                    without the flag (same kernel, same name in mirt_ctx_last_kernel), when MIRT_RADIANCE_FLAT is set, when
+ *                    num_bounces > 255 (the pool's bounce counters are 8 bit), or when mirt_bvh_pool_plan of the resident tree's depth
+ *                    gives slots == 0.  The geometry is mirt_bvh_pool_plan's for that depth and sky, as the pooled render's is.
+ *   state            as for every radiance launch: the launch ring, MirtStats and the accumulation are untouched;
+ *                    mirt_ctx_trace_stats().kernel_ms spans the launch, with the sort in front of it under _SORT; mirt_ctx_last_kernel
+ *                    names radiance_rays_pool_kernel<THREADS,SLOTS,MINW,HOSEK,SORTED>.
+ *   sharing          no context state is added beyond what radiance launches already write -- there is no dispenser word -- so pooled
+ *                    launches need no ordering among themselves beyond what _SORT asks for its scratch. */
 
 /* ---- sorted ray batches: MIRT_RAYS_SORT, MIRT_RADIANCE_SORT ----
  * Lane = ray and 64 consecutive records form a wave, so a batch that is not in a coherent order (probe grids, shuffled training rays)

@@ -282,6 +282,8 @@ pub const MIRT_RADIANCE_ACCUMULATE: u32 = 1 << 1;
 pub const MIRT_RADIANCE_SKY_HOSEK: u32 = 1 << 2;
 /// The batch runs in an order the library derives on the device; same records.  Bit 3 is unassigned.
 pub const MIRT_RADIANCE_SORT: u32 = 1 << 4;
+/// A hint: the pooled schedule (a wave deals the samples of 16 rays to its lanes); same records.  Bit 5 is unassigned.
+pub const MIRT_RADIANCE_POOL: u32 = 1 << 6;
 
 pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
 /// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.

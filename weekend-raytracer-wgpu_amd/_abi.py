@@ -46,6 +46,7 @@ MIRT_RADIANCE_FLAT = 1 << 0
 MIRT_RADIANCE_ACCUMULATE = 1 << 1
 MIRT_RADIANCE_SKY_HOSEK = 1 << 2
 MIRT_RADIANCE_SORT = 1 << 4             # bit 3 is unassigned
+MIRT_RADIANCE_POOL = 1 << 6             # bit 5 is unassigned
 # the sort code of MIRT_RAYS_SORT / MIRT_RADIANCE_SORT: bits per origin axis / per octahedral direction axis
 MIRT_RAY_SORT_ORIGIN_BITS = 5
 MIRT_RAY_SORT_DIRECTION_BITS = 8

@@ -247,17 +247,17 @@ def radiance_ray_records(rays) -> np.ndarray:
     raise ValueError(f"rays must be a one-dimensional RADIANCE_RAY_DTYPE array or uint32 [n, 8], not {rays.dtype} of shape {rays.shape}")
 
 
-def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort=False) -> _abi.MirtRadianceParams:
+def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort=False, pool=False) -> _abi.MirtRadianceParams:
     for name, v in (("spp", spp), ("sample_begin", sample_begin), ("num_bounces", num_bounces)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
             raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
     if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= int(seed) < 1 << 64:
         raise ValueError(f"seed must be an integer in [0, 2^64), not {seed!r}")
-    for name, v in (("flat", flat), ("hosek", hosek), ("accumulate", accumulate), ("sort", sort)):
+    for name, v in (("flat", flat), ("hosek", hosek), ("accumulate", accumulate), ("sort", sort), ("pool", pool)):
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError(f"{name} must be a bool, not {v!r}")
     flags = (_abi.MIRT_RADIANCE_FLAT if flat else 0) | (_abi.MIRT_RADIANCE_SKY_HOSEK if hosek else 0) | (_abi.MIRT_RADIANCE_ACCUMULATE if accumulate else 0) \
-        | (_abi.MIRT_RADIANCE_SORT if sort else 0)
+        | (_abi.MIRT_RADIANCE_SORT if sort else 0) | (_abi.MIRT_RADIANCE_POOL if pool else 0)
     return _abi.MirtRadianceParams(int(spp), int(sample_begin), int(num_bounces), flags, int(seed))
 
 
@@ -434,17 +434,18 @@ class Context:
 
     # ---- path-traced radiance for a caller's rays against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
     def trace_radiance(self, rays, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0, flat: bool = False,
-                       hosek: bool = False, into: Optional[np.ndarray] = None, sort: bool = False) -> np.ndarray:
+                       hosek: bool = False, into: Optional[np.ndarray] = None, sort: bool = False, pool: bool = False) -> np.ndarray:
         """mirt_ctx_trace_radiance: `spp` samples of the path tracer for every ray -> a RADIANCE_DTYPE array {"sum" [3] in 2^-20 units,
         "samples"}, one record per ray in the caller's order (radiance_mean gives the means).  A sample is the renderer's from its
         primary ray on: samples sample_begin .. sample_begin + spp - 1 of the RNG stream a pixel of index `stream` has under `seed`.
         `rays`: see radiance_ray_records (make_radiance_rays builds them).  flat=True: the flat scan instead of the tree; hosek=True:
         the scene's Hosek sky.  into: a RADIANCE_DTYPE array [n] to ADD to (MIRT_RADIANCE_ACCUMULATE), changed in place and
         returned -- a progressive probe passes sample_begin = the samples it holds.  sort=True (MIRT_RADIANCE_SORT): the batch runs in
-        an order derived on the device, for batches that are not in a coherent order; the records are the same.  Needs a scene set
-        with hbm=True.  Blocking."""
+        an order derived on the device, for batches that are not in a coherent order; the records are the same.  pool=True (MIRT_RADIANCE_POOL): a hint to run the
+        pooled schedule, which deals the samples of 16 rays to a wave's lanes (Context.last_kernel tells whether it ran); the records are
+        the same.  Needs a scene set with hbm=True.  Blocking."""
         recs = radiance_ray_records(rays)
-        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, into is not None, sort)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, into is not None, sort, pool)
         if into is None:
             out = np.zeros(len(recs), RADIANCE_DTYPE)
         else:
@@ -458,13 +459,13 @@ class Context:
 
     def trace_radiance_device(self, d_rays: int, n: int, d_out: int, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0,
                               flat: bool = False, hosek: bool = False, accumulate: bool = False, stream: Optional[int] = None,
-                              sort: bool = False) -> None:
+                              sort: bool = False, pool: bool = False) -> None:
         """mirt_ctx_trace_radiance_device: `n` 32-byte MirtRadianceRay records at device address `d_rays` -> `n` MirtRadiance records at
         `d_out` (e.g. torch tensors' data_ptr()), one kernel queued on `stream` (see _stream_arg); no host synchronisation.
         accumulate=True adds to the records already at `d_out`.  sort=True: the code kernel and the sort are queued in front of it (sorted
-        launches of one context are kept in order by the caller)."""
+        launches of one context are kept in order by the caller).  pool=True: the pooled schedule (a hint, as in trace_radiance)."""
         _check_range(0, n)
-        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort, pool)
         if int(n):
             d_rays, d_out = _check_address("d_rays", d_rays), _check_address("d_out", d_out)
         check(lib().mirt_ctx_trace_radiance_device(self._h, C.c_void_p(d_rays) if int(n) else None, int(n), C.byref(params),

@@ -297,6 +297,7 @@ struct Tuning {
     int      static_grid = -1;        // MIRT_STATIC_GRID=k (A/B runs): launches with one unit per wave run k x the resident blocks instead, units dealt round-robin
     int      timing = -1;             // MIRT_TIMING=0/1: the context's initial mirt_ctx_set_timing state (A/B runs; default 1)
     uint32_t hbm_pool_slots = 0;      // MIRT_HBM_POOL_SLOTS=n (A/B runs): the pooled build of MIRT_SCENE_HBM scenes takes this one of kBvhPoolSlotChoices
+    uint32_t radiance_pool_blocks = 0;    // MIRT_RADIANCE_POOL_BLOCKS=n (A/B runs, tests): a pooled radiance query launches at most n blocks, whose waves stride over the units
     bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
 };
 
@@ -328,6 +329,7 @@ Tuning read_tuning()
         const uint32_t v = (uint32_t)std::atoi(e);
         for (uint32_t s : mirt::kBvhPoolSlotChoices) if (v == s) t.hbm_pool_slots = v;
     }
+    if (const char* e = std::getenv("MIRT_RADIANCE_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.radiance_pool_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_GRID_BIG")) { const double v = std::atof(e); if (v >= 1.0 && v <= 1024.0) t.grid_big = v; }
     return t;
 }
@@ -1967,7 +1969,7 @@ static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, co
     *go = false;
     if (!c || !p) return fail(MIRT_ERR_NULL_POINTER, "ctx/params is null");
     if (n && (!rays || !out)) return fail(MIRT_ERR_NULL_POINTER, "rays/out is null");
-    if (p->flags & ~(uint32_t)(MIRT_RADIANCE_FLAT | MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_SKY_HOSEK | MIRT_RADIANCE_SORT))
+    if (p->flags & ~(uint32_t)(MIRT_RADIANCE_FLAT | MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_SKY_HOSEK | MIRT_RADIANCE_SORT | MIRT_RADIANCE_POOL))
         return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RADIANCE_* bits 0x%x", p->flags);
     if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
     if (p->spp == 0) return fail(MIRT_ERR_SPP_ZERO, "spp is zero");
@@ -1983,9 +1985,16 @@ static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, co
 // Queue radiance_rays_kernel<hosek, bvh> (radiance_rays_sorted_kernel behind the code kernel and the sort with MIRT_RADIANCE_SORT) for n > 0 rays in
 // device memory on `st`.  No host synchronisation.  The launch ring, MirtStats and
 // the accumulation stay as they are; the event pair and the pending flag are the ray queries' (mirt_ctx_trace_stats folds the time).
+// MIRT_RADIANCE_POOL on the BVH build: radiance_rays_pool_kernel in the geometry the pooled render would take for the resident tree
+// (plan_bvh_pool), where the pool's own limits allow it -- 8-bit bounce counters, a geometry that fits beside the stacks of a tree this
+// deep; otherwise the launch is the one without the flag.
 static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const MirtRadianceParams* p, void* d_out, hipStream_t st)
 {
     const bool bvh = !(p->flags & MIRT_RADIANCE_FLAT), hosek = (p->flags & MIRT_RADIANCE_SKY_HOSEK) != 0, sort = (p->flags & MIRT_RADIANCE_SORT) != 0;
+    MirtBvhPoolPlan plan{};
+    if ((p->flags & MIRT_RADIANCE_POOL) && bvh && p->num_bounces <= 255u)
+        plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, c->tuning.hbm_pool_slots);
+    const bool pooled = plan.slots != 0u && plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
     mirt::RenderArgs a{};                                 // (the camera stays zero: a query has none)
     a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
     a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
@@ -1994,20 +2003,34 @@ static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const
     a.sample_begin = p->sample_begin;
     a.n_units = n;
     // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
-    fill_bvh_args(c, &a, 0u);
+    fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
     a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
+    uint32_t pool_blocks = 0;
+    if (pooled) {                                         // units of 16 slots of the batch, one unit per wave: the hardware's dispatcher is the balancer
+        const uint32_t waves = plan.threads / 64u;
+        a.width = n;
+        a.height = 1u;
+        a.n_units = (uint32_t)(((uint64_t)n + mirt::kStripPixels - 1u) / mirt::kStripPixels);
+        a.lds_bytes = plan.lds_bytes_per_block;           // camera words (+ sky), the block's pools, its waves' traversal stacks
+        pool_blocks = (a.n_units + waves - 1u) / waves;
+        if (c->tuning.radiance_pool_blocks != 0u && pool_blocks > c->tuning.radiance_pool_blocks) pool_blocks = c->tuning.radiance_pool_blocks;
+    }
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    const uint32_t* d_order = nullptr;
     if (sort) {
-        const uint32_t* d_order = nullptr;
         const int rc = queue_ray_sort(c, d_rays, n, st, &d_order);
         if (rc != MIRT_OK) return rc;
-        HIP_TRY(kx::launch_radiance_sorted(a, d_rays, d_out, d_order, hosek, bvh, st));
-    } else {
-        HIP_TRY(kx::launch_radiance(a, d_rays, d_out, hosek, bvh, st));
     }
     const char* tf[2] = { "false", "true" };
-    snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays%s_kernel<%s,%s>", sort ? "_sorted" : "", tf[hosek], tf[bvh]);
+    if (pooled) {
+        HIP_TRY(kx::launch_radiance_pool(a, d_rays, d_out, d_order, pool_blocks, plan.slots, hosek, st));
+        snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays_pool_kernel<%u,%u,%u,%s,%s>", plan.threads, plan.slots, mirt::kBvhPoolMinWaves, tf[hosek], tf[sort]);
+    } else {
+        if (sort) HIP_TRY(kx::launch_radiance_sorted(a, d_rays, d_out, d_order, hosek, bvh, st));
+        else HIP_TRY(kx::launch_radiance(a, d_rays, d_out, hosek, bvh, st));
+        snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays%s_kernel<%s,%s>", sort ? "_sorted" : "", tf[hosek], tf[bvh]);
+    }
     HIP_TRY(hipEventRecord(c->ev_trace_end, st));
     c->trace_pending = true;
     c->trace_timed = timed;

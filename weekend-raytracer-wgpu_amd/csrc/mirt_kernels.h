@@ -311,6 +311,11 @@ hipError_t launch_features(const RenderArgs& a, void* d_out, bool bvh, hipStream
 hipError_t launch_radiance(const RenderArgs& a, const void* d_rays, void* d_out, bool hosek, bool bvh, hipStream_t stream);
 // MIRT_RADIANCE_SORT: radiance_rays_sorted_kernel<hosek, bvh>, slot k working on record d_order[k] ([n_units] uint32 in device memory)
 hipError_t launch_radiance_sorted(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, bool hosek, bool bvh, hipStream_t stream);
+// MIRT_RADIANCE_POOL: radiance_rays_pool_kernel<kBvhPoolThreads, slots, kBvhPoolMinWaves, hosek, d_order != nullptr> (mirt_radiance_pool_kernel.inc),
+// the pooled HBM render's schedule on units of 16 rays.  `a` as for launch_radiance, but n_units = ceil(n_rays / 16), width = n_rays, and
+// bvh_stack_entries / lds_bytes as the pooled render's (mirt_bvh_pool_plan); grid_blocks blocks of kBvhPoolThreads, whose waves stride over the units.
+hipError_t launch_radiance_pool(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, uint32_t grid_blocks, uint32_t slots, bool hosek,
+                                hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);
 size_t     scene_lds_bytes(uint32_t n_spheres, uint32_t n_mats, bool pt, bool hosek);
 size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);

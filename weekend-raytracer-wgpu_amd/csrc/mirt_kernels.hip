@@ -2186,6 +2186,7 @@ struct PoolHbmState {
 #include "mirt_trace_kernel.inc"
 #include "mirt_feature_kernel.inc"
 #include "mirt_radiance_kernel.inc"
+#include "mirt_radiance_pool_kernel.inc"
 
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns

@@ -106,7 +106,9 @@ inline MirtRay camera_pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32
     return r;
 }
 // mirt_ctx_trace_radiance: params.spp samples of the path tracer for every ray (the renderer's samples from the primary ray on; `stream`
-// of a ray takes the place of a pixel's index) -> one record of exact sums per ray; params.flags = MIRT_RADIANCE_* (the records start at zero, so _ACCUMULATE changes nothing here).  Blocking.
+// of a ray takes the place of a pixel's index) -> one record of exact sums per ray; params.flags = MIRT_RADIANCE_* (the records start at zero, so _ACCUMULATE changes nothing here);
+// MIRT_RADIANCE_POOL among them asks for the pooled schedule (a hint: same records).  Blocking.
+static_assert(MIRT_RADIANCE_POOL == 1u << 6, "MirtRadianceParams.flags: the pooled schedule");
 inline std::vector<MirtRadiance> trace_radiance(MirtContext* ctx, const std::vector<MirtRadianceRay>& rays, const MirtRadianceParams& params)
 {
     std::vector<MirtRadiance> out(rays.size());

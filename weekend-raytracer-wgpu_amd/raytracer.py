@@ -457,7 +457,7 @@ def _features(owner, spp: int, seed: int, width: int, height: int, camera: _abi.
     return {k: rec[k].copy() for k in ("albedo", "normal", "t", "sphere")}
 
 
-def _radiance(owner, rays, spp: int, seed: int, num_bounces: int, hosek: bool, scene_data, sort: bool = False) -> np.ndarray:
+def _radiance(owner, rays, spp: int, seed: int, num_bounces: int, hosek: bool, scene_data, sort: bool = False, pool: bool = False) -> np.ndarray:
     """Layer.radiance / Raytracer.radiance: Context.trace_radiance of `rays` (RADIANCE_RAY_DTYPE: make_radiance_rays) -> float64 means
     [n, 3]; sort=True: in an order derived on the device (MIRT_RADIANCE_SORT), the same means.  Like _pick: a resident LDS scene -- or none yet -- is set again as a MIRT_SCENE_HBM scene first, and on a node the query
     runs on member 0's context."""
@@ -466,7 +466,7 @@ def _radiance(owner, rays, spp: int, seed: int, num_bounces: int, hosek: bool, s
         target.set_scene(scene_data(), hbm=True)
         owner._hbm = True
     ctx = target.context(0) if hasattr(target, "context") else target
-    return radiance_mean(ctx.trace_radiance(rays, spp, num_bounces=num_bounces, seed=seed, hosek=hosek, sort=sort))
+    return radiance_mean(ctx.trace_radiance(rays, spp, num_bounces=num_bounces, seed=seed, hosek=hosek, sort=sort, pool=pool))
 
 
 def _jpeg_check(rc: int) -> None:
@@ -633,12 +633,13 @@ class Layer:
         Like pick, it needs the world in device memory and sets it as a MIRT_SCENE_HBM scene first where it is not."""
         return _features(self, spp, seed, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data)
 
-    def radiance(self, rays, spp: int = 16, *, seed: int = 0, num_bounces: int = 8, sort: bool = False) -> np.ndarray:
+    def radiance(self, rays, spp: int = 16, *, seed: int = 0, num_bounces: int = 8, sort: bool = False, pool: bool = False) -> np.ndarray:
         """Path-traced radiance of `world` along rays the caller chooses (make_radiance_rays: panorama and fisheye cameras, probes)
         -> float64 means [n, 3] over samples 0 .. spp - 1 of every ray's stream, by Context.trace_radiance.  Like pick, it needs the
         world in device memory and sets it as a MIRT_SCENE_HBM scene first where it is not.  sort=True traces the batch in an order
-        derived on the device: for rays that are not in a coherent order (probe grids, shuffled batches); the means are the same."""
-        return _radiance(self, rays, spp, seed, num_bounces, False, self.scene_data, sort)
+        derived on the device: for rays that are not in a coherent order (probe grids, shuffled batches); the means are the same.
+        pool=True asks for the pooled schedule (MIRT_RADIANCE_POOL, a hint): the means are the same."""
+        return _radiance(self, rays, spp, seed, num_bounces, False, self.scene_data, sort, pool)
 
     def register_texture(self) -> np.ndarray:         # layer.rs:150-176: the RGBA8 bytes imgui would receive
         if self._rgba is None:
@@ -821,13 +822,13 @@ class Raytracer:
             spp = self.render_params.sampling.num_samples_per_pixel
         return _features(self, spp, seed, int(w), int(h), self.camera.c, self.scene_data)
 
-    def radiance(self, rays, spp: Optional[int] = None, *, seed: int = 0, sort: bool = False) -> np.ndarray:
+    def radiance(self, rays, spp: Optional[int] = None, *, seed: int = 0, sort: bool = False, pool: bool = False) -> np.ndarray:
         """Path-traced radiance of the scene along rays the caller chooses (make_radiance_rays) -> float64 means [n, 3], as
         Layer.radiance.  spp = None takes `sampling.num_samples_per_pixel`; the bounces are `sampling.num_bounces` and the sky is the
-        scene's (the Hosek blob where there is one).  The accumulation is not touched.  sort: as Layer.radiance."""
+        scene's (the Hosek blob where there is one).  The accumulation is not touched.  sort, pool: as Layer.radiance."""
         if spp is None:
             spp = self.render_params.sampling.num_samples_per_pixel
-        return _radiance(self, rays, spp, seed, self.render_params.sampling.num_bounces, self.sky_state is not None, self.scene_data, sort)
+        return _radiance(self, rays, spp, seed, self.render_params.sampling.num_bounces, self.sky_state is not None, self.scene_data, sort, pool)
 
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
         """All `max_samples_per_pixel` samples in one launch -> RGBA8 [h][w][4].
