@@ -714,6 +714,73 @@ int mirt_ctx_accum_frame_device(MirtContext* ctx, const MirtParams* params, void
  * mirt_ctx_render_device.  For hosts without HIP. */
 int mirt_ctx_accum_frame(MirtContext* ctx, const MirtParams* params, uint8_t* out_rgba8, size_t out_len);
 
+/* ---- adaptive sampling for progressive frames of a MIRT_SCENE_HBM scene ----
+ * mirt_ctx_accum_add gives every pixel the same number of samples.  Here the context keeps one 64-byte record per pixel and a step
+ * samples only the pixels that have not converged: sky, ground and plain lambertians settle after a handful of samples, glass, metal
+ * reflections and defocused edges take hundreds.  Everything is integer: a pixel's sample s depends on (pixel index, s, seed) alone, so
+ * a pixel's sums after n samples are the same whatever the other pixels received, and the whole loop -- which pixels a step samples,
+ * and every sum -- has ONE right answer.
+ *   the record       sum[k] = the sum of to_fixed(radiance[k]) over the pixel's samples 0 .. samples - 1, the units of the accumulation
+ *                    buffer (2^-20, each sample clamped to [0, 4096)); even[k] = the same sum over the samples whose index is even; the
+ *                    pads are written as 0.  The records are a buffer of their own: the accumulation API neither sees nor disturbs it.
+ *   the rule         exact, in integers of unlimited width (128 bits suffice for EVERY bit pattern of a record), per pixel, no neighbourhood:
+ *                      e = sum over k of |2 * even[k] - sum[k]|      m = sum over k of sum[k]      n = samples
+ *                      converged  <=>  n >= 2  and  e * 2^16 <= tolerance * (m + n * MIRT_ADAPT_FLOOR)
+ *                      active     <=>  n < max_samples  and  (n < min_samples  or  not converged)
+ *                    `tolerance` is a relative error in units of 2^-16: the difference of the even and the odd half against the mean.
+ *                    MIRT_ADAPT_FLOOR is 0.125 of radiance per sample, summed over the channels: it keeps dark, noisy pixels from
+ *                    taking every sample.  mirt_adapt_active is that rule for one record, HOST ONLY (no device, no context; *out = 1 or 0;
+ *                    MIRT_ERR_NULL_POINTER for a null pointer): the device evaluates the same function, so the two agree on every record.
+ *   a step           two stages on `hip_stream` (NULL = the context's stream), no host synchronisation.  Select: the rule for every
+ *                    record (adapt_select_kernel), the indices of the active records in ASCENDING order into a list in device memory
+ *                    and their count into a device word (a block scan: adapt_scan_kernel, adapt_compact_kernel); the same stage adds
+ *                    count * spp to a 64-bit device counter.  Render (adapt_pixels_kernel<HOSEK,BVH>: lane = list entry, one wave per block,
+ *                    the grid sized for all pixels, blocks beyond the count return at once): every listed pixel receives exactly
+ *                    params->spp further samples, indices samples .. samples + spp - 1 of its own stream -- the renderer's sample for the
+ *                    pixel's ABSOLUTE index x + y * width, whatever band the buffer covers.  A pixel may therefore overshoot max_samples
+ *                    by less than spp.  A record's place is the pixel's place in the compact band (row-major, mirt_params_out_row_index).
+ *   of MirtParams    a step reads width, height, the row fields, spp, num_bounces, seed and of flags MIRT_FLAG_SKY_HOSEK and
+ *                    MIRT_FLAG_NO_GRID (the flat scan of the table, the comparison build); sample_begin is ignored, schedule hints
+ *                    (MIRT_FLAG_KERNEL_STRIP / _POOL, _TEXEL_TILES, _FAST_MATH) are ignored; the resolve flags matter to the resolve only.
+ *   errors of a step MIRT_ERR_NULL_POINTER: ctx, params or adapt is null;  MIRT_ERR_NO_SCENE: no scene, or not a MIRT_SCENE_HBM one;
+ *                    MIRT_ERR_BAD_MODE: mode is not MIRT_MODE_PT, adapt->flags != 0, or a counting flag (MIRT_FLAG_COUNT_WORK, _COUNT_GRID);
+ *                    MIRT_ERR_FRAME_SPP: frame_spp != 0 (a pixel's samples must be independent);  MIRT_ERR_SPP_RANGE: spp is odd (the two
+ *                    halves grow together), or max_samples > MIRT_MAX_SPP_PER_CALL;  MIRT_ERR_OUT_BUFFER: no buffer, or another width or
+ *                    row count than the reset's;  every other check and code is that of a path-traced render on that scene.  A refused
+ *                    call queues nothing and writes nothing.
+ *   ordering         a step is ordered against set_scene*, update_spheres* and set_spheres* the way radiance queries are (they wait for
+ *                    the device).  Steps, resolves, reads and writes of one context are ordered among themselves by the caller (one
+ *                    stream); the blocking calls wait for the last step first.  The launch ring, MirtStats and the accumulation are
+ *                    untouched; mirt_ctx_last_kernel names the render kernel; mirt_ctx_synchronize and mirt_ctx_destroy wait for a step.
+ *   mirt_ctx_adapt_reset           sizes the buffer for the rows `params` selects and clears it, records, counters and list: the rules of
+ *                                  mirt_ctx_accum_reset (bands and tile partitions included).  The list, its count and the select
+ *                                  stage's storage are sized here, belong to the context and only grow: a step allocates nothing.
+ *   mirt_ctx_adapt_step_device     one step, as above.
+ *   mirt_ctx_adapt_resolve_device  adapt_resolve_kernel: per pixel the resolve of sum[k] over ITS samples, tone curves per params->flags,
+ *                                  RGBA8 into device memory on `hip_stream`; a pixel with samples == 0 is black, A = 255.  MIRT_ERR_NO_SCENE
+ *                                  before the first step since the reset, MIRT_ERR_OUT_BUFFER if out_len < pixels * 4.
+ *   mirt_ctx_adapt_resolve         the same into HOST memory; blocking.
+ *   mirt_ctx_adapt_read / _write   blocking copies of the records to / from the host (len in records, at least / exactly the buffer's
+ *                                  pixels: MIRT_ERR_OUT_BUFFER otherwise; MIRT_ERR_NO_SCENE without a buffer): checkpoints and tests.
+ *   mirt_ctx_adapt_list_read       blocking: the list of the LAST step and its count, like mirt_ctx_trace_order_read.  MIRT_ERR_NO_SCENE before
+ *                                  the first step since the reset, MIRT_ERR_OUT_BUFFER if len < count (*count is set all the same).
+ *   mirt_ctx_adapt_stats           blocking: pixels of the buffer, `active` = the count of the last step, steps and samples added since the
+ *                                  reset (the device counter), kernel_ms of the last step, select through render (0 with timing off).
+ * A stopping rule makes the mean of a stopped pixel slightly biased, and a moved world or camera makes the records stale: reset. */
+typedef struct MirtAdaptPixel { uint64_t sum[3]; uint64_t even[3]; uint32_t samples; uint32_t _pad0; uint64_t _pad1; } MirtAdaptPixel; /* 64 B */
+typedef struct MirtAdaptParams { uint32_t min_samples, max_samples, tolerance, flags; } MirtAdaptParams;                               /* 16 B */
+typedef struct MirtAdaptStats { uint64_t pixels, total_samples; uint32_t active, steps; double kernel_ms; } MirtAdaptStats;            /* 32 B */
+#define MIRT_ADAPT_FLOOR (1u << 17)
+int mirt_adapt_active(const MirtAdaptPixel* pixel, const MirtAdaptParams* adapt, uint32_t* out);
+int mirt_ctx_adapt_reset(MirtContext* ctx, const MirtParams* params);
+int mirt_ctx_adapt_step_device(MirtContext* ctx, const MirtParams* params, const MirtAdaptParams* adapt, void* hip_stream);
+int mirt_ctx_adapt_resolve_device(MirtContext* ctx, const MirtParams* params, void* d_out_rgba8, size_t out_len, void* hip_stream);
+int mirt_ctx_adapt_resolve(MirtContext* ctx, const MirtParams* params, uint8_t* out_rgba8, size_t out_len);
+int mirt_ctx_adapt_read(MirtContext* ctx, MirtAdaptPixel* out, size_t len);
+int mirt_ctx_adapt_write(MirtContext* ctx, const MirtAdaptPixel* in, size_t len);
+int mirt_ctx_adapt_list_read(MirtContext* ctx, uint32_t* list, size_t len, uint32_t* count);
+int mirt_ctx_adapt_stats(MirtContext* ctx, MirtAdaptStats* out);
+
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE
  * expansions over ALL 2^32 binary32 bit patterns.  Writes the two mismatch counts (sqrt, 1/x);
@@ -851,6 +918,9 @@ static_assert(sizeof(MirtFeaturePixel) == 32, "MirtFeaturePixel is two 16-byte s
 static_assert(sizeof(MirtRadianceRay) == 32, "MirtRadianceRay is two 16-byte loads");
 static_assert(sizeof(MirtRadiance) == 32, "MirtRadiance is two 16-byte stores");
 static_assert(sizeof(MirtRadianceParams) == 24, "MirtRadianceParams is four u32 and a u64");
+static_assert(sizeof(MirtAdaptPixel) == 64, "MirtAdaptPixel is four 16-byte accesses");
+static_assert(sizeof(MirtAdaptParams) == 16, "MirtAdaptParams is four u32");
+static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32 and a double");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -865,6 +935,9 @@ _Static_assert(sizeof(MirtFeaturePixel) == 32, "MirtFeaturePixel is two 16-byte 
 _Static_assert(sizeof(MirtRadianceRay) == 32, "MirtRadianceRay is two 16-byte loads");
 _Static_assert(sizeof(MirtRadiance) == 32, "MirtRadiance is two 16-byte stores");
 _Static_assert(sizeof(MirtRadianceParams) == 24, "MirtRadianceParams is four u32 and a u64");
+_Static_assert(sizeof(MirtAdaptPixel) == 64, "MirtAdaptPixel is four 16-byte accesses");
+_Static_assert(sizeof(MirtAdaptParams) == 16, "MirtAdaptParams is four u32");
+_Static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32 and a double");
 #endif
 
 #endif /* MIRT_H */

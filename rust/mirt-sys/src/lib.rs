@@ -265,6 +265,41 @@ pub struct MirtRadiance {
     pub _pad: u32,
 }
 
+/// One pixel of the adaptive buffer (`mirt_ctx_adapt_*`): the exact sums of all its samples and of its even-indexed samples, 2^-20 units.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtAdaptPixel {
+    pub sum: [u64; 3],
+    pub even: [u64; 3],
+    pub samples: u32,
+    pub _pad0: u32,
+    pub _pad1: u64,
+}
+
+/// The stopping rule of an adaptive step: `tolerance` is a relative error in units of 2^-16; `flags` must be 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtAdaptParams {
+    pub min_samples: u32,
+    pub max_samples: u32,
+    pub tolerance: u32,
+    pub flags: u32,
+}
+
+/// `mirt_ctx_adapt_stats`: the buffer's pixels, samples added since the reset, the last step's count, steps since the reset, its time.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtAdaptStats {
+    pub pixels: u64,
+    pub total_samples: u64,
+    pub active: u32,
+    pub steps: u32,
+    pub kernel_ms: f64,
+}
+
+/// The rule's floor: 0.125 of radiance per sample, summed over the channels, in 2^-20 units.
+pub const MIRT_ADAPT_FLOOR: u32 = 1 << 17;
+
 /// What a `mirt_ctx_trace_radiance*` call traces: samples `sample_begin .. sample_begin + spp - 1` of every ray's stream.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -401,6 +436,16 @@ extern "C" {
     pub fn mirt_ctx_accum_read(ctx: *mut MirtContext, out_sums: *mut u64, out_len_u64: usize) -> c_int;
     pub fn mirt_ctx_accum_frame_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_ctx_accum_frame(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
+    // adaptive sampling for progressive frames of a MIRT_SCENE_HBM scene (include/mirt.h: mirt_ctx_adapt_*)
+    pub fn mirt_adapt_active(pixel: *const MirtAdaptPixel, adapt: *const MirtAdaptParams, out: *mut u32) -> c_int;
+    pub fn mirt_ctx_adapt_reset(ctx: *mut MirtContext, params: *const MirtParams) -> c_int;
+    pub fn mirt_ctx_adapt_step_device(ctx: *mut MirtContext, params: *const MirtParams, adapt: *const MirtAdaptParams, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ctx_adapt_resolve_device(ctx: *mut MirtContext, params: *const MirtParams, d_out_rgba8: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ctx_adapt_resolve(ctx: *mut MirtContext, params: *const MirtParams, out_rgba8: *mut u8, out_len: usize) -> c_int;
+    pub fn mirt_ctx_adapt_read(ctx: *mut MirtContext, out: *mut MirtAdaptPixel, len: usize) -> c_int;
+    pub fn mirt_ctx_adapt_write(ctx: *mut MirtContext, input: *const MirtAdaptPixel, len: usize) -> c_int;
+    pub fn mirt_ctx_adapt_list_read(ctx: *mut MirtContext, list: *mut u32, len: usize, count: *mut u32) -> c_int;
+    pub fn mirt_ctx_adapt_stats(ctx: *mut MirtContext, out: *mut MirtAdaptStats) -> c_int;
     pub fn mirt_ctx_selftest_math(ctx: *mut MirtContext, out_mismatches: *mut u64) -> c_int;
     pub fn mirt_render(scene: *const MirtScene, params: *const MirtParams, device: c_int, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_rgba8_to_rgb8(rgba: *const u8, n_pixels: usize, rgb: *mut u8) -> c_int;

@@ -1,0 +1,242 @@
+#!/usr/bin/env python3
+"""Adaptive-sampling rates (mirt_ctx_adapt_*): one JSON line per case, APPENDED to profiles/r16_adaptive_rates.jsonl
+and printed.
+
+Worlds: the RTIOW-style fields of tests/hbm_worlds.py at 484 and at 1 M spheres (--spheres), set with MIRT_SCENE_HBM, the tree built
+on the device, seen at 1920 x 1080 with 8 bounces.  Cases (--cases, any of a,b,c), every one in alternating windows in ONE process,
+the median of --reps windows after a warm-up of each variant, every window's figure beside it:
+  a  adaptive against uniform.  `uniform`: mirt_ctx_accum_add of --max-spp samples in one launch (what the library offered before).
+     `adaptive_<tolerance>`: mirt_ctx_adapt_step_device in steps of --step until a step lists nothing (the host reads the count after
+     every step, as Raytracer.render_adaptive does), min_samples = the step, max_samples = --max-spp, for every --tolerances entry.
+     A window is ONE such run from cleared records, host clock around it, ending in a synchronise; the resets are outside.  Reported:
+     time, samples taken, and both as ratios to uniform; for the adaptive runs also the sum of the steps' own device times.
+  b  the price of the machinery: tolerance 0 and min = max = --machinery-spp, so every pixel is in every step, against mirt_ctx_accum_add
+     of the same samples in the same steps.  Windows of untimed launches back to back between two device events on one torch stream.
+     The sums are compared once.  (The split into select and render comes from a kernel trace, a run of its own: --fold-trace.)
+  c  mirt_ctx_adapt_resolve_device against resolve_accum_kernel (mirt_ctx_accum_frame_device with spp = 0), the same kind of windows.
+--fold-trace FILE   no device: reads the *_kernel_trace.csv of a rocprofv3 --kernel-trace --stats run and appends one line with the calls
+                    and the median time of every adapt_*, render_pt_hbm* and resolve_accum kernel in it.
+
+Run every world and case as a process of its own under its own time limit, e.g.
+  timeout -k 10 300 python tools/adaptive_rates.py --spheres 484 --cases a
+usage: python tools/adaptive_rates.py [--spheres 484,1000000] [--cases a,b,c] [--reps 5] [--max-spp 256] [--step 8] [--tolerances 4096,1024]
+                                      [--machinery-spp 32] [--window-ms 200] [--out profiles/r16_adaptive_rates.jsonl] [--fold-trace FILE]"""
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (str(ROOT), str(ROOT / "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+W, H = 1920, 1080
+BOUNCES = 8
+
+
+def fold_trace(path: str) -> dict:
+    durations = {}
+    with open(path, newline="") as f:
+        for r in csv.DictReader(f):
+            name = r["Kernel_Name"]
+            if "adapt_" in name or "render_pt_hbm" in name or "resolve_accum" in name:
+                short = name.replace("mirt::exact_build::", "").replace("void ", "").split("(")[0]
+                durations.setdefault(short, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    return {"case": "kernel_trace", "source": Path(path).name,
+            "kernels": {k: {"calls": len(v), "median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
+                        for k, v in durations.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--spheres", default="484,1000000")
+    ap.add_argument("--cases", default="a,b,c")
+    ap.add_argument("--max-spp", type=int, default=256)
+    ap.add_argument("--step", type=int, default=8)
+    ap.add_argument("--tolerances", default="4096,1024")
+    ap.add_argument("--machinery-spp", type=int, default=32)
+    ap.add_argument("--window-ms", type=float, default=200.0)
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "r16_adaptive_rates.jsonl"))
+    ap.add_argument("--fold-trace", default="")
+    ap.add_argument("--note", default="", help="copied into every line")
+    a = ap.parse_args()
+
+    def emit(line):
+        if a.note:
+            line["note"] = a.note
+        print(json.dumps(line), flush=True)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+
+    if a.fold_trace:
+        emit(fold_trace(a.fold_trace))
+        return
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("adaptive_rates.py measures on the GPU: no device visible")
+    import weekend_raytracer_wgpu_amd as m
+    from hbm_worlds import look, rtiow_field, scene_from_arrays
+    npix = W * H
+    cases = [c for c in a.cases.split(",") if c]
+    stream = torch.cuda.Stream(device="cuda:0")
+    d_img = torch.zeros(4 * npix, dtype=torch.uint8, device="cuda:0")
+
+    def window(fn, count):
+        """`count` calls back to back between two device events on the torch stream -> ms per call."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(count):
+            fn()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / count
+
+    for n in [int(x) for x in a.spheres.split(",") if x]:
+        arr, mats, tex = rtiow_field(n, seed=n)
+        eye = (13, 2, 3) if n < 5000 else (40, 6, 30)                 # the views of tools/radiance_rates.py
+        sd = scene_from_arrays(look(W, H, eye, (0, 0, 0), vfov=25 if n < 5000 else 35), arr, mats, tex)
+        ctx = m.Context(0)
+        ctx.set_scene(sd, hbm=True, bvh="device")
+        base = {"world": f"rtiow_field({n})", "n_spheres": n, "max_depth": ctx.bvh_info()["plan"]["max_depth"], "width": W, "height": H,
+                "num_bounces": BOUNCES, "reps": a.reps}
+        pt = lambda spp: m.make_params(W, H, spp, mode=m.MIRT_MODE_PT, num_bounces=BOUNCES)
+
+        if "a" in cases:
+            p_step, p_all = pt(a.step), pt(a.max_spp)
+
+            def uniform():
+                ctx.accum_reset(p_all)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                ctx.accum_add(p_all)
+                ctx.synchronize()
+                return {"ms": (time.perf_counter() - t0) * 1e3, "samples": npix * a.max_spp, "kernel": ctx.last_kernel()}
+
+            def adaptive(tol):
+                adapt = m.make_adapt_params(a.step, a.max_spp, tol)
+                ctx.adapt_reset(p_step)
+                ctx.synchronize()
+                device_ms, active = 0.0, []
+                t0 = time.perf_counter()
+                while True:
+                    ctx.adapt_step(p_step, adapt)
+                    st = ctx.adapt_stats()                          # waits for the step: the host must know whether to go on
+                    device_ms += st["kernel_ms"]
+                    active.append(st["active"])
+                    if st["active"] == 0:
+                        break
+                ms = (time.perf_counter() - t0) * 1e3
+                return {"ms": ms, "samples": st["total_samples"], "steps": st["steps"], "device_ms": device_ms, "active": active, "kernel": ctx.last_kernel()}
+
+            runs = {"uniform": uniform}
+            for tol in [int(x) for x in a.tolerances.split(",") if x]:
+                runs[f"adaptive_{tol}"] = lambda tol=tol: adaptive(tol)
+            last = {k: fn() for k, fn in runs.items()}                 # warm-up
+            t = {k: [] for k in runs}
+            for _ in range(a.reps):
+                for k, fn in runs.items():
+                    last[k] = fn()
+                    t[k].append(last[k]["ms"])
+            med = {k: statistics.median(v) for k, v in t.items()}
+            counts = ctx.adapt_read()["samples"]                        # of the last adaptive run
+            emit({**base, "case": "a_adaptive_against_uniform", "max_spp": a.max_spp, "step": a.step, "min_samples": a.step,
+                  "ms": {k: round(v, 2) for k, v in med.items()}, "samples": {k: int(last[k]["samples"]) for k in runs},
+                  "time_over_uniform": {k: round(med[k] / med["uniform"], 3) for k in runs},
+                  "samples_over_uniform": {k: round(last[k]["samples"] / last["uniform"]["samples"], 4) for k in runs},
+                  "steps": {k: last[k]["steps"] for k in runs if "steps" in last[k]},
+                  "device_ms_of_the_steps": {k: round(last[k]["device_ms"], 2) for k in runs if "device_ms" in last[k]},
+                  "active_per_step": {k: last[k]["active"] for k in runs if "active" in last[k]},
+                  "last_run_pixels_at_max": int((counts >= a.max_spp).sum()), "last_run_median_samples": int(np.median(counts)),
+                  "kernels": {k: last[k]["kernel"] for k in runs}, "all_ms": {k: [round(x, 2) for x in v] for k, v in t.items()}})
+
+        if "b" in cases:
+            n_steps = a.machinery_spp // a.step
+            p_step = pt(a.step)
+            adapt = m.make_adapt_params(a.machinery_spp, a.machinery_spp, 0)
+
+            def run_adapt():
+                for _ in range(n_steps):
+                    ctx.adapt_step(p_step, adapt, stream=stream.cuda_stream)
+
+            def run_accum():
+                for _ in range(n_steps):
+                    ctx.accum_add(p_step, stream=stream.cuda_stream)
+
+            # the same sums, once (timing on: the launches carry their events)
+            ctx.adapt_reset(p_step)
+            ctx.accum_reset(p_step)
+            run_adapt()
+            run_accum()
+            torch.cuda.synchronize()
+            same = bool(np.array_equal(ctx.adapt_read()["sum"], ctx.accum_read(p_step).reshape(-1, 3)))
+            kernels = {}
+            ctx.adapt_step(p_step, adapt, stream=stream.cuda_stream)
+            kernels["adapt"] = ctx.last_kernel()
+            ctx.accum_add(p_step, stream=stream.cuda_stream)
+            kernels["accum"] = ctx.last_kernel()
+            torch.cuda.synchronize()
+            ctx.set_timing(False)
+
+            def fresh(fn, reset):
+                """one window: cleared buffers (outside the events), then n_steps steps"""
+                reset(p_step)
+                torch.cuda.synchronize()
+                return window(fn, 1)
+
+            variants = {"adapt": (run_adapt, ctx.adapt_reset), "accum": (run_accum, ctx.accum_reset)}
+            for fn, reset in variants.values():
+                fresh(fn, reset)
+            t = {k: [] for k in variants}
+            for _ in range(a.reps):
+                for k, (fn, reset) in variants.items():
+                    t[k].append(fresh(fn, reset))
+            ctx.set_timing(True)
+            med = {k: statistics.median(v) for k, v in t.items()}
+            emit({**base, "case": "b_price_of_the_machinery", "samples_per_pixel": a.machinery_spp, "step": a.step, "steps": n_steps,
+                  "ms": {k: round(v, 3) for k, v in med.items()}, "adapt_over_accum": round(med["adapt"] / med["accum"], 3), "same_sums": same,
+                  "kernels": kernels, "all_ms": {k: [round(x, 3) for x in v] for k, v in t.items()}})
+
+        if "c" in cases:
+            p = pt(a.step)
+            adapt = m.make_adapt_params(a.step, a.step, 0)
+            ctx.adapt_reset(p)
+            ctx.accum_reset(p)
+            ctx.adapt_step(p, adapt)
+            ctx.accum_add(p)
+            ctx.synchronize()
+            p0 = pt(0)
+            launch = {"adapt_resolve": lambda: ctx.adapt_resolve_device(p, d_img.data_ptr(), stream=stream.cuda_stream),
+                      "accum_resolve": lambda: ctx.accum_frame_device(p0, d_img.data_ptr(), stream=stream.cuda_stream)}
+            img = {}
+            ctx.set_timing(False)
+            counts = {}
+            for k, fn in launch.items():
+                window(fn, 1)
+                img[k] = d_img.cpu().numpy().copy()
+                counts[k] = max(1, int(round(a.window_ms / max(window(fn, 4), 1e-3))))
+                window(fn, counts[k])
+            t = {k: [] for k in launch}
+            for _ in range(a.reps):
+                for k, fn in launch.items():
+                    t[k].append(window(fn, counts[k]))
+            ctx.set_timing(True)
+            med = {k: statistics.median(v) for k, v in t.items()}
+            emit({**base, "case": "c_resolve", "us": {k: round(v * 1e3, 1) for k, v in med.items()},
+                  "adapt_over_accum": round(med["adapt_resolve"] / med["accum_resolve"], 3), "same_image": bool(np.array_equal(img["adapt_resolve"], img["accum_resolve"])),
+                  "bytes_read_per_pixel": {"adapt_resolve": 48, "accum_resolve": 24}, "launches_per_window": counts,
+                  "all_us": {k: [round(x * 1e3, 1) for x in v] for k, v in t.items()}})
+        ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -51,6 +51,9 @@ MIRT_RADIANCE_POOL = 1 << 6             # bit 5 is unassigned
 MIRT_RAY_SORT_ORIGIN_BITS = 5
 MIRT_RAY_SORT_DIRECTION_BITS = 8
 
+# mirt_ctx_adapt_*: the rule's floor, 0.125 of radiance per sample summed over the channels, in 2^-20 units
+MIRT_ADAPT_FLOOR = 1 << 17
+
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
 MIRT_NODE_RCCL = 1 << 0
@@ -211,6 +214,22 @@ class MirtRadianceParams(C.Structure):
     _fields_ = [("spp", C.c_uint32), ("sample_begin", C.c_uint32), ("num_bounces", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class MirtAdaptPixel(C.Structure):
+    _fields_ = [("sum", C.c_uint64 * 3), ("even", C.c_uint64 * 3), ("samples", C.c_uint32), ("_pad0", C.c_uint32), ("_pad1", C.c_uint64)]
+
+
+class MirtAdaptParams(C.Structure):
+    _fields_ = [("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("tolerance", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MirtAdaptStats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("total_samples", C.c_uint64), ("active", C.c_uint32), ("steps", C.c_uint32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "total_samples": int(self.total_samples), "active": int(self.active), "steps": int(self.steps),
+                "kernel_ms": self.kernel_ms}
+
+
 class MirtRayStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("rays", C.c_uint64), ("sphere_tests", C.c_uint64), ("roots", C.c_uint64),
                 ("hits", C.c_uint64), ("nodes", C.c_uint64), ("wave_nodes", C.c_uint64)]
@@ -278,6 +297,15 @@ SYMBOLS = {
     "mirt_ctx_accum_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mirt_ctx_accum_frame_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),
     "mirt_ctx_accum_frame": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
+    "mirt_adapt_active": (C.c_int, [_P(MirtAdaptPixel), _P(MirtAdaptParams), _P(C.c_uint32)]),
+    "mirt_ctx_adapt_reset": (C.c_int, [C.c_void_p, _P(MirtParams)]),
+    "mirt_ctx_adapt_step_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtAdaptParams), C.c_void_p]),
+    "mirt_ctx_adapt_resolve_device": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mirt_ctx_adapt_resolve": (C.c_int, [C.c_void_p, _P(MirtParams), C.c_void_p, C.c_size_t]),
+    "mirt_ctx_adapt_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mirt_ctx_adapt_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mirt_ctx_adapt_list_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint32)]),
+    "mirt_ctx_adapt_stats": (C.c_int, [C.c_void_p, _P(MirtAdaptStats)]),
     "mirt_ctx_selftest_math": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "mirt_ctx_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "mirt_ctx_frame_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -247,6 +247,37 @@ def radiance_ray_records(rays) -> np.ndarray:
     raise ValueError(f"rays must be a one-dimensional RADIANCE_RAY_DTYPE array or uint32 [n, 8], not {rays.dtype} of shape {rays.shape}")
 
 
+# MirtAdaptPixel as a numpy record (64 bytes): what adapt_read returns and adapt_write takes
+ADAPT_PIXEL_DTYPE = np.dtype([("sum", "<u8", (3,)), ("even", "<u8", (3,)), ("samples", "<u4"), ("_pad0", "<u4"), ("_pad1", "<u8")])
+
+
+def make_adapt_params(min_samples: int, max_samples: int, tolerance: int) -> _abi.MirtAdaptParams:
+    """MirtAdaptParams: a pixel is sampled while it holds fewer than max_samples and either fewer than min_samples or its even and odd
+    halves differ by more than tolerance x 2^-16 of its mean (include/mirt.h has the exact rule)."""
+    for name, v in (("min_samples", min_samples), ("max_samples", max_samples), ("tolerance", tolerance)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    a = _abi.MirtAdaptParams()
+    a.min_samples, a.max_samples, a.tolerance, a.flags = int(min_samples), int(max_samples), int(tolerance), 0
+    return a
+
+
+def adapt_active(records, adapt: _abi.MirtAdaptParams) -> np.ndarray:
+    """mirt_adapt_active for every record of an ADAPT_PIXEL_DTYPE array -> bool [n]: the rule a step's select stage evaluates on the
+    device.  Needs no device."""
+    if not isinstance(records, np.ndarray) or records.dtype != ADAPT_PIXEL_DTYPE:
+        raise ValueError("records must be an ADAPT_PIXEL_DTYPE array")
+    if not isinstance(adapt, _abi.MirtAdaptParams):
+        raise ValueError(f"adapt must be a MirtAdaptParams (make_adapt_params builds one), not {type(adapt).__name__}")
+    recs = np.ascontiguousarray(records).reshape(-1)
+    out = np.zeros(len(recs), bool)
+    f, flag = lib().mirt_adapt_active, C.c_uint32()
+    for i in range(len(recs)):
+        check(f(C.cast(C.c_void_p(recs.ctypes.data + 64 * i), C.POINTER(_abi.MirtAdaptPixel)), C.byref(adapt), C.byref(flag)))
+        out[i] = flag.value != 0
+    return out.reshape(records.shape)
+
+
 def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort=False, pool=False) -> _abi.MirtRadianceParams:
     for name, v in (("spp", spp), ("sample_begin", sample_begin), ("num_bounces", num_bounces)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
@@ -556,6 +587,59 @@ class Context:
         out = np.empty((params_out_rows(params), params.width, 4), dtype=np.uint8)
         check(lib().mirt_ctx_accum_frame(self._h, C.byref(params), out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
+
+    # ---- adaptive sampling for progressive frames of the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+    def adapt_reset(self, params: _abi.MirtParams) -> None:
+        """mirt_ctx_adapt_reset: one cleared 64-byte record per pixel of the rows `params` selects (a buffer apart from accum_*)."""
+        check(lib().mirt_ctx_adapt_reset(self._h, C.byref(_check_params(params))))
+
+    def adapt_step(self, params: _abi.MirtParams, adapt: _abi.MirtAdaptParams, stream: Optional[int] = None) -> None:
+        """mirt_ctx_adapt_step_device: one adaptive step on `stream` (see _stream_arg), no host synchronisation -- the rule for every
+        record, the active pixels listed in ascending order, then exactly params.spp (even) further samples for every listed pixel."""
+        if not isinstance(adapt, _abi.MirtAdaptParams):
+            raise ValueError(f"adapt must be a MirtAdaptParams (make_adapt_params builds one), not {type(adapt).__name__}")
+        check(lib().mirt_ctx_adapt_step_device(self._h, C.byref(_check_params(params)), C.byref(adapt), _stream_arg(stream)))
+
+    def adapt_resolve(self, params: _abi.MirtParams) -> np.ndarray:
+        """mirt_ctx_adapt_resolve: every pixel's mean over ITS samples, tone curves per params.flags -> uint8 [rows, width, 4]; blocking."""
+        params = _check_params(params)
+        out = np.empty((max(params_out_rows(params), 0), params.width, 4), dtype=np.uint8)
+        check(lib().mirt_ctx_adapt_resolve(self._h, C.byref(params), out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def adapt_resolve_device(self, params: _abi.MirtParams, d_out: int, stream: Optional[int] = None, nbytes: Optional[int] = None) -> None:
+        """mirt_ctx_adapt_resolve_device: the same into device memory at `d_out` (rows x width x 4 bytes unless `nbytes` says more)
+        on `stream`; no host synchronisation."""
+        params = _check_params(params)
+        if nbytes is None:
+            nbytes = params_out_rows(params) * params.width * 4
+        check(lib().mirt_ctx_adapt_resolve_device(self._h, C.byref(params), C.c_void_p(_check_address("d_out", d_out)), int(nbytes), _stream_arg(stream)))
+
+    def adapt_read(self) -> np.ndarray:
+        """mirt_ctx_adapt_read: the records -> an ADAPT_PIXEL_DTYPE array [pixels], the pixels of the band row-major; blocking."""
+        out = np.zeros(max(self.adapt_stats()["pixels"], 1), ADAPT_PIXEL_DTYPE)
+        check(lib().mirt_ctx_adapt_read(self._h, C.c_void_p(out.ctypes.data), out.size))
+        return out[:self.adapt_stats()["pixels"]]
+
+    def adapt_write(self, records: np.ndarray) -> None:
+        """mirt_ctx_adapt_write: replaces the records (an ADAPT_PIXEL_DTYPE array with one record per pixel of the buffer); blocking."""
+        if not isinstance(records, np.ndarray) or records.dtype != ADAPT_PIXEL_DTYPE:
+            raise ValueError("records must be an ADAPT_PIXEL_DTYPE array")
+        recs = np.ascontiguousarray(records).reshape(-1)
+        check(lib().mirt_ctx_adapt_write(self._h, C.c_void_p(recs.ctypes.data) if len(recs) else None, len(recs)))
+
+    def adapt_list(self) -> np.ndarray:
+        """mirt_ctx_adapt_list_read: the pixels the last step sampled -> uint32 [count], ascending places in the band; blocking."""
+        n = C.c_uint32()
+        buf = np.zeros(max(self.adapt_stats()["pixels"], 1), np.uint32)
+        check(lib().mirt_ctx_adapt_list_read(self._h, C.c_void_p(buf.ctypes.data), buf.size, C.byref(n)))
+        return buf[:n.value].copy()
+
+    def adapt_stats(self) -> dict:
+        """mirt_ctx_adapt_stats: waits for the last step -> {"pixels", "total_samples", "active", "steps", "kernel_ms"}."""
+        st = _abi.MirtAdaptStats()
+        check(lib().mirt_ctx_adapt_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def selftest_math(self) -> tuple:
         """(sqrt mismatches, reciprocal mismatches) of the fast sequences vs IEEE over all 2^32 floats."""

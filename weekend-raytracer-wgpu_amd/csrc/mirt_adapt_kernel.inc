@@ -1,0 +1,198 @@
+// mirt_adapt_kernel.inc -- adaptive sampling for progressive frames of a resident MIRT_SCENE_HBM scene (mirt_ctx_adapt_*; include/mirt.h,
+// DESIGN.md 10.12).  Included once by mirt_kernels.hip behind mirt_radiance_pool_kernel.inc, exact build only: there is no fast_build::
+// copy, no counting build and no dispenser.  The context keeps one MirtAdaptPixel per pixel (64 bytes: three u64 sums, the three sums of
+// the even-indexed samples, samples, pads), 16-byte aligned: a record is four 16-byte accesses {sum0, sum1} {sum2, even0} {even1, even2}
+// {samples, 0, 0, 0}.
+//
+// A step is four kernels on one stream:
+//   adapt_select_kernel   lane = record: three 16-byte loads of the sums and one of the count, then the rule of mirt_adapt_rule.h (the
+//                         function mirt_adapt_active runs on the host: 128-bit products).  One flag byte per record, and per block of
+//                         kAdaptSelectThreads records the number of active ones.
+//   adapt_scan_kernel     ONE block: the exclusive prefix sums of the block counts, in place, 1024 at a time with a running carry; thread 0
+//                         then writes the step's count into the head word and adds count x spp to the 64-bit sample counter behind it.
+//   adapt_compact_kernel  lane = record again: a record's place in the list is its block's offset + the active records before it in the
+//                         block (ballot + popcount within the wave, the waves' totals through LDS), so the list is ASCENDING by
+//                         construction and the same whatever order the blocks run in.
+//   adapt_pixels_kernel<HOSEK, BVH>   the shape of radiance_rays_kernel: lane = list entry, 64 consecutive entries per wave, ONE wave per
+//                         block, LDS = stage_scene's image without the tables (the launch's camera, the sky blob) | the wave's traversal
+//                         stacks, 8 KB.  The grid is sized for ALL pixels (the host does not know the count): the count is read as a
+//                         wave-uniform word before anything is staged and blocks beyond it return at once.  A lane loads its record,
+//                         takes spp samples n .. n + spp - 1 of ITS pixel's stream -- generate_primary with the camera from LDS as in
+//                         the strip body, for the pixel's absolute (x, y), then path_radiance with the source render_pt_hbm_kernel gives
+//                         it -- adds every sample's three fixed-point values to `sum` and those of even-indexed samples to `even`, and
+//                         writes the record back with four 16-byte stores.  Lanes of the last wave beyond the count load nothing, take
+//                         part in the wave's loops with their tests masked off and store nothing.
+//   adapt_resolve_kernel  per pixel resolve_channel(sum[k], samples, flags); samples == 0: black, A = 255.
+
+typedef uint32_t adapt_u4 __attribute__((ext_vector_type(4)));        // a record's quarter, 16-byte aligned (the buffer is the context's own)
+
+constexpr uint32_t kAdaptThreads = 64;              // adapt_pixels_kernel: one wave per block, as kRadianceThreads
+constexpr uint32_t kAdaptSelectThreads = 256;       // adapt_select_kernel / adapt_compact_kernel: records per block
+constexpr uint32_t kAdaptScanThreads = 1024;
+
+MIRT_DEV unsigned long long adapt_u64(uint32_t lo, uint32_t hi) { return (unsigned long long)lo | ((unsigned long long)hi << 32); }
+
+__global__ __launch_bounds__(kAdaptSelectThreads) void adapt_select_kernel(const adapt_u4* recs, uint32_t n, MirtAdaptParams P, unsigned char* flags,
+                                                                           uint32_t* block_counts)
+{
+    __shared__ uint32_t wave_count[kAdaptSelectThreads / 64u];
+    const uint64_t i = (uint64_t)blockIdx.x * kAdaptSelectThreads + threadIdx.x;
+    bool active = false;
+    if (i < n) {
+        const adapt_u4 q0 = recs[4u * i], q1 = recs[4u * i + 1u], q2 = recs[4u * i + 2u], q3 = recs[4u * i + 3u];
+        const uint64_t sum[3] = { adapt_u64(q0.x, q0.y), adapt_u64(q0.z, q0.w), adapt_u64(q1.x, q1.y) };
+        const uint64_t even[3] = { adapt_u64(q1.z, q1.w), adapt_u64(q2.x, q2.y), adapt_u64(q2.z, q2.w) };
+        active = adapt_active(sum, even, q3.x, P);
+        flags[i] = active ? 1u : 0u;
+    }
+    const unsigned long long mask = ballot_(active);
+    if ((threadIdx.x & 63u) == 0u) wave_count[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < kAdaptSelectThreads / 64u; ++w) t += wave_count[w];
+        block_counts[blockIdx.x] = t;
+    }
+}
+
+// head[0] = the step's count; the 64-bit word at head + 2 = samples added since the reset
+__global__ __launch_bounds__(kAdaptScanThreads) void adapt_scan_kernel(uint32_t* block_counts, uint32_t n_blocks, uint32_t* head, uint32_t spp)
+{
+    __shared__ uint32_t wave_total[kAdaptScanThreads / 64u];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n_blocks; base += kAdaptScanThreads) {      // (base stays below 2^24: at most 2^32 / 256 blocks)
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < n_blocks ? block_counts[i] : 0u;
+        uint32_t incl = v;
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63u) wave_total[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < kAdaptScanThreads / 64u; ++w) {
+            const uint32_t t = wave_total[w];
+            if (w < wave) before += t;
+            all += t;
+        }
+        if (i < n_blocks) block_counts[i] = carry + before + incl - v;
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u) {
+        head[0] = carry;
+        unsigned long long* total = reinterpret_cast<unsigned long long*>(head + 2);
+        *total += (unsigned long long)carry * spp;
+    }
+}
+
+__global__ __launch_bounds__(kAdaptSelectThreads) void adapt_compact_kernel(const unsigned char* flags, uint32_t n, const uint32_t* block_offsets, uint32_t* list)
+{
+    __shared__ uint32_t wave_count[kAdaptSelectThreads / 64u];
+    const uint64_t i = (uint64_t)blockIdx.x * kAdaptSelectThreads + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const bool active = i < n && flags[i] != 0u;
+    const unsigned long long mask = ballot_(active);
+    if (lane == 0u) wave_count[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (active) {
+        uint32_t at = block_offsets[blockIdx.x] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wave; ++w) at += wave_count[w];
+        list[at] = (uint32_t)i;          // at < the step's count <= n: the offsets are the prefix sums of these very flags
+    }
+}
+
+template <bool HOSEK, bool BVH>
+__global__ __launch_bounds__(kAdaptThreads, 5) void adapt_pixels_kernel(RenderArgs A, adapt_u4* recs, const uint32_t* list, const uint32_t* count_word)
+{
+    constexpr uint32_t SRC = BVH ? kSrcBvh : kSrcHbmFlat;
+    const uint32_t count = __builtin_amdgcn_readfirstlane(*count_word);
+    if (blockIdx.x * kAdaptThreads >= count) return;                   // the whole block (one wave): nothing staged, no barrier met
+    extern __shared__ __align__(16) unsigned char smem[];
+    const SceneLds S = stage_scene<true, false>(A, smem, HOSEK);
+    const GridLds G{};
+    uint32_t* bvh_stack = nullptr;
+    if constexpr (BVH)
+        bvh_stack = reinterpret_cast<uint32_t*>(smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, HOSEK, false)) + (threadIdx.x >> 6) * (kBvhStackBytesPerWave / 4u);      // (one wave per block: + 0)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t slot = blockIdx.x * kAdaptThreads + threadIdx.x;    // < 2^32: the grid covers out_rows x width <= 2^32 - 1 pixels
+    const bool alive = slot < count;
+    const uint64_t pi = alive ? list[slot] : 0u;                       // the record's place in the band; < out_rows x width (adapt_compact_kernel)
+    const uint32_t ci = (uint32_t)pi / A.width;
+    const uint32_t x = (uint32_t)pi - ci * A.width;
+    const uint32_t y = abs_row(A, ci);
+    adapt_u4 q0 = { 0u, 0u, 0u, 0u }, q1 = q0, q2 = q0, q3 = q0;
+    if (alive) { q0 = recs[4u * pi]; q1 = recs[4u * pi + 1u]; q2 = recs[4u * pi + 2u]; q3 = recs[4u * pi + 3u]; }
+    const uint32_t n = q3.x;
+
+    Work<false> work;
+    work.clear();
+    unsigned long long sum_r = adapt_u64(q0.x, q0.y), sum_g = adapt_u64(q0.z, q0.w), sum_b = adapt_u64(q1.x, q1.y);
+    unsigned long long even_r = adapt_u64(q1.z, q1.w), even_g = adapt_u64(q2.x, q2.y), even_b = adapt_u64(q2.z, q2.w);
+    for (uint32_t s = 0; s < A.spp; ++s) {
+        Rng rng;
+        f3 ro, rd;
+        {   // camera constants are re-read from LDS per sample instead of living in 21 VGPRs (strip_kernel_body)
+            const CamRegs C = load_camera(S, A);
+            generate_primary(A, C, x, y, n + s, rng, ro, rd);
+        }
+        const f3 c = path_radiance<false, HOSEK, false, SRC>(A, S, G, alive, rng, ro, rd, work, lane, nullptr, kNoCand, bvh_stack);
+        const unsigned long long fr = to_fixed(c.x), fg = to_fixed(c.y), fb = to_fixed(c.z);
+        sum_r += fr; sum_g += fg; sum_b += fb;
+        if (((n + s) & 1u) == 0u) { even_r += fr; even_g += fg; even_b += fb; }
+    }
+    if (alive) {
+        recs[4u * pi] = adapt_u4{ (uint32_t)sum_r, (uint32_t)(sum_r >> 32), (uint32_t)sum_g, (uint32_t)(sum_g >> 32) };
+        recs[4u * pi + 1u] = adapt_u4{ (uint32_t)sum_b, (uint32_t)(sum_b >> 32), (uint32_t)even_r, (uint32_t)(even_r >> 32) };
+        recs[4u * pi + 2u] = adapt_u4{ (uint32_t)even_g, (uint32_t)(even_g >> 32), (uint32_t)even_b, (uint32_t)(even_b >> 32) };
+        recs[4u * pi + 3u] = adapt_u4{ n + A.spp, 0u, 0u, 0u };
+    }
+}
+
+__global__ __launch_bounds__(256) void adapt_resolve_kernel(const adapt_u4* recs, uint32_t* out, uint64_t n_pixels, uint32_t flags)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pixels; i += (uint64_t)gridDim.x * blockDim.x) {
+        const adapt_u4 q0 = recs[4u * i], q1 = recs[4u * i + 1u], q3 = recs[4u * i + 3u];
+        const uint32_t n = q3.x;
+        uint32_t rgba = 0xff000000u;
+        if (n != 0u)
+            rgba = pack_rgba(resolve_channel(adapt_u64(q0.x, q0.y), n, flags), resolve_channel(adapt_u64(q0.z, q0.w), n, flags),
+                             resolve_channel(adapt_u64(q1.x, q1.y), n, flags));
+        out[i] = rgba;
+    }
+}
+
+// The select stage of a step for n >= 1 records at d_recs: flags [n] bytes, block counts [ceil(n / 256)] words, the list [n] words and the
+// head {count, -, 64-bit sample counter} are the context's (16-byte aligned head and records).
+hipError_t launch_adapt_select(const void* d_recs, uint32_t n, const MirtAdaptParams& adapt, uint32_t spp, unsigned char* d_flags, uint32_t* d_block_counts,
+                               uint32_t* d_list, uint32_t* d_head, hipStream_t stream)
+{
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + kAdaptSelectThreads - 1u) / kAdaptSelectThreads);
+    hipLaunchKernelGGL(adapt_select_kernel, dim3(blocks), dim3(kAdaptSelectThreads), 0, stream, static_cast<const adapt_u4*>(d_recs), n, adapt, d_flags, d_block_counts);
+    hipLaunchKernelGGL(adapt_scan_kernel, dim3(1), dim3(kAdaptScanThreads), 0, stream, d_block_counts, blocks, d_head, spp);
+    hipLaunchKernelGGL(adapt_compact_kernel, dim3(blocks), dim3(kAdaptSelectThreads), 0, stream, d_flags, n, d_block_counts, d_list);
+    return hipGetLastError();
+}
+
+// The render stage: one thread per pixel of the buffer (a.n_units of them), one wave per block; a.lds_bytes = stage_scene's image without
+// the tables + the wave's traversal stacks (BVH build); `a` carries the camera, the tables, the sky, the tree, the row fields, spp,
+// num_bounces and seed_mix as a render launch's does.
+hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, hipStream_t stream)
+{
+    const uint32_t blocks = (uint32_t)(((uint64_t)a.n_units + kAdaptThreads - 1u) / kAdaptThreads);
+    auto k = hosek ? (bvh ? adapt_pixels_kernel<true, true> : adapt_pixels_kernel<true, false>)
+                   : (bvh ? adapt_pixels_kernel<false, true> : adapt_pixels_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(kAdaptThreads), a.lds_bytes, stream, a, static_cast<adapt_u4*>(d_recs), d_list, d_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream)
+{
+    uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    if (blocks == 0) blocks = 1;
+    hipLaunchKernelGGL(adapt_resolve_kernel, dim3(blocks), dim3(256), 0, stream, static_cast<const adapt_u4*>(d_recs), out, n_pixels, flags);
+    return hipGetLastError();
+}

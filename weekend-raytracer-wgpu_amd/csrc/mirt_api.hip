@@ -20,6 +20,7 @@
 #include "../../include/mirt.h"
 #include "mirt_kernels.h"
 #include "mirt_bvh.h"
+#include "mirt_adapt_rule.h"
 
 namespace kx = mirt::exact_build;     // the kernels of the bit-exact build (default)
 namespace kf = mirt::fast_build;      // MIRT_FLAG_FAST_MATH: the same kernels with hardware transcendentals
@@ -506,6 +507,20 @@ struct MirtContext {
     size_t              ray_sort_off_order = 0;    // of the last sorted launch: its permutation in ray_sort.d, [ray_sort_n] uint32
     uint32_t            ray_sort_n = 0;
     bool                ray_sort_any = false;      // a sorted launch has been queued on this context
+
+    // mirt_ctx_adapt_* (DESIGN.md 10.12): the records and the select stage's storage, state of their own like the ray queries'; both grow, never shrink
+    unsigned char*      d_adapt = nullptr;         // [adapt_pixels] MirtAdaptPixel
+    size_t              cap_adapt = 0;
+    unsigned char*      d_adapt_sel = nullptr;     // head {count, -, u64 samples added} | list [pixels] u32 | block counts [ceil(pixels / 256)] u32 | flags [pixels] u8
+    size_t              cap_adapt_sel = 0;
+    size_t              adapt_off_counts = 0, adapt_off_flags = 0;
+    uint64_t            adapt_pixels = 0;
+    uint32_t            adapt_width = 0, adapt_rows = 0;
+    uint32_t            adapt_steps = 0;           // since the reset
+    hipEvent_t          ev_adapt_begin = nullptr, ev_adapt_end = nullptr;   // around the last step (select through render), on its stream
+    bool                adapt_pending = false;     // ev_adapt_end is recorded and nobody has waited for it yet
+    bool                adapt_timed = false;
+    double              adapt_ms = 0.0;
 };
 
 extern "C" {
@@ -714,6 +729,10 @@ void mirt_ctx_destroy(MirtContext* c)
     if (c->frame_stream_b) (void)hipStreamSynchronize(c->frame_stream_b);
     if (!c->untimed_streams.empty()) (void)hipDeviceSynchronize();      // launches without an event may still read the tables freed below
     if (c->trace_pending) (void)hipEventSynchronize(c->ev_trace_end);    // a trace on a caller stream reads them too
+    if (c->adapt_pending) (void)hipEventSynchronize(c->ev_adapt_end);    // ... and so does an adaptive step
+    (void)hipFree(c->d_adapt); (void)hipFree(c->d_adapt_sel);
+    if (c->ev_adapt_begin) (void)hipEventDestroy(c->ev_adapt_begin);
+    if (c->ev_adapt_end) (void)hipEventDestroy(c->ev_adapt_end);
     (void)hipFree(c->d_trace_counters); (void)hipFree(c->d_trace_rays); (void)hipFree(c->d_trace_hits); (void)hipFree(c->ray_sort.d);
     if (c->ev_trace_begin) (void)hipEventDestroy(c->ev_trace_begin);
     if (c->ev_trace_end) (void)hipEventDestroy(c->ev_trace_end);
@@ -1650,6 +1669,7 @@ int mirt_ctx_synchronize(MirtContext* c)
     for (hipStream_t st : c->untimed_streams) HIP_TRY(hipStreamSynchronize(st));      // launches that carried no event (mirt_ctx_set_timing(0))
     c->untimed_streams.clear();
     if (c->trace_pending) HIP_TRY(hipEventSynchronize(c->ev_trace_end));              // a ray query on a caller stream (mirt_ctx_trace_stats folds it)
+    if (c->adapt_pending) HIP_TRY(hipEventSynchronize(c->ev_adapt_end));              // an adaptive step on a caller stream (mirt_ctx_adapt_stats folds it)
     return MIRT_OK;
 }
 
@@ -2237,6 +2257,208 @@ int mirt_ctx_accum_read(MirtContext* c, uint64_t* out_sums, size_t out_len_u64)
     if (c->accum_pending) HIP_TRY(hipEventSynchronize(c->ev_accum));                 // adds may sit on a caller stream
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out_sums, c->d_accum, (size_t)c->accum_pixels * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return MIRT_OK;
+}
+
+// ---- adaptive sampling for progressive frames of the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
+int mirt_adapt_active(const MirtAdaptPixel* px, const MirtAdaptParams* adapt, uint32_t* out)
+{
+    if (!px || !adapt || !out) return fail(MIRT_ERR_NULL_POINTER, "pixel/adapt/out is null");
+    *out = mirt::adapt_active(px->sum, px->even, px->samples, *adapt) ? 1u : 0u;
+    return MIRT_OK;
+}
+
+// the blocking calls wait for the last step, on whatever stream it was queued, and fold its time
+static int adapt_await(MirtContext* c)
+{
+    if (c->adapt_pending) {
+        HIP_TRY(hipEventSynchronize(c->ev_adapt_end));
+        c->adapt_pending = false;
+        if (c->adapt_timed) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, c->ev_adapt_begin, c->ev_adapt_end));
+            c->adapt_ms = ms;
+        }
+    }
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_reset(MirtContext* c, const MirtParams* p)
+{
+    int rc = check_params(c, p);
+    if (rc != MIRT_OK) return rc;
+    if (p->mode != MIRT_MODE_PT) return fail(MIRT_ERR_BAD_MODE, "adaptive sampling exists in path-traced mode only");
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t npix = (uint64_t)out_rows(p) * p->width;
+    if ((rc = adapt_await(c)) != MIRT_OK) return rc;       // no step may still be running
+    c->adapt_pixels = 0;                                   // a failed allocation below leaves no buffer: steps answer MIRT_ERR_OUT_BUFFER
+    c->adapt_steps = 0;
+    if (!c->ev_adapt_begin) HIP_TRY(hipEventCreate(&c->ev_adapt_begin));
+    if (!c->ev_adapt_end) HIP_TRY(hipEventCreate(&c->ev_adapt_end));
+    // head 16 bytes | list | block counts | flags
+    const uint64_t n_blocks = (npix + 255u) / 256u;
+    const size_t off_counts = 16u + (size_t)npix * 4u, off_flags = off_counts + (size_t)n_blocks * 4u;
+    if ((rc = ensure_capacity(&c->d_adapt, &c->cap_adapt, (size_t)npix * sizeof(MirtAdaptPixel))) != MIRT_OK) return rc;
+    if ((rc = ensure_capacity(&c->d_adapt_sel, &c->cap_adapt_sel, off_flags + (size_t)npix)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->d_adapt, 0, (size_t)npix * sizeof(MirtAdaptPixel), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_adapt_sel, 0, off_flags + (size_t)npix, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->adapt_off_counts = off_counts;
+    c->adapt_off_flags = off_flags;
+    c->adapt_pixels = npix;
+    c->adapt_width = p->width;
+    c->adapt_rows = out_rows(p);
+    c->adapt_steps = 0;
+    c->adapt_ms = 0.0;
+    return MIRT_OK;
+}
+
+// What a step is refused for, in the header's order; *q = the params the launch runs with.  Nothing is queued before the last check has passed.
+static int check_adapt_step(const MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, MirtParams* q)
+{
+    if (!c || !p || !adapt) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/adapt is null");
+    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (p->mode != MIRT_MODE_PT) return fail(MIRT_ERR_BAD_MODE, "adaptive sampling exists in path-traced mode only");
+    if (adapt->flags != 0u) return fail(MIRT_ERR_BAD_MODE, "unknown MirtAdaptParams.flags bits 0x%x", adapt->flags);
+    if (p->flags & (MIRT_FLAG_COUNT_WORK | MIRT_FLAG_COUNT_GRID)) return fail(MIRT_ERR_BAD_MODE, "an adaptive step has no counting build");
+    if (p->frame_spp != 0u) return fail(MIRT_ERR_FRAME_SPP, "frame_spp %u: an adaptive step needs independent samples (frame_spp 0)", p->frame_spp);
+    *q = *p;
+    q->sample_begin = 0;                                    // ignored: every pixel continues its own stream
+    const int rc = check_params(c, q);
+    if (rc != MIRT_OK) return rc;
+    if (p->spp & 1u) return fail(MIRT_ERR_SPP_RANGE, "spp %u is odd: an adaptive step adds to the even and the odd half alike", p->spp);
+    if (adapt->max_samples > MIRT_MAX_SPP_PER_CALL)
+        return fail(MIRT_ERR_SPP_RANGE, "max_samples %u is out of range: at most %u", adapt->max_samples, (unsigned)MIRT_MAX_SPP_PER_CALL);
+    if (!c->d_adapt || c->adapt_pixels == 0 || c->adapt_width != p->width || c->adapt_rows != out_rows(p))
+        return fail(MIRT_ERR_OUT_BUFFER, "the adaptive buffer does not match these params: call mirt_ctx_adapt_reset first");
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_step_device(MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, void* hip_stream)
+{
+    MirtParams q;
+    const int rc = check_adapt_step(c, p, adapt, &q);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const bool bvh = !(q.flags & MIRT_FLAG_NO_GRID), hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
+    mirt::RenderArgs a{};
+    a.cam = c->cam;
+    { const uint32_t flag = (c->tuning.pinhole != 0 && camera_is_pinhole(c->cam)) ? 1u : 0u; std::memcpy(&a.cam._padding5, &flag, 4); }   // as launch_render
+    a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
+    a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
+    a.width = q.width; a.height = q.height; a.spp = q.spp; a.num_bounces = q.num_bounces; a.flags = q.flags;
+    a.seed_mix = jenkins_hash((uint32_t)q.seed ^ jenkins_hash((uint32_t)(q.seed >> 32)));       // as launch_render derives it
+    a.row_begin = q.row_begin; a.tile_rows = q.tile_rows; a.n_parts = q.n_parts; a.part = q.part;
+    a.out_rows = c->adapt_rows;
+    a.n_units = (uint32_t)c->adapt_pixels;
+    // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
+    fill_bvh_args(c, &a, 0u);
+    a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
+    uint32_t* head = reinterpret_cast<uint32_t*>(c->d_adapt_sel);
+    uint32_t* list = reinterpret_cast<uint32_t*>(c->d_adapt_sel + 16u);
+    const bool timed = c->timing;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_adapt_begin, st));
+    HIP_TRY(kx::launch_adapt_select(c->d_adapt, (uint32_t)c->adapt_pixels, *adapt, q.spp, c->d_adapt_sel + c->adapt_off_flags,
+                                    reinterpret_cast<uint32_t*>(c->d_adapt_sel + c->adapt_off_counts), list, head, st));
+    HIP_TRY(kx::launch_adapt_pixels(a, c->d_adapt, list, head, hosek, bvh, st));
+    const char* tf[2] = { "false", "true" };
+    snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_kernel<%s,%s>", tf[hosek], tf[bvh]);
+    HIP_TRY(hipEventRecord(c->ev_adapt_end, st));
+    c->adapt_pending = true;
+    c->adapt_timed = timed;
+    c->adapt_ms = 0.0;
+    c->adapt_steps += 1;
+    return MIRT_OK;
+}
+
+static int check_adapt_resolve(const MirtContext* c, const MirtParams* p, const void* out, size_t out_len)
+{
+    if (!c || !p || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/out is null");
+    if (!c->d_adapt || c->adapt_pixels == 0 || c->adapt_steps == 0) return fail(MIRT_ERR_NO_SCENE, "no adaptive step has run since the reset");
+    if (out_len < c->adapt_pixels * 4) return fail(MIRT_ERR_OUT_BUFFER, "output buffer holds %zu bytes, %llu needed", out_len, (unsigned long long)c->adapt_pixels * 4);
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_resolve_device(MirtContext* c, const MirtParams* p, void* d_out, size_t out_len, void* hip_stream)
+{
+    const int rc = check_adapt_resolve(c, p, d_out, out_len);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(kx::launch_adapt_resolve(c->d_adapt, (uint32_t*)d_out, c->adapt_pixels, p->flags, hip_stream ? (hipStream_t)hip_stream : c->stream));
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_resolve(MirtContext* c, const MirtParams* p, uint8_t* out, size_t out_len)
+{
+    int rc = check_adapt_resolve(c, p, out, out_len);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = ensure_capacity(&c->d_out, &c->cap_out, (size_t)c->adapt_pixels)) != MIRT_OK) return rc;
+    if ((rc = adapt_await(c)) != MIRT_OK) return rc;       // the HOST waits for a step on a caller stream (see mirt_ctx_accum_resolve)
+    HIP_TRY(kx::launch_adapt_resolve(c->d_adapt, c->d_out, c->adapt_pixels, p->flags, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_out, (size_t)c->adapt_pixels * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_read(MirtContext* c, MirtAdaptPixel* out, size_t len)
+{
+    if (!c || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/out is null");
+    if (!c->d_adapt || c->adapt_pixels == 0) return fail(MIRT_ERR_NO_SCENE, "no adaptive buffer: call mirt_ctx_adapt_reset first");
+    if (len < c->adapt_pixels) return fail(MIRT_ERR_OUT_BUFFER, "the buffer holds %llu records, room for %zu", (unsigned long long)c->adapt_pixels, len);
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = adapt_await(c);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, c->d_adapt, (size_t)c->adapt_pixels * sizeof(MirtAdaptPixel), hipMemcpyDeviceToHost));
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_write(MirtContext* c, const MirtAdaptPixel* in, size_t len)
+{
+    if (!c || !in) return fail(MIRT_ERR_NULL_POINTER, "ctx/in is null");
+    if (!c->d_adapt || c->adapt_pixels == 0) return fail(MIRT_ERR_NO_SCENE, "no adaptive buffer: call mirt_ctx_adapt_reset first");
+    if (len != c->adapt_pixels) return fail(MIRT_ERR_OUT_BUFFER, "the buffer holds %llu records, %zu given", (unsigned long long)c->adapt_pixels, len);
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = adapt_await(c);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->d_adapt, in, (size_t)c->adapt_pixels * sizeof(MirtAdaptPixel), hipMemcpyHostToDevice));
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_list_read(MirtContext* c, uint32_t* list, size_t len, uint32_t* count)
+{
+    if (!c || !count) return fail(MIRT_ERR_NULL_POINTER, "ctx/count is null");
+    if (!c->d_adapt_sel || c->adapt_steps == 0) return fail(MIRT_ERR_NO_SCENE, "no adaptive step has run since the reset");
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = adapt_await(c);
+    if (rc != MIRT_OK) return rc;
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, c->d_adapt_sel, sizeof n, hipMemcpyDeviceToHost));
+    *count = n;
+    if (len < n) return fail(MIRT_ERR_OUT_BUFFER, "the list holds %u indices, room for %zu", n, len);
+    if (n && !list) return fail(MIRT_ERR_NULL_POINTER, "list is null");
+    if (n) HIP_TRY(hipMemcpy(list, c->d_adapt_sel + 16u, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_stats(MirtContext* c, MirtAdaptStats* out)
+{
+    if (!c || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/out is null");
+    *out = MirtAdaptStats{};
+    if (!c->d_adapt_sel || c->adapt_pixels == 0) return MIRT_OK;       // all 0 before the first reset
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = adapt_await(c);
+    if (rc != MIRT_OK) return rc;
+    unsigned long long head[2] = { 0, 0 };
+    HIP_TRY(hipMemcpy(head, c->d_adapt_sel, sizeof head, hipMemcpyDeviceToHost));
+    out->pixels = c->adapt_pixels;
+    out->total_samples = head[1];
+    out->active = (uint32_t)head[0];
+    out->steps = c->adapt_steps;
+    out->kernel_ms = c->adapt_ms;
     return MIRT_OK;
 }
 

@@ -316,6 +316,17 @@ hipError_t launch_radiance_sorted(const RenderArgs& a, const void* d_rays, void*
 // bvh_stack_entries / lds_bytes as the pooled render's (mirt_bvh_pool_plan); grid_blocks blocks of kBvhPoolThreads, whose waves stride over the units.
 hipError_t launch_radiance_pool(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, uint32_t grid_blocks, uint32_t slots, bool hosek,
                                 hipStream_t stream);
+// mirt_ctx_adapt_* (mirt_adapt_kernel.inc).  The select stage of a step over n >= 1 records (MirtAdaptPixel, 16-byte aligned):
+// adapt_select_kernel, adapt_scan_kernel, adapt_compact_kernel -- d_flags [n] bytes, d_block_counts [ceil(n / 256)] words, d_list [n] words, d_head
+// four words {count of the step, unused, 64-bit counter of samples added (+= count x spp)}, 8-byte aligned.
+hipError_t launch_adapt_select(const void* d_recs, uint32_t n, const MirtAdaptParams& adapt, uint32_t spp, unsigned char* d_flags, uint32_t* d_block_counts,
+                               uint32_t* d_list, uint32_t* d_head, hipStream_t stream);
+// ... and its render stage: adapt_pixels_kernel<hosek, bvh>, one thread per pixel of the buffer (a.n_units = out_rows x width), one wave per block; blocks
+// beyond *d_count return at once.  `a` carries the camera (with the pinhole word set), the tables, the sky, the tree, the row fields, width, height, spp,
+// num_bounces and seed_mix as a render launch's does; lds_bytes as launch_radiance wants them.
+hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, hipStream_t stream);
+// adapt_resolve_kernel: n_pixels records -> RGBA8, every pixel over its own sample count
+hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);
 size_t     scene_lds_bytes(uint32_t n_spheres, uint32_t n_mats, bool pt, bool hosek);
 size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);

@@ -27,6 +27,7 @@
 #include "mirt_kernels.h"
 #include "mirt_device_math.h"
 #include "mirt_device_resolve.h"
+#include "mirt_adapt_rule.h"
 
 namespace mirt {
 namespace MIRT_KNS {
@@ -2187,6 +2188,7 @@ struct PoolHbmState {
 #include "mirt_feature_kernel.inc"
 #include "mirt_radiance_kernel.inc"
 #include "mirt_radiance_pool_kernel.inc"
+#include "mirt_adapt_kernel.inc"
 
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns

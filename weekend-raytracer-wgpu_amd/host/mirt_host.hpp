@@ -131,6 +131,56 @@ inline std::vector<uint32_t> trace_order(MirtContext* ctx, uint32_t n_rays)
     order.resize(n_rays);
     return order;
 }
+// mirt_ctx_adapt_* (adaptive sampling for progressive frames of a MIRT_SCENE_HBM scene): thin wrappers.  adapt_reset sizes and clears the
+// records for the rows `params` selects; adapt_step queues one step (select, then params.spp -- even -- further samples for every active pixel)
+// on `hip_stream` and returns at once; the others block.  adapt_active is the rule for one record, host only.
+static_assert(sizeof(MirtAdaptPixel) == 64 && sizeof(MirtAdaptParams) == 16 && MIRT_ADAPT_FLOOR == 1u << 17, "the adaptive records of include/mirt.h");
+inline bool adapt_active(const MirtAdaptPixel& pixel, const MirtAdaptParams& adapt)
+{
+    uint32_t on = 0;
+    check(mirt_adapt_active(&pixel, &adapt, &on));
+    return on != 0u;
+}
+inline void adapt_reset(MirtContext* ctx, const MirtParams& params) { check(mirt_ctx_adapt_reset(ctx, &params)); }
+inline void adapt_step(MirtContext* ctx, const MirtParams& params, const MirtAdaptParams& adapt, void* hip_stream = nullptr)
+{
+    check(mirt_ctx_adapt_step_device(ctx, &params, &adapt, hip_stream));
+}
+inline MirtAdaptStats adapt_stats(MirtContext* ctx)
+{
+    MirtAdaptStats st{};
+    check(mirt_ctx_adapt_stats(ctx, &st));
+    return st;
+}
+inline std::vector<uint8_t> adapt_resolve(MirtContext* ctx, const MirtParams& params)
+{
+    std::vector<uint8_t> out((size_t)adapt_stats(ctx).pixels * 4u);
+    uint8_t none[4];
+    check(mirt_ctx_adapt_resolve(ctx, &params, out.empty() ? none : out.data(), out.size()));
+    return out;
+}
+// the same resolve into `out_len` bytes of device memory on `hip_stream`, no host synchronisation
+inline void adapt_resolve_device(MirtContext* ctx, const MirtParams& params, void* d_out_rgba8, size_t out_len, void* hip_stream = nullptr)
+{
+    check(mirt_ctx_adapt_resolve_device(ctx, &params, d_out_rgba8, out_len, hip_stream));
+}
+inline std::vector<MirtAdaptPixel> adapt_read(MirtContext* ctx)
+{
+    std::vector<MirtAdaptPixel> out((size_t)adapt_stats(ctx).pixels);
+    MirtAdaptPixel none{};
+    check(mirt_ctx_adapt_read(ctx, out.empty() ? &none : out.data(), out.size()));
+    return out;
+}
+inline void adapt_write(MirtContext* ctx, const std::vector<MirtAdaptPixel>& records) { check(mirt_ctx_adapt_write(ctx, records.data(), records.size())); }
+// the pixels the last step sampled: ascending places in the band
+inline std::vector<uint32_t> adapt_list(MirtContext* ctx)
+{
+    std::vector<uint32_t> list((size_t)adapt_stats(ctx).pixels + 1u);
+    uint32_t count = 0;
+    check(mirt_ctx_adapt_list_read(ctx, list.data(), list.size(), &count));
+    list.resize(count);
+    return list;
+}
 // the pinhole ray through the centre of pixel (x, y), row 0 on top: cameraMakeRay with a zero lens
 inline MirtRay pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float t_max = 1000.0f)
 {

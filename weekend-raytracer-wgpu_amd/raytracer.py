@@ -830,6 +830,35 @@ class Raytracer:
             spp = self.render_params.sampling.num_samples_per_pixel
         return _radiance(self, rays, spp, seed, self.render_params.sampling.num_bounces, self.sky_state is not None, self.scene_data, sort, pool)
 
+    def render_adaptive(self, tolerance: int, max_spp: int, step: int = 4, min_spp: int = 4, *, seed: int = 0, flags: int = 0) -> tuple:
+        """Adaptive sampling of the current viewport (mirt_ctx_adapt_*): steps of `step` (even) samples for the pixels that have not
+        converged -- fewer than `min_spp` samples, or even and odd halves further apart than tolerance x 2^-16 of the mean -- until no
+        pixel below `max_spp` is left -> (RGBA8 [h][w][4], samples per pixel uint32 [h][w]).  One RNG stream per sample whatever
+        `reference_stream` says (a pixel's samples must be independent).  A scene held in LDS is set again as a MIRT_SCENE_HBM scene
+        first and stays one; on a node member 0's context renders the whole viewport.  The accumulation is not touched.  The mean of
+        a pixel that a stopping rule has stopped is slightly biased."""
+        from .context import make_adapt_params
+        adapt = make_adapt_params(min_spp, max_spp, tolerance)
+        if not isinstance(step, (int, np.integer)) or isinstance(step, bool) or int(step) < 2 or int(step) % 2:
+            raise ValueError(f"step must be an even sample count >= 2, not {step!r}")
+        target = self._pick_target()
+        if not self._hbm:
+            target.set_scene(self.scene_data(), hbm=True)
+            self._hbm = True
+        ctx = target.context(0) if hasattr(target, "context") else target
+        ctx.set_camera(self.camera.c)
+        rp = self.render_params
+        if self.sky_state is not None:
+            flags |= _abi.MIRT_FLAG_SKY_HOSEK
+        w, h = int(rp.viewport_size[0]), int(rp.viewport_size[1])
+        params = make_params(w, h, int(step), mode=_abi.MIRT_MODE_PT, num_bounces=rp.sampling.num_bounces, flags=flags, seed=seed)
+        ctx.adapt_reset(params)
+        while True:
+            ctx.adapt_step(params, adapt)
+            if ctx.adapt_stats()["active"] == 0:
+                break
+        return ctx.adapt_resolve(params), ctx.adapt_read()["samples"].reshape(h, w).copy()
+
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
         """All `max_samples_per_pixel` samples in one launch -> RGBA8 [h][w][4].
 
