@@ -743,7 +743,7 @@ int mirt_ctx_accum_frame(MirtContext* ctx, const MirtParams* params, uint8_t* ou
  *                    MIRT_FLAG_NO_GRID (the flat scan of the table, the comparison build); sample_begin is ignored, schedule hints
  *                    (MIRT_FLAG_KERNEL_STRIP / _POOL, _TEXEL_TILES, _FAST_MATH) are ignored; the resolve flags matter to the resolve only.
  *   errors of a step MIRT_ERR_NULL_POINTER: ctx, params or adapt is null;  MIRT_ERR_NO_SCENE: no scene, or not a MIRT_SCENE_HBM one;
- *                    MIRT_ERR_BAD_MODE: mode is not MIRT_MODE_PT, adapt->flags != 0, or a counting flag (MIRT_FLAG_COUNT_WORK, _COUNT_GRID);
+ *                    MIRT_ERR_BAD_MODE: mode is not MIRT_MODE_PT, a bit of adapt->flags other than MIRT_ADAPT_POOL, or a counting flag (MIRT_FLAG_COUNT_WORK, _COUNT_GRID);
  *                    MIRT_ERR_FRAME_SPP: frame_spp != 0 (a pixel's samples must be independent);  MIRT_ERR_SPP_RANGE: spp is odd (the two
  *                    halves grow together), or max_samples > MIRT_MAX_SPP_PER_CALL;  MIRT_ERR_OUT_BUFFER: no buffer, or another width or
  *                    row count than the reset's;  every other check and code is that of a path-traced render on that scene.  A refused
@@ -771,6 +771,7 @@ typedef struct MirtAdaptPixel { uint64_t sum[3]; uint64_t even[3]; uint32_t samp
 typedef struct MirtAdaptParams { uint32_t min_samples, max_samples, tolerance, flags; } MirtAdaptParams;                               /* 16 B */
 typedef struct MirtAdaptStats { uint64_t pixels, total_samples; uint32_t active, steps; double kernel_ms; } MirtAdaptStats;            /* 32 B */
 #define MIRT_ADAPT_FLOOR (1u << 17)
+enum { MIRT_ADAPT_POOL = 1u << 1 };   /* MirtAdaptParams.flags; bit 0: unassigned */
 int mirt_adapt_active(const MirtAdaptPixel* pixel, const MirtAdaptParams* adapt, uint32_t* out);
 int mirt_ctx_adapt_reset(MirtContext* ctx, const MirtParams* params);
 int mirt_ctx_adapt_step_device(MirtContext* ctx, const MirtParams* params, const MirtAdaptParams* adapt, void* hip_stream);
@@ -780,6 +781,28 @@ int mirt_ctx_adapt_read(MirtContext* ctx, MirtAdaptPixel* out, size_t len);
 int mirt_ctx_adapt_write(MirtContext* ctx, const MirtAdaptPixel* in, size_t len);
 int mirt_ctx_adapt_list_read(MirtContext* ctx, uint32_t* list, size_t len, uint32_t* count);
 int mirt_ctx_adapt_stats(MirtContext* ctx, MirtAdaptStats* out);
+
+/* ---- pooled adaptive steps: MIRT_ADAPT_POOL in MirtAdaptParams.flags ----
+ * Without the flag lane = list entry: a lane walks its pixel's spp samples one after the other, in every sample the wave waits for its
+ * longest path, and a late, short list is a handful of waves on a device that holds thousands.  With it a wave owns 16 consecutive
+ * entries of the list and deals their 16 x spp (pixel, sample) items to a wave-private pool of paths, as MIRT_RADIANCE_POOL does with
+ * 16 rays: a finished path's slot takes the next item at once.
+ *   same bytes in the same places   the sums are exact integers, so after a step with the flag the list and its count, the 64-bit
+ *                    sample counter and all 64 bytes of every record (pads written as 0, unlisted records untouched) equal those of
+ *                    the same step without it, for every record mirt_ctx_adapt_write can put there.  Errors are unchanged, except that
+ *                    MIRT_ADAPT_POOL is a known bit; a refused call queues nothing and writes nothing.
+ *   a hint           like MIRT_FLAG_KERNEL_POOL and MIRT_RADIANCE_POOL.  The pooled kernel runs on the BVH build.  The step runs exactly
+ *                    as without the flag (same kernel, same name in mirt_ctx_last_kernel) when MIRT_FLAG_NO_GRID is set, when
+ *                    num_bounces > 255 (the pool's bounce counters are 8 bit), or when mirt_adapt_pool_plan of the resident tree's
+ *                    depth gives slots == 0.
+ *   state            as for every adaptive step: one event pair around select through render; the launch ring, MirtStats and the
+ *                    accumulation untouched; steps of one context ordered by the caller.  There is no dispenser word.
+ *                    mirt_ctx_last_kernel names adapt_pixels_pool_kernel<THREADS,SLOTS,MINW,HOSEK>.
+ *   mirt_adapt_pool_plan   HOST-ONLY, the function the launch itself uses: the arguments, struct, rule and errors of mirt_bvh_pool_plan.
+ *                    Beside the 16 x 3 sums a wave's pool keeps the 16 x 3 sums of the even-indexed samples (384 bytes) and
+ *                    {place in the band, samples so far} of its 16 entries (128 bytes):
+ *                      lds_bytes_per_block = 96 (+ 144) + threads / 64 * (50 * slots + 896 + 256 * max_depth). */
+int mirt_adapt_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtBvhPoolPlan* out);
 
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE

@@ -319,6 +319,8 @@ pub const MIRT_RADIANCE_SKY_HOSEK: u32 = 1 << 2;
 pub const MIRT_RADIANCE_SORT: u32 = 1 << 4;
 /// A hint: the pooled schedule (a wave deals the samples of 16 rays to its lanes); same records.  Bit 5 is unassigned.
 pub const MIRT_RADIANCE_POOL: u32 = 1 << 6;
+/// `MirtAdaptParams.flags`: the pooled schedule for the step's render stage (a hint: same records); bit 0 is unassigned.
+pub const MIRT_ADAPT_POOL: u32 = 1 << 1;
 
 pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
 /// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.
@@ -404,6 +406,7 @@ extern "C" {
     pub fn mirt_ctx_set_scene_ex(ctx: *mut MirtContext, scene: *const MirtScene, flags: u32) -> c_int;
     pub fn mirt_bvh_plan(spheres: *const MirtSphere, n_spheres: u32, out: *mut MirtBvhPlan) -> c_int;
     pub fn mirt_bvh_pool_plan(max_depth: u32, hosek: u32, lds_bytes_per_cu: u64, out: *mut MirtBvhPoolPlan) -> c_int;
+    pub fn mirt_adapt_pool_plan(max_depth: u32, hosek: u32, lds_bytes_per_cu: u64, out: *mut MirtBvhPoolPlan) -> c_int;
     pub fn mirt_ctx_bvh_info(ctx: *mut MirtContext, out: *mut MirtBvhInfo) -> c_int;
     pub fn mirt_ctx_bvh_read(ctx: *mut MirtContext, nodes: *mut c_void, nodes_bytes: usize, recs: *mut f32, recs_len: usize, ids: *mut u32, ids_len: usize) -> c_int;
     pub fn mirt_ctx_update_spheres(ctx: *mut MirtContext, first: u32, count: u32, spheres: *const MirtSphere) -> c_int;

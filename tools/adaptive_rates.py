@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Adaptive-sampling rates (mirt_ctx_adapt_*): one JSON line per case, APPENDED to profiles/r16_adaptive_rates.jsonl
-and printed.
+"""Adaptive-sampling rates (mirt_ctx_adapt_*): one JSON line per case, APPENDED to
+profiles/r16_adaptive_rates.jsonl (profiles/r17_adaptive_pool_rates.jsonl with --pool) and printed.
 
 Worlds: the RTIOW-style fields of tests/hbm_worlds.py at 484 and at 1 M spheres (--spheres), set with MIRT_SCENE_HBM, the tree built
 on the device, seen at 1920 x 1080 with 8 bounces.  Cases (--cases, any of a,b,c), every one in alternating windows in ONE process,
@@ -14,12 +14,16 @@ the median of --reps windows after a warm-up of each variant, every window's fig
      of the same samples in the same steps.  Windows of untimed launches back to back between two device events on one torch stream.
      The sums are compared once.  (The split into select and render comes from a kernel trace, a run of its own: --fold-trace.)
   c  mirt_ctx_adapt_resolve_device against resolve_accum_kernel (mirt_ctx_accum_frame_device with spp = 0), the same kind of windows.
+  e  the empty step (--pool only): the records of a finished run, so that a step lists nothing and its render launch is a grid of blocks
+     that return at once -- the whole step (select, scan, compact, render) with and without MIRT_ADAPT_POOL, windows as in c.
+--pool     adds the twin of every adaptive variant with MIRT_ADAPT_POOL (a: adaptive_<tolerance>_pool, b: adapt_pool) in
+           the same alternating windows, compares their records with the unpooled variant's, and enables case e.
 --fold-trace FILE   no device: reads the *_kernel_trace.csv of a rocprofv3 --kernel-trace --stats run and appends one line with the calls
                     and the median time of every adapt_*, render_pt_hbm* and resolve_accum kernel in it.
 
 Run every world and case as a process of its own under its own time limit, e.g.
   timeout -k 10 300 python tools/adaptive_rates.py --spheres 484 --cases a
-usage: python tools/adaptive_rates.py [--spheres 484,1000000] [--cases a,b,c] [--reps 5] [--max-spp 256] [--step 8] [--tolerances 4096,1024]
+usage: python tools/adaptive_rates.py [--pool] [--spheres 484,1000000] [--cases a,b,c,e] [--reps 5] [--max-spp 256] [--step 8] [--tolerances 4096,1024]
                                       [--machinery-spp 32] [--window-ms 200] [--out profiles/r16_adaptive_rates.jsonl] [--fold-trace FILE]"""
 from __future__ import annotations
 
@@ -65,10 +69,13 @@ def main():
     ap.add_argument("--tolerances", default="4096,1024")
     ap.add_argument("--machinery-spp", type=int, default=32)
     ap.add_argument("--window-ms", type=float, default=200.0)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r16_adaptive_rates.jsonl"))
+    ap.add_argument("--pool", action="store_true", help="also time every adaptive variant with MIRT_ADAPT_POOL")
+    ap.add_argument("--out", default="")
     ap.add_argument("--fold-trace", default="")
     ap.add_argument("--note", default="", help="copied into every line")
     a = ap.parse_args()
+    if not a.out:
+        a.out = str(ROOT / "profiles" / ("r17_adaptive_pool_rates.jsonl" if a.pool else "r16_adaptive_rates.jsonl"))
 
     def emit(line):
         if a.note:
@@ -122,8 +129,8 @@ def main():
                 ctx.synchronize()
                 return {"ms": (time.perf_counter() - t0) * 1e3, "samples": npix * a.max_spp, "kernel": ctx.last_kernel()}
 
-            def adaptive(tol):
-                adapt = m.make_adapt_params(a.step, a.max_spp, tol)
+            def adaptive(tol, pool=False):
+                adapt = m.make_adapt_params(a.step, a.max_spp, tol, pool)
                 ctx.adapt_reset(p_step)
                 ctx.synchronize()
                 device_ms, active = 0.0, []
@@ -141,7 +148,14 @@ def main():
             runs = {"uniform": uniform}
             for tol in [int(x) for x in a.tolerances.split(",") if x]:
                 runs[f"adaptive_{tol}"] = lambda tol=tol: adaptive(tol)
-            last = {k: fn() for k, fn in runs.items()}                 # warm-up
+                if a.pool:
+                    runs[f"adaptive_{tol}_pool"] = lambda tol=tol: adaptive(tol, True)
+            last, recs = {}, {}
+            for k, fn in runs.items():                                 # warm-up; the records of every adaptive variant, once
+                last[k] = fn()
+                if k != "uniform":
+                    recs[k] = ctx.adapt_read()
+            same = {k: bool(np.array_equal(recs[k].view(np.uint8), recs[k[:-5]].view(np.uint8))) for k in recs if k.endswith("_pool")}
             t = {k: [] for k in runs}
             for _ in range(a.reps):
                 for k, fn in runs.items():
@@ -157,6 +171,7 @@ def main():
                   "device_ms_of_the_steps": {k: round(last[k]["device_ms"], 2) for k in runs if "device_ms" in last[k]},
                   "active_per_step": {k: last[k]["active"] for k in runs if "active" in last[k]},
                   "last_run_pixels_at_max": int((counts >= a.max_spp).sum()), "last_run_median_samples": int(np.median(counts)),
+                  **({"pooled_records_equal": same, "time_over_unpooled": {k: round(med[k] / med[k[:-5]], 3) for k in same}} if a.pool else {}),
                   "kernels": {k: last[k]["kernel"] for k in runs}, "all_ms": {k: [round(x, 2) for x in v] for k, v in t.items()}})
 
         if "b" in cases:
@@ -167,6 +182,12 @@ def main():
             def run_adapt():
                 for _ in range(n_steps):
                     ctx.adapt_step(p_step, adapt, stream=stream.cuda_stream)
+
+            adapt_pool = m.make_adapt_params(a.machinery_spp, a.machinery_spp, 0, True)
+
+            def run_adapt_pool():
+                for _ in range(n_steps):
+                    ctx.adapt_step(p_step, adapt_pool, stream=stream.cuda_stream)
 
             def run_accum():
                 for _ in range(n_steps):
@@ -180,6 +201,14 @@ def main():
             torch.cuda.synchronize()
             same = bool(np.array_equal(ctx.adapt_read()["sum"], ctx.accum_read(p_step).reshape(-1, 3)))
             kernels = {}
+            same_pool = None
+            if a.pool:
+                plain = ctx.adapt_read()
+                ctx.adapt_reset(p_step)
+                run_adapt_pool()
+                torch.cuda.synchronize()
+                kernels["adapt_pool"] = ctx.last_kernel()
+                same_pool = bool(np.array_equal(ctx.adapt_read().view(np.uint8), plain.view(np.uint8)))
             ctx.adapt_step(p_step, adapt, stream=stream.cuda_stream)
             kernels["adapt"] = ctx.last_kernel()
             ctx.accum_add(p_step, stream=stream.cuda_stream)
@@ -194,6 +223,8 @@ def main():
                 return window(fn, 1)
 
             variants = {"adapt": (run_adapt, ctx.adapt_reset), "accum": (run_accum, ctx.accum_reset)}
+            if a.pool:
+                variants["adapt_pool"] = (run_adapt_pool, ctx.adapt_reset)
             for fn, reset in variants.values():
                 fresh(fn, reset)
             t = {k: [] for k in variants}
@@ -204,6 +235,8 @@ def main():
             med = {k: statistics.median(v) for k, v in t.items()}
             emit({**base, "case": "b_price_of_the_machinery", "samples_per_pixel": a.machinery_spp, "step": a.step, "steps": n_steps,
                   "ms": {k: round(v, 3) for k, v in med.items()}, "adapt_over_accum": round(med["adapt"] / med["accum"], 3), "same_sums": same,
+                  **({"pool_over_accum": round(med["adapt_pool"] / med["accum"], 3), "pool_over_adapt": round(med["adapt_pool"] / med["adapt"], 3),
+                      "pooled_records_equal": same_pool} if a.pool else {}),
                   "kernels": kernels, "all_ms": {k: [round(x, 3) for x in v] for k, v in t.items()}})
 
         if "c" in cases:
@@ -235,6 +268,36 @@ def main():
                   "adapt_over_accum": round(med["adapt_resolve"] / med["accum_resolve"], 3), "same_image": bool(np.array_equal(img["adapt_resolve"], img["accum_resolve"])),
                   "bytes_read_per_pixel": {"adapt_resolve": 48, "accum_resolve": 24}, "launches_per_window": counts,
                   "all_us": {k: [round(x * 1e3, 1) for x in v] for k, v in t.items()}})
+        if "e" in cases and a.pool:
+            p = pt(a.step)
+            done = m.make_adapt_params(a.step, a.step, 0)
+            ctx.adapt_reset(p)
+            ctx.adapt_step(p, done)                                     # every pixel holds min = max samples: the next step lists nothing
+            ctx.synchronize()
+            launch, kernels = {}, {}
+            for k, pool in (("empty_step", False), ("empty_step_pool", True)):
+                ad = m.make_adapt_params(a.step, a.step, 0, pool)
+                launch[k] = lambda ad=ad: ctx.adapt_step(p, ad, stream=stream.cuda_stream)
+                launch[k]()
+                torch.cuda.synchronize()
+                assert ctx.adapt_stats()["active"] == 0
+                kernels[k] = ctx.last_kernel()
+            ctx.set_timing(False)
+            counts = {}
+            for k, fn in launch.items():
+                window(fn, 1)
+                counts[k] = max(1, int(round(a.window_ms / max(window(fn, 4), 1e-3))))
+                window(fn, counts[k])
+            t = {k: [] for k in launch}
+            for _ in range(a.reps):
+                for k, fn in launch.items():
+                    t[k].append(window(fn, counts[k]))
+            ctx.set_timing(True)
+            med = {k: statistics.median(v) for k, v in t.items()}
+            emit({**base, "case": "e_empty_step", "what": "select + scan + compact + a render launch whose every block returns at once",
+                  "us": {k: round(v * 1e3, 1) for k, v in med.items()}, "pool_over_plain": round(med["empty_step_pool"] / med["empty_step"], 3),
+                  "render_blocks": {"empty_step": (npix + 63) // 64, "empty_step_pool": ((npix + 15) // 16 + 3) // 4},
+                  "kernels": kernels, "launches_per_window": counts, "all_us": {k: [round(x * 1e3, 1) for x in v] for k, v in t.items()}})
         ctx.close()
 
 

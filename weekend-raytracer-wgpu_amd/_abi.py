@@ -53,6 +53,7 @@ MIRT_RAY_SORT_DIRECTION_BITS = 8
 
 # mirt_ctx_adapt_*: the rule's floor, 0.125 of radiance per sample summed over the channels, in 2^-20 units
 MIRT_ADAPT_FLOOR = 1 << 17
+MIRT_ADAPT_POOL = 1 << 1                # MirtAdaptParams.flags; bit 0 is unassigned
 
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
@@ -268,6 +269,7 @@ SYMBOLS = {
     "mirt_bvh_plan": (C.c_int, [C.c_void_p, C.c_uint32, _P(MirtBvhPlan)]),
     "mirt_ctx_bvh_info": (C.c_int, [C.c_void_p, _P(MirtBvhInfo)]),
     "mirt_bvh_pool_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, _P(MirtBvhPoolPlan)]),
+    "mirt_adapt_pool_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, _P(MirtBvhPoolPlan)]),
     "mirt_ctx_bvh_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "mirt_ctx_update_spheres": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "mirt_ctx_update_spheres_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),

@@ -85,6 +85,15 @@ def bvh_pool_plan(max_depth: int, hosek: bool = False, lds_bytes_per_cu: int = 0
     return out.as_dict()
 
 
+def adapt_pool_plan(max_depth: int, hosek: bool = False, lds_bytes_per_cu: int = 0) -> dict:
+    """mirt_adapt_pool_plan: the geometry an adaptive step with MIRT_ADAPT_POOL runs on a MIRT_SCENE_HBM scene whose tree is `max_depth`
+    deep, host only: the dict of bvh_pool_plan, with the 512 bytes per wave the pooled step keeps beside its pool; slots == 0: none fits
+    and the step runs as without the flag.  lds_bytes_per_cu = 0: gfx950's 163 840."""
+    out = _abi.MirtBvhPoolPlan()
+    check(lib().mirt_adapt_pool_plan(int(max_depth), 1 if hosek else 0, int(lds_bytes_per_cu), C.byref(out)))
+    return out.as_dict()
+
+
 # one inner node as mirt_ctx_bvh_read returns it (csrc/mirt_bvh.h: BvhNode, 64 bytes)
 BVH_NODE_DTYPE = np.dtype([("lmin", "<f4", (3,)), ("lmax", "<f4", (3,)), ("rmin", "<f4", (3,)), ("rmax", "<f4", (3,)),
                            ("left", "<u4"), ("right", "<u4"), ("pad", "<u4", (2,))])
@@ -251,14 +260,17 @@ def radiance_ray_records(rays) -> np.ndarray:
 ADAPT_PIXEL_DTYPE = np.dtype([("sum", "<u8", (3,)), ("even", "<u8", (3,)), ("samples", "<u4"), ("_pad0", "<u4"), ("_pad1", "<u8")])
 
 
-def make_adapt_params(min_samples: int, max_samples: int, tolerance: int) -> _abi.MirtAdaptParams:
+def make_adapt_params(min_samples: int, max_samples: int, tolerance: int, pool: bool = False) -> _abi.MirtAdaptParams:
     """MirtAdaptParams: a pixel is sampled while it holds fewer than max_samples and either fewer than min_samples or its even and odd
-    halves differ by more than tolerance x 2^-16 of its mean (include/mirt.h has the exact rule)."""
+    halves differ by more than tolerance x 2^-16 of its mean (include/mirt.h has the exact rule).  pool=True (MIRT_ADAPT_POOL): a hint
+    to run the step's render stage on the pooled schedule; the records, the list and the counters are the same."""
+    if not isinstance(pool, (bool, np.bool_)):
+        raise ValueError(f"pool must be a bool, not {pool!r}")
     for name, v in (("min_samples", min_samples), ("max_samples", max_samples), ("tolerance", tolerance)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
             raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
     a = _abi.MirtAdaptParams()
-    a.min_samples, a.max_samples, a.tolerance, a.flags = int(min_samples), int(max_samples), int(tolerance), 0
+    a.min_samples, a.max_samples, a.tolerance, a.flags = int(min_samples), int(max_samples), int(tolerance), (_abi.MIRT_ADAPT_POOL if pool else 0)
     return a
 
 

@@ -299,6 +299,7 @@ struct Tuning {
     int      timing = -1;             // MIRT_TIMING=0/1: the context's initial mirt_ctx_set_timing state (A/B runs; default 1)
     uint32_t hbm_pool_slots = 0;      // MIRT_HBM_POOL_SLOTS=n (A/B runs): the pooled build of MIRT_SCENE_HBM scenes takes this one of kBvhPoolSlotChoices
     uint32_t radiance_pool_blocks = 0;    // MIRT_RADIANCE_POOL_BLOCKS=n (A/B runs, tests): a pooled radiance query launches at most n blocks, whose waves stride over the units
+    uint32_t adapt_pool_blocks = 0;   // MIRT_ADAPT_POOL_BLOCKS=n (A/B runs, tests): a pooled adaptive step launches at most n blocks, whose waves stride over the units
     bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
 };
 
@@ -331,6 +332,7 @@ Tuning read_tuning()
         for (uint32_t s : mirt::kBvhPoolSlotChoices) if (v == s) t.hbm_pool_slots = v;
     }
     if (const char* e = std::getenv("MIRT_RADIANCE_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.radiance_pool_blocks = (uint32_t)v; }
+    if (const char* e = std::getenv("MIRT_ADAPT_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_pool_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_GRID_BIG")) { const double v = std::atof(e); if (v >= 1.0 && v <= 1024.0) t.grid_big = v; }
     return t;
 }
@@ -339,14 +341,16 @@ Tuning read_tuning()
 // `max_depth` deep: per block the camera (+ sky), and per wave a pool and 64 stacks of max_depth entries.  The rule (mirt_kernels.h,
 // DESIGN.md 10.6): the first of kBvhPoolSlotChoices -- largest pools first -- that leaves kBvhPoolWavesPerCu waves resident, else the
 // choice with most waves, the larger pools on a tie.  slots == 0: not even one block fits.  `only_slots` != 0 (A/B runs): that choice alone.
-MirtBvhPoolPlan plan_bvh_pool(uint32_t max_depth, bool hosek, uint64_t lds_per_cu, uint32_t only_slots)
+// `extra_per_wave`: bytes a wave keeps beside its pool -- 0 for the pooled render and the pooled query, kAdaptPoolExtraBytes for the
+// pooled adaptive step (mirt_adapt_pool_plan).
+MirtBvhPoolPlan plan_bvh_pool(uint32_t max_depth, bool hosek, uint64_t lds_per_cu, uint32_t only_slots, uint32_t extra_per_wave)
 {
     MirtBvhPoolPlan best{};
     const uint32_t waves = mirt::kBvhPoolThreads / 64u;
     const uint64_t scene = kx::scene_lds_bytes_grid(0u, hosek);
     for (uint32_t slots : mirt::kBvhPoolSlotChoices) {
         if (only_slots != 0u && slots != only_slots) continue;
-        const uint64_t block = scene + (uint64_t)waves * (mirt::bvh_pool_bytes_per_wave(slots) + 256ull * max_depth);
+        const uint64_t block = scene + (uint64_t)waves * (mirt::bvh_pool_bytes_per_wave(slots) + extra_per_wave + 256ull * max_depth);
         uint64_t blocks = lds_per_cu / block;
         if (blocks > mirt::kBvhPoolWavesPerCu / waves) blocks = mirt::kBvhPoolWavesPerCu / waves;
         if ((uint32_t)blocks * waves > best.waves_per_cu)
@@ -662,7 +666,16 @@ int mirt_bvh_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_pe
     if (!out) return fail(MIRT_ERR_NULL_POINTER, "out is null");
     *out = MirtBvhPoolPlan{};
     if (max_depth > MIRT_BVH_MAX_DEPTH) return fail(MIRT_ERR_BAD_ROWS, "max_depth %u exceeds MIRT_BVH_MAX_DEPTH (%u)", max_depth, (unsigned)MIRT_BVH_MAX_DEPTH);
-    *out = plan_bvh_pool(max_depth, hosek != 0u, lds_bytes_per_cu ? lds_bytes_per_cu : (uint64_t)160 * 1024, 0u);
+    *out = plan_bvh_pool(max_depth, hosek != 0u, lds_bytes_per_cu ? lds_bytes_per_cu : (uint64_t)160 * 1024, 0u, 0u);
+    return MIRT_OK;
+}
+
+int mirt_adapt_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtBvhPoolPlan* out)
+{
+    if (!out) return fail(MIRT_ERR_NULL_POINTER, "out is null");
+    *out = MirtBvhPoolPlan{};
+    if (max_depth > MIRT_BVH_MAX_DEPTH) return fail(MIRT_ERR_BAD_ROWS, "max_depth %u exceeds MIRT_BVH_MAX_DEPTH (%u)", max_depth, (unsigned)MIRT_BVH_MAX_DEPTH);
+    *out = plan_bvh_pool(max_depth, hosek != 0u, lds_bytes_per_cu ? lds_bytes_per_cu : (uint64_t)160 * 1024, 0u, mirt::kAdaptPoolExtraBytes);
     return MIRT_OK;
 }
 
@@ -1360,7 +1373,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     const bool hbm_bvh = hbm && pt && !(p->flags & MIRT_FLAG_NO_GRID) && (!count || (p->flags & MIRT_FLAG_COUNT_GRID));
     MirtBvhPoolPlan hbm_plan{};
     if (hbm_bvh && (p->flags & MIRT_FLAG_KERNEL_POOL) && !(p->flags & MIRT_FLAG_KERNEL_STRIP) && !frame_stream && p->num_bounces <= 255u)
-        hbm_plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, tune.hbm_pool_slots);
+        hbm_plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, tune.hbm_pool_slots, 0u);
     const bool pool_hbm = hbm_plan.slots != 0u && hbm_plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
     if (pool_hbm) pool = true;
     // the geometry of the pool kernel that will run
@@ -2013,7 +2026,7 @@ static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const
     const bool bvh = !(p->flags & MIRT_RADIANCE_FLAT), hosek = (p->flags & MIRT_RADIANCE_SKY_HOSEK) != 0, sort = (p->flags & MIRT_RADIANCE_SORT) != 0;
     MirtBvhPoolPlan plan{};
     if ((p->flags & MIRT_RADIANCE_POOL) && bvh && p->num_bounces <= 255u)
-        plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, c->tuning.hbm_pool_slots);
+        plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, c->tuning.hbm_pool_slots, 0u);
     const bool pooled = plan.slots != 0u && plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
     mirt::RenderArgs a{};                                 // (the camera stays zero: a query has none)
     a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
@@ -2319,7 +2332,7 @@ static int check_adapt_step(const MirtContext* c, const MirtParams* p, const Mir
     if (!c || !p || !adapt) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/adapt is null");
     if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
     if (p->mode != MIRT_MODE_PT) return fail(MIRT_ERR_BAD_MODE, "adaptive sampling exists in path-traced mode only");
-    if (adapt->flags != 0u) return fail(MIRT_ERR_BAD_MODE, "unknown MirtAdaptParams.flags bits 0x%x", adapt->flags);
+    if (adapt->flags & ~(uint32_t)MIRT_ADAPT_POOL) return fail(MIRT_ERR_BAD_MODE, "unknown MirtAdaptParams.flags bits 0x%x", adapt->flags);
     if (p->flags & (MIRT_FLAG_COUNT_WORK | MIRT_FLAG_COUNT_GRID)) return fail(MIRT_ERR_BAD_MODE, "an adaptive step has no counting build");
     if (p->frame_spp != 0u) return fail(MIRT_ERR_FRAME_SPP, "frame_spp %u: an adaptive step needs independent samples (frame_spp 0)", p->frame_spp);
     *q = *p;
@@ -2352,18 +2365,37 @@ int mirt_ctx_adapt_step_device(MirtContext* c, const MirtParams* p, const MirtAd
     a.row_begin = q.row_begin; a.tile_rows = q.tile_rows; a.n_parts = q.n_parts; a.part = q.part;
     a.out_rows = c->adapt_rows;
     a.n_units = (uint32_t)c->adapt_pixels;
+    // MIRT_ADAPT_POOL on the BVH build: adapt_pixels_pool_kernel in the geometry mirt_adapt_pool_plan gives for the resident tree, where the
+    // pool's own limits allow it -- 8-bit bounce counters, a geometry that fits beside the stacks of a tree this deep; otherwise the step
+    // is the one without the flag.
+    MirtBvhPoolPlan plan{};
+    if ((adapt->flags & MIRT_ADAPT_POOL) && bvh && q.num_bounces <= 255u)
+        plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, c->tuning.hbm_pool_slots, mirt::kAdaptPoolExtraBytes);
+    const bool pooled = plan.slots != 0u && plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
     // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
-    fill_bvh_args(c, &a, 0u);
+    fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
     a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
+    uint32_t pool_blocks = 0;
+    if (pooled) {                                           // units of 16 list entries; the host does not know the count: a grid for all pixels
+        const uint64_t waves = plan.threads / 64u, units = (c->adapt_pixels + mirt::kStripPixels - 1u) / mirt::kStripPixels;
+        a.lds_bytes = plan.lds_bytes_per_block;             // camera words (+ sky), the block's pools, its waves' traversal stacks
+        pool_blocks = (uint32_t)((units + waves - 1u) / waves);
+        if (c->tuning.adapt_pool_blocks != 0u && pool_blocks > c->tuning.adapt_pool_blocks) pool_blocks = c->tuning.adapt_pool_blocks;
+    }
     uint32_t* head = reinterpret_cast<uint32_t*>(c->d_adapt_sel);
     uint32_t* list = reinterpret_cast<uint32_t*>(c->d_adapt_sel + 16u);
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_adapt_begin, st));
     HIP_TRY(kx::launch_adapt_select(c->d_adapt, (uint32_t)c->adapt_pixels, *adapt, q.spp, c->d_adapt_sel + c->adapt_off_flags,
                                     reinterpret_cast<uint32_t*>(c->d_adapt_sel + c->adapt_off_counts), list, head, st));
-    HIP_TRY(kx::launch_adapt_pixels(a, c->d_adapt, list, head, hosek, bvh, st));
     const char* tf[2] = { "false", "true" };
-    snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_kernel<%s,%s>", tf[hosek], tf[bvh]);
+    if (pooled) {
+        HIP_TRY(kx::launch_adapt_pixels_pool(a, c->d_adapt, list, head, pool_blocks, plan.slots, hosek, st));
+        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_pool_kernel<%u,%u,%u,%s>", plan.threads, plan.slots, mirt::kBvhPoolMinWaves, tf[hosek]);
+    } else {
+        HIP_TRY(kx::launch_adapt_pixels(a, c->d_adapt, list, head, hosek, bvh, st));
+        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_kernel<%s,%s>", tf[hosek], tf[bvh]);
+    }
     HIP_TRY(hipEventRecord(c->ev_adapt_end, st));
     c->adapt_pending = true;
     c->adapt_timed = timed;

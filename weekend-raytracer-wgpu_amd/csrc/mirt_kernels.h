@@ -233,6 +233,10 @@ constexpr uint32_t kBvhPoolMinWaves = 4;                          // waves per S
 constexpr uint32_t kBvhPoolWavesPerCu = 4u * kBvhPoolMinWaves;
 constexpr uint32_t kBvhPoolSlotChoices[4] = { 112, 96, 80, 64 };
 constexpr uint32_t bvh_pool_bytes_per_wave(uint32_t slots) { return 50u * slots + 384u; }     // == WavePoolLayout<slots, 1>::kBytes (static_assert in the kernel)
+// The pooled adaptive step (adapt_pixels_pool_kernel, MIRT_ADAPT_POOL) keeps behind that pool the 16 x 3 `even` accumulators
+// (384 bytes) and the {place in the band, samples so far} of its 16 list entries (128 bytes): mirt_adapt_pool_plan's bytes per wave
+constexpr uint32_t kAdaptPoolExtraBytes = 512;
+constexpr uint32_t adapt_pool_bytes_per_wave(uint32_t slots) { return bvh_pool_bytes_per_wave(slots) + kAdaptPoolExtraBytes; }     // (static_assert in the kernel)
 
 // The parts of a tile-interleaved frame and where they go (assemble_parts_kernel).  Two forms:
 //   table  (part_stride_px == 0): parts[i] is part i's compact buffer, n_parts <= kAssembleMaxParts (the node's members);
@@ -325,6 +329,11 @@ hipError_t launch_adapt_select(const void* d_recs, uint32_t n, const MirtAdaptPa
 // beyond *d_count return at once.  `a` carries the camera (with the pinhole word set), the tables, the sky, the tree, the row fields, width, height, spp,
 // num_bounces and seed_mix as a render launch's does; lds_bytes as launch_radiance wants them.
 hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, hipStream_t stream);
+// MIRT_ADAPT_POOL: adapt_pixels_pool_kernel<kBvhPoolThreads, slots, kBvhPoolMinWaves, hosek> (mirt_adapt_pool_kernel.inc), the pooled schedule on units of
+// 16 list entries.  `a` as for launch_adapt_pixels, but bvh_stack_entries / lds_bytes as mirt_adapt_pool_plan gives them; grid_blocks blocks of
+// kBvhPoolThreads, whose waves stride over the units; blocks beyond ceil(*d_count / 16) units return at once.
+hipError_t launch_adapt_pixels_pool(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, uint32_t slots, bool hosek,
+                                    hipStream_t stream);
 // adapt_resolve_kernel: n_pixels records -> RGBA8, every pixel over its own sample count
 hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);

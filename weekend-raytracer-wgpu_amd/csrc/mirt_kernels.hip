@@ -2189,6 +2189,7 @@ struct PoolHbmState {
 #include "mirt_radiance_kernel.inc"
 #include "mirt_radiance_pool_kernel.inc"
 #include "mirt_adapt_kernel.inc"
+#include "mirt_adapt_pool_kernel.inc"
 
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns

@@ -141,6 +141,15 @@ inline bool adapt_active(const MirtAdaptPixel& pixel, const MirtAdaptParams& ada
     check(mirt_adapt_active(&pixel, &adapt, &on));
     return on != 0u;
 }
+// MIRT_ADAPT_POOL in MirtAdaptParams.flags asks for the pooled schedule of the step's render stage (a hint: same records).
+static_assert(MIRT_ADAPT_POOL == 1u << 1, "MirtAdaptParams.flags: the pooled schedule");
+// mirt_adapt_pool_plan: the geometry such a step runs on a tree `max_depth` deep (host only; slots == 0: none fits, the step runs as without the flag)
+inline MirtBvhPoolPlan adapt_pool_plan(uint32_t max_depth, bool hosek = false, uint64_t lds_bytes_per_cu = 0)
+{
+    MirtBvhPoolPlan plan;
+    check(mirt_adapt_pool_plan(max_depth, hosek ? 1u : 0u, lds_bytes_per_cu, &plan));
+    return plan;
+}
 inline void adapt_reset(MirtContext* ctx, const MirtParams& params) { check(mirt_ctx_adapt_reset(ctx, &params)); }
 inline void adapt_step(MirtContext* ctx, const MirtParams& params, const MirtAdaptParams& adapt, void* hip_stream = nullptr)
 {

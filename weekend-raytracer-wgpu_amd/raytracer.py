@@ -830,15 +830,16 @@ class Raytracer:
             spp = self.render_params.sampling.num_samples_per_pixel
         return _radiance(self, rays, spp, seed, self.render_params.sampling.num_bounces, self.sky_state is not None, self.scene_data, sort, pool)
 
-    def render_adaptive(self, tolerance: int, max_spp: int, step: int = 4, min_spp: int = 4, *, seed: int = 0, flags: int = 0) -> tuple:
+    def render_adaptive(self, tolerance: int, max_spp: int, step: int = 4, min_spp: int = 4, *, seed: int = 0, flags: int = 0, pool: bool = False) -> tuple:
         """Adaptive sampling of the current viewport (mirt_ctx_adapt_*): steps of `step` (even) samples for the pixels that have not
         converged -- fewer than `min_spp` samples, or even and odd halves further apart than tolerance x 2^-16 of the mean -- until no
         pixel below `max_spp` is left -> (RGBA8 [h][w][4], samples per pixel uint32 [h][w]).  One RNG stream per sample whatever
         `reference_stream` says (a pixel's samples must be independent).  A scene held in LDS is set again as a MIRT_SCENE_HBM scene
         first and stays one; on a node member 0's context renders the whole viewport.  The accumulation is not touched.  The mean of
-        a pixel that a stopping rule has stopped is slightly biased."""
+        a pixel that a stopping rule has stopped is slightly biased.  pool=True asks for the pooled schedule
+        (MIRT_ADAPT_POOL, a hint): the image and the counts are the same."""
         from .context import make_adapt_params
-        adapt = make_adapt_params(min_spp, max_spp, tolerance)
+        adapt = make_adapt_params(min_spp, max_spp, tolerance, pool)
         if not isinstance(step, (int, np.integer)) or isinstance(step, bool) or int(step) < 2 or int(step) % 2:
             raise ValueError(f"step must be an even sample count >= 2, not {step!r}")
         target = self._pick_target()
