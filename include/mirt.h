@@ -810,6 +810,14 @@ int mirt_adapt_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_
  * both must be 0 for the bit-parity claim to hold on this device. */
 int mirt_ctx_selftest_math(MirtContext* ctx, uint64_t out_mismatches[2]);
 
+/* Device self-test of the checkerboard's guarded fast path (spec S9 evaluates the sign of sin(5x) sin(5y) sin(5z) from the
+ * argument reduction of the sine; the kernels first try the parity of floor(a / pi) and keep the reduction for the lanes
+ * where rounding could decide).  For EVERY binary32 pattern a, as one axis: out[0] = the inputs the fast path calls decided,
+ * out[1] = those among them whose parity disagrees with the reduction's sign, out[2] = those among them for which the
+ * reduction reports sin(a) == 0.  out[1] and out[2] must be 0: agreement on every axis is agreement of the product, and
+ * the undecided lanes run the reduction itself. */
+int mirt_ctx_selftest_checker_sign(MirtContext* ctx, uint64_t out_counts[3]);
+
 /* One-shot convenience: create context on `device`, set scene, render to host, destroy.
  * Signature a Rust `set_data` binds when it does not keep a context. */
 int mirt_render(const MirtScene* scene, const MirtParams* params, int device,

@@ -450,6 +450,7 @@ extern "C" {
     pub fn mirt_ctx_adapt_list_read(ctx: *mut MirtContext, list: *mut u32, len: usize, count: *mut u32) -> c_int;
     pub fn mirt_ctx_adapt_stats(ctx: *mut MirtContext, out: *mut MirtAdaptStats) -> c_int;
     pub fn mirt_ctx_selftest_math(ctx: *mut MirtContext, out_mismatches: *mut u64) -> c_int;
+    pub fn mirt_ctx_selftest_checker_sign(ctx: *mut MirtContext, out_counts: *mut u64) -> c_int;
     pub fn mirt_render(scene: *const MirtScene, params: *const MirtParams, device: c_int, out_rgba8: *mut u8, out_len: usize) -> c_int;
     pub fn mirt_rgba8_to_rgb8(rgba: *const u8, n_pixels: usize, rgb: *mut u8) -> c_int;
     // `Texture::new_from_image` (texture.rs:21-46) without the `image` crate: JPEG bytes -> RGB8 -> [f32;3] texels

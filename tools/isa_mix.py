@@ -6,7 +6,7 @@ mirt_kernels.hip holds, under -DMIRT_ISA_PROBES, one small kernel per routine ar
 class, subtracts the frame and writes profiles/<tag>_isa_mix.md: what a routine costs one wave per execution, and --
 weighted with how often a sample runs each routine on config 3 (work counters) -- where the instructions of a sample go.
 
-    python tools/isa_mix.py [tag]
+    python tools/isa_mix.py [tag] [--extra=-DMIRT_X]      (--extra: more compiler flags, e.g. -DMIRT_CHECKER_SIGN_FULL)
 """
 import collections
 import re
@@ -58,13 +58,15 @@ COLS = ["valu_fp", "valu_seed", "valu_int", "valu_cmp_select", "valu_convert", "
 
 
 def main() -> int:
+    extra = [f for a in sys.argv[1:] if a.startswith("--extra=") for f in a[len("--extra="):].split()]
+    sys.argv = [a for a in sys.argv if not a.startswith("--extra=")]
     if len(sys.argv) > 1 and sys.argv[1].startswith("-"):
-        print("usage: tools/isa_mix.py [TAG]   -> profiles/TAG_isa_mix.md (static instruction mix of the probe kernels; builds them first)")
+        print("usage: tools/isa_mix.py [TAG] [--extra=FLAGS]   -> profiles/TAG_isa_mix.md (static instruction mix of the probe kernels; builds them first)")
         return 0
     tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
     out = CSRC / "build" / "probes"
     out.mkdir(parents=True, exist_ok=True)
-    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-save-temps=obj", "-c", "mirt_kernels.hip", "-o", str(out / "k.o")], cwd=CSRC, check=True,
+    subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "-save-temps=obj", "-c", "mirt_kernels.hip", "-o", str(out / "k.o")], cwd=CSRC, check=True,
                    capture_output=True)
     asm = (out / "mirt_kernels-hip-amdgcn-amd-amdhsa-gfx950.s").read_text().splitlines()
     counts: dict = {}

@@ -659,6 +659,12 @@ class Context:
         check(lib().mirt_ctx_selftest_math(self._h, out))
         return int(out[0]), int(out[1])
 
+    def selftest_checker_sign(self) -> tuple:
+        """(decided, parity mismatches, zeros) of the checkerboard's fast sign path, axis by axis over all 2^32 floats."""
+        out = (C.c_uint64 * 3)()
+        check(lib().mirt_ctx_selftest_checker_sign(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def last_kernel(self) -> str:
         """Name of the render kernel the last render call launched (as rocprofv3 traces spell it)."""
         s = lib().mirt_ctx_last_kernel(self._h)

@@ -2509,6 +2509,21 @@ int mirt_ctx_selftest_math(MirtContext* c, uint64_t out[2])
     return MIRT_OK;
 }
 
+int mirt_ctx_selftest_checker_sign(MirtContext* c, uint64_t out[3])
+{
+    if (!c || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/out is null");
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = mirt_ctx_synchronize(c); if (rc != MIRT_OK) return rc; }    // borrows counter block 0
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, 3 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(kx::launch_selftest_checker_sign(c->d_counters, c->stream));
+    unsigned long long h[3] = { 0, 0, 0 };
+    HIP_TRY(hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, 3 * sizeof(unsigned long long), c->stream));      // the block goes back as it came
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 3; ++i) out[i] = h[i];
+    return MIRT_OK;
+}
+
 int mirt_render(const MirtScene* scene, const MirtParams* params, int device, uint8_t* out, size_t out_len)
 {
     MirtContext* c = nullptr;

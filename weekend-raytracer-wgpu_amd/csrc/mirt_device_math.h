@@ -220,13 +220,82 @@ MIRT_DEV uint32_t sin_sign_bits(float x, uint32_t& neg)
     return (br << 1) | (q & 1u);
 }
 
-// sin(a) sin(b) sin(c) < 0, decided exactly as sin_sign(a) * sin_sign(b) * sin_sign(c) < 0
-MIRT_DEV bool sin_product_negative(float a, float b, float c)
+// sin(a) sin(b) sin(c) < 0, decided exactly as sin_sign(a) * sin_sign(b) * sin_sign(c) < 0: the three full reductions
+MIRT_DEV bool sin_product_negative_full(float a, float b, float c)
 {
     uint32_t n0, n1, n2;
     const uint32_t z0 = sin_sign_bits(a, n0), z1 = sin_sign_bits(b, n1), z2 = sin_sign_bits(c, n2);
     const uint32_t zmin = (z0 < z1) ? ((z0 < z2) ? z0 : z2) : ((z1 < z2) ? z1 : z2);      // v_min3_u32
     return (((n0 ^ n1 ^ n2) & 1u) != 0u) && (zmin != 0u);
+}
+
+// The guarded fast path of sin_product_negative (spec S9 is unchanged: where this function answers, it answers what the
+// reductions answer).  Per axis t = a * fl(1/pi), n = floor(t), fr = t - n (v_fract_f32): when fr keeps a distance of more
+// than thr = d0 + d1 * |t| from both 0 and 1, sin(a) is not zero and is negative exactly when n is odd.  Returns "all three
+// axes are decided" and sets bit 0 of `odd` to the parity of n_a + n_b + n_c, which is then the sign of the product.
+//
+// The band, on paper.  Write tau = a / pi.  (1) t = fl(a * c) with c = fl(1/pi) = (1/pi)(1 - 4.04e-8): |t - tau| <=
+// |tau| (2^-24 + 4.04e-8 + 2^-48) < 1.0005e-7 |t|; fr = t - n is exact for |t| >= 1 and for 0 <= t < 1, and for -1 < t < 0
+// it rounds only where the nearest integer is 0 and the sign (n = -1, sin < 0) does not depend on it.  (2) The reduction
+// itself, r = ((a - q kHi) - q kMd) - q kLo with q <= 667544: the first fma is exact (q kHi has 28 bits and the difference
+// fits 24), the second rounds by at most half an ulp of |r2| <= |r| + q kLo, and kHi + kMd + kLo misses pi/2 by 4.5e-15; close
+// to a multiple of pi that is |a - k pi| <= q (4.5e-15 + 2^-25 * 7.55e-8) = 6.8e-15 q, in units of t less than 1.4e-14 |t|.  Both
+// errors are proportional to |t|, so d0 = 0 and d1 > 1.0006e-7 = 2^-23.25 suffice; a d0 > 0 would only guard the 100
+// binades of floats below it, where sin(a) has the sign of a and t, fr and n say so exactly.  |a| <= 2^20, the domain of
+// the reduction (beyond it the spec's sine is 0), follows from |t| <= 333772: a <= 333772 / (c (1 - 2^-24)) < 1048575.8.
+// NaN: v_fract_f32 gives NaN, the UNSIGNED maximum of the three fr patterns keeps it (a float maximum would drop it), and
+// 1 - NaN > thr is false; +-0 gives fr = +-0, which is not > thr = 0; inf gives |t| = inf.
+// Measured (mirt_ctx_selftest_checker_sign on gfx950, all 2^32 patterns; builds with -DMIRT_CHECKER_BAND=x): d1 = 7.9e-8 lets 66 decided
+// inputs disagree, d1 = 8.05e-8 none; the neighbours of every k pi on the CPU (tests/test_checker_sign_cpu.py's inputs) put the smallest
+// passing d1 at 8.017e-8, needed at a = fl(194898 pi).  Shipped: 2^-21 = 4.77e-7, 5.9 x that and 4.8 x the paper bound; 99.67 % of the
+// finite inputs of the domain are then decided, and 0.7 % of the pool kernel's checker steps on config 3 take the branch.
+// One band serves the three axes: min3 / max3 of the fr, and the threshold of the largest |t|, which is at least each axis' own.
+#ifndef MIRT_CHECKER_BAND             // experiment builds narrow it to find the smallest band that passes exhaustively
+#define MIRT_CHECKER_BAND 0x1p-21f    // d1 shipped; d0 = 0
+#endif
+constexpr float kCheckerBand = MIRT_CHECKER_BAND;
+constexpr float kCheckerMaxT = 333772.0f;
+MIRT_DEV bool sin_product_decided(float a, float b, float c, uint32_t& odd)
+{
+    const float t0 = a * kFrac1Pi, t1 = b * kFrac1Pi, t2 = c * kFrac1Pi;
+    const float f0 = __builtin_amdgcn_fractf(t0), f1 = __builtin_amdgcn_fractf(t1), f2 = __builtin_amdgcn_fractf(t2);
+    const float lo = __builtin_fminf(__builtin_fminf(f0, f1), f2);                                 // v_min3_f32
+    const uint32_t u0 = bits(f0), u1 = bits(f1), u2 = bits(f2);                                      // fr in [0, 1): bit order is value order
+    const float hi = from_bits((u0 > u1) ? ((u0 > u2) ? u0 : u2) : ((u1 > u2) ? u1 : u2));         // v_max3_u32
+    const float tmax = __builtin_fmaxf(__builtin_fmaxf(abs_(t0), abs_(t1)), abs_(t2));           // v_max3_f32, |.| as modifiers
+    const float thr = kCheckerBand * tmax;
+    // the floors are integers below 2^19 in magnitude wherever the answer is used: their float sum is exact
+    odd = (uint32_t)(int)((__builtin_floorf(t0) + __builtin_floorf(t1)) + __builtin_floorf(t2));
+    return (lo > thr) & ((1.0f - hi) > thr) & (tmax <= kCheckerMaxT);
+}
+
+#ifdef MIRT_DIAG_CHECKER              // diagnosis build (tools/checker_slow_share.py): waves through the function, waves that took the branch
+__device__ unsigned long long g_checker_diag[2];
+#endif
+
+MIRT_DEV bool sin_product_negative(float a, float b, float c)
+{
+#ifdef MIRT_CHECKER_SIGN_FULL        // A/B builds: the three reductions on every lane, as before the fast path
+    return sin_product_negative_full(a, b, c);
+#else
+    uint32_t odd;
+    const bool decided = sin_product_decided(a, b, c, odd);
+    bool negative = (odd & 1u) != 0u;
+#ifdef MIRT_DIAG_CHECKER
+    {
+        const unsigned long long active = __builtin_amdgcn_ballot_w64(true), slow = __builtin_amdgcn_ballot_w64(!decided);
+        if (__builtin_amdgcn_mbcnt_hi((uint32_t)(active >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)active, 0u)) == 0u) {
+            atomicAdd(&g_checker_diag[0], 1ull);
+            if (slow != 0ull) atomicAdd(&g_checker_diag[1], 1ull);
+        }
+    }
+#endif
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!decided) != 0ull, 0)) {    // wave-uniform and rare
+        asm volatile("; sin_product_negative: full reduction" ::);              // keeps this a real branch
+        negative = decided ? negative : sin_product_negative_full(a, b, c);
+    }
+    return negative;
+#endif
 }
 
 MIRT_DEV float asin_core(float x, float z)

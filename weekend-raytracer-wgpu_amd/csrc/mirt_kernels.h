@@ -297,6 +297,8 @@ uint32_t pool_scatter_queues(uint32_t n_routines, bool count);
 hipError_t launch_resolve(const unsigned long long* accum, uint32_t* out, uint64_t n_pixels, uint32_t n_samples,
                           uint32_t flags, hipStream_t stream);
 hipError_t launch_selftest_math(unsigned long long* d_mismatches, hipStream_t stream);
+// d_counts[3]: decided inputs, parity mismatches and zeros among them (mirt_ctx_selftest_checker_sign)
+hipError_t launch_selftest_checker_sign(unsigned long long* d_counts, hipStream_t stream);
 // mirt_ctx_trace_rays*: trace_rays_kernel<bvh, any, count> (mirt_trace_kernel.inc), one thread per ray.  `a` carries the tree exactly as a render
 // launch's does, bvh_stack_entries = the stack entries per lane, lds_bytes = 256 x that per wave of the block (0 for the flat scan), and
 // `counters`; d_rays / d_hits: [n_rays] MirtRay / MirtRayHit in device memory, 4-byte aligned.

@@ -2220,6 +2220,51 @@ hipError_t launch_selftest_math(unsigned long long* d_mismatches, hipStream_t st
     return hipGetLastError();
 }
 
+// self-test: the fast path of sin_product_negative, one axis at a time, against sin_sign_bits over ALL 2^32 patterns.
+// sin_product_decided(a, a, a) is the shipped code with every axis the same: it is decided exactly when the one axis is,
+// under its own threshold, and the parity of 3 n is the parity of n.
+__global__ __launch_bounds__(256) void selftest_checker_sign_kernel(unsigned long long* counts)
+{
+    unsigned long long decided = 0, bad = 0, zeros = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32); i += (uint64_t)gridDim.x * blockDim.x) {
+        const float a = from_bits((uint32_t)i);
+        uint32_t odd, neg;
+        const bool d = sin_product_decided(a, a, a, odd);
+        const uint32_t z = sin_sign_bits(a, neg);
+        decided += d;
+        bad += d && z != 0u && ((odd ^ neg) & 1u) != 0u;
+        zeros += d && z == 0u;
+    }
+    decided = wave_sum_u64(decided);
+    bad = wave_sum_u64(bad);
+    zeros = wave_sum_u64(zeros);
+    if ((threadIdx.x & 63u) == 0) {
+        atomicAdd(&counts[0], decided);
+        if (bad) atomicAdd(&counts[1], bad);
+        if (zeros) atomicAdd(&counts[2], zeros);
+    }
+}
+
+#ifdef MIRT_DIAG_CHECKER
+// diagnosis build only: {waves that ran sin_product_negative, waves among them that took the full reduction} since the last reset
+extern "C" __attribute__((visibility("default"))) int mirt_diag_checker_sign(unsigned long long out[2], int reset)
+{
+    unsigned long long h[2] = { 0, 0 };
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_checker_diag), sizeof h) != hipSuccess) return -1;
+    out[0] = h[0]; out[1] = h[1];
+    h[0] = h[1] = 0;
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_checker_diag), h, sizeof h) != hipSuccess) return -1;
+    return 0;
+}
+#endif
+
+hipError_t launch_selftest_checker_sign(unsigned long long* d_counts, hipStream_t stream)
+{
+    hipLaunchKernelGGL(selftest_checker_sign_kernel, dim3(4096), dim3(256), 0, stream, d_counts);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 // resolve of the progressive accumulation buffer: exact sums -> mean -> tonemap -> RGBA8
 // (the `invN * pixel` + uncharted2 tail of fsMain, wgsl:75-80)
