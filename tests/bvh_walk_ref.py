@@ -23,10 +23,11 @@ SLACK = f32(1.0) + f32(2.0 ** -9)                 # kBvhSlack
 E_SCALE = f32(f32(2.0 ** -8) * f32(1.01))         # 0x1p-8f * 1.01f
 
 
-def _slab(lo, hi, ro, inv, sgn, e_cone):
-    """bvh_slab for boxes (lo, hi) [k, 3] and rays (ro, inv, sgn) [k, 3], e_cone [k] -> (tn, tf)."""
+def _slab(lo, hi, ro, inv, sgn, e_cone, e_scale=E_SCALE):
+    """bvh_slab for boxes (lo, hi) [k, 3] and rays (ro, inv, sgn) [k, 3], e_cone [k] -> (tn, tf).  `e_scale` stands for the kernel's
+    0x1p-8f * 1.01f in the farthest-corner bound."""
     d = np.maximum(np.abs(lo - ro), np.abs(hi - ro))
-    e_box = E_SCALE * np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    e_box = f32(e_scale) * np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
     e = np.where(e_box < e_cone, e_box, e_cone)
     ev = e[:, None] * np.abs(inv)
     near = (np.where(sgn, lo, hi) - ro) * inv - ev
@@ -36,10 +37,16 @@ def _slab(lo, hi, ro, inv, sgn, e_cone):
     return tn, tf
 
 
-def walk(nodes, recs, ids, info, o, d, t_max, stack_cap, radii=None):
+def walk(nodes, recs, ids, info, o, d, t_max, stack_cap, radii=None, e_scale=E_SCALE, slack=SLACK, cone_rmax=True):
     """-> (hits RAY_HIT_DTYPE [n], high water [n], dropped pushes [n]) of rays (o, d) [n, 3] bounded by t_max (scalar or [n]) on the
     tree (nodes, recs, ids, info) with a stack of `stack_cap` entries.  `radii` [n_spheres] in original order give the hit records
-    their normals; None: the square roots of the records' r * r (exact for the power-of-two radii of the deep worlds)."""
+    their normals; None: the square roots of the records' r * r (exact for the power-of-two radii of the deep worlds).
+
+    The slack of the walk as parameters, the kernel's values the defaults -- anything else is a MUTANT, a walk the kernel does not
+    perform, for showing that a set of rays needs the slack (tests/test_bvh_rounding_cpu.py): `e_scale` replaces 0x1p-8f * 1.01f in
+    all three bounds of E (0: boxes are not grown), `slack` replaces kBvhSlack in both comparisons that carry it, and
+    cone_rmax=False drops the 2 r_max term of the cone bound."""
+    e_scale, slack = f32(e_scale), f32(slack)
     o, d = np.asarray(o, f32), np.asarray(d, f32)
     n = len(o)
     recs = np.asarray(recs, f32).reshape(-1, 4)
@@ -67,12 +74,12 @@ def walk(nodes, recs, ids, info, o, d, t_max, stack_cap, radii=None):
         inv = (f32(1.0) / d).astype(f32)
         sgn = inv >= 0
         dc = (o - np.asarray(info["centre"], f32)).astype(f32)
-        e_world = E_SCALE * (np.sqrt(dot32(dc[:, 0], dc[:, 1], dc[:, 2], dc[:, 0], dc[:, 1], dc[:, 2])) + f32(info["radius"]))
+        e_world = e_scale * (np.sqrt(dot32(dc[:, 0], dc[:, 1], dc[:, 2], dc[:, 0], dc[:, 1], dc[:, 2])) + f32(info["radius"]))
         len_d = f32(1.01) * np.sqrt(a)
-        two_rmax = f32(2.0) * f32(info["r_max"])
+        two_rmax = f32(2.0) * f32(info["r_max"]) if cone_rmax else f32(0.0)
 
         def grow(rays):
-            e = E_SCALE * (closest[rays] * len_d[rays] + two_rmax)
+            e = e_scale * (closest[rays] * len_d[rays] + two_rmax)
             return np.where(e < e_world[rays], e, e_world[rays])
 
         e_cone = grow(everyone)
@@ -98,11 +105,11 @@ def walk(nodes, recs, ids, info, o, d, t_max, stack_cap, radii=None):
             if len(iv):
                 nd = nodes[ref[iv]]
                 ro, ri, sg, ec = o[iv], inv[iv], sgn[iv], e_cone[iv]
-                tnl, tfl = _slab(nd["lmin"], nd["lmax"], ro, ri, sg, ec)
-                tnr, tfr = _slab(nd["rmin"], nd["rmax"], ro, ri, sg, ec)
-                lim = closest[iv] * SLACK
-                vl = ~(tnl > lim) & ~(tfl < 0) & ~(tnl > tfl * SLACK)
-                vr = ~(tnr > lim) & ~(tfr < 0) & ~(tnr > tfr * SLACK)
+                tnl, tfl = _slab(nd["lmin"], nd["lmax"], ro, ri, sg, ec, e_scale)
+                tnr, tfr = _slab(nd["rmin"], nd["rmax"], ro, ri, sg, ec, e_scale)
+                lim = closest[iv] * slack
+                vl = ~(tnl > lim) & ~(tfl < 0) & ~(tnl > tfl * slack)
+                vr = ~(tnr > lim) & ~(tfr < 0) & ~(tnr > tfr * slack)
                 lref, rref = nd["left"].astype(np.int64), nd["right"].astype(np.int64)
                 both, one = vl & vr, vl ^ vr
                 left_first = ~(tnr < tnl)

@@ -1618,7 +1618,16 @@ MIRT_DEV uint32_t strip_candidates(const RenderArgs& AP, const SceneLds& S, uint
 // which every negated comparison above turns into "visit".  Non-finite boxes (a tree sphere beyond the always-tested list's
 // capacity) are infinite: always visited.  Adversarial cases (tests/test_gpu_hbm_scene.py): 1 000 copies of one sphere, tangent
 // lattices whose boxes share faces, axis-aligned cameras, a camera inside a sphere, grazing rays at r = 10^-3 / distance 10^3,
-// zero-radius and non-finite spheres -- all byte-equal to the flat scan.
+// zero-radius and non-finite spheres -- all byte-equal to the flat scan.  None of those needs more than a sliver of E.  The ray
+// sets that do (tests/bvh_rounding.py, through host-built, device-built, set_spheres and refitted trees in
+// tests/test_gpu_bvh_rounding.py): a jittered plane lattice of r = 0.2 / 10^-3 seen from a column 10^3 .. 10^19 above it (rays
+// almost parallel to an axis, whose slabs resolve a lateral miss sharply: without E 1 159 to 4 004 of 4 096 records change from
+// 10^5 on), the same lattice translated by 2^12 .. 2^20, the worst phantoms of a directed search (reach up to 2^-11.2 L of the
+// 2^-9.4 L derived above) against spheres strung along a line, rays grazing spheres of r = 1 with a small sphere just ahead
+// (closest |d| << r_max), directions of length 2^-66 .. 2^-60 and 2^55 .. 2^63, and the scenes of tests/grid_rounding.py as HBM
+// scenes.  What they can tell apart: the numpy walk (tests/bvh_walk_ref.py) with E / 2^4 changes >= 16 records of the searched
+// set, with E / 2^3 none -- 2^-8 is told from 2^-12, not from 2^-11; no ray was found on which kBvhSlack = 1 or a cone bound
+// without 2 r_max changes a record (DESIGN.md 10.1 has the table and the search).
 //
 // Traversal: near child first, the far one on a per-lane stack in LDS of `stack_cap` entries.  An entry is pushed only at an inner
 // node, at most one per level of the path from the root, so a stack of as many entries as the tree is deep can FILL EXACTLY (a ray
