@@ -45,31 +45,10 @@ int fail(int status, const char* fmt, ...)
             return fail(MIRT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// ---- MirtParams row selection ----
-bool rows_valid(const MirtParams* p, uint32_t* rb, uint32_t* re)
-{
-    const uint32_t b = p->row_begin, e = p->row_end == 0 ? p->height : p->row_end;
-    if (b >= e || e > p->height) return false;
-    if (p->tile_rows != 0 && p->n_parts > 1 && p->part >= p->n_parts) return false;
-    *rb = b;
-    *re = e;
-    return true;
-}
-
-uint32_t out_rows(const MirtParams* p)
-{
-    uint32_t rb, re;
-    if (!p || p->width == 0 || p->height == 0 || !rows_valid(p, &rb, &re)) return 0;
-    const uint32_t band = re - rb;
-    if (p->tile_rows == 0 || p->n_parts <= 1) return band;
-    const uint32_t tr = p->tile_rows;
-    const uint32_t tiles = (band + tr - 1) / tr;
-    if (tiles <= p->part) return 0;
-    const uint32_t owned = (tiles - p->part + p->n_parts - 1) / p->n_parts;
-    uint32_t rows = owned * tr;
-    if ((tiles - 1) % p->n_parts == p->part) rows -= tiles * tr - band;
-    return rows;
-}
+using mirt::rows_valid;     // MirtParams row selection, the knobs and the pooled BVH geometry: mirt_launch_plan.h
+using mirt::out_rows;
+using mirt::Tuning;
+using mirt::plan_bvh_pool;
 
 bool desc_ok(const MirtTextureDescriptor& d, uint64_t n_texels)
 {
@@ -272,37 +251,7 @@ std::vector<unsigned char> plan_grid(const MirtSphere* sph, uint32_t n, double c
     return grid;
 }
 
-// Tuning / experiment knobs.  They are read from the environment ONCE, when a context is created
-// (mirt_ctx_create), never inside a render call: a shipped library must not change its schedule
-// because a variable appeared mid-run, and getenv has no place in a sub-millisecond launch path.
-struct Tuning {
-    int      pool_config = -1;        // MIRT_POOL_CONFIG: geometry of the path pool (index into kPoolConfigs)
-    int      pool_grid = -1;          // MIRT_POOL_GRID=0: never take the pool kernel's grid build
-    bool     fixed_strips = false;    // MIRT_STRIP_MODE=16: fixed 16-pixel strips (no guided self-scheduling)
-    uint32_t gss_min_width = 0;       // MIRT_GSS_MINW: narrowest strip of the guided schedule
-    double   gss_keep = 0.0;          // MIRT_GSS_KEEP: strips per resident wave kept for the narrower levels
-    int      by_pixel = -1;           // MIRT_BY_PIXEL=0/1: force lane = sample / lane = pixel in the strip kernel
-    uint32_t pool_blocks_per_cu = 0;  // MIRT_POOL_BLOCKS_PER_CU: fewer resident pool blocks (occupancy experiments)
-    double   grid_cell = 0.0;         // MIRT_GRID_CELL: cell size of the uniform grid in median radii
-    double   grid_big = 0.0;          // MIRT_GRID_BIG: spheres above this many median radii stay outside the grid
-    int      pinhole = -1;            // MIRT_PINHOLE=0: never take the pinhole-camera shortcut (A/B runs)
-    int      spread_units = -1;       // MIRT_SPREAD_UNITS=0: strip-type launches use one dispenser word (A/B runs)
-    int      static_units = -1;       // MIRT_STATIC_UNITS=0/1: lane-per-pixel units dispensed to a persistent grid / one unit per wave (A/B runs, tests)
-    int      pool_min_spp = -1;       // MIRT_POOL_MIN_SPP=n: flat scenes take the pooled kernel from n samples per pixel on (A/B runs: the crossovers kPoolMinSpp*)
-    int      stream = -1;             // MIRT_STREAM=0/1: lane-per-pixel launches in flat scenes never / always run the streaming build (A/B runs)
-    int      px_groups = -1;          // MIRT_PX_GROUPS=0: lane-per-pixel units are always 64 pixels; 1 / 2 / 3: force 1 / 2 / 4 sample groups (A/B runs)
-    int      strip_cand = -1;         // MIRT_STRIP_CAND=0: camera rays of grid builds take the grid like every other ray (A/B runs)
-    int      grid_flat_y = -1;        // MIRT_GRID_FLAT_Y=0: a grid one cell high is walked in three dimensions like any other (A/B runs, tests)
-    bool     debug_slots = false;     // MIRT_DEBUG_SLOTS=1: every launch checks (synchronously) that its slot's dispenser words are zero
-    uint32_t static_block = 0;        // MIRT_STATIC_BLOCK=64/128/256 (A/B runs): threads per block of the launches that run one unit per wave
-    int      static_grid = -1;        // MIRT_STATIC_GRID=k (A/B runs): launches with one unit per wave run k x the resident blocks instead, units dealt round-robin
-    int      timing = -1;             // MIRT_TIMING=0/1: the context's initial mirt_ctx_set_timing state (A/B runs; default 1)
-    uint32_t hbm_pool_slots = 0;      // MIRT_HBM_POOL_SLOTS=n (A/B runs): the pooled build of MIRT_SCENE_HBM scenes takes this one of kBvhPoolSlotChoices
-    uint32_t radiance_pool_blocks = 0;    // MIRT_RADIANCE_POOL_BLOCKS=n (A/B runs, tests): a pooled radiance query launches at most n blocks, whose waves stride over the units
-    uint32_t adapt_pool_blocks = 0;   // MIRT_ADAPT_POOL_BLOCKS=n (A/B runs, tests): a pooled adaptive step launches at most n blocks, whose waves stride over the units
-    bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
-};
-
+// The knobs of mirt_launch_plan.h's Tuning, read from the environment (once per context: mirt_ctx_create).
 Tuning read_tuning()
 {
     Tuning t;
@@ -335,29 +284,6 @@ Tuning read_tuning()
     if (const char* e = std::getenv("MIRT_ADAPT_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_pool_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_GRID_BIG")) { const double v = std::atof(e); if (v >= 1.0 && v <= 1024.0) t.grid_big = v; }
     return t;
-}
-
-// The geometry of the pooled kernel of MIRT_SCENE_HBM scenes (mirt_bvh_pool_plan; the launch calls this very function) for a tree
-// `max_depth` deep: per block the camera (+ sky), and per wave a pool and 64 stacks of max_depth entries.  The rule (mirt_kernels.h,
-// DESIGN.md 10.6): the first of kBvhPoolSlotChoices -- largest pools first -- that leaves kBvhPoolWavesPerCu waves resident, else the
-// choice with most waves, the larger pools on a tie.  slots == 0: not even one block fits.  `only_slots` != 0 (A/B runs): that choice alone.
-// `extra_per_wave`: bytes a wave keeps beside its pool -- 0 for the pooled render and the pooled query, kAdaptPoolExtraBytes for the
-// pooled adaptive step (mirt_adapt_pool_plan).
-MirtBvhPoolPlan plan_bvh_pool(uint32_t max_depth, bool hosek, uint64_t lds_per_cu, uint32_t only_slots, uint32_t extra_per_wave)
-{
-    MirtBvhPoolPlan best{};
-    const uint32_t waves = mirt::kBvhPoolThreads / 64u;
-    const uint64_t scene = kx::scene_lds_bytes_grid(0u, hosek);
-    for (uint32_t slots : mirt::kBvhPoolSlotChoices) {
-        if (only_slots != 0u && slots != only_slots) continue;
-        const uint64_t block = scene + (uint64_t)waves * (mirt::bvh_pool_bytes_per_wave(slots) + extra_per_wave + 256ull * max_depth);
-        uint64_t blocks = lds_per_cu / block;
-        if (blocks > mirt::kBvhPoolWavesPerCu / waves) blocks = mirt::kBvhPoolWavesPerCu / waves;
-        if ((uint32_t)blocks * waves > best.waves_per_cu)
-            best = MirtBvhPoolPlan{ mirt::kBvhPoolThreads, slots, (uint32_t)blocks * waves, max_depth, (uint32_t)block };
-        if (best.waves_per_cu == mirt::kBvhPoolWavesPerCu) break;
-    }
-    return best;
 }
 
 // A camera whose thin-lens offset is exactly zero for every lens draw, so that `origin = eye + lens_radius * (...)`
@@ -1282,288 +1208,200 @@ static void fill_bvh_args(const MirtContext* c, mirt::RenderArgs* a, uint32_t st
     a->bvh_stack_entries = stack_entries;
 }
 
+// The tree and the traversal stacks of the query kernels that run one thread per ray or pixel in kBlockThreads blocks (ray queries, feature
+// frames): the stacks hold as many node references per lane as the resident tree is deep (a push happens at inner nodes only, at
+// most one per level): 256 x depth bytes per wave, as in the pooled kernel -- at most 32 KB per block (MIRT_BVH_MAX_DEPTH)
+static void fill_query_stacks(const MirtContext* c, mirt::RenderArgs* a, bool bvh)
+{
+    const uint32_t entries = bvh ? (c->bvh_plan.max_depth ? c->bvh_plan.max_depth : 1u) : 0u;
+    fill_bvh_args(c, a, entries);
+    a->lds_bytes = (mirt::kBlockThreads / 64u) * 64u * 4u * entries;
+}
+
+// Blocks of a pooled query launch (radiance query, adaptive step) over `units` units of 16, one unit per wave; `at_most` != 0
+// (MIRT_*_POOL_BLOCKS): no more blocks than that, their waves stride over the units
+static uint32_t pooled_query_blocks(uint64_t units, uint32_t threads, uint32_t at_most)
+{
+    const uint64_t waves = threads / 64u, blocks = (units + waves - 1u) / waves;
+    return (uint32_t)(at_most != 0u && blocks > at_most ? at_most : blocks);
+}
+
+// a query kernel is queued behind ev_trace_begin / before ev_trace_end: what mirt_ctx_trace_stats will wait for and fold
+static void mark_trace_queued(MirtContext* c, bool timed, bool counted)
+{
+    c->trace_pending = true;
+    c->trace_timed = timed;
+    c->trace_counted = counted;
+    c->trace_stats = MirtRayStats{};
+}
+
+// jenkins-folds a caller's 64-bit seed into the 32-bit key of a launch's RNG streams (RenderArgs.seed_mix)
+static uint32_t seed_mix(uint64_t seed) { return jenkins_hash((uint32_t)seed ^ jenkins_hash((uint32_t)(seed >> 32))); }
+
+// What every launch copies from the context and its params: the tables and counts, the sampling and row fields, seed_mix and -- unless
+// `pinhole` < 0: a launch without a camera (ray queries) -- the camera.
+// The kernels' pinhole shortcut (generate_primary): the flag `pinhole` travels in the padding word beside lower_left_corner of
+// THIS launch's by-value copy of the camera; the caller's struct is never touched.
+static void fill_common_args(const MirtContext* c, mirt::RenderArgs* a, const MirtParams& p, uint32_t rows, int pinhole)
+{
+    if (pinhole >= 0) {
+        a->cam = c->cam;
+        const uint32_t flag = (uint32_t)pinhole;
+        std::memcpy(&a->cam._padding5, &flag, 4);
+    }
+    a->spheres = c->d_spheres; a->mats = c->d_mats; a->pmats = c->d_pmats; a->texels = c->d_texels; a->sky = c->d_sky;
+    a->n_texels = c->n_texels; a->n_spheres = c->n_spheres; a->n_mats = c->n_mats;
+    a->width = p.width; a->height = p.height; a->spp = p.spp; a->num_bounces = p.num_bounces; a->flags = p.flags;
+    a->seed_mix = seed_mix(p.seed);
+    a->sample_begin = p.sample_begin;
+    a->row_begin = p.row_begin; a->tile_rows = p.tile_rows; a->n_parts = p.n_parts; a->part = p.part;
+    a->out_rows = rows;
+}
+
+// the pinhole word of the launches beside launch_render (all path-traced): MIRT_PINHOLE=0 switches the shortcut off
+static int pinhole_word(const MirtContext* c) { return (c->tuning.pinhole != 0 && camera_is_pinhole(c->cam)) ? 1 : 0; }
+
+// what the launch plan reads of a context (mirt_launch_plan.h)
+static mirt::PlanFacts plan_facts(const MirtContext* c)
+{
+    mirt::PlanFacts f{};
+    f.cu_count = (uint32_t)c->cu_count; f.lds_per_cu = c->lds_per_cu; f.lds_per_block = c->lds_per_block;
+    f.n_spheres = c->n_spheres; f.n_mats = c->n_mats; f.n_shading_routines = c->n_shading_routines;
+    f.has_image_texture = c->has_image_texture; f.have_sky = c->have_sky; f.fits_flat = c->fits_flat; f.hbm = c->hbm;
+    f.grid_bytes = c->grid_bytes; f.grid_packable = c->grid_packable; f.grid_flat_y = c->grid_flat_y; f.have_shade = c->have_shade;
+    f.bvh_max_depth = c->bvh_plan.max_depth;
+    f.camera_is_pinhole = camera_is_pinhole(c->cam);
+    return f;
+}
+
+// The path-traced kernels exist in two builds: the bit-exact one and the opt-in fast-math one (counting launches always run the exact
+// build).  A plan picks its build HERE (kPtBuilds[plan.fast]) and nowhere else.
+struct PtBuild {
+    decltype(&kx::launch_pt_strip)        strip;     decltype(&kx::strip_blocks_per_cu)    strip_per_cu;
+    decltype(&kx::launch_pt_hbm)          hbm;       decltype(&kx::hbm_blocks_per_cu)      hbm_per_cu;
+    decltype(&kx::launch_pt_pool_hbm)     pool_hbm;  decltype(&kx::hbm_pool_blocks_per_cu) pool_hbm_per_cu;
+    decltype(&kx::launch_pt_pool)         pool;
+    const char*                           prefix;
+};
+static const PtBuild kPtBuilds[2] = {
+    { kx::launch_pt_strip, kx::strip_blocks_per_cu, kx::launch_pt_hbm, kx::hbm_blocks_per_cu, kx::launch_pt_pool_hbm, kx::hbm_pool_blocks_per_cu, kx::launch_pt_pool, "" },
+    { kf::launch_pt_strip, kf::strip_blocks_per_cu, kf::launch_pt_hbm, kf::hbm_blocks_per_cu, kf::launch_pt_pool_hbm, kf::hbm_pool_blocks_per_cu, kf::launch_pt_pool, "fast_build::" },
+};
+
+// Blocks of the plan's kernel that are resident per CU at once (registers and LDS decide); 0: the flat and grid pool kernels, whose
+// LDS alone decides (plan_render).
+static uint32_t plan_resident_per_cu(const mirt::RenderPlan& pl)
+{
+    const PtBuild& b = kPtBuilds[pl.fast];
+    const uint32_t threads = pl.launch_threads ? pl.launch_threads : mirt::kBlockThreads;
+    switch (pl.kernel) {
+    case mirt::kKernelParity:    return kx::parity_blocks_per_cu(pl.count, pl.by_pixel, pl.lds_bytes);
+    case mirt::kKernelParityHbm: return kx::parity_hbm_blocks_per_cu(pl.count, pl.by_pixel, threads, pl.lds_bytes);
+    case mirt::kKernelPtStrip:   return b.strip_per_cu(pl.hosek, pl.count, pl.use_grid, pl.by_pixel, pl.lds_bytes, pl.stream, pl.frame);
+    case mirt::kKernelPtHbm:     return b.hbm_per_cu(pl.hosek, pl.count, pl.hbm_bvh, pl.by_pixel, threads, pl.lds_bytes, pl.frame);
+    case mirt::kKernelPtPoolHbm: return b.pool_hbm_per_cu(pl.pool.slots, pl.hosek, pl.count, pl.lds_bytes, pl.frame);
+    default:                     return 0u;
+    }
+}
+
+static hipError_t dispatch_plan(const mirt::RenderPlan& pl, const mirt::RenderArgs& a, mirt::LaunchOn on)
+{
+    const PtBuild& b = kPtBuilds[pl.fast];
+    switch (pl.kernel) {
+    case mirt::kKernelParity:    return kx::launch_parity(a, pl.blocks, pl.count, pl.by_pixel, on);
+    case mirt::kKernelParityHbm: return kx::launch_parity_hbm(a, pl.blocks, pl.count, pl.by_pixel, on);
+    case mirt::kKernelPtStrip:   return b.strip(a, pl.blocks, pl.count, pl.use_grid, pl.by_pixel, on);
+    case mirt::kKernelPtHbm:     return b.hbm(a, pl.blocks, pl.count, pl.hbm_bvh, pl.by_pixel, on);
+    case mirt::kKernelPtPoolHbm: return b.pool_hbm(a, pl.blocks, pl.pool.slots, pl.count, on);
+    default:                     return b.pool(a, pl.blocks, pl.pool_cfg, pl.count, pl.pool_nq, on);
+    }
+}
+
+// the name mirt_ctx_last_kernel reports: the kernel template and its arguments, as the tests and tools read them
+static void plan_kernel_name(const mirt::RenderPlan& pl, const mirt::RenderArgs& a, char* out, size_t n)
+{
+    const char* const tf[2] = { "false", "true" };
+    const char* const fast = kPtBuilds[pl.fast].prefix, *const kframe = pl.frame ? "_frame" : "";
+    const char* const count = tf[pl.count], *const hosek = tf[pl.hosek], *const by_pixel = tf[pl.by_pixel];
+    char kname[112] = "";
+    switch (pl.kernel) {
+    case mirt::kKernelParity:    snprintf(out, n, "render_parity_kernel<%s,%s>", count, by_pixel); break;
+    case mirt::kKernelParityHbm: snprintf(out, n, "render_parity_hbm_kernel<%s,%s>", count, by_pixel); break;
+    case mirt::kKernelPtStrip:
+        if (pl.stream) snprintf(out, n, "%srender_pt_stream%s_kernel<%s>", fast, kframe, hosek);
+        else snprintf(out, n, "%srender_pt_strip%s_kernel<%s,%s,%s,%s>", fast, kframe, count, hosek, tf[pl.use_grid], by_pixel);
+        break;
+    case mirt::kKernelPtHbm:     snprintf(out, n, "%srender_pt_hbm%s_kernel<%s,%s,%s,%s>", fast, kframe, count, hosek, tf[pl.hbm_bvh], by_pixel); break;
+    case mirt::kKernelPtPoolHbm:
+        snprintf(out, n, "%srender_pt_pool_hbm%s_kernel<%u,%u,%u,%s,%s>", fast, kframe, pl.pool.threads, pl.pool.slots, pl.count ? 1u : mirt::kBvhPoolMinWaves, count, hosek);
+        break;
+    default:
+        kx::pool_kernel_name(a, pl.pool_cfg, pl.count, pl.pool_nq, kname, sizeof kname);
+        snprintf(out, n, "%s%s", fast, kname);
+    }
+}
+
+// The ring's next slot.  When the ring enters a batch of 16 slots, the batch HALF A RING AHEAD is retired (retire_slots): its launches
+// -- 32 to 17 launches old -- have normally finished long ago (the waits return at once; a caller more than 17 launches ahead of the
+// GPU is held here, which is what a bounded queue should do), their times are folded and their dispenser words re-zeroed on the
+// context's own stream.  By the time the ring reaches those slots they are clean: the pipeline is never drained.
+static int acquire_slot(MirtContext* c, size_t ev)
+{
+    static_assert(kEventPool % (2 * kRingBatch) == 0, "the ring is a whole number of batch pairs");
+    int rc = MIRT_OK;
+    if (ev % kRingBatch == 0) rc = retire_slots(c, (ev + kEventPool / 2) % kEventPool, kRingBatch);
+    if (rc == MIRT_OK && (c->slot_busy[ev] || c->slot_dirty[ev])) rc = retire_slots(c, ev, 1);   // (not in the normal flow: the batch ahead was retired 32 launches ago)
+    if (rc == MIRT_OK) rc = await_zero(c, ev);               // at most one wait for the batch's memset, 32 launches old
+    if (rc != MIRT_OK) return rc;
+    if (c->tuning.debug_slots) {                 // MIRT_DEBUG_SLOTS=1 (tests): the slot's eight dispenser words ARE zero now
+        uint32_t wds[8];
+        HIP_TRY(hipMemcpy2D(wds, sizeof(uint32_t), c->d_work_counter + ev * kDispenserWords, sizeof(uint32_t) * kDispenserStride, sizeof(uint32_t), 8, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 8; ++k)
+            if (wds[k] != 0u) return fail(MIRT_ERR_HIP, "launch slot %zu: dispenser word %d holds %u before the launch", ev, k, wds[k]);
+    }
+    return MIRT_OK;
+}
+
+// The kernel arguments of a planned render launch in slot `ev`: the context's tables, the caller's params and buffers, the plan's schedule.
+static void fill_render_args(const MirtContext* c, const mirt::RenderPlan& pl, const MirtParams* p, uint32_t* d_out, unsigned long long* d_accum, size_t ev,
+                             mirt::RenderArgs* a)
+{
+    const bool pt = p->mode == MIRT_MODE_PT;
+    fill_common_args(c, a, *p, pl.out_rows, (int)pl.pinhole);
+    a->out = d_out; a->counters = c->d_counters + ev * mirt::kNumCounters; a->work_counter = c->d_work_counter + ev * kDispenserWords; a->accum = d_accum;
+    a->frame_spp = pt ? p->frame_spp : 0u;
+    a->frame_begin = pt ? p->frame_begin : 0u;
+    for (int q = 0; q < 5; ++q) a->queue_routine[q] = c->queue_routine[q];
+    for (int k = 0; k < 12; ++k) a->sph3[k] = c->sph3[k];
+    a->n_units = pl.n_units;
+    for (uint32_t l = 0; l <= mirt::kStripLevels; ++l) { a->lvl_unit[l] = pl.lvl_unit[l]; a->lvl_pix[l] = pl.lvl_pix[l]; }
+    a->grid = pl.use_grid ? c->d_grid : nullptr;
+    a->grid_bytes = pl.use_grid ? c->grid_bytes : 0u;
+    a->shade = (pl.use_grid && c->have_shade) ? c->d_shade : nullptr;
+    a->grid_pool_slots = pl.grid_pool_slots; a->strip_cand = pl.strip_cand; a->grid_flat_y = pl.grid_flat_y;
+    a->lds_bytes = pl.lds_bytes; a->launch_threads = pl.launch_threads;
+    if (c->hbm) fill_bvh_args(c, a, pl.bvh_stack_entries);
+    a->static_units = pl.static_units; a->px_groups_log2 = pl.px_groups_log2; a->stream_samples = pl.stream_samples; a->spread_units = pl.spread_units;
+    a->first_dispensed = pl.first_dispensed;
+    for (uint32_t x = 0; x < 8u; ++x) a->disp_taken[x] = pl.disp_taken[x];
+}
+
+// A render launch: a slot of the launch ring, the launch plan (mirt_launch_plan.h: which kernel, which geometry, which schedule), the
+// kernel's occupancy, the plan's block count, the kernel arguments, one dispatch, and the slot's and the accumulation's bookkeeping.
+// d_out and d_accum both set: a progressive frame (mirt_ctx_accum_frame_device): sums AND image -> the *_frame_kernel build of
+// whatever schedule the plan chooses.
 static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, hipStream_t stream,
                          unsigned long long* d_accum = nullptr)
 {
-    // The ring's next slot.  When the ring enters a batch of 16 slots, the batch HALF A RING AHEAD is retired (retire_slots): its launches
-    // -- 32 to 17 launches old -- have normally finished long ago (the waits return at once; a caller more than 17 launches ahead of the
-    // GPU is held here, which is what a bounded queue should do), their times are folded and their dispenser words re-zeroed on the
-    // context's own stream.  By the time the ring reaches those slots they are clean: the pipeline is never drained.
-    static_assert(kEventPool % (2 * kRingBatch) == 0, "the ring is a whole number of batch pairs");
     const size_t ev = c->ev_next;
-    {
-        int rc = MIRT_OK;
-        if (ev % kRingBatch == 0) rc = retire_slots(c, (ev + kEventPool / 2) % kEventPool, kRingBatch);
-        if (rc == MIRT_OK && (c->slot_busy[ev] || c->slot_dirty[ev])) rc = retire_slots(c, ev, 1);   // (not in the normal flow: the batch ahead was retired 32 launches ago)
-        if (rc == MIRT_OK) rc = await_zero(c, ev);               // at most one wait for the batch's memset, 32 launches old
-        if (rc != MIRT_OK) return rc;
-        if (c->tuning.debug_slots) {                 // MIRT_DEBUG_SLOTS=1 (tests): the slot's eight dispenser words ARE zero now
-            uint32_t wds[8];
-            HIP_TRY(hipMemcpy2D(wds, sizeof(uint32_t), c->d_work_counter + ev * kDispenserWords, sizeof(uint32_t) * kDispenserStride, sizeof(uint32_t), 8, hipMemcpyDeviceToHost));
-            for (int k = 0; k < 8; ++k)
-                if (wds[k] != 0u) return fail(MIRT_ERR_HIP, "launch slot %zu: dispenser word %d holds %u before the launch", ev, k, wds[k]);
-        }
-    }
-    const uint32_t rows = out_rows(p);
-    const uint64_t npix = (uint64_t)rows * p->width;
-    const bool count = (p->flags & MIRT_FLAG_COUNT_WORK) != 0;
-    const bool hosek = p->mode == MIRT_MODE_PT && (p->flags & MIRT_FLAG_SKY_HOSEK);
-
-    const bool pt = p->mode == MIRT_MODE_PT;
-    // a progressive frame (mirt_ctx_accum_frame_device): sums AND image -> the *_frame_kernel build of whatever schedule is chosen below
-    const bool frame = d_out != nullptr && d_accum != nullptr;
-    const char* const kframe = frame ? "_frame" : "";
-    const size_t scene_lds = kx::scene_lds_bytes(c->n_spheres, c->n_mats, pt, hosek);
-    // kernel choice (path-traced mode): the pooled kernel needs enough samples per tile to keep
-    // its path pool full, 8-bit bounce counters and room for the pool beside the scene in LDS
-    const Tuning& tune = c->tuning;
-    // MIRT_FLAG_TEXEL_TILES: flat scenes with an image texture run the pool geometry that keeps a texel window per wave
-    const bool tiles = pt && (p->flags & MIRT_FLAG_TEXEL_TILES) && c->has_image_texture && tune.pool_config < 0;
-    const uint32_t pool_cfg = tune.pool_config >= 0 ? (uint32_t)tune.pool_config : (tiles ? mirt::kTilePoolConfig : mirt::kDefaultPoolConfig);
-    const uint32_t pool_nq = kx::pool_scatter_queues(c->n_shading_routines, count);
-    const mirt::PoolConfig pc = kx::pool_config(pool_cfg, pool_nq);
-    // Default schedule: the pooled kernel pays off when a strip holds enough samples to keep the pool full and the
-    // pools still leave >= 16 waves per CU resident beside the scene tables; the sample counts from which it does are
-    // measured crossovers against the strip kernel's lane-per-pixel schedule (mirt_kernels.h: kPoolMinSpp*): 28 for scenes
-    // with several shading routines, 600 for single-routine scenes (nothing diverges there, so lane = pixel is hard to
-    // beat: single metal sphere, 1080p x 100 spp, 1.38 ms against the pool's 1.82 and the lane-per-sample schedule's 2.27),
-    // 16 for many-sphere scenes, where the pool's re-compaction of grid walks is worth most.
-    const size_t lds_pool_block = scene_lds + pc.lds_bytes;
-    const uint32_t pool_waves_per_cu = (uint32_t)(c->lds_per_cu / (lds_pool_block ? lds_pool_block : 1)) * (pc.threads / 64u);
-    // (round 4, the streaming build of lane = pixel: a single-routine scene on a frame of at least eight rounds of 16-pixel units per resident
-    //  wave -- 1 Mpixel on 256 CUs -- never takes the pool: single sphere 1080p x 800 / 2000 / 4000 spp 5.38 / 13.3 / 26.5 ms against the pool's
-    //  6.34 / 15.5 / 31.2, 3840x2160 x 1000 spp 26.3 / 30.5; at 800x600 x 1000 spp the pool still wins, 2.17 against 2.31.  Scenes with several
-    //  routines: streaming 1.16 ms at 32 spp, pool 1.17; 36 / 48 spp 1.28 / 1.61 against 1.24 / 1.50 -- the crossover stays.  r04_lowspp_ab.txt block 9)
-    const bool stream_any_spp = c->n_shading_routines <= 1 && !hosek && npix >= 16ull * 8u * 32u * (uint64_t)c->cu_count;
-    const uint32_t pool_min_spp = tune.pool_min_spp > 0 ? (uint32_t)tune.pool_min_spp
-                                : stream_any_spp ? UINT32_MAX
-                                : c->n_shading_routines <= 1 ? mirt::kPoolMinSppOneRoutine : mirt::kPoolMinSpp;
-    bool pool = pt && p->spp >= pool_min_spp && c->n_shading_routines >= 1 && pool_waves_per_cu >= 16;
-    if (p->flags & MIRT_FLAG_KERNEL_STRIP) pool = false;
-    if (p->flags & MIRT_FLAG_KERNEL_POOL) pool = pt;
-    // the reference's per-frame RNG stream makes a pixel's samples sequentially dependent: lane-per-pixel strip kernel only
-    const bool frame_stream = pt && p->frame_spp != 0;
-    if (frame_stream) pool = false;
-    if (p->num_bounces > 255u || scene_lds + pc.lds_bytes > (size_t)c->lds_per_block || !c->fits_flat) pool = false;
-    // Many-sphere scenes: the pool kernel's grid build keeps spheres + grid + pools in LDS (materials in L2).  It
-    // is taken when the flat pool is not (too few waves per CU beside a big sphere table) and >= 12 waves fit.
-    const size_t scene_lds_g = kx::scene_lds_bytes_grid(c->n_spheres, hosek);
-    const bool grid_ok = pt && (!count || ((p->flags & MIRT_FLAG_COUNT_GRID) && !frame_stream)) && c->grid_bytes != 0 &&
-                         !(p->flags & MIRT_FLAG_NO_GRID);
-    // one 1024-thread block per CU; its path pools take what scene + grid leave of the block's LDS (counting launches:
-    // the largest geometry only)
-    const size_t lds_beside = scene_lds_g + c->grid_bytes;
-    const size_t lds_grid_block = (size_t)c->lds_per_block / mirt::kGridPoolBlocksPerCu;
-    mirt::PoolConfig pcg = kx::pool_config_grid(lds_grid_block > lds_beside ? lds_grid_block - lds_beside : 0);
-    if (count && pcg.slots != mirt::kGridPoolSlotChoices[0] && pcg.slots != mirt::kGridPoolSlotChoices[1]) pcg.slots = 0;
-    const size_t lds_pool_grid_block = lds_beside + pcg.lds_bytes;
-    const uint32_t pool_grid_waves_per_cu = pcg.slots ? (uint32_t)(c->lds_per_cu / lds_pool_grid_block) * (pcg.threads / 64u) : 0u;
-    bool pool_grid = grid_ok && c->grid_packable && pcg.slots != 0 && tune.pool_config < 0 && p->num_bounces <= 255u &&
-                     !(p->flags & MIRT_FLAG_KERNEL_STRIP) && !frame_stream &&
-                     ((p->flags & MIRT_FLAG_KERNEL_POOL) ||
-                      (!pool && p->spp >= mirt::kPoolMinSppGrid && c->n_shading_routines >= 1 && pool_grid_waves_per_cu >= 16));
-    if (tune.pool_grid == 0) pool_grid = false;
-    if (pool_grid) pool = true;
-    // MIRT_SCENE_HBM scene: the strip kernel (parity kernel) with the tables in device memory -- the BVH build unless NO_GRID asks for the
-    // flat scan or a counting launch asks for the flat scan's counters (COUNT_WORK without COUNT_GRID); tile hints do not apply.
-    // MIRT_FLAG_KERNEL_POOL on the BVH build: the pooled kernel (render_pt_pool_hbm_kernel) where the pool's own limits allow it -- 8-bit
-    // bounce counters, no per-frame RNG stream, a geometry that fits beside the stacks of a tree this deep -- and _STRIP does not object.
-    // Never by default: DESIGN.md 10.6 has the measured crossovers.
-    const bool hbm = c->hbm;
-    const bool hbm_bvh = hbm && pt && !(p->flags & MIRT_FLAG_NO_GRID) && (!count || (p->flags & MIRT_FLAG_COUNT_GRID));
-    MirtBvhPoolPlan hbm_plan{};
-    if (hbm_bvh && (p->flags & MIRT_FLAG_KERNEL_POOL) && !(p->flags & MIRT_FLAG_KERNEL_STRIP) && !frame_stream && p->num_bounces <= 255u)
-        hbm_plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, tune.hbm_pool_slots, 0u);
-    const bool pool_hbm = hbm_plan.slots != 0u && hbm_plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
-    if (pool_hbm) pool = true;
-    // the geometry of the pool kernel that will run
-    const mirt::PoolConfig pcu = pool_hbm ? mirt::PoolConfig{ hbm_plan.threads, hbm_plan.slots, hbm_plan.lds_bytes_per_block } : pool_grid ? pcg : pc;
-    const uint32_t resident_pool_waves = pool_hbm ? hbm_plan.waves_per_cu : pool_grid ? pool_grid_waves_per_cu : pool_waves_per_cu;
-
+    const int rc = acquire_slot(c, ev);
+    if (rc != MIRT_OK) return rc;
+    mirt::RenderPlan pl = mirt::plan_render(plan_facts(c), c->tuning, *p, d_out != nullptr && d_accum != nullptr);
+    if (pl.status != MIRT_OK) return fail(pl.status, "%s", pl.message);
+    mirt::plan_blocks(pl, plan_resident_per_cu(pl));
     mirt::RenderArgs a{};
-    a.cam = c->cam;
-    // the kernels' pinhole shortcut (generate_primary): the flag travels in the padding word beside lower_left_corner of
-    // THIS launch's by-value copy of the camera; the caller's struct is never touched
-    { const uint32_t flag = (pt && tune.pinhole != 0 && camera_is_pinhole(c->cam)) ? 1u : 0u; std::memcpy(&a.cam._padding5, &flag, 4); }
-    a.spheres = c->d_spheres; a.mats = c->d_mats; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
-    a.out = d_out; a.counters = c->d_counters + ev * mirt::kNumCounters; a.work_counter = c->d_work_counter + ev * kDispenserWords; a.accum = d_accum;
-    a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
-    a.width = p->width; a.height = p->height; a.spp = p->spp; a.num_bounces = p->num_bounces; a.flags = p->flags;
-    a.seed_mix = jenkins_hash((uint32_t)p->seed ^ jenkins_hash((uint32_t)(p->seed >> 32)));
-    a.sample_begin = p->sample_begin;
-    a.frame_spp = pt ? p->frame_spp : 0u;
-    a.frame_begin = pt ? p->frame_begin : 0u;
-    a.row_begin = p->row_begin; a.tile_rows = p->tile_rows; a.n_parts = p->n_parts; a.part = p->part;
-    a.out_rows = rows;
-    for (int q = 0; q < 5; ++q) a.queue_routine[q] = c->queue_routine[q];
-    for (int k = 0; k < 12; ++k) a.sph3[k] = c->sph3[k];
-    a.n_units = (uint32_t)((npix + mirt::kStripPixels - 1) / mirt::kStripPixels);
-    for (uint32_t l = 0; l <= mirt::kStripLevels; ++l) { a.lvl_unit[l] = a.n_units; a.lvl_pix[l] = (uint32_t)npix; }
-    a.lvl_unit[0] = 0;
-    a.lvl_pix[0] = 0;
-    if (pool) {
-        // Guided self-scheduling for the pool kernel: 16-pixel strips while more than 4 strips per resident
-        // wave remain, then 8- and 4-pixel strips under the same rule, so that the waves finish within a
-        // fraction of a strip of each other.  Measured on config 3 (tools/part_timing.py, one rank's share of
-        // an N-way partition vs 1/N of the whole frame): fixed 16-pixel strips 95 / 83 / 67 % at N = 2 / 4 / 8,
-        // this schedule 99 / 95 / 90 %; strips narrower than 4 pixels lose more to pool fill/drain than they
-        // gain.  Narrow strips also need width x spp >= 512 work items to keep a wave's pool busy.
-        const uint64_t waves = (uint64_t)c->cu_count * (resident_pool_waves < 32u ? resident_pool_waves : 32u);   // resident waves (LDS-bound)
-        uint32_t min_width = 4;
-        while (min_width < mirt::kStripPixels && (uint64_t)min_width * p->spp < 512u) min_width *= 2;
-        if (tune.fixed_strips) min_width = mirt::kStripPixels;
-        if (tune.gss_min_width) min_width = tune.gss_min_width;
-        const double keep_factor = tune.gss_keep > 0.0 ? tune.gss_keep : 4.0;
-        uint64_t pix = 0, unit = 0;
-        for (uint32_t l = 0; l < mirt::kStripLevels; ++l) {
-            const uint32_t width = mirt::kStripPixels >> l;
-            a.lvl_unit[l] = (uint32_t)unit;
-            a.lvl_pix[l] = (uint32_t)pix;
-            uint64_t level_px;
-            if (width <= min_width) {
-                level_px = npix - pix;                               // last usable level takes the rest
-            } else {
-                const uint64_t keep = (uint64_t)(keep_factor * (double)(waves * width));   // pixels left for the narrower levels
-                const uint64_t left = npix - pix;
-                level_px = left > keep ? (left - keep) / width * width : 0;
-            }
-            pix += level_px;
-            unit += (level_px + width - 1) / width;
-        }
-        a.lvl_unit[mirt::kStripLevels] = (uint32_t)unit;
-        a.lvl_pix[mirt::kStripLevels] = (uint32_t)npix;
-        a.n_units = (uint32_t)unit;
-    }
-    // many-sphere scenes: nearest hit through the uniform grid (strip kernel, non-counting build only:
-    // the counting build keeps the reference's flat scan so that its work counters stay comparable)
-    const bool use_grid = pool_grid || (grid_ok && !pool && scene_lds_g + c->grid_bytes + 4u * 48u <= (size_t)c->lds_per_block);
-    a.grid = use_grid ? c->d_grid : nullptr;
-    a.grid_bytes = use_grid ? c->grid_bytes : 0u;
-    a.shade = (use_grid && c->have_shade) ? c->d_shade : nullptr;
-    a.grid_pool_slots = pool_grid ? pcg.slots : 0u;
-    // camera-ray candidate lists (mirt_kernels.hip: strip_candidates): always in the pooled kernel (a list serves 16 pixels x spp rays);
-    // in the strip kernel's lane-per-pixel units (64 pixels x spp) from 4 samples per pixel on -- measured on RTIOW 1080p: 2 spp +2 %
-    // (selecting among 484 spheres costs more than 128 camera rays save), 8 spp -6 %
-    a.strip_cand = (use_grid && tune.strip_cand != 0 && (pool_grid || p->spp >= 4u)) ? 1u : 0u;
-    a.grid_flat_y = (use_grid && c->grid_flat_y) ? 1u : 0u;
-    // (the strip kernel's grid build keeps a camera-ray candidate list per wave behind the blob: 4 waves x 48 bytes)
-    a.lds_bytes = use_grid ? (uint32_t)(scene_lds_g + a.grid_bytes + (pool ? pcu.lds_bytes : 4u * 48u)) : (uint32_t)(scene_lds + (pool ? pcu.lds_bytes : 0));
-    if (pool_hbm) a.lds_bytes = hbm_plan.lds_bytes_per_block;     // camera (+ sky), the block's pools, its waves' traversal stacks
-    if (hbm) fill_bvh_args(c, &a, pool_hbm ? hbm_plan.stack_entries : 0u);
-    if (!use_grid && !c->fits_flat && !hbm)
-        return fail(MIRT_ERR_SCENE_TOO_LARGE, "this scene only fits LDS in the grid build of the path-traced mode "
-                    "(no parity mode, no MIRT_FLAG_COUNT_WORK / MIRT_FLAG_NO_GRID / MIRT_FLAG_KERNEL_POOL)");
-
-    // few samples per pixel (the reference's interactive loop adds 2 per frame): lane = pixel instead of lane = sample
-    // (single-routine scenes: lane = pixel at any sample count, but only for frames that give every CU a few 64-pixel units;
-    //  a tiny frame with many samples per pixel needs the lanes of a wave on the samples)
-    bool by_pixel = pt && !pool && !count && (p->spp < mirt::kByPixelMaxSpp || (c->n_shading_routines <= 1 && npix >= 64ull * 4u * c->cu_count));
-    if (tune.by_pixel >= 0) by_pixel = pt && !pool && !count && tune.by_pixel == 1;
-    if (hbm_bvh && !count && !pool_hbm) by_pixel = true;  // the BVH build's strip kernel: lane = pixel at every sample count
-    if (frame_stream) by_pixel = true;                    // also for counting launches (flat scan) and any spp
-    // parity mode: lane = pixel at EVERY sample count, counting or not (round 3: below 64 spp).  The reference's loop returns at the first
-    // terminating sample (layer.rs:320-378), which a lane that walks its own pixel's samples does too, while lane = sample computes 64
-    // samples of a pixel to find it: with one unit per wave 1080p x 64 / 100 / 1000 spp take 0.29 / 0.34 / 1.89 ms against 1.14 / 1.17 /
-    // 2.08 (profiles/r04_lowspp_ab.txt block 7).  MIRT_FLAG_KERNEL_STRIP still forces lane = sample (same image, same work counters).
-    if (!pt) by_pixel = (p->flags & MIRT_FLAG_KERNEL_STRIP) ? false : (tune.by_pixel >= 0 ? tune.by_pixel == 1 : true);
-    a.static_units = 0;
-    a.px_groups_log2 = 0;
-    // lane = pixel in a flat scene from 16 spp on: the streaming build -- a lane starts its pixel's next sample without waiting for the wave
-    // (mirt_kernels.hip: strip_kernel_body<STREAM>; MIRT_STREAM=0/1 for A/B runs)
-    a.stream_samples = (pt && by_pixel && !count && !use_grid && p->spp >= 16u) ? 1u : 0u;
-    if (tune.stream >= 0 && pt && by_pixel && !count && !use_grid) a.stream_samples = (uint32_t)tune.stream;
-    if (hbm) a.stream_samples = 0u;
-    if (by_pixel) {
-        // Path-traced lane-per-pixel units: 64 pixels x all samples -- or 32 / 16 pixels with the samples dealt to 2 / 4 groups of lanes:
-        // smaller units are more units, and the last unit of a wave is then a smaller part of its life (config 2, 1080p x 100 spp, had 4
-        // units per wave: 1.21 ms; 16-pixel units, with the eight-word dispenser they need: 0.86).  Measured (tools/ab_libs.py with
-        // MIRT_PX_GROUPS, profiles/r03_flat_ab.txt block 9; 1080p unless stated): as many groups as leave each >= 8 samples -- three spheres
-        // at 32 / 16 / 8 spp: 1 / 2 / 4 groups 1.33 / 1.20 / 1.16, 0.68 / 0.63 / 0.66, 0.36 / 0.37 / 0.43 ms; config 2 1.17 / 0.93 / 0.86;
-        // the same at 3840x2160 3.20 / 2.96 / 2.89, at 800x600 0.71 / 0.41 / 0.33 -- and one more for many-sphere scenes (RTIOW 8 spp:
-        // 1.54 / 1.40).  The samples must divide evenly; never with the reference's per-frame stream (sequentially dependent samples).
-        if (pt && !frame_stream && tune.px_groups != 0) {
-            // (round 4, one unit per wave, profiles/r04_lowspp_ab.txt block 4: two groups from shares of 4 -- three spheres 8 spp 0.337 ms against
-            //  0.359, main.rs scene 0.434 / 0.459 --, four groups from shares of 6: 16 spp 0.610 with two groups, 0.617 with four; 24 spp 0.884 / 0.881)
-            // (streaming launches, below: shares of at least 8 samples -- three spheres 16 spp 0.588 ms with two groups, 0.643 with four; 24 spp
-            //  0.822 / 0.886; config 2 at 25 per lane, four groups: 0.750, two: 0.829, eight (128 spp): +-0; block 9)
-            const uint32_t min_share[2] = { a.stream_samples ? 8u : 4u, a.stream_samples ? 8u : (use_grid ? 4u : 6u) };
-            while (a.px_groups_log2 < 2u && p->spp % (2u << a.px_groups_log2) == 0u && (p->spp >> (a.px_groups_log2 + 1u)) >= min_share[a.px_groups_log2])
-                a.px_groups_log2 += 1u;
-            if (tune.px_groups > 0 && p->spp % (1u << (tune.px_groups - 1)) == 0u) a.px_groups_log2 = (uint32_t)tune.px_groups - 1u;
-        }
-        a.n_units = (uint32_t)((npix + (64u >> a.px_groups_log2) - 1u) / (64u >> a.px_groups_log2));
-        // ONE UNIT PER WAVE instead of units dispensed to a persistent grid (a.static_units; round 4): the launch has as many waves as units, and
-        // the hardware's workgroup dispatcher -- which starts a block wherever a CU has room -- is the load balancer: no dispenser atomic
-        // (one returning device-scope atomic per unit, 14 ns each on one address, was the whole kernel time of a 2-spp frame), and none of
-        // the imbalance of dealing units round-robin to resident waves (rounds 2-3: a wave's four units are a quarter of its life each).
-        // Measured against both (profiles/r04_lowspp_ab.txt block 3; 1080p, three spheres): 1 / 2 / 4 / 8 / 16 / 24 spp -14 / -16 / -13 / -4 / -2 /
-        // +-0 %; main.rs scene 2 spp -20 %; config 2 -1.6 %; parity mode's lane = pixel 2 spp (1080p) -11 %, 32 spp -21 %.  Every block stages
-        // the scene itself, which is why many-sphere scenes (a 25 KB grid blob per block) keep the dispenser from 4 spp on (RTIOW: 2 spp -21 %,
-        // 4 / 8 / 12 spp +7 / +8 / +7 %).
-        a.static_units = (!pt || !use_grid || p->spp < 4u) ? 1u : 0u;
-        if (tune.static_units >= 0) a.static_units = (uint32_t)tune.static_units;
-    }
-
-    // the opt-in fast-math build of the path-traced kernels; counting launches always run the exact build
-    const bool fast = pt && !count && (p->flags & MIRT_FLAG_FAST_MATH);
-    uint32_t blocks;
-    if (pool) {
-        uint32_t per_cu = (uint32_t)(c->lds_per_cu / (a.lds_bytes ? a.lds_bytes : 1));
-        const uint32_t by_waves = 32u / (pcu.threads / 64u);   // upper bound; LDS decides (6 blocks of 4 waves with 112-slot pools)
-        if (per_cu > by_waves) per_cu = by_waves;
-        if (pool_hbm) {                                        // the plan's waves, and no more blocks than the build's registers keep resident
-            const uint32_t planned = hbm_plan.waves_per_cu / (pcu.threads / 64u);
-            const uint32_t fit = fast ? kf::hbm_pool_blocks_per_cu(pcu.slots, hosek, count, a.lds_bytes, frame)
-                                      : kx::hbm_pool_blocks_per_cu(pcu.slots, hosek, count, a.lds_bytes, frame);
-            if (per_cu > planned) per_cu = planned;
-            if (fit >= 1u && per_cu > fit) per_cu = fit;
-        }
-        if (tune.pool_blocks_per_cu >= 1 && tune.pool_blocks_per_cu < per_cu) per_cu = tune.pool_blocks_per_cu;
-        if (per_cu == 0u) per_cu = 1u;
-        blocks = (uint32_t)c->cu_count * per_cu;
-        const uint32_t units_per_block = pcu.threads / 64u;
-        const uint32_t need = (a.n_units + units_per_block - 1) / units_per_block;
-        if (blocks > need) blocks = need;
-    } else {
-        // One unit per wave in a flat scene: one WAVE per block, too -- a block leaves when its slowest wave is done, and the scene a block
-        // stages is a few hundred bytes (1080p, three spheres 2 / 4 / 8 / 16 spp -1.6 / -2.2 / -1.5 / -1.3 %, config 2 -1.9 %, parity mode at
-        // 1000 spp nominal -15 %; profiles/r04_lowspp_ab.txt block 8).  Many-sphere scenes stage a 25 KB grid blob per block: 256 threads
-        // (RTIOW 2 spp with 64-thread blocks: 2.4 x the time).  MIRT_STATIC_BLOCK=64/128/256 for A/B runs.
-        a.launch_threads = 0u;
-        if (a.static_units != 0u && tune.static_grid <= 0) a.launch_threads = tune.static_block ? tune.static_block : (use_grid ? 0u : 64u);
-        const uint32_t waves_per_block = (a.launch_threads ? a.launch_threads : mirt::kBlockThreads) / 64;
-        blocks = (a.n_units + waves_per_block - 1) / waves_per_block;
-        // MIRT_SCENE_HBM: LDS holds the camera (+ sky) and, in the BVH build, every wave's traversal stacks
-        if (hbm) a.lds_bytes = (uint32_t)(scene_lds_g + (hbm_bvh ? waves_per_block * mirt::kBvhStackBytesPerWave : 0u));
-        // a persistent grid of exactly the blocks that are resident at once: registers and LDS decide (4-8 per CU for these
-        // kernels).  A block beyond that would hold its first unit until the dispenser has run dry and run it alone at the end.
-        const bool fast_strip = pt && !count && (p->flags & MIRT_FLAG_FAST_MATH);
-        const uint32_t threads = a.launch_threads ? a.launch_threads : mirt::kBlockThreads;
-        uint32_t per_cu = hbm ? (!pt ? kx::parity_hbm_blocks_per_cu(count, by_pixel, threads, a.lds_bytes)
-                                     : fast_strip ? kf::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes, frame)
-                                                  : kx::hbm_blocks_per_cu(hosek, count, hbm_bvh, by_pixel, threads, a.lds_bytes, frame))
-                        : !pt ? kx::parity_blocks_per_cu(count, by_pixel, a.lds_bytes)
-                        : fast_strip ? kf::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u, frame)
-                                     : kx::strip_blocks_per_cu(hosek, count, use_grid, by_pixel, a.lds_bytes, a.stream_samples != 0u, frame);
-        if (per_cu > 8u) per_cu = 8u;                                 // 2048 threads per CU / 256
-        const uint32_t resident = (uint32_t)c->cu_count * per_cu;
-        // ... unless the launch runs one unit per wave (a.static_units): then the grid is the units (MIRT_STATIC_GRID=k, A/B runs: k x the
-        // resident blocks with the units dealt round-robin, rounds 2-3's schedule at k = 1)
-        uint32_t cap = resident;
-        if (a.static_units != 0u) cap = tune.static_grid > 0 ? resident * (uint32_t)tune.static_grid : blocks;
-        if (blocks > cap) blocks = cap;
-    }
-    if (blocks == 0) blocks = 1;
-
-    // the dispenser continues after the units the waves take by their own index (first_unit() in the kernels)
-    const uint32_t launched_waves = blocks * ((pool ? pcu.threads : (a.launch_threads ? a.launch_threads : mirt::kBlockThreads)) / 64u);
-    // kernels with dispensed units take them from eight dispenser words (mirt_kernels.hip: next_unit_any): the strip-type kernels
-    // (path-traced strip kernel, both schedules; parity kernel) always.
-    // The pooled kernel's strips last long at high sample counts (config 3: 9 atomics per microsecond); below 128 spp they do not
-    // (three spheres, 1080p, pool forced: 48 / 64 / 100 / 200 spp -13.5 / -8.5 / -2 / +1 % with eight words; RTIOW 16 spp -4.5 %).
-    a.spread_units = (a.static_units == 0u && tune.spread_units != 0 && (!pool || p->spp < 128u)) ? 1u : 0u;
-    a.first_dispensed = launched_waves;          // the words themselves are zero (retire_slots): no memset node in front of the kernel
-    for (uint32_t x = 0; x < 8u; ++x) a.disp_taken[x] = launched_waves > x ? (launched_waves - x + 7u) / 8u : 0u;
+    fill_render_args(c, pl, p, d_out, d_accum, ev, &a);
+    const bool count = pl.count;
 #ifdef MIRT_DIAG_STAMPS
     HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(unsigned long long) * mirt::kNumCounters, stream));
 #endif
@@ -1576,37 +1414,11 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     // dealt round-robin -- carry none.
     const bool timed = c->timing;
     const bool need_end = timed || count || a.static_units == 0u;
-    const bool ext_events = tune.ext_events && need_end;
+    const bool ext_events = c->tuning.ext_events && need_end;
     if (timed && !ext_events) HIP_TRY(hipEventRecord(c->ev_begin[ev], stream));
     const mirt::LaunchOn on = ext_events ? mirt::LaunchOn(stream, timed ? c->ev_begin[ev] : nullptr, c->ev_end[ev]) : mirt::LaunchOn(stream);
-    const char* tf[2] = { "false", "true" };
-    char kname[112] = "";
-    if (pool_hbm) {
-        HIP_TRY(fast ? kf::launch_pt_pool_hbm(a, blocks, pcu.slots, count, on) : kx::launch_pt_pool_hbm(a, blocks, pcu.slots, count, on));
-        snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_pool_hbm%s_kernel<%u,%u,%u,%s,%s>", fast ? "fast_build::" : "", kframe, pcu.threads,
-                 pcu.slots, count ? 1u : mirt::kBvhPoolMinWaves, tf[count], tf[hosek]);
-    } else if (hbm) {
-        if (p->mode == MIRT_MODE_PARITY) {
-            HIP_TRY(kx::launch_parity_hbm(a, blocks, count, by_pixel, on));
-            snprintf(c->last_kernel, sizeof c->last_kernel, "render_parity_hbm_kernel<%s,%s>", tf[count], tf[by_pixel]);
-        } else {
-            HIP_TRY(fast ? kf::launch_pt_hbm(a, blocks, count, hbm_bvh, by_pixel, on) : kx::launch_pt_hbm(a, blocks, count, hbm_bvh, by_pixel, on));
-            snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_hbm%s_kernel<%s,%s,%s,%s>", fast ? "fast_build::" : "", kframe, tf[count], tf[hosek],
-                     tf[hbm_bvh], tf[by_pixel]);
-        }
-    } else if (p->mode == MIRT_MODE_PARITY) {
-        HIP_TRY(kx::launch_parity(a, blocks, count, by_pixel, on));
-        snprintf(c->last_kernel, sizeof c->last_kernel, "render_parity_kernel<%s,%s>", tf[count], tf[by_pixel]);
-    } else if (pool) {
-        HIP_TRY(fast ? kf::launch_pt_pool(a, blocks, pool_cfg, count, pool_nq, on) : kx::launch_pt_pool(a, blocks, pool_cfg, count, pool_nq, on));
-        kx::pool_kernel_name(a, pool_cfg, count, pool_nq, kname, sizeof kname);
-        snprintf(c->last_kernel, sizeof c->last_kernel, "%s%s", fast ? "fast_build::" : "", kname);
-    } else {
-        HIP_TRY(fast ? kf::launch_pt_strip(a, blocks, count, use_grid, by_pixel, on) : kx::launch_pt_strip(a, blocks, count, use_grid, by_pixel, on));
-        if (a.stream_samples) snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_stream%s_kernel<%s>", fast ? "fast_build::" : "", kframe, tf[hosek]);
-        else snprintf(c->last_kernel, sizeof c->last_kernel, "%srender_pt_strip%s_kernel<%s,%s,%s,%s>", fast ? "fast_build::" : "", kframe, tf[count], tf[hosek],
-                      tf[use_grid], tf[by_pixel]);
-    }
+    HIP_TRY(dispatch_plan(pl, a, on));
+    plan_kernel_name(pl, a, c->last_kernel, sizeof c->last_kernel);
     // The kernel is enqueued: from here on the slot is in use, whatever happens below (a failure after this point must not hand the
     // slot -- its dispenser words no longer zero -- to the next launch: poison_slot).
     c->ev_next = (ev + 1) % c->ev_begin.size();
@@ -1638,7 +1450,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     c->last_slot = ev;
     c->stats_counted = count;
     c->stats = MirtStats{};
-    c->stats.samples = npix * p->spp;
+    c->stats.samples = (uint64_t)pl.out_rows * p->width * p->spp;
     return MIRT_OK;
 }
 
@@ -1799,14 +1611,9 @@ static int launch_trace(MirtContext* c, const void* d_rays, uint32_t n, uint32_t
     const bool bvh = !(flags & MIRT_RAYS_FLAT), any = (flags & MIRT_RAYS_ANY_HIT) != 0, count = (flags & MIRT_RAYS_COUNT) != 0;
     const bool sort = (flags & MIRT_RAYS_SORT) != 0;
     mirt::RenderArgs a{};
-    a.spheres = c->d_spheres;
-    a.n_spheres = c->n_spheres;
+    fill_common_args(c, &a, MirtParams{}, 0u, -1);
     a.counters = c->d_trace_counters;
-    // the traversal stacks hold as many node references per lane as the resident tree is deep (a push happens at inner nodes only, at
-    // most one per level): 256 x depth bytes per wave, as in the pooled kernel -- at most 32 KB per block (MIRT_BVH_MAX_DEPTH)
-    const uint32_t entries = bvh ? (c->bvh_plan.max_depth ? c->bvh_plan.max_depth : 1u) : 0u;
-    fill_bvh_args(c, &a, entries);
-    a.lds_bytes = (mirt::kBlockThreads / 64u) * 64u * 4u * entries;
+    fill_query_stacks(c, &a, bvh);
     const bool timed = c->timing;
     const uint32_t* d_order = nullptr;
     if (sort) {           // first: a failed allocation leaves nothing queued
@@ -1821,10 +1628,7 @@ static int launch_trace(MirtContext* c, const void* d_rays, uint32_t n, uint32_t
     const char* tf[2] = { "false", "true" };
     snprintf(c->last_kernel, sizeof c->last_kernel, "trace_rays%s_kernel<%s,%s,%s>", sort ? "_sorted" : "", tf[bvh], tf[any], tf[count]);
     HIP_TRY(hipEventRecord(c->ev_trace_end, st));
-    c->trace_pending = true;
-    c->trace_timed = timed;
-    c->trace_counted = count;
-    c->trace_stats = MirtRayStats{};
+    mark_trace_queued(c, timed, count);
     return MIRT_OK;
 }
 
@@ -1928,29 +1732,14 @@ static int launch_features(MirtContext* c, const MirtParams* p, uint32_t flags, 
 {
     const bool bvh = !(flags & MIRT_FEATURES_FLAT);
     mirt::RenderArgs a{};
-    a.cam = c->cam;
-    // generate_primary's pinhole shortcut: the flag travels in the padding word of THIS launch's copy of the camera, as in launch_render
-    { const uint32_t flag = (c->tuning.pinhole != 0 && camera_is_pinhole(c->cam)) ? 1u : 0u; std::memcpy(&a.cam._padding5, &flag, 4); }
-    a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels;
-    a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
-    a.width = p->width; a.height = p->height; a.spp = p->spp;
-    a.seed_mix = jenkins_hash((uint32_t)p->seed ^ jenkins_hash((uint32_t)(p->seed >> 32)));
-    a.sample_begin = p->sample_begin;
-    a.row_begin = p->row_begin; a.tile_rows = p->tile_rows; a.n_parts = p->n_parts; a.part = p->part;
-    a.out_rows = out_rows(p);
-    // traversal stacks as for ray queries: as many node references per lane as the resident tree is deep, 256 x depth bytes per wave
-    const uint32_t entries = bvh ? (c->bvh_plan.max_depth ? c->bvh_plan.max_depth : 1u) : 0u;
-    fill_bvh_args(c, &a, entries);
-    a.lds_bytes = (mirt::kBlockThreads / 64u) * 64u * 4u * entries;
+    fill_common_args(c, &a, *p, out_rows(p), pinhole_word(c));     // the camera with generate_primary's pinhole word, as in launch_render
+    fill_query_stacks(c, &a, bvh);                                 // traversal stacks as for ray queries
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
     HIP_TRY(kx::launch_features(a, d_out, bvh, st));
     snprintf(c->last_kernel, sizeof c->last_kernel, "feature_frame_kernel<%s>", bvh ? "true" : "false");
     HIP_TRY(hipEventRecord(c->ev_trace_end, st));
-    c->trace_pending = true;
-    c->trace_timed = timed;
-    c->trace_counted = false;
-    c->trace_stats = MirtRayStats{};
+    mark_trace_queued(c, timed, false);
     return MIRT_OK;
 }
 
@@ -2025,28 +1814,23 @@ static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const
 {
     const bool bvh = !(p->flags & MIRT_RADIANCE_FLAT), hosek = (p->flags & MIRT_RADIANCE_SKY_HOSEK) != 0, sort = (p->flags & MIRT_RADIANCE_SORT) != 0;
     MirtBvhPoolPlan plan{};
-    if ((p->flags & MIRT_RADIANCE_POOL) && bvh && p->num_bounces <= 255u)
-        plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, c->tuning.hbm_pool_slots, 0u);
-    const bool pooled = plan.slots != 0u && plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
-    mirt::RenderArgs a{};                                 // (the camera stays zero: a query has none)
-    a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
-    a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
-    a.spp = p->spp; a.num_bounces = p->num_bounces; a.flags = p->flags;
-    a.seed_mix = jenkins_hash((uint32_t)p->seed ^ jenkins_hash((uint32_t)(p->seed >> 32)));      // as launch_render derives it
-    a.sample_begin = p->sample_begin;
+    if ((p->flags & MIRT_RADIANCE_POOL) && bvh) plan = mirt::pooled_bvh_plan(plan_facts(c), c->tuning, hosek, 0u, p->num_bounces);
+    const bool pooled = plan.slots != 0u;
+    MirtParams q{};                                       // the query's sampling fields as a render call's; no frame, no rows
+    q.spp = p->spp; q.num_bounces = p->num_bounces; q.flags = p->flags; q.seed = p->seed; q.sample_begin = p->sample_begin;
+    mirt::RenderArgs a{};
+    fill_common_args(c, &a, q, 0u, -1);                   // (the camera stays zero: a query has none)
     a.n_units = n;
     // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
     fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
     a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
     uint32_t pool_blocks = 0;
     if (pooled) {                                         // units of 16 slots of the batch, one unit per wave: the hardware's dispatcher is the balancer
-        const uint32_t waves = plan.threads / 64u;
         a.width = n;
         a.height = 1u;
         a.n_units = (uint32_t)(((uint64_t)n + mirt::kStripPixels - 1u) / mirt::kStripPixels);
         a.lds_bytes = plan.lds_bytes_per_block;           // camera words (+ sky), the block's pools, its waves' traversal stacks
-        pool_blocks = (a.n_units + waves - 1u) / waves;
-        if (c->tuning.radiance_pool_blocks != 0u && pool_blocks > c->tuning.radiance_pool_blocks) pool_blocks = c->tuning.radiance_pool_blocks;
+        pool_blocks = pooled_query_blocks(a.n_units, plan.threads, c->tuning.radiance_pool_blocks);
     }
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
@@ -2065,10 +1849,7 @@ static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const
         snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays%s_kernel<%s,%s>", sort ? "_sorted" : "", tf[hosek], tf[bvh]);
     }
     HIP_TRY(hipEventRecord(c->ev_trace_end, st));
-    c->trace_pending = true;
-    c->trace_timed = timed;
-    c->trace_counted = false;
-    c->trace_stats = MirtRayStats{};
+    mark_trace_queued(c, timed, false);
     return MIRT_OK;
 }
 
@@ -2356,31 +2137,21 @@ int mirt_ctx_adapt_step_device(MirtContext* c, const MirtParams* p, const MirtAd
     const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const bool bvh = !(q.flags & MIRT_FLAG_NO_GRID), hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
     mirt::RenderArgs a{};
-    a.cam = c->cam;
-    { const uint32_t flag = (c->tuning.pinhole != 0 && camera_is_pinhole(c->cam)) ? 1u : 0u; std::memcpy(&a.cam._padding5, &flag, 4); }   // as launch_render
-    a.spheres = c->d_spheres; a.pmats = c->d_pmats; a.texels = c->d_texels; a.sky = c->d_sky;
-    a.n_texels = c->n_texels; a.n_spheres = c->n_spheres; a.n_mats = c->n_mats;
-    a.width = q.width; a.height = q.height; a.spp = q.spp; a.num_bounces = q.num_bounces; a.flags = q.flags;
-    a.seed_mix = jenkins_hash((uint32_t)q.seed ^ jenkins_hash((uint32_t)(q.seed >> 32)));       // as launch_render derives it
-    a.row_begin = q.row_begin; a.tile_rows = q.tile_rows; a.n_parts = q.n_parts; a.part = q.part;
-    a.out_rows = c->adapt_rows;
+    fill_common_args(c, &a, q, c->adapt_rows, pinhole_word(c));       // as launch_render
     a.n_units = (uint32_t)c->adapt_pixels;
     // MIRT_ADAPT_POOL on the BVH build: adapt_pixels_pool_kernel in the geometry mirt_adapt_pool_plan gives for the resident tree, where the
     // pool's own limits allow it -- 8-bit bounce counters, a geometry that fits beside the stacks of a tree this deep; otherwise the step
     // is the one without the flag.
     MirtBvhPoolPlan plan{};
-    if ((adapt->flags & MIRT_ADAPT_POOL) && bvh && q.num_bounces <= 255u)
-        plan = plan_bvh_pool(c->bvh_plan.max_depth, hosek, c->lds_per_cu, c->tuning.hbm_pool_slots, mirt::kAdaptPoolExtraBytes);
-    const bool pooled = plan.slots != 0u && plan.lds_bytes_per_block <= (size_t)c->lds_per_block;
+    if ((adapt->flags & MIRT_ADAPT_POOL) && bvh) plan = mirt::pooled_bvh_plan(plan_facts(c), c->tuning, hosek, mirt::kAdaptPoolExtraBytes, q.num_bounces);
+    const bool pooled = plan.slots != 0u;
     // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
     fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
     a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
     uint32_t pool_blocks = 0;
     if (pooled) {                                           // units of 16 list entries; the host does not know the count: a grid for all pixels
-        const uint64_t waves = plan.threads / 64u, units = (c->adapt_pixels + mirt::kStripPixels - 1u) / mirt::kStripPixels;
         a.lds_bytes = plan.lds_bytes_per_block;             // camera words (+ sky), the block's pools, its waves' traversal stacks
-        pool_blocks = (uint32_t)((units + waves - 1u) / waves);
-        if (c->tuning.adapt_pool_blocks != 0u && pool_blocks > c->tuning.adapt_pool_blocks) pool_blocks = c->tuning.adapt_pool_blocks;
+        pool_blocks = pooled_query_blocks((c->adapt_pixels + mirt::kStripPixels - 1u) / mirt::kStripPixels, plan.threads, c->tuning.adapt_pool_blocks);
     }
     uint32_t* head = reinterpret_cast<uint32_t*>(c->d_adapt_sel);
     uint32_t* list = reinterpret_cast<uint32_t*>(c->d_adapt_sel + 16u);

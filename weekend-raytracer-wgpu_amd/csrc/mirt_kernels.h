@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/mirt.h"
+#include "mirt_launch_plan.h"     // PoolConfig, the strip constants and the pool thresholds: what the launch plan shares with the kernels
 
 namespace mirt {
 
@@ -97,9 +98,6 @@ constexpr uint32_t kGridMinSpheres = 32;
 constexpr uint32_t kGridMaxCells   = 4096;   // x 8 bytes per cell entry = the 32 KB of LDS that round 3's 8 192 four-byte entries could take: the pools keep their room
                                             // (a soup of 700 small spheres over a wide volume lost every pool geometry to a 64 KB cell table: soak seed 3150)
 
-constexpr uint32_t kStripLevels   = 5;    // strip widths 16, 8, 4, 2, 1
-constexpr uint32_t kStripPixels   = 16;   // strip kernels: pixels one wave owns per work unit (64-B RGBA8 store)
-constexpr uint32_t kBlockThreads  = 256;  // strip kernels: 4 waves
 #if defined(MIRT_DIAG_STEPS) || defined(MIRT_DIAG_STAMPS)   // diagnosis builds (tools/step_stats.py): ten more counters, printed by mirt_ctx_get_stats
 constexpr uint32_t kNumCounters   = 31;
 #else
@@ -114,8 +112,6 @@ constexpr uint32_t kDefaultPoolConfig = 0;
 #define MIRT_TILE_SLOTS 112
 #endif
 constexpr uint32_t kTilePoolConfig = 5, kTilePoolSlots = MIRT_TILE_SLOTS;
-constexpr uint32_t kByPixelMaxSpp = 64;   // strip kernel: below this many samples per pixel a wave takes 64 pixels, lane = pixel (scenes with
-                                          // one shading routine: at any sample count -- nothing diverges, 1.51 ms against 2.27 on config 2)
 // pool kernel, grid build (many-sphere scenes): ONE 1024-thread block per CU, so that the grid blob (~20 KB for RTIOW)
 // is staged once for all 16 waves and the rest of the 160 KB goes to the path pools.  Measured on RTIOW 1080p x 128 spp:
 // 512 threads x 112 slots, two blocks 17.3 ms; x 128 slots 16.6; 1024 x 144 15.9; 1024 x 152 15.7; one 512-thread
@@ -133,26 +129,6 @@ constexpr uint32_t kGridPoolThreads = MIRT_GRID_THREADS;
 constexpr uint32_t kGridPoolBlocksPerCu = MIRT_GRID_BLOCKS;    // blocks of the grid build that share a CU's LDS
 constexpr uint32_t kGridPoolMinWaves = MIRT_GRID_MINW;         // waves per SIMD the build is held to (launch bounds)
 constexpr uint32_t kGridPoolSlotChoices[4] = { MIRT_GRID_SLOTS };   // the largest geometry whose block fits LDS is taken
-// Samples per pixel from which the pooled kernel is the default (below: the strip kernel, lane = pixel).  A 16-pixel strip
-// of few samples cannot keep a pool full (about 25 steps of fill and drain per strip whatever it holds), so the thresholds are
-// measured crossovers (tools/ab_libs.py with MIRT_FLAG_KERNEL_STRIP / _POOL, 1080p):
-//   several shading routines (config 3): strip 1.58 / 1.73 / 1.94 ms at 36 / 40 / 44 spp, pool 1.61 / 1.67 / 1.74   -> 40 (round 2)
-//     round 3 (sample groups; eight-word dispenser in both kernels): strip 0.98 / 1.13 / 1.24 / 1.37 / 1.54 ms at 24 / 28 / 32 / 36 / 40 spp, pool
-//     1.00 / 1.11 / 1.21 / 1.30 / 1.41 (main.rs 5-sphere scene: 1.32 / 1.65 against 1.33 / 1.55 at 24 / 32 spp)                                   -> 28
-//   ONE routine (config 2, no divergence for the lane-per-pixel kernel to lose): round 2 184; round 3: strip 0.93 / 1.78 / 3.55 / 5.21 / 6.98 /
-//     8.48 ms at 100 / 200 / 400 / 600 / 800 / 1000 spp, pool 1.81 / 2.42 / 3.85 / 5.17 / 6.52 / 7.96                                           -> 600
-//   many-sphere scenes (grid build, RTIOW): round 2: strip 2.09 / 4.11 / 7.69 ms at 8 / 16 / 32 spp, pool 2.31 / 3.14 / 4.66 -> 16;
-//     round 3: strip 1.54 / 2.19 / 2.70 ms at 8 / 12 / 16 spp, pool 1.99 / 2.28 / 2.61                                                          -> 16
-//   round 4 (lane-per-pixel launches run one unit per wave; profiles/r04_lowspp_ab.txt block 5): several routines: strip 0.96 / 1.10 / 1.27 /
-//     1.52 ms at 24 / 28 / 32 / 40 spp, pool 1.01 / 1.12 / 1.20 / 1.39 (main.rs scene 1.26 / 1.66 against 1.32 / 1.56 at 24 / 32)             -> 32
-//     ONE routine: strip 3.36 / 4.81 / 6.49 / 8.11 ms at 400 / 600 / 800 / 1000 spp, pool 3.80 / 5.25 / 6.52 / 7.93                           -> 800
-//     with the streaming build of lane = pixel (from 16 spp on; block 9): several routines: 0.94 / 1.16 / 1.28 / 1.61 ms at 28 / 32 / 36 / 48 spp, pool
-//     - / 1.17 / 1.24 / 1.50                                                                                                                  -> 32
-//     ONE routine: 5.38 / 13.3 / 26.5 ms at 800 / 2000 / 4000 spp, pool 6.34 / 15.5 / 31.2; 3840x2160 x 1000 spp 26.3 against 30.5 -> frames of
-//     >= 1 Mpixel never take the pool (mirt_api.hip: stream_any_spp); 800x600 x 1000 spp 2.31 against the pool's 2.17                          -> 800 below that
-constexpr uint32_t kPoolMinSpp           = 32;
-constexpr uint32_t kPoolMinSppOneRoutine = 800;
-constexpr uint32_t kPoolMinSppGrid       = 16;
 
 enum CounterSlot : uint32_t {
     kCntRays = 0, kCntTests, kCntRoots, kCntHits,
@@ -225,7 +201,7 @@ constexpr uint32_t kBvhStackBytesPerWave = 64u * MIRT_BVH_MAX_DEPTH * 4u;
 
 // MIRT_SCENE_HBM, pooled build (render_pt_pool_hbm_kernel, MIRT_FLAG_KERNEL_POOL): 256-thread blocks whose waves keep a
 // two-queue pool (WavePoolLayout<SLOTS, 1>: 50 x SLOTS + 384 bytes) and, behind the block's pools, 64 traversal stacks of as many
-// entries as the resident tree is deep (256 x depth bytes per wave).  The geometry is chosen per launch by plan_bvh_pool (mirt_api.hip,
+// entries as the resident tree is deep (256 x depth bytes per wave).  The geometry is chosen per launch by plan_bvh_pool (mirt_launch_plan.hip,
 // mirt_bvh_pool_plan): the largest pools that leave kBvhPoolWavesPerCu waves resident, or, where no choice does, the choice that keeps
 // most waves (the larger pools on a tie).  The non-counting builds are held to the registers of that many waves.
 constexpr uint32_t kBvhPoolThreads = 256;
@@ -262,7 +238,6 @@ struct LaunchOn {
 // launchers (mirt_kernels.hip).  That file is compiled twice: namespace exact_build (the default, bit-exact arithmetic;
 // everything below) and namespace fast_build (mirt_kernels_fast.hip: MIRT_FLAG_FAST_MATH, hardware transcendentals;
 // path-traced launchers and the host helpers only).
-struct PoolConfig { uint32_t threads, slots, lds_bytes; };
 namespace fast_build {
 hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream);
 uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream, bool frame = false);

@@ -1,0 +1,129 @@
+// mirt_launch_plan.h — the launch plan of a render call: which kernel runs, in which geometry and with which schedule, as plain
+// data computed by two pure functions (mirt_launch_plan.hip).  No HIP call, no context, no getenv, no allocation: host arithmetic
+// over a handful of numbers, so that a machine without a GPU can check it (host/plan_check.cpp, tests/test_launch_plan.py).
+// Plain C++ on top of include/mirt.h: g++ compiles it.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/mirt.h"
+
+namespace mirt {
+
+constexpr uint32_t kStripLevels   = 5;    // strip widths 16, 8, 4, 2, 1
+constexpr uint32_t kStripPixels   = 16;   // strip kernels: pixels one wave owns per work unit (64-B RGBA8 store)
+constexpr uint32_t kBlockThreads  = 256;  // strip kernels: 4 waves
+constexpr uint32_t kByPixelMaxSpp = 64;   // strip kernel: below this many samples per pixel a wave takes 64 pixels, lane = pixel (scenes with
+                                          // one shading routine: at any sample count -- nothing diverges, 1.51 ms against 2.27 on config 2)
+// Samples per pixel from which the pooled kernel is the default (below: the strip kernel, lane = pixel).  A 16-pixel strip
+// of few samples cannot keep a pool full (about 25 steps of fill and drain per strip whatever it holds), so the thresholds are
+// measured crossovers (tools/ab_libs.py with MIRT_FLAG_KERNEL_STRIP / _POOL, 1080p):
+//   several shading routines (config 3): strip 1.58 / 1.73 / 1.94 ms at 36 / 40 / 44 spp, pool 1.61 / 1.67 / 1.74   -> 40 (round 2)
+//     round 3 (sample groups; eight-word dispenser in both kernels): strip 0.98 / 1.13 / 1.24 / 1.37 / 1.54 ms at 24 / 28 / 32 / 36 / 40 spp, pool
+//     1.00 / 1.11 / 1.21 / 1.30 / 1.41 (main.rs 5-sphere scene: 1.32 / 1.65 against 1.33 / 1.55 at 24 / 32 spp)                                   -> 28
+//   ONE routine (config 2, no divergence for the lane-per-pixel kernel to lose): round 2 184; round 3: strip 0.93 / 1.78 / 3.55 / 5.21 / 6.98 /
+//     8.48 ms at 100 / 200 / 400 / 600 / 800 / 1000 spp, pool 1.81 / 2.42 / 3.85 / 5.17 / 6.52 / 7.96                                           -> 600
+//   many-sphere scenes (grid build, RTIOW): round 2: strip 2.09 / 4.11 / 7.69 ms at 8 / 16 / 32 spp, pool 2.31 / 3.14 / 4.66 -> 16;
+//     round 3: strip 1.54 / 2.19 / 2.70 ms at 8 / 12 / 16 spp, pool 1.99 / 2.28 / 2.61                                                          -> 16
+//   round 4 (lane-per-pixel launches run one unit per wave; profiles/r04_lowspp_ab.txt block 5): several routines: strip 0.96 / 1.10 / 1.27 /
+//     1.52 ms at 24 / 28 / 32 / 40 spp, pool 1.01 / 1.12 / 1.20 / 1.39 (main.rs scene 1.26 / 1.66 against 1.32 / 1.56 at 24 / 32)             -> 32
+//     ONE routine: strip 3.36 / 4.81 / 6.49 / 8.11 ms at 400 / 600 / 800 / 1000 spp, pool 3.80 / 5.25 / 6.52 / 7.93                           -> 800
+//     with the streaming build of lane = pixel (from 16 spp on; block 9): several routines: 0.94 / 1.16 / 1.28 / 1.61 ms at 28 / 32 / 36 / 48 spp, pool
+//     - / 1.17 / 1.24 / 1.50                                                                                                                  -> 32
+//     ONE routine: 5.38 / 13.3 / 26.5 ms at 800 / 2000 / 4000 spp, pool 6.34 / 15.5 / 31.2; 3840x2160 x 1000 spp 26.3 against 30.5 -> frames of
+//     >= 1 Mpixel never take the pool (mirt_launch_plan.hip: stream_any_spp); 800x600 x 1000 spp 2.31 against the pool's 2.17                  -> 800 below that
+constexpr uint32_t kPoolMinSpp           = 32;
+constexpr uint32_t kPoolMinSppOneRoutine = 800;
+constexpr uint32_t kPoolMinSppGrid       = 16;
+
+struct PoolConfig { uint32_t threads, slots, lds_bytes; };
+
+// Tuning / experiment knobs.  They are read from the environment ONCE, when a context is created
+// (mirt_ctx_create), never inside a render call: a shipped library must not change its schedule
+// because a variable appeared mid-run, and getenv has no place in a sub-millisecond launch path.
+struct Tuning {
+    int      pool_config = -1;        // MIRT_POOL_CONFIG: geometry of the path pool (index into kPoolConfigs)
+    int      pool_grid = -1;          // MIRT_POOL_GRID=0: never take the pool kernel's grid build
+    bool     fixed_strips = false;    // MIRT_STRIP_MODE=16: fixed 16-pixel strips (no guided self-scheduling)
+    uint32_t gss_min_width = 0;       // MIRT_GSS_MINW: narrowest strip of the guided schedule
+    double   gss_keep = 0.0;          // MIRT_GSS_KEEP: strips per resident wave kept for the narrower levels
+    int      by_pixel = -1;           // MIRT_BY_PIXEL=0/1: force lane = sample / lane = pixel in the strip kernel
+    uint32_t pool_blocks_per_cu = 0;  // MIRT_POOL_BLOCKS_PER_CU: fewer resident pool blocks (occupancy experiments)
+    double   grid_cell = 0.0;         // MIRT_GRID_CELL: cell size of the uniform grid in median radii
+    double   grid_big = 0.0;          // MIRT_GRID_BIG: spheres above this many median radii stay outside the grid
+    int      pinhole = -1;            // MIRT_PINHOLE=0: never take the pinhole-camera shortcut (A/B runs)
+    int      spread_units = -1;       // MIRT_SPREAD_UNITS=0: strip-type launches use one dispenser word (A/B runs)
+    int      static_units = -1;       // MIRT_STATIC_UNITS=0/1: lane-per-pixel units dispensed to a persistent grid / one unit per wave (A/B runs, tests)
+    int      pool_min_spp = -1;       // MIRT_POOL_MIN_SPP=n: flat scenes take the pooled kernel from n samples per pixel on (A/B runs: the crossovers kPoolMinSpp*)
+    int      stream = -1;             // MIRT_STREAM=0/1: lane-per-pixel launches in flat scenes never / always run the streaming build (A/B runs)
+    int      px_groups = -1;          // MIRT_PX_GROUPS=0: lane-per-pixel units are always 64 pixels; 1 / 2 / 3: force 1 / 2 / 4 sample groups (A/B runs)
+    int      strip_cand = -1;         // MIRT_STRIP_CAND=0: camera rays of grid builds take the grid like every other ray (A/B runs)
+    int      grid_flat_y = -1;        // MIRT_GRID_FLAT_Y=0: a grid one cell high is walked in three dimensions like any other (A/B runs, tests)
+    bool     debug_slots = false;     // MIRT_DEBUG_SLOTS=1: every launch checks (synchronously) that its slot's dispenser words are zero
+    uint32_t static_block = 0;        // MIRT_STATIC_BLOCK=64/128/256 (A/B runs): threads per block of the launches that run one unit per wave
+    int      static_grid = -1;        // MIRT_STATIC_GRID=k (A/B runs): launches with one unit per wave run k x the resident blocks instead, units dealt round-robin
+    int      timing = -1;             // MIRT_TIMING=0/1: the context's initial mirt_ctx_set_timing state (A/B runs; default 1)
+    uint32_t hbm_pool_slots = 0;      // MIRT_HBM_POOL_SLOTS=n (A/B runs): the pooled build of MIRT_SCENE_HBM scenes takes this one of kBvhPoolSlotChoices
+    uint32_t radiance_pool_blocks = 0;    // MIRT_RADIANCE_POOL_BLOCKS=n (A/B runs, tests): a pooled radiance query launches at most n blocks, whose waves stride over the units
+    uint32_t adapt_pool_blocks = 0;   // MIRT_ADAPT_POOL_BLOCKS=n (A/B runs, tests): a pooled adaptive step launches at most n blocks, whose waves stride over the units
+    bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
+};
+
+// What the planner reads of a context, and nothing more.
+struct PlanFacts {
+    uint32_t cu_count;                            // device
+    uint64_t lds_per_cu, lds_per_block;
+    uint32_t n_spheres, n_mats, n_shading_routines;   // scene
+    bool     has_image_texture, have_sky, fits_flat, hbm;
+    uint32_t grid_bytes;                          // grid (0: the scene has none)
+    bool     grid_packable, grid_flat_y, have_shade;
+    uint32_t bvh_max_depth;                       // tree of a MIRT_SCENE_HBM scene
+    bool     camera_is_pinhole;                   // camera
+};
+
+// The kernel a plan runs.  Together with the bits below it names one template instance; occupancy, dispatch and the name reported by
+// mirt_ctx_last_kernel are functions of it (mirt_api.hip).
+enum PlanKernel : uint32_t { kKernelParity, kKernelParityHbm, kKernelPtStrip, kKernelPtHbm, kKernelPtPool, kKernelPtPoolHbm };
+
+struct RenderPlan {
+    int         status;               // MIRT_OK, or the one refusal (MIRT_ERR_SCENE_TOO_LARGE) with its message
+    const char* message;
+    // the kernel
+    PlanKernel kernel;
+    bool       fast, count, hosek, frame, use_grid, hbm_bvh, by_pixel, stream;
+    uint32_t   pool_cfg, pool_nq;
+    PoolConfig pool;                  // geometry of the pool kernel that runs: threads / slots / lds (zero for the other kernels)
+    // the schedule (the RenderArgs fields of the same names)
+    uint32_t out_rows, n_units, lvl_unit[kStripLevels + 1], lvl_pix[kStripLevels + 1];
+    uint32_t px_groups_log2, static_units, stream_samples, strip_cand, grid_flat_y, grid_pool_slots;
+    uint32_t launch_threads, lds_bytes, bvh_stack_entries, spread_units;
+    uint32_t pinhole;                 // the word that travels in the camera's padding (generate_primary's shortcut)
+    uint32_t blocks;                  // plan_render: before the occupancy cap; plan_blocks: the grid of the launch
+    // what plan_blocks needs besides the occupancy answer, and what it adds
+    uint32_t cu_count, per_cu_cap;    // blocks per CU at most: LDS, waves, the pooled HBM plan, MIRT_POOL_BLOCKS_PER_CU (pool kernels); 8 (strip-type)
+    int      static_grid;             // Tuning.static_grid
+    uint32_t first_dispensed, disp_taken[8];
+};
+
+// The geometry of the pooled kernel of MIRT_SCENE_HBM scenes (mirt_bvh_pool_plan; the launch calls this very function) for a tree
+// `max_depth` deep: per block the camera (+ sky), and per wave a pool and 64 stacks of max_depth entries.  The rule (mirt_kernels.h,
+// DESIGN.md 10.6): the first of kBvhPoolSlotChoices -- largest pools first -- that leaves kBvhPoolWavesPerCu waves resident, else the
+// choice with most waves, the larger pools on a tie.  slots == 0: not even one block fits.  `only_slots` != 0 (A/B runs): that choice alone.
+// `extra_per_wave`: bytes a wave keeps beside its pool -- 0 for the pooled render and the pooled query, kAdaptPoolExtraBytes for the
+// pooled adaptive step (mirt_adapt_pool_plan).
+MirtBvhPoolPlan plan_bvh_pool(uint32_t max_depth, bool hosek, uint64_t lds_per_cu, uint32_t only_slots, uint32_t extra_per_wave);
+
+// The gate every pooled BVH launch passes (render, radiance query, adaptive step): 8-bit bounce counters, and a geometry for the
+// resident tree that fits the block's LDS.  slots == 0: none, the launch is the one without the pool.
+MirtBvhPoolPlan pooled_bvh_plan(const PlanFacts& f, const Tuning& tune, bool hosek, uint32_t extra_per_wave, uint32_t num_bounces);
+
+// MirtParams row selection: is it valid (then [*rb, *re) is the band), and the rows a call writes (mirt_params_out_rows)
+bool     rows_valid(const MirtParams* p, uint32_t* rb, uint32_t* re);
+uint32_t out_rows(const MirtParams* p);
+
+// Everything a render launch decides before it asks for occupancy: kernel, geometry, schedule.  `frame`: a progressive frame (sums AND image).
+RenderPlan plan_render(const PlanFacts& f, const Tuning& tune, const MirtParams& p, bool frame);
+// The caps that need the occupancy answer -- blocks of the chosen kernel resident per CU (0: no answer) --, then the dispenser's start.
+void plan_blocks(RenderPlan& plan, uint32_t resident_per_cu);
+
+}  // namespace mirt

@@ -1,0 +1,318 @@
+// mirt_launch_plan.hip — the launch plan of a render call (mirt_launch_plan.h): host arithmetic only.  launch_render (mirt_api.hip)
+// is its one caller in the library; host/plan_check.cpp calls it without a device.
+#include "mirt_kernels.h"
+
+namespace kx = mirt::exact_build;
+
+namespace mirt {
+
+// ---- MirtParams row selection ----
+bool rows_valid(const MirtParams* p, uint32_t* rb, uint32_t* re)
+{
+    const uint32_t b = p->row_begin, e = p->row_end == 0 ? p->height : p->row_end;
+    if (b >= e || e > p->height) return false;
+    if (p->tile_rows != 0 && p->n_parts > 1 && p->part >= p->n_parts) return false;
+    *rb = b;
+    *re = e;
+    return true;
+}
+
+uint32_t out_rows(const MirtParams* p)
+{
+    uint32_t rb, re;
+    if (!p || p->width == 0 || p->height == 0 || !rows_valid(p, &rb, &re)) return 0;
+    const uint32_t band = re - rb;
+    if (p->tile_rows == 0 || p->n_parts <= 1) return band;
+    const uint32_t tr = p->tile_rows;
+    const uint32_t tiles = (band + tr - 1) / tr;
+    if (tiles <= p->part) return 0;
+    const uint32_t owned = (tiles - p->part + p->n_parts - 1) / p->n_parts;
+    uint32_t rows = owned * tr;
+    if ((tiles - 1) % p->n_parts == p->part) rows -= tiles * tr - band;
+    return rows;
+}
+
+MirtBvhPoolPlan plan_bvh_pool(uint32_t max_depth, bool hosek, uint64_t lds_per_cu, uint32_t only_slots, uint32_t extra_per_wave)
+{
+    MirtBvhPoolPlan best{};
+    const uint32_t waves = kBvhPoolThreads / 64u;
+    const uint64_t scene = kx::scene_lds_bytes_grid(0u, hosek);
+    for (uint32_t slots : kBvhPoolSlotChoices) {
+        if (only_slots != 0u && slots != only_slots) continue;
+        const uint64_t block = scene + (uint64_t)waves * (bvh_pool_bytes_per_wave(slots) + extra_per_wave + 256ull * max_depth);
+        uint64_t blocks = lds_per_cu / block;
+        if (blocks > kBvhPoolWavesPerCu / waves) blocks = kBvhPoolWavesPerCu / waves;
+        if ((uint32_t)blocks * waves > best.waves_per_cu)
+            best = MirtBvhPoolPlan{ kBvhPoolThreads, slots, (uint32_t)blocks * waves, max_depth, (uint32_t)block };
+        if (best.waves_per_cu == kBvhPoolWavesPerCu) break;
+    }
+    return best;
+}
+
+MirtBvhPoolPlan pooled_bvh_plan(const PlanFacts& f, const Tuning& tune, bool hosek, uint32_t extra_per_wave, uint32_t num_bounces)
+{
+    if (num_bounces > 255u) return MirtBvhPoolPlan{};
+    const MirtBvhPoolPlan plan = plan_bvh_pool(f.bvh_max_depth, hosek, f.lds_per_cu, tune.hbm_pool_slots, extra_per_wave);
+    return plan.slots != 0u && plan.lds_bytes_per_block <= f.lds_per_block ? plan : MirtBvhPoolPlan{};
+}
+
+RenderPlan plan_render(const PlanFacts& f, const Tuning& tune, const MirtParams& p, bool frame)
+{
+    RenderPlan a{};
+    const uint32_t rows = out_rows(&p);
+    const uint64_t npix = (uint64_t)rows * p.width;
+    const bool count = (p.flags & MIRT_FLAG_COUNT_WORK) != 0;
+    const bool hosek = p.mode == MIRT_MODE_PT && (p.flags & MIRT_FLAG_SKY_HOSEK);
+
+    const bool pt = p.mode == MIRT_MODE_PT;
+    const size_t scene_lds = kx::scene_lds_bytes(f.n_spheres, f.n_mats, pt, hosek);
+    // kernel choice (path-traced mode): the pooled kernel needs enough samples per tile to keep
+    // its path pool full, 8-bit bounce counters and room for the pool beside the scene in LDS
+    // MIRT_FLAG_TEXEL_TILES: flat scenes with an image texture run the pool geometry that keeps a texel window per wave
+    const bool tiles = pt && (p.flags & MIRT_FLAG_TEXEL_TILES) && f.has_image_texture && tune.pool_config < 0;
+    const uint32_t pool_cfg = tune.pool_config >= 0 ? (uint32_t)tune.pool_config : (tiles ? kTilePoolConfig : kDefaultPoolConfig);
+    const uint32_t pool_nq = kx::pool_scatter_queues(f.n_shading_routines, count);
+    const PoolConfig pc = kx::pool_config(pool_cfg, pool_nq);
+    // Default schedule: the pooled kernel pays off when a strip holds enough samples to keep the pool full and the
+    // pools still leave >= 16 waves per CU resident beside the scene tables; the sample counts from which it does are
+    // measured crossovers against the strip kernel's lane-per-pixel schedule (mirt_kernels.h: kPoolMinSpp*): 28 for scenes
+    // with several shading routines, 600 for single-routine scenes (nothing diverges there, so lane = pixel is hard to
+    // beat: single metal sphere, 1080p x 100 spp, 1.38 ms against the pool's 1.82 and the lane-per-sample schedule's 2.27),
+    // 16 for many-sphere scenes, where the pool's re-compaction of grid walks is worth most.
+    const size_t lds_pool_block = scene_lds + pc.lds_bytes;
+    const uint32_t pool_waves_per_cu = (uint32_t)(f.lds_per_cu / (lds_pool_block ? lds_pool_block : 1)) * (pc.threads / 64u);
+    // (round 4, the streaming build of lane = pixel: a single-routine scene on a frame of at least eight rounds of 16-pixel units per resident
+    //  wave -- 1 Mpixel on 256 CUs -- never takes the pool: single sphere 1080p x 800 / 2000 / 4000 spp 5.38 / 13.3 / 26.5 ms against the pool's
+    //  6.34 / 15.5 / 31.2, 3840x2160 x 1000 spp 26.3 / 30.5; at 800x600 x 1000 spp the pool still wins, 2.17 against 2.31.  Scenes with several
+    //  routines: streaming 1.16 ms at 32 spp, pool 1.17; 36 / 48 spp 1.28 / 1.61 against 1.24 / 1.50 -- the crossover stays.  r04_lowspp_ab.txt block 9)
+    const bool stream_any_spp = f.n_shading_routines <= 1 && !hosek && npix >= 16ull * 8u * 32u * (uint64_t)f.cu_count;
+    const uint32_t pool_min_spp = tune.pool_min_spp > 0 ? (uint32_t)tune.pool_min_spp
+                                : stream_any_spp ? UINT32_MAX
+                                : f.n_shading_routines <= 1 ? kPoolMinSppOneRoutine : kPoolMinSpp;
+    bool pool = pt && p.spp >= pool_min_spp && f.n_shading_routines >= 1 && pool_waves_per_cu >= 16;
+    if (p.flags & MIRT_FLAG_KERNEL_STRIP) pool = false;
+    if (p.flags & MIRT_FLAG_KERNEL_POOL) pool = pt;
+    // the reference's per-frame RNG stream makes a pixel's samples sequentially dependent: lane-per-pixel strip kernel only
+    const bool frame_stream = pt && p.frame_spp != 0;
+    if (frame_stream) pool = false;
+    if (p.num_bounces > 255u || scene_lds + pc.lds_bytes > (size_t)f.lds_per_block || !f.fits_flat) pool = false;
+    // Many-sphere scenes: the pool kernel's grid build keeps spheres + grid + pools in LDS (materials in L2).  It
+    // is taken when the flat pool is not (too few waves per CU beside a big sphere table) and >= 12 waves fit.
+    const size_t scene_lds_g = kx::scene_lds_bytes_grid(f.n_spheres, hosek);
+    const bool grid_ok = pt && (!count || ((p.flags & MIRT_FLAG_COUNT_GRID) && !frame_stream)) && f.grid_bytes != 0 &&
+                         !(p.flags & MIRT_FLAG_NO_GRID);
+    // one 1024-thread block per CU; its path pools take what scene + grid leave of the block's LDS (counting launches:
+    // the largest geometry only)
+    const size_t lds_beside = scene_lds_g + f.grid_bytes;
+    const size_t lds_grid_block = (size_t)f.lds_per_block / kGridPoolBlocksPerCu;
+    PoolConfig pcg = kx::pool_config_grid(lds_grid_block > lds_beside ? lds_grid_block - lds_beside : 0);
+    if (count && pcg.slots != kGridPoolSlotChoices[0] && pcg.slots != kGridPoolSlotChoices[1]) pcg.slots = 0;
+    const size_t lds_pool_grid_block = lds_beside + pcg.lds_bytes;
+    const uint32_t pool_grid_waves_per_cu = pcg.slots ? (uint32_t)(f.lds_per_cu / lds_pool_grid_block) * (pcg.threads / 64u) : 0u;
+    bool pool_grid = grid_ok && f.grid_packable && pcg.slots != 0 && tune.pool_config < 0 && p.num_bounces <= 255u &&
+                     !(p.flags & MIRT_FLAG_KERNEL_STRIP) && !frame_stream &&
+                     ((p.flags & MIRT_FLAG_KERNEL_POOL) ||
+                      (!pool && p.spp >= kPoolMinSppGrid && f.n_shading_routines >= 1 && pool_grid_waves_per_cu >= 16));
+    if (tune.pool_grid == 0) pool_grid = false;
+    if (pool_grid) pool = true;
+    // MIRT_SCENE_HBM scene: the strip kernel (parity kernel) with the tables in device memory -- the BVH build unless NO_GRID asks for the
+    // flat scan or a counting launch asks for the flat scan's counters (COUNT_WORK without COUNT_GRID); tile hints do not apply.
+    // MIRT_FLAG_KERNEL_POOL on the BVH build: the pooled kernel (render_pt_pool_hbm_kernel) where the pool's own limits allow it -- 8-bit
+    // bounce counters, no per-frame RNG stream, a geometry that fits beside the stacks of a tree this deep -- and _STRIP does not object.
+    // Never by default: DESIGN.md 10.6 has the measured crossovers.
+    const bool hbm = f.hbm;
+    const bool hbm_bvh = hbm && pt && !(p.flags & MIRT_FLAG_NO_GRID) && (!count || (p.flags & MIRT_FLAG_COUNT_GRID));
+    MirtBvhPoolPlan hbm_plan{};
+    if (hbm_bvh && (p.flags & MIRT_FLAG_KERNEL_POOL) && !(p.flags & MIRT_FLAG_KERNEL_STRIP) && !frame_stream)
+        hbm_plan = pooled_bvh_plan(f, tune, hosek, 0u, p.num_bounces);
+    const bool pool_hbm = hbm_plan.slots != 0u;
+    if (pool_hbm) pool = true;
+    // the geometry of the pool kernel that will run
+    const PoolConfig pcu = pool_hbm ? PoolConfig{ hbm_plan.threads, hbm_plan.slots, hbm_plan.lds_bytes_per_block } : pool_grid ? pcg : pc;
+    const uint32_t resident_pool_waves = pool_hbm ? hbm_plan.waves_per_cu : pool_grid ? pool_grid_waves_per_cu : pool_waves_per_cu;
+
+    // the kernels' pinhole shortcut (generate_primary): the flag travels in the padding word beside lower_left_corner of
+    // THIS launch's by-value copy of the camera; the caller's struct is never touched
+    a.pinhole = (pt && tune.pinhole != 0 && f.camera_is_pinhole) ? 1u : 0u;
+    a.out_rows = rows;
+    a.n_units = (uint32_t)((npix + kStripPixels - 1) / kStripPixels);
+    for (uint32_t l = 0; l <= kStripLevels; ++l) { a.lvl_unit[l] = a.n_units; a.lvl_pix[l] = (uint32_t)npix; }
+    a.lvl_unit[0] = 0;
+    a.lvl_pix[0] = 0;
+    if (pool) {
+        // Guided self-scheduling for the pool kernel: 16-pixel strips while more than 4 strips per resident
+        // wave remain, then 8- and 4-pixel strips under the same rule, so that the waves finish within a
+        // fraction of a strip of each other.  Measured on config 3 (tools/part_timing.py, one rank's share of
+        // an N-way partition vs 1/N of the whole frame): fixed 16-pixel strips 95 / 83 / 67 % at N = 2 / 4 / 8,
+        // this schedule 99 / 95 / 90 %; strips narrower than 4 pixels lose more to pool fill/drain than they
+        // gain.  Narrow strips also need width x spp >= 512 work items to keep a wave's pool busy.
+        const uint64_t waves = (uint64_t)f.cu_count * (resident_pool_waves < 32u ? resident_pool_waves : 32u);   // resident waves (LDS-bound)
+        uint32_t min_width = 4;
+        while (min_width < kStripPixels && (uint64_t)min_width * p.spp < 512u) min_width *= 2;
+        if (tune.fixed_strips) min_width = kStripPixels;
+        if (tune.gss_min_width) min_width = tune.gss_min_width;
+        const double keep_factor = tune.gss_keep > 0.0 ? tune.gss_keep : 4.0;
+        uint64_t pix = 0, unit = 0;
+        for (uint32_t l = 0; l < kStripLevels; ++l) {
+            const uint32_t width = kStripPixels >> l;
+            a.lvl_unit[l] = (uint32_t)unit;
+            a.lvl_pix[l] = (uint32_t)pix;
+            uint64_t level_px;
+            if (width <= min_width) {
+                level_px = npix - pix;                               // last usable level takes the rest
+            } else {
+                const uint64_t keep = (uint64_t)(keep_factor * (double)(waves * width));   // pixels left for the narrower levels
+                const uint64_t left = npix - pix;
+                level_px = left > keep ? (left - keep) / width * width : 0;
+            }
+            pix += level_px;
+            unit += (level_px + width - 1) / width;
+        }
+        a.lvl_unit[kStripLevels] = (uint32_t)unit;
+        a.lvl_pix[kStripLevels] = (uint32_t)npix;
+        a.n_units = (uint32_t)unit;
+    }
+    // many-sphere scenes: nearest hit through the uniform grid (strip kernel, non-counting build only:
+    // the counting build keeps the reference's flat scan so that its work counters stay comparable)
+    const bool use_grid = pool_grid || (grid_ok && !pool && scene_lds_g + f.grid_bytes + 4u * 48u <= (size_t)f.lds_per_block);
+    const uint32_t grid_bytes = use_grid ? f.grid_bytes : 0u;
+    a.grid_pool_slots = pool_grid ? pcg.slots : 0u;
+    // camera-ray candidate lists (mirt_kernels.hip: strip_candidates): always in the pooled kernel (a list serves 16 pixels x spp rays);
+    // in the strip kernel's lane-per-pixel units (64 pixels x spp) from 4 samples per pixel on -- measured on RTIOW 1080p: 2 spp +2 %
+    // (selecting among 484 spheres costs more than 128 camera rays save), 8 spp -6 %
+    a.strip_cand = (use_grid && tune.strip_cand != 0 && (pool_grid || p.spp >= 4u)) ? 1u : 0u;
+    a.grid_flat_y = (use_grid && f.grid_flat_y) ? 1u : 0u;
+    // (the strip kernel's grid build keeps a camera-ray candidate list per wave behind the blob: 4 waves x 48 bytes)
+    a.lds_bytes = use_grid ? (uint32_t)(scene_lds_g + grid_bytes + (pool ? pcu.lds_bytes : 4u * 48u)) : (uint32_t)(scene_lds + (pool ? pcu.lds_bytes : 0));
+    if (pool_hbm) a.lds_bytes = hbm_plan.lds_bytes_per_block;     // camera (+ sky), the block's pools, its waves' traversal stacks
+    a.bvh_stack_entries = pool_hbm ? hbm_plan.stack_entries : 0u;
+    if (!use_grid && !f.fits_flat && !hbm) {
+        a.status = MIRT_ERR_SCENE_TOO_LARGE;
+        a.message = "this scene only fits LDS in the grid build of the path-traced mode "
+                    "(no parity mode, no MIRT_FLAG_COUNT_WORK / MIRT_FLAG_NO_GRID / MIRT_FLAG_KERNEL_POOL)";
+        return a;
+    }
+
+    // few samples per pixel (the reference's interactive loop adds 2 per frame): lane = pixel instead of lane = sample
+    // (single-routine scenes: lane = pixel at any sample count, but only for frames that give every CU a few 64-pixel units;
+    //  a tiny frame with many samples per pixel needs the lanes of a wave on the samples)
+    bool by_pixel = pt && !pool && !count && (p.spp < kByPixelMaxSpp || (f.n_shading_routines <= 1 && npix >= 64ull * 4u * f.cu_count));
+    if (tune.by_pixel >= 0) by_pixel = pt && !pool && !count && tune.by_pixel == 1;
+    if (hbm_bvh && !count && !pool_hbm) by_pixel = true;  // the BVH build's strip kernel: lane = pixel at every sample count
+    if (frame_stream) by_pixel = true;                    // also for counting launches (flat scan) and any spp
+    // parity mode: lane = pixel at EVERY sample count, counting or not (round 3: below 64 spp).  The reference's loop returns at the first
+    // terminating sample (layer.rs:320-378), which a lane that walks its own pixel's samples does too, while lane = sample computes 64
+    // samples of a pixel to find it: with one unit per wave 1080p x 64 / 100 / 1000 spp take 0.29 / 0.34 / 1.89 ms against 1.14 / 1.17 /
+    // 2.08 (profiles/r04_lowspp_ab.txt block 7).  MIRT_FLAG_KERNEL_STRIP still forces lane = sample (same image, same work counters).
+    if (!pt) by_pixel = (p.flags & MIRT_FLAG_KERNEL_STRIP) ? false : (tune.by_pixel >= 0 ? tune.by_pixel == 1 : true);
+    a.static_units = 0;
+    a.px_groups_log2 = 0;
+    // lane = pixel in a flat scene from 16 spp on: the streaming build -- a lane starts its pixel's next sample without waiting for the wave
+    // (mirt_kernels.hip: strip_kernel_body<STREAM>; MIRT_STREAM=0/1 for A/B runs)
+    a.stream_samples = (pt && by_pixel && !count && !use_grid && p.spp >= 16u) ? 1u : 0u;
+    if (tune.stream >= 0 && pt && by_pixel && !count && !use_grid) a.stream_samples = (uint32_t)tune.stream;
+    if (hbm) a.stream_samples = 0u;
+    if (by_pixel) {
+        // Path-traced lane-per-pixel units: 64 pixels x all samples -- or 32 / 16 pixels with the samples dealt to 2 / 4 groups of lanes:
+        // smaller units are more units, and the last unit of a wave is then a smaller part of its life (config 2, 1080p x 100 spp, had 4
+        // units per wave: 1.21 ms; 16-pixel units, with the eight-word dispenser they need: 0.86).  Measured (tools/ab_libs.py with
+        // MIRT_PX_GROUPS, profiles/r03_flat_ab.txt block 9; 1080p unless stated): as many groups as leave each >= 8 samples -- three spheres
+        // at 32 / 16 / 8 spp: 1 / 2 / 4 groups 1.33 / 1.20 / 1.16, 0.68 / 0.63 / 0.66, 0.36 / 0.37 / 0.43 ms; config 2 1.17 / 0.93 / 0.86;
+        // the same at 3840x2160 3.20 / 2.96 / 2.89, at 800x600 0.71 / 0.41 / 0.33 -- and one more for many-sphere scenes (RTIOW 8 spp:
+        // 1.54 / 1.40).  The samples must divide evenly; never with the reference's per-frame stream (sequentially dependent samples).
+        if (pt && !frame_stream && tune.px_groups != 0) {
+            // (round 4, one unit per wave, profiles/r04_lowspp_ab.txt block 4: two groups from shares of 4 -- three spheres 8 spp 0.337 ms against
+            //  0.359, main.rs scene 0.434 / 0.459 --, four groups from shares of 6: 16 spp 0.610 with two groups, 0.617 with four; 24 spp 0.884 / 0.881)
+            // (streaming launches, below: shares of at least 8 samples -- three spheres 16 spp 0.588 ms with two groups, 0.643 with four; 24 spp
+            //  0.822 / 0.886; config 2 at 25 per lane, four groups: 0.750, two: 0.829, eight (128 spp): +-0; block 9)
+            const uint32_t min_share[2] = { a.stream_samples ? 8u : 4u, a.stream_samples ? 8u : (use_grid ? 4u : 6u) };
+            while (a.px_groups_log2 < 2u && p.spp % (2u << a.px_groups_log2) == 0u && (p.spp >> (a.px_groups_log2 + 1u)) >= min_share[a.px_groups_log2])
+                a.px_groups_log2 += 1u;
+            if (tune.px_groups > 0 && p.spp % (1u << (tune.px_groups - 1)) == 0u) a.px_groups_log2 = (uint32_t)tune.px_groups - 1u;
+        }
+        a.n_units = (uint32_t)((npix + (64u >> a.px_groups_log2) - 1u) / (64u >> a.px_groups_log2));
+        // ONE UNIT PER WAVE instead of units dispensed to a persistent grid (a.static_units; round 4): the launch has as many waves as units, and
+        // the hardware's workgroup dispatcher -- which starts a block wherever a CU has room -- is the load balancer: no dispenser atomic
+        // (one returning device-scope atomic per unit, 14 ns each on one address, was the whole kernel time of a 2-spp frame), and none of
+        // the imbalance of dealing units round-robin to resident waves (rounds 2-3: a wave's four units are a quarter of its life each).
+        // Measured against both (profiles/r04_lowspp_ab.txt block 3; 1080p, three spheres): 1 / 2 / 4 / 8 / 16 / 24 spp -14 / -16 / -13 / -4 / -2 /
+        // +-0 %; main.rs scene 2 spp -20 %; config 2 -1.6 %; parity mode's lane = pixel 2 spp (1080p) -11 %, 32 spp -21 %.  Every block stages
+        // the scene itself, which is why many-sphere scenes (a 25 KB grid blob per block) keep the dispenser from 4 spp on (RTIOW: 2 spp -21 %,
+        // 4 / 8 / 12 spp +7 / +8 / +7 %).
+        a.static_units = (!pt || !use_grid || p.spp < 4u) ? 1u : 0u;
+        if (tune.static_units >= 0) a.static_units = (uint32_t)tune.static_units;
+    }
+
+    // the opt-in fast-math build of the path-traced kernels; counting launches always run the exact build
+    const bool fast = pt && !count && (p.flags & MIRT_FLAG_FAST_MATH);
+    a.cu_count = f.cu_count;
+    a.static_grid = tune.static_grid;
+    if (pool) {
+        uint32_t per_cu = (uint32_t)(f.lds_per_cu / (a.lds_bytes ? a.lds_bytes : 1));
+        const uint32_t by_waves = 32u / (pcu.threads / 64u);   // upper bound; LDS decides (6 blocks of 4 waves with 112-slot pools)
+        if (per_cu > by_waves) per_cu = by_waves;
+        if (pool_hbm) {                                        // the plan's waves, and no more blocks than the build's registers keep resident (plan_blocks)
+            const uint32_t planned = hbm_plan.waves_per_cu / (pcu.threads / 64u);
+            if (per_cu > planned) per_cu = planned;
+        }
+        if (tune.pool_blocks_per_cu >= 1 && tune.pool_blocks_per_cu < per_cu) per_cu = tune.pool_blocks_per_cu;
+        a.per_cu_cap = per_cu;
+        const uint32_t units_per_block = pcu.threads / 64u;
+        a.blocks = (a.n_units + units_per_block - 1) / units_per_block;
+    } else {
+        // One unit per wave in a flat scene: one WAVE per block, too -- a block leaves when its slowest wave is done, and the scene a block
+        // stages is a few hundred bytes (1080p, three spheres 2 / 4 / 8 / 16 spp -1.6 / -2.2 / -1.5 / -1.3 %, config 2 -1.9 %, parity mode at
+        // 1000 spp nominal -15 %; profiles/r04_lowspp_ab.txt block 8).  Many-sphere scenes stage a 25 KB grid blob per block: 256 threads
+        // (RTIOW 2 spp with 64-thread blocks: 2.4 x the time).  MIRT_STATIC_BLOCK=64/128/256 for A/B runs.
+        a.launch_threads = 0u;
+        if (a.static_units != 0u && tune.static_grid <= 0) a.launch_threads = tune.static_block ? tune.static_block : (use_grid ? 0u : 64u);
+        const uint32_t waves_per_block = (a.launch_threads ? a.launch_threads : kBlockThreads) / 64;
+        a.blocks = (a.n_units + waves_per_block - 1) / waves_per_block;
+        // MIRT_SCENE_HBM: LDS holds the camera (+ sky) and, in the BVH build, every wave's traversal stacks
+        if (hbm) a.lds_bytes = (uint32_t)(scene_lds_g + (hbm_bvh ? waves_per_block * kBvhStackBytesPerWave : 0u));
+        a.per_cu_cap = 8u;                                            // 2048 threads per CU / 256
+    }
+    // kernels with dispensed units take them from eight dispenser words (mirt_kernels.hip: next_unit_any): the strip-type kernels
+    // (path-traced strip kernel, both schedules; parity kernel) always.
+    // The pooled kernel's strips last long at high sample counts (config 3: 9 atomics per microsecond); below 128 spp they do not
+    // (three spheres, 1080p, pool forced: 48 / 64 / 100 / 200 spp -13.5 / -8.5 / -2 / +1 % with eight words; RTIOW 16 spp -4.5 %).
+    a.spread_units = (a.static_units == 0u && tune.spread_units != 0 && (!pool || p.spp < 128u)) ? 1u : 0u;
+
+    a.kernel = pool_hbm ? kKernelPtPoolHbm : hbm ? (pt ? kKernelPtHbm : kKernelParityHbm) : !pt ? kKernelParity : pool ? kKernelPtPool : kKernelPtStrip;
+    a.fast = fast; a.count = count; a.hosek = hosek; a.frame = frame; a.use_grid = use_grid; a.hbm_bvh = hbm_bvh; a.by_pixel = by_pixel;
+    a.stream = a.stream_samples != 0u;
+    a.pool_cfg = pool_cfg; a.pool_nq = pool_nq;
+    if (pool) a.pool = pcu;
+    return a;
+}
+
+void plan_blocks(RenderPlan& a, uint32_t resident_per_cu)
+{
+    const bool pool = a.kernel == kKernelPtPool || a.kernel == kKernelPtPoolHbm;
+    uint32_t blocks = a.blocks;
+    if (pool) {
+        uint32_t per_cu = a.per_cu_cap;
+        if (resident_per_cu >= 1u && per_cu > resident_per_cu) per_cu = resident_per_cu;
+        if (per_cu == 0u) per_cu = 1u;
+        if (blocks > a.cu_count * per_cu) blocks = a.cu_count * per_cu;
+    } else {
+        // a persistent grid of exactly the blocks that are resident at once: registers and LDS decide (4-8 per CU for these
+        // kernels).  A block beyond that would hold its first unit until the dispenser has run dry and run it alone at the end.
+        const uint32_t per_cu = resident_per_cu > a.per_cu_cap ? a.per_cu_cap : resident_per_cu;
+        const uint32_t resident = a.cu_count * per_cu;
+        // ... unless the launch runs one unit per wave (a.static_units): then the grid is the units (MIRT_STATIC_GRID=k, A/B runs: k x the
+        // resident blocks with the units dealt round-robin, rounds 2-3's schedule at k = 1)
+        uint32_t cap = resident;
+        if (a.static_units != 0u) cap = a.static_grid > 0 ? resident * (uint32_t)a.static_grid : blocks;
+        if (blocks > cap) blocks = cap;
+    }
+    if (blocks == 0) blocks = 1;
+    a.blocks = blocks;
+
+    // the dispenser continues after the units the waves take by their own index (first_unit() in the kernels)
+    const uint32_t launched_waves = blocks * ((pool ? a.pool.threads : (a.launch_threads ? a.launch_threads : kBlockThreads)) / 64u);
+    a.first_dispensed = launched_waves;          // the words themselves are zero (retire_slots): no memset node in front of the kernel
+    for (uint32_t x = 0; x < 8u; ++x) a.disp_taken[x] = launched_waves > x ? (launched_waves - x + 7u) / 8u : 0u;
+}
+
+}  // namespace mirt
