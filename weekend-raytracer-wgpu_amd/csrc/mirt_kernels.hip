@@ -658,16 +658,11 @@ MIRT_DEV CamRegs load_camera(const SceneLds& S, const RenderArgs& A, const CamHe
 // fma(lpy, v_k, lpx * u_k) = +-0, and eye_k + (+-0) == eye_k bit for bit unless eye_k is -0 (then the sum's sign would
 // depend on the draw).  The host sets the flag only when lens_radius == 0, eye / u / v are finite and no eye component is
 // -0 (mirt_api.hip: camera_is_pinhole); the two lens draws are still consumed, so the stream is the reference's.
-template <bool RESEED = true>
-MIRT_DEV void generate_primary(const RenderArgs& A, const CamRegs& C, uint32_t x, uint32_t y, uint32_t sample,
-                               Rng& rng, f3& ro, f3& rd)
+// The ray itself comes from primary_ray: a seeded stream and the pixel's coordinates as floats, (float)x and (float)y.
+MIRT_DEV void primary_ray(const CamRegs& C, float fx, float fy, Rng& rng, f3& ro, f3& rd)
 {
-    if constexpr (RESEED) {
-        const uint32_t pixel_index = x + y * A.width;
-        rng.state = jenkins_hash((pixel_index ^ jenkins_hash(sample + 1u)) ^ A.seed_mix);
-    }
-    const float u = ((float)x + rng.next()) * C.inv_w;
-    const float v = 1.0f - ((float)y + rng.next()) * C.inv_h;
+    const float u = (fx + rng.next()) * C.inv_w;
+    const float v = 1.0f - (fy + rng.next()) * C.inv_h;
     if (C.pinhole) {
         asm volatile("; generate_primary: pinhole camera" ::);       // keeps this a real (scalar) branch
         rng.skip();
@@ -681,6 +676,25 @@ MIRT_DEV void generate_primary(const RenderArgs& A, const CamRegs& C, uint32_t x
         ro = C.eye + fma3(lpy, C.cam_v, lpx * C.cam_u);
     }
     rd = fma3(v, C.ver, fma3(u, C.hor, C.llc)) - ro;
+}
+
+template <bool RESEED = true>
+MIRT_DEV void generate_primary(const RenderArgs& A, const CamRegs& C, uint32_t x, uint32_t y, uint32_t sample,
+                               Rng& rng, f3& ro, f3& rd)
+{
+    if constexpr (RESEED) {
+        const uint32_t pixel_index = x + y * A.width;
+        rng.state = jenkins_hash((pixel_index ^ jenkins_hash(sample + 1u)) ^ A.seed_mix);
+    }
+    primary_ray(C, (float)x, (float)y, rng, ro, rd);
+}
+
+// generate_primary<true> for a pixel whose part of the work was done once per strip (the pooled kernel's pixel records):
+// fx = (float)x, fy = (float)y, pixel_key = (x + y * width) ^ seed_mix.  XOR is associative, so the seed is the same word.
+MIRT_DEV void generate_primary(const CamRegs& C, float fx, float fy, uint32_t pixel_key, uint32_t sample, Rng& rng, f3& ro, f3& rd)
+{
+    rng.state = jenkins_hash(pixel_key ^ jenkins_hash(sample + 1u));
+    primary_ray(C, fx, fy, rng, ro, rd);
 }
 
 // nearest hit (wgsl:135-145, 407-429): every lane walks the same sphere list in LDS.
@@ -2114,6 +2128,13 @@ constexpr uint32_t kFastForwardMin = MIRT_FF_MIN;
 // accumulators, the item counter and all queue depths in SGPRs.  Nothing is shared between waves after the
 // scene has been staged: no barrier, no inter-wave atomic.  (A block-level pool with barriers was measured
 // 20 % slower)
+// The fourth word of q2 belongs to the path only in grid builds (the nearest hit of a parked walk).  The flat builds keep the
+// strip's PIXEL RECORDS there (MIRT_GEN_PIXEL_RECORDS): what a GEN step needs of pixel p -- (float)x,
+// (float)y, (x + y * width) ^ seed_mix -- in that word of slots 3 p, 3 p + 1, 3 p + 2, written once per strip by its prologue and
+// read once per sample, so a path's q2 is stored as 12 bytes there.  No byte of LDS is added: the launch plans do not move.
+#ifndef MIRT_GEN_PIXEL_RECORDS
+#define MIRT_GEN_PIXEL_RECORDS 1          // 0: every GEN step derives them from the strip's addressing again (A/B builds)
+#endif
 template <uint32_t SLOTS, uint32_t NQ, bool GRID = false, bool TILE = false>
 struct WavePoolLayout {
     static constexpr uint32_t kQueues   = NQ + 1 + (GRID ? 1 : 0);            // scatter queues, OP_GEN, and OP_WALK in grid builds

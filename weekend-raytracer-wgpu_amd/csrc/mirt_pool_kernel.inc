@@ -38,6 +38,12 @@ __global__ __launch_bounds__(THREADS, MINW) void MIRT_POOL_KERNEL_NAME(RenderArg
     unsigned short* const L_cell = reinterpret_cast<unsigned short*>(pool + Lay::kOffCell);
     unsigned short* const L_cand = reinterpret_cast<unsigned short*>(pool + Lay::kOffCand);             // GRID: ids [kMaxCand], then the count
     uint32_t* const L_cand_n = reinterpret_cast<uint32_t*>(pool + Lay::kOffCand + 2 * kMaxCand);
+    // PIXREC: the strip's pixel records in the spare fourth word of the slots' third vector (see WavePoolLayout's notes); word k of pixel
+    // p's record lies 144 p + 48 k bytes behind slot 0's (a 24-bit multiply-add: p < 16)
+    constexpr bool PIXREC = MIRT_GEN_PIXEL_RECORDS != 0 && !GRID;
+    static_assert(!PIXREC || SLOTS >= 3 * kStripPixels, "three slots per pixel of a strip");
+    unsigned char* const L_pixw = pool + Lay::kOffState + 44;
+    const auto pix_word = [L_pixw](uint32_t p, uint32_t k) -> uint32_t& { return *reinterpret_cast<uint32_t*>(L_pixw + __umul24(p, 144u) + 48u * k); };
     TexelTile tile{ reinterpret_cast<uint32_t*>(pool + Lay::kOffTile), reinterpret_cast<float*>(pool + Lay::kOffTile + 16), 0u, 0u, 0u, 0u, 0u, 0u };
     TexelTile* const T = TILE ? &tile : nullptr;
 
@@ -71,6 +77,16 @@ __global__ __launch_bounds__(THREADS, MINW) void MIRT_POOL_KERNEL_NAME(RenderArg
         // all slots start in the OP_GEN queue
         for (uint32_t s = lane; s < SLOTS; s += 64) { L_ring[OP_GEN * RING + s] = (unsigned char)s; L_state[s * 3].w = 0u; }
         if (lane < kStripPixels * 3) L_acc[lane] = 0ull;
+        if constexpr (PIXREC) {
+            // what a GEN step needs of its pixel, once per strip instead of once per sample: pixel `lane` of the strip -> (x, y) -- the strip
+            // starts at (base_x, row0) and may wrap into following rows -- as floats, and the pixel's part of the seed (generate_primary)
+            if (lane < strip_pixels) {
+                uint32_t x = base_x + lane, y = row0;
+                if (wide) { if (x >= AP.width) { x -= AP.width; y = row1; } }
+                else { const uint32_t pi = base_pix + lane; const uint32_t ci = pi / AP.width; x = pi - ci * AP.width; y = abs_row(AP, ci); }
+                pix_word(lane, 0) = bits((float)x); pix_word(lane, 1) = bits((float)y); pix_word(lane, 2) = (x + y * AP.width) ^ AP.seed_mix;
+            }
+        }
         if constexpr (TILE) tile.reset(lane);              // the strip's first image fetch places the window
         if constexpr (GRID) {                              // the spheres this strip's camera rays can touch (strip_candidates)
             uint32_t n_cand = kNoCand;
@@ -164,14 +180,22 @@ __global__ __launch_bounds__(THREADS, MINW) void MIRT_POOL_KERNEL_NAME(RenderArg
                 uint32_t sample;
                 if (strip_pixels == want_pixels) { sample = item >> width_log2; pix = item & (want_pixels - 1u); }
                 else { sample = item / strip_pixels; pix = item - sample * strip_pixels; }      // ragged last strip
-                // pixel -> (x, y): the strip starts at (base_x, row0) and may wrap into following rows
-                uint32_t x = base_x + pix, y = row0;
-                if (wide) { if (x >= A.width) { x -= A.width; y = row1; } }
-                else { const uint32_t pi = base_pix + pix; const uint32_t ci = pi / A.width; x = pi - ci * A.width; y = abs_row(A, ci); }
                 // camera constants are (re)read from LDS here, 6 broadcast ds_read_b128 per GEN step, instead of
                 // living in 21 VGPRs across the whole kernel: the kernel then fits 6 waves per SIMD
-                const CamRegs C = HOLD_CAM ? load_camera(S, A, CH) : load_camera(S, A);
-                generate_primary(A, C, x, y, A.sample_begin + sample, rng, ro, rd);
+                if constexpr (PIXREC) {
+                    // the pixel's record, read with the camera rows: the same wait
+                    const float fx = from_bits(pix_word(pix, 0)), fy = from_bits(pix_word(pix, 1));
+                    const uint32_t pixel_key = pix_word(pix, 2);
+                    const CamRegs C = HOLD_CAM ? load_camera(S, A, CH) : load_camera(S, A);
+                    generate_primary(C, fx, fy, pixel_key, A.sample_begin + sample, rng, ro, rd);
+                } else {
+                    // pixel -> (x, y): the strip starts at (base_x, row0) and may wrap into following rows
+                    uint32_t x = base_x + pix, y = row0;
+                    if (wide) { if (x >= A.width) { x -= A.width; y = row1; } }
+                    else { const uint32_t pi = base_pix + pix; const uint32_t ci = pi / A.width; x = pi - ci * A.width; y = abs_row(A, ci); }
+                    const CamRegs C = HOLD_CAM ? load_camera(S, A, CH) : load_camera(S, A);
+                    generate_primary(A, C, x, y, A.sample_begin + sample, rng, ro, rd);
+                }
                 thr = mk(1, 1, 1);
                 bounce = 0;
             } else if (GRID && my_k == OP_WALK) {
@@ -315,7 +339,8 @@ __global__ __launch_bounds__(THREADS, MINW) void MIRT_POOL_KERNEL_NAME(RenderArg
                 const uint32_t packed = (uint32_t)(nb < 0 ? 0 : nb) | (pix << 12) | (bounce << 16) | (miss << 24) | ((nb >= 0 ? 1u : 0u) << 25);
                 L_state[slot * 3 + 0] = make_uint4(bits(hp.x), bits(hp.y), bits(hp.z), packed);
                 L_state[slot * 3 + 1] = make_uint4(bits(rd.x), bits(rd.y), bits(rd.z), rng.state);
-                L_state[slot * 3 + 2] = make_uint4(bits(thr.x), bits(thr.y), bits(thr.z), GRID ? bits(closest) : 0u);
+                if constexpr (PIXREC) *reinterpret_cast<uint3*>(&L_state[slot * 3 + 2]) = make_uint3(bits(thr.x), bits(thr.y), bits(thr.z));   // .w: a word of a pixel record
+                else L_state[slot * 3 + 2] = make_uint4(bits(thr.x), bits(thr.y), bits(thr.z), GRID ? bits(closest) : 0u);
                 if constexpr (GRID) { if (cut) L_cell[slot] = (unsigned short)walk_cell; }
             }
 #define MIRT_PROBE_SITE 3           // experiment builds only: expands to nothing in libmirt.so
