@@ -22,6 +22,7 @@
 // Compiled with -ffp-contract=off: every fused multiply-add in this file is an explicit fma_().
 #include <cstdio>
 #include <mutex>
+#include <type_traits>
 
 #include <hip/hip_ext.h>
 #include "mirt_kernels.h"
@@ -2209,6 +2210,42 @@ struct PoolHbmState {
 #undef MIRT_POOL_HBM_KERNEL_NAME
 #undef MIRT_POOL_HBM_KERNEL_FRAME
 
+// ------------------------------------------------------------------------------------------
+// launch helpers (host side; the launchers of the .inc files below use them too)
+// ------------------------------------------------------------------------------------------
+
+// kernel<<<g, b, a.lds_bytes, stream>>>(a, more...): the launch of every kernel whose first argument is RenderArgs.  `more` by
+// reference: a deduced value parameter drops the typedef of a pointer to 4-byte aligned vectors (trace_u4) and with it the alignment
+template <typename K, typename... More>
+static hipError_t launch_with_lds(K kernel, dim3 g, dim3 b, const RenderArgs& a, LaunchOn stream, const More&... more)
+{
+    if (a.lds_bytes > 48u * 1024u) {        // more than the default dynamic-LDS window: ask for it
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    if (stream.end != nullptr) {                   // the launch's event pair rides on the dispatch
+        hipExtLaunchKernelGGL(kernel, g, b, a.lds_bytes, stream.stream, stream.begin, stream.end, 0u, a, more...);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(kernel, g, b, a.lds_bytes, stream.stream, a, more...);
+    return hipGetLastError();
+}
+
+// The build of a pooled BVH kernel for `slots` path slots per wave: build(std::integral_constant<uint32_t, SLOTS>) for the entry of
+// kBvhPoolSlotChoices that equals `slots`, nullptr for every other number.  The one place that knows the table's length.
+template <uint32_t I> using BvhPoolSlots = std::integral_constant<uint32_t, kBvhPoolSlotChoices[I]>;
+template <typename Build>
+static auto for_bvh_pool_slots(uint32_t slots, Build build) -> decltype(build(BvhPoolSlots<0>{}))
+{
+    static_assert(sizeof(kBvhPoolSlotChoices) / sizeof(kBvhPoolSlotChoices[0]) == 4, "one line below per geometry");
+    if (slots == kBvhPoolSlotChoices[0]) return build(BvhPoolSlots<0>{});
+    if (slots == kBvhPoolSlotChoices[1]) return build(BvhPoolSlots<1>{});
+    if (slots == kBvhPoolSlotChoices[2]) return build(BvhPoolSlots<2>{});
+    if (slots == kBvhPoolSlotChoices[3]) return build(BvhPoolSlots<3>{});
+    return nullptr;
+}
+
 #ifdef MIRT_ISA_PROBES
 #include "mirt_isa_probes.inc"       // tools/isa_mix.py; never part of libmirt.so
 #endif
@@ -2359,23 +2396,6 @@ size_t scene_lds_bytes_grid(uint32_t n_spheres, bool hosek)      // GRID build: 
 {
     (void)n_spheres;
     return sizeof(MirtGpuCamera) + (hosek ? sizeof(MirtSkyState) : 0);
-}
-
-
-template <typename K>
-static hipError_t launch_with_lds(K kernel, dim3 g, dim3 b, const RenderArgs& a, LaunchOn stream)
-{
-    if (a.lds_bytes > 48u * 1024u) {        // more than the default dynamic-LDS window: ask for it
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    if (stream.end != nullptr) {                   // the launch's event pair rides on the dispatch
-        hipExtLaunchKernelGGL(kernel, g, b, a.lds_bytes, stream.stream, stream.begin, stream.end, 0u, a);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(kernel, g, b, a.lds_bytes, stream.stream, a);
-    return hipGetLastError();
 }
 
 #ifndef MIRT_FAST_MATH
@@ -2539,11 +2559,7 @@ static StripKernel hbm_pool_kernel_(bool count, bool hosek, bool frame)
 
 static StripKernel hbm_pool_kernel(uint32_t slots, bool count, bool hosek, bool frame)
 {
-    if (slots == kBvhPoolSlotChoices[0]) return hbm_pool_kernel_<kBvhPoolSlotChoices[0]>(count, hosek, frame);
-    if (slots == kBvhPoolSlotChoices[1]) return hbm_pool_kernel_<kBvhPoolSlotChoices[1]>(count, hosek, frame);
-    if (slots == kBvhPoolSlotChoices[2]) return hbm_pool_kernel_<kBvhPoolSlotChoices[2]>(count, hosek, frame);
-    if (slots == kBvhPoolSlotChoices[3]) return hbm_pool_kernel_<kBvhPoolSlotChoices[3]>(count, hosek, frame);
-    return nullptr;
+    return for_bvh_pool_slots(slots, [=](auto sl) { return hbm_pool_kernel_<decltype(sl)::value>(count, hosek, frame); });
 }
 
 hipError_t launch_pt_pool_hbm(const RenderArgs& a, uint32_t grid_blocks, uint32_t slots, bool count, LaunchOn stream)
