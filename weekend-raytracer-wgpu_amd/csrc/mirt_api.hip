@@ -245,7 +245,7 @@ std::vector<unsigned char> plan_grid(const MirtSphere* sph, uint32_t n, double c
         if (cell_knob > 0.0 || f >= 4.0) break;                                // a forced cell, or the coarsest one: take what it gives
         if (grid.empty()) { if (overflow) continue; break; }                   // too many entries: coarser; a grid would not help: none
         const size_t beside = kx::scene_lds_bytes_grid(n, true) + grid.size();
-        if (beside < lds_per_block && kx::pool_config_grid(lds_per_block - beside).slots >= 152u) break;
+        if (beside < lds_per_block && kx::pool_config_grid(lds_per_block - beside, false).slots >= 152u) break;
     }
     if (factor_out) *factor_out = grid.empty() ? 0.0 : f;
     return grid;
@@ -583,7 +583,7 @@ int mirt_grid_plan(const MirtSphere* spheres, uint32_t n_spheres, uint64_t lds_b
     out->n_entries = gh->n_entries;
     out->n_big = gh->n_big;
     const size_t beside = kx::scene_lds_bytes_grid(n_spheres, true) + grid.size();
-    out->pool_slots = beside < lds ? kx::pool_config_grid(lds - beside).slots : 0u;
+    out->pool_slots = beside < lds ? kx::pool_config_grid(lds - beside, false).slots : 0u;
     return MIRT_OK;
 }
 
@@ -1274,71 +1274,34 @@ static mirt::PlanFacts plan_facts(const MirtContext* c)
     return f;
 }
 
-// The path-traced kernels exist in two builds: the bit-exact one and the opt-in fast-math one (counting launches always run the exact
-// build).  A plan picks its build HERE (kPtBuilds[plan.fast]) and nowhere else.
-struct PtBuild {
-    decltype(&kx::launch_pt_strip)        strip;     decltype(&kx::strip_blocks_per_cu)    strip_per_cu;
-    decltype(&kx::launch_pt_hbm)          hbm;       decltype(&kx::hbm_blocks_per_cu)      hbm_per_cu;
-    decltype(&kx::launch_pt_pool_hbm)     pool_hbm;  decltype(&kx::hbm_pool_blocks_per_cu) pool_hbm_per_cu;
-    decltype(&kx::launch_pt_pool)         pool;
-    const char*                           prefix;
-};
-static const PtBuild kPtBuilds[2] = {
-    { kx::launch_pt_strip, kx::strip_blocks_per_cu, kx::launch_pt_hbm, kx::hbm_blocks_per_cu, kx::launch_pt_pool_hbm, kx::hbm_pool_blocks_per_cu, kx::launch_pt_pool, "" },
-    { kf::launch_pt_strip, kf::strip_blocks_per_cu, kf::launch_pt_hbm, kf::hbm_blocks_per_cu, kf::launch_pt_pool_hbm, kf::hbm_pool_blocks_per_cu, kf::launch_pt_pool, "fast_build::" },
-};
+// The path-traced kernels exist in two builds: the bit-exact one and the opt-in fast-math one (counting launches and parity mode always
+// run the exact build).  A plan picks its build HERE (kRenderKernel[plan.fast]) and nowhere else.
+static mirt::RenderKernel (*const kRenderKernel[2])(const mirt::RenderPlan&) = { kx::render_kernel, kf::render_kernel };
 
-// Blocks of the plan's kernel that are resident per CU at once (registers and LDS decide); 0: the flat and grid pool kernels, whose
-// LDS alone decides (plan_render).
+// threads per block of the plan's launch
+static uint32_t plan_threads(const mirt::RenderPlan& pl)
+{
+    if (pl.kernel == mirt::kKernelPtPool || pl.kernel == mirt::kKernelPtPoolHbm) return pl.pool.threads;
+    return pl.launch_threads ? pl.launch_threads : mirt::kBlockThreads;
+}
+
+// Blocks of the plan's kernel that are resident per CU at once (registers and LDS decide).
 static uint32_t plan_resident_per_cu(const mirt::RenderPlan& pl)
 {
-    const PtBuild& b = kPtBuilds[pl.fast];
-    const uint32_t threads = pl.launch_threads ? pl.launch_threads : mirt::kBlockThreads;
-    switch (pl.kernel) {
-    case mirt::kKernelParity:    return kx::parity_blocks_per_cu(pl.count, pl.by_pixel, pl.lds_bytes);
-    case mirt::kKernelParityHbm: return kx::parity_hbm_blocks_per_cu(pl.count, pl.by_pixel, threads, pl.lds_bytes);
-    case mirt::kKernelPtStrip:   return b.strip_per_cu(pl.hosek, pl.count, pl.use_grid, pl.by_pixel, pl.lds_bytes, pl.stream, pl.frame);
-    case mirt::kKernelPtHbm:     return b.hbm_per_cu(pl.hosek, pl.count, pl.hbm_bvh, pl.by_pixel, threads, pl.lds_bytes, pl.frame);
-    case mirt::kKernelPtPoolHbm: return b.pool_hbm_per_cu(pl.pool.slots, pl.hosek, pl.count, pl.lds_bytes, pl.frame);
-    default:                     return 0u;
-    }
+    if (pl.kernel == mirt::kKernelPtPool) return 0u;       // the flat and grid pool kernels: LDS alone decides (plan_render), the runtime is not asked
+    const mirt::RenderKernel k = kRenderKernel[pl.fast](pl);
+    // no such build (the dispatch will refuse the launch): pooled HBM has always answered "no answer", the other families one block
+    if (!k) return pl.kernel == mirt::kKernelPtPoolHbm ? 0u : 1u;
+    // The parity and strip kernels are asked about kBlockThreads even where the launch runs launch_threads; the HBM kernels about the
+    // launch's threads.  Either number decides block counts on the device, so both stay as they were measured.
+    const bool block_threads = pl.kernel == mirt::kKernelParity || pl.kernel == mirt::kKernelPtStrip;
+    return kx::blocks_per_cu(k, block_threads ? mirt::kBlockThreads : plan_threads(pl), pl.lds_bytes);
 }
 
 static hipError_t dispatch_plan(const mirt::RenderPlan& pl, const mirt::RenderArgs& a, mirt::LaunchOn on)
 {
-    const PtBuild& b = kPtBuilds[pl.fast];
-    switch (pl.kernel) {
-    case mirt::kKernelParity:    return kx::launch_parity(a, pl.blocks, pl.count, pl.by_pixel, on);
-    case mirt::kKernelParityHbm: return kx::launch_parity_hbm(a, pl.blocks, pl.count, pl.by_pixel, on);
-    case mirt::kKernelPtStrip:   return b.strip(a, pl.blocks, pl.count, pl.use_grid, pl.by_pixel, on);
-    case mirt::kKernelPtHbm:     return b.hbm(a, pl.blocks, pl.count, pl.hbm_bvh, pl.by_pixel, on);
-    case mirt::kKernelPtPoolHbm: return b.pool_hbm(a, pl.blocks, pl.pool.slots, pl.count, on);
-    default:                     return b.pool(a, pl.blocks, pl.pool_cfg, pl.count, pl.pool_nq, on);
-    }
-}
-
-// the name mirt_ctx_last_kernel reports: the kernel template and its arguments, as the tests and tools read them
-static void plan_kernel_name(const mirt::RenderPlan& pl, const mirt::RenderArgs& a, char* out, size_t n)
-{
-    const char* const tf[2] = { "false", "true" };
-    const char* const fast = kPtBuilds[pl.fast].prefix, *const kframe = pl.frame ? "_frame" : "";
-    const char* const count = tf[pl.count], *const hosek = tf[pl.hosek], *const by_pixel = tf[pl.by_pixel];
-    char kname[112] = "";
-    switch (pl.kernel) {
-    case mirt::kKernelParity:    snprintf(out, n, "render_parity_kernel<%s,%s>", count, by_pixel); break;
-    case mirt::kKernelParityHbm: snprintf(out, n, "render_parity_hbm_kernel<%s,%s>", count, by_pixel); break;
-    case mirt::kKernelPtStrip:
-        if (pl.stream) snprintf(out, n, "%srender_pt_stream%s_kernel<%s>", fast, kframe, hosek);
-        else snprintf(out, n, "%srender_pt_strip%s_kernel<%s,%s,%s,%s>", fast, kframe, count, hosek, tf[pl.use_grid], by_pixel);
-        break;
-    case mirt::kKernelPtHbm:     snprintf(out, n, "%srender_pt_hbm%s_kernel<%s,%s,%s,%s>", fast, kframe, count, hosek, tf[pl.hbm_bvh], by_pixel); break;
-    case mirt::kKernelPtPoolHbm:
-        snprintf(out, n, "%srender_pt_pool_hbm%s_kernel<%u,%u,%u,%s,%s>", fast, kframe, pl.pool.threads, pl.pool.slots, pl.count ? 1u : mirt::kBvhPoolMinWaves, count, hosek);
-        break;
-    default:
-        kx::pool_kernel_name(a, pl.pool_cfg, pl.count, pl.pool_nq, kname, sizeof kname);
-        snprintf(out, n, "%s%s", fast, kname);
-    }
+    const mirt::RenderKernel k = kRenderKernel[pl.fast](pl);
+    return k ? kx::launch_with_lds(k, pl.blocks, plan_threads(pl), a, on) : hipErrorInvalidValue;
 }
 
 // The ring's next slot.  When the ring enters a batch of 16 slots, the batch HALF A RING AHEAD is retired (retire_slots): its launches
@@ -1418,7 +1381,7 @@ static int launch_render(MirtContext* c, const MirtParams* p, uint32_t* d_out, h
     if (timed && !ext_events) HIP_TRY(hipEventRecord(c->ev_begin[ev], stream));
     const mirt::LaunchOn on = ext_events ? mirt::LaunchOn(stream, timed ? c->ev_begin[ev] : nullptr, c->ev_end[ev]) : mirt::LaunchOn(stream);
     HIP_TRY(dispatch_plan(pl, a, on));
-    plan_kernel_name(pl, a, c->last_kernel, sizeof c->last_kernel);
+    mirt::plan_kernel_name(pl, c->last_kernel, sizeof c->last_kernel);
     // The kernel is enqueued: from here on the slot is in use, whatever happens below (a failure after this point must not hand the
     // slot -- its dispenser words no longer zero -- to the next launch: poison_slot).
     c->ev_next = (ev + 1) % c->ev_begin.size();

@@ -237,37 +237,25 @@ struct LaunchOn {
 
 // launchers (mirt_kernels.hip).  That file is compiled twice: namespace exact_build (the default, bit-exact arithmetic;
 // everything below) and namespace fast_build (mirt_kernels_fast.hip: MIRT_FLAG_FAST_MATH, hardware transcendentals;
-// path-traced launchers and the host helpers only).
+// the path-traced render kernels only).
+// render_kernel: the one template instance a launch plan names -- of all six PlanKernel families, from the plan's bits alone --, or nullptr
+// where the build has none (parity mode and every counting launch in fast_build).  mirt_ctx_last_kernel reports the same instance
+// (plan_kernel_name, mirt_launch_plan.h).
+using RenderKernel = void (*)(RenderArgs);
 namespace fast_build {
-hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream);
-uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream, bool frame = false);
-hipError_t launch_pt_pool(const RenderArgs& a, uint32_t grid_blocks, uint32_t cfg, bool count, uint32_t nq, LaunchOn stream);
-hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
-uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame = false);
-hipError_t launch_pt_pool_hbm(const RenderArgs& a, uint32_t grid_blocks, uint32_t slots, bool count, LaunchOn stream);
-uint32_t   hbm_pool_blocks_per_cu(uint32_t slots, bool hosek, bool count, uint32_t lds_bytes, bool frame = false);
+RenderKernel render_kernel(const RenderPlan& plan);
 }
 namespace exact_build {
-// MIRT_SCENE_HBM scenes: the strip kernel with the scene in device memory -- a flat scan (bvh = false) or the BVH traversal -- and
-// the parity kernel's flat scan reading the spheres from device memory
-hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream);
-uint32_t   hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame = false);
-// ... and the pooled build of `slots` path slots per wave (kBvhPoolSlotChoices); blocks per CU 0: no such build
-hipError_t launch_pt_pool_hbm(const RenderArgs& a, uint32_t grid_blocks, uint32_t slots, bool count, LaunchOn stream);
-uint32_t   hbm_pool_blocks_per_cu(uint32_t slots, bool hosek, bool count, uint32_t lds_bytes, bool frame = false);
-hipError_t launch_parity_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);
-uint32_t   parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, uint32_t lds_bytes);
-hipError_t launch_parity(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream);
-hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream);
-// blocks of the kernel such a launch runs that are resident per CU at once (hipOccupancyMaxActiveBlocksPerMultiprocessor)
-uint32_t   strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream, bool frame = false);
-uint32_t   parity_blocks_per_cu(bool count, bool by_pixel, uint32_t lds_bytes);
+RenderKernel render_kernel(const RenderPlan& plan);
+// kernel<<<blocks, threads, a.lds_bytes, on>>>(a), for the kernels of either build
+hipError_t launch_with_lds(RenderKernel kernel, uint32_t blocks, uint32_t threads, const RenderArgs& a, LaunchOn on);
+// blocks of `kernel` that are resident per CU at once (hipOccupancyMaxActiveBlocksPerMultiprocessor), asked once per kernel and LDS size
+uint32_t   blocks_per_cu(RenderKernel kernel, uint32_t threads, uint32_t lds_bytes);
 uint32_t   pool_config_count();
-PoolConfig pool_config(uint32_t i, uint32_t nq);
-PoolConfig pool_config_grid(size_t lds_for_pools);   // grid build: slots by the LDS left beside scene + grid (slots = 0: none fits)
-hipError_t launch_pt_pool(const RenderArgs& a, uint32_t grid_blocks, uint32_t cfg, bool count, uint32_t nq, LaunchOn stream);
-// template arguments of the pool kernel launch_pt_pool would start: <threads, slots, min waves, COUNT, HOSEK, NQ, GRID, FLATY>
-void       pool_kernel_name(const RenderArgs& a, uint32_t cfg, bool count, uint32_t nq, char* out, size_t out_len);
+// the geometry of the pool build that runs: flat geometry i for a scene of nq shading queues ...
+PoolConfig pool_config(uint32_t i, uint32_t nq, bool count);
+// ... and the grid build's: slots by the LDS left beside scene + grid (slots = 0: none fits)
+PoolConfig pool_config_grid(size_t lds_for_pools, bool count);
 uint32_t pool_scatter_queues(uint32_t n_routines, bool count);
 hipError_t launch_resolve(const unsigned long long* accum, uint32_t* out, uint64_t n_pixels, uint32_t n_samples,
                           uint32_t flags, hipStream_t stream);

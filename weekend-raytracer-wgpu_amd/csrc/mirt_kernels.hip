@@ -2398,69 +2398,276 @@ size_t scene_lds_bytes_grid(uint32_t n_spheres, bool hosek)      // GRID build: 
     return sizeof(MirtGpuCamera) + (hosek ? sizeof(MirtSkyState) : 0);
 }
 
-#ifndef MIRT_FAST_MATH
-using ParityKernel = void (*)(RenderArgs);
-static ParityKernel parity_kernel(bool count, bool by_pixel)
+// pool geometries {threads per block, slots per wave, waves per SIMD the build is held to (launch bounds), whether the 1-, 2- and
+// 4-queue builds exist}; [0] is the default.  The kernel is held to 80 VGPRs
+// (6 waves per SIMD = 24 per CU); 112 slots x 48 B + rings + accumulators = 6.4 KB per wave keeps all 24
+// resident in a CU's 160 KB of LDS.  Measured on config 3 (DESIGN.md 4.2): 128 slots (5 waves/SIMD)
+// +2.5 % time; 64 slots -> 68 % lane use, 1.4x; 256 slots -> 8 waves per CU, 1.7x; 88 slots at 7
+// waves per SIMD (72 VGPRs, spills) +10 %.  [1]-[3] carry no register bound (min waves 1); [4] is held to 7 waves per SIMD: <= 72 VGPRs.
+// [kTilePoolConfig] is the tile build: the default geometry + a texel window per wave in the spare LDS of its 6 blocks per CU.
+// Builds by scatter queues: 3 and 5 for every geometry; 1, 2 and 4 as well for the default and the tile geometry -- a scene with fewer
+// shading routines than queues would carry empty queues through every pick and push (two routines, config 4: -1.2 %)
+struct PoolGeometry { uint32_t threads, slots, min_waves; bool few_queues; };
+static constexpr PoolGeometry kPoolConfigs[] = { { 256, 112, 6, true }, { 256, 128, 1, false }, { 256, 64, 1, false }, { 256, 256, 1, false },
+                                                 { 256, 96, 7, false }, { 256, kTilePoolSlots, 6, true } };
+
+uint32_t pool_config_count() { return (uint32_t)(sizeof(kPoolConfigs) / sizeof(kPoolConfigs[0])); }
+
+template <uint32_t NQ>
+static uint32_t pool_bytes_per_wave(uint32_t slots)
 {
-    if (by_pixel) return count ? render_parity_kernel<true, true> : render_parity_kernel<false, true>;
-    return count ? render_parity_kernel<true, false> : render_parity_kernel<false, false>;
+    return (slots == 64) ? WavePoolLayout<64, NQ>::kBytes : (slots == 96) ? WavePoolLayout<96, NQ>::kBytes
+         : (slots == 112) ? WavePoolLayout<112, NQ>::kBytes : (slots == 128) ? WavePoolLayout<128, NQ>::kBytes : WavePoolLayout<256, NQ>::kBytes;
 }
 
-hipError_t launch_parity(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream)
+// nq = scatter queues the scene needs (pool_scatter_queues).  The geometry of the build that runs: a counting build has five queues
+// and no register bound; the others the scene's queues where the table has such a build, else 3 or 5.  The LDS layout is that build's.
+PoolConfig pool_config(uint32_t i, uint32_t nq, bool count)
 {
-    return launch_with_lds(parity_kernel(count, by_pixel), dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
+    if (i >= pool_config_count()) i = 0;
+    const PoolGeometry& g = kPoolConfigs[i];
+    const uint32_t q = count ? 5u : (g.few_queues && nq >= 1 && nq <= 4) ? nq : (nq <= 3 ? 3u : 5u);
+    uint32_t per_wave = q == 1 ? pool_bytes_per_wave<1>(g.slots) : q == 2 ? pool_bytes_per_wave<2>(g.slots)
+                      : q == 3 ? pool_bytes_per_wave<3>(g.slots) : q == 4 ? pool_bytes_per_wave<4>(g.slots) : pool_bytes_per_wave<5>(g.slots);
+    if (i == kTilePoolConfig)
+        per_wave = q == 1 ? WavePoolLayout<kTilePoolSlots, 1, false, true>::kBytes : q == 2 ? WavePoolLayout<kTilePoolSlots, 2, false, true>::kBytes
+                 : q == 3 ? WavePoolLayout<kTilePoolSlots, 3, false, true>::kBytes : q == 4 ? WavePoolLayout<kTilePoolSlots, 4, false, true>::kBytes
+                 : WavePoolLayout<kTilePoolSlots, 5, false, true>::kBytes;
+    return PoolConfig{ g.threads, g.slots, per_wave * (g.threads / 64), count ? 1u : g.min_waves, q };
 }
 
+// the grid build's geometry: 1024 threads, one scatter queue (per-lane material switch), one more queue (OP_WALK) and a cell word per slot
+PoolConfig pool_config_grid(size_t lds_for_pools, bool count)
+{
+    const uint32_t waves = kGridPoolThreads / 64;
+    const uint32_t bytes[4] = { WavePoolLayout<kGridPoolSlotChoices[0], 1, true>::kBytes * waves, WavePoolLayout<kGridPoolSlotChoices[1], 1, true>::kBytes * waves,
+                                WavePoolLayout<kGridPoolSlotChoices[2], 1, true>::kBytes * waves, WavePoolLayout<kGridPoolSlotChoices[3], 1, true>::kBytes * waves };
+    for (int i = 0; i < 4; ++i)
+        if (bytes[i] <= lds_for_pools) return PoolConfig{ kGridPoolThreads, kGridPoolSlotChoices[i], bytes[i], count ? 1u : kGridPoolMinWaves, 1u };
+    return PoolConfig{ kGridPoolThreads, 0, 0, 0, 0 };
+}
+
+// scatter queues a scene needs: one per shading routine (builds exist for 1 ... 5); the counting build always has 5
+uint32_t pool_scatter_queues(uint32_t n_routines, bool count)
+{
+    if (count || n_routines > 4) return 5u;
+    return n_routines < 1 ? 1u : n_routines;
+}
+
+// ---- the kernel of a render launch ----
+// render_kernel(plan) is the template instance a launch plan names (mirt_launch_plan.h), nullptr where this build of the file has no
+// such instance.  Every bit comes from the plan, none from the kernel arguments, and plan_kernel_name (mirt_launch_plan.hip) prints the
+// same bits.  What the functions below can return is exactly what the library carries: the set is sparse on purpose, and each gap is
+// noted where it lies.  They are written in the order, outermost choice first and `true` first, in which the builds stand in the code object.
+
+// run-time bools as compile-time ones: build(std::true_type / std::false_type ...), the first bool outermost
+template <typename Build>
+static RenderKernel with_bools(Build build) { return build(); }
+template <typename Build, typename... Rest>
+static RenderKernel with_bools(Build build, bool b, Rest... rest)
+{
+    return b ? with_bools([=](auto... more) { return build(std::true_type{}, more...); }, rest...)
+             : with_bools([=](auto... more) { return build(std::false_type{}, more...); }, rest...);
+}
+
+// a family's render build, or its progressive-frame build (mirt_ctx_accum_frame_device: the *_frame_kernel of the same arguments)
+template <bool FRAME, auto... A> static RenderKernel strip_build() { if constexpr (FRAME) return render_pt_strip_frame_kernel<A...>; else return render_pt_strip_kernel<A...>; }
+template <bool FRAME, auto... A> static RenderKernel stream_build() { if constexpr (FRAME) return render_pt_stream_frame_kernel<A...>; else return render_pt_stream_kernel<A...>; }
+template <bool FRAME, auto... A> static RenderKernel hbm_build() { if constexpr (FRAME) return render_pt_hbm_frame_kernel<A...>; else return render_pt_hbm_kernel<A...>; }
+template <bool FRAME, auto... A> static RenderKernel pool_hbm_build() { if constexpr (FRAME) return render_pt_pool_hbm_frame_kernel<A...>; else return render_pt_pool_hbm_kernel<A...>; }
+template <bool FRAME, bool TILE, auto... A> static RenderKernel pool_build()
+{
+    if constexpr (TILE) { if constexpr (FRAME) return render_pt_pool_tile_frame_kernel<A...>; else return render_pt_pool_tile_kernel<A...>; }
+    else { if constexpr (FRAME) return render_pt_pool_frame_kernel<A...>; else return render_pt_pool_kernel<A...>; }
+}
+
+#ifndef MIRT_FAST_MATH       // parity mode exists in the exact build only: every combination
+static RenderKernel parity_kernel(const RenderPlan& p)
+{
+    return with_bools([](auto B, auto C) -> RenderKernel { return render_parity_kernel<C.value, B.value>; }, p.by_pixel, p.count);
+}
 #endif
 
-using StripKernel = void (*)(RenderArgs);
-
-// a progressive frame (mirt_ctx_accum_frame_device): the launch both adds to the sums and writes the image -> the *_frame_kernel builds
-static bool is_frame(const RenderArgs& a) { return a.accum != nullptr && a.out != nullptr; }
-
-// the build of the strip kernel a launch runs (nullptr: no such build -- counting launches of the fast-math library); frame = the
-// progressive-frame build of the same schedule.  One text for both families:
+// The strip kernel, <COUNT, HOSEK, GRID, BY_PIXEL>.  The streaming builds exist for lane = pixel without counters or grid only; the
+// bit is plan.stream, which is stream_samples != 0 in every plan plan_render makes (checked over the recorded plans).
+template <bool FRAME>
+static RenderKernel strip_kernel_(const RenderPlan& p)
+{
+    if (p.stream && p.by_pixel && !p.count && !p.use_grid) return with_bools([](auto H) { return stream_build<FRAME, H.value>(); }, p.hosek);
+    if (p.count) {
 #ifdef MIRT_FAST_MATH
-#define MIRT_STRIP_COUNT_TREE(K) if (count) return nullptr;                  /* the counting builds exist in the exact build only */
+        return nullptr;                           // the fast library has no counting builds
 #else
-#define MIRT_STRIP_COUNT_TREE(K)                                                                                                   \
-    if (count && use_grid) return hosek ? K<true, true, true> : K<true, false, true>;                                             \
-    if (count && by_pixel) return hosek ? K<true, true, false, true> : K<true, false, false, true>;                               \
-    if (count) return hosek ? K<true, true, false> : K<true, false, false>;
+        // a counting grid build ignores by_pixel: it exists as lane = sample only
+        return with_bools([](auto G, auto B, auto H) -> RenderKernel {
+            if constexpr (G.value && B.value) return nullptr; else return strip_build<FRAME, true, H.value, G.value, B.value>();
+        }, p.use_grid, p.by_pixel && !p.use_grid, p.hosek);
 #endif
-#define MIRT_STRIP_TREE(K, KSTREAM)                                                                                                \
-    if (stream && by_pixel && !count && !use_grid) return hosek ? KSTREAM<true> : KSTREAM<false>;                                  \
-    MIRT_STRIP_COUNT_TREE(K)                                                                                                       \
-    if (by_pixel) {                                                                                                                \
-        if (use_grid) return hosek ? K<false, true, true, true> : K<false, false, true, true>;                                     \
-        return hosek ? K<false, true, false, true> : K<false, false, false, true>;                                                 \
-    }                                                                                                                              \
-    if (use_grid) return hosek ? K<false, true, true> : K<false, false, true>;                                                     \
-    return hosek ? K<false, true, false> : K<false, false, false>;
+    }
+    return with_bools([](auto B, auto G, auto H) { return strip_build<FRAME, false, H.value, G.value, B.value>(); }, p.by_pixel, p.use_grid, p.hosek);
+}
+static RenderKernel strip_kernel(const RenderPlan& p) { return p.frame ? strip_kernel_<true>(p) : strip_kernel_<false>(p); }
 
-static StripKernel strip_kernel(bool count, bool hosek, bool use_grid, bool by_pixel, bool stream = false, bool frame = false)
+// MIRT_SCENE_HBM scenes: the strip kernel with the scene in device memory, <COUNT, HOSEK, BVH, BY_PIXEL>
+template <bool FRAME>
+static RenderKernel hbm_kernel_(const RenderPlan& p)
 {
-    if (frame) { MIRT_STRIP_TREE(render_pt_strip_frame_kernel, render_pt_stream_frame_kernel) }
-    MIRT_STRIP_TREE(render_pt_strip_kernel, render_pt_stream_kernel)
+    if (p.count) {
+#ifdef MIRT_FAST_MATH
+        return nullptr;                           // the fast library has no counting builds
+#else
+        return with_bools([](auto V, auto B, auto H) { return hbm_build<FRAME, true, H.value, V.value, B.value>(); }, p.hbm_bvh, p.by_pixel, p.hosek);
+#endif
+    }
+    // the non-counting BVH build is lane = pixel only, whatever the plan's by_pixel says
+    return with_bools([](auto V, auto B, auto H) -> RenderKernel {
+        if constexpr (V.value && !B.value) return nullptr; else return hbm_build<FRAME, false, H.value, V.value, B.value>();
+    }, p.hbm_bvh, p.by_pixel || p.hbm_bvh, p.hosek);
+}
+static RenderKernel hbm_kernel(const RenderPlan& p) { return p.frame ? hbm_kernel_<true>(p) : hbm_kernel_<false>(p); }
+
+#ifndef MIRT_FAST_MATH
+static RenderKernel parity_hbm_kernel(const RenderPlan& p)
+{
+    return with_bools([](auto B, auto C) -> RenderKernel { return render_parity_hbm_kernel<C.value, B.value>; }, p.by_pixel, p.count);
+}
+#endif
+
+// MIRT_SCENE_HBM scenes, pooled (MIRT_FLAG_KERNEL_POOL): one build per geometry of kBvhPoolSlotChoices, <threads, slots, min waves, COUNT, HOSEK>;
+// the counting builds carry no register bound (min waves 1)
+static RenderKernel pool_hbm_kernel(const RenderPlan& p)
+{
+    return for_bvh_pool_slots(p.pool.slots, [&](auto sl) -> RenderKernel {
+        constexpr uint32_t T = kBvhPoolThreads, SL = decltype(sl)::value;
+        if (p.count) {
+#ifdef MIRT_FAST_MATH
+            return nullptr;                       // the fast library has no counting builds
+#else
+            return with_bools([](auto F, auto H) { return pool_hbm_build<F.value, T, SL, 1, true, H.value>(); }, p.frame, p.hosek);
+#endif
+        }
+        return with_bools([](auto F, auto H) { return pool_hbm_build<F.value, T, SL, kBvhPoolMinWaves, false, H.value>(); }, p.frame, p.hosek);
+    });
 }
 
-hipError_t launch_pt_strip(const RenderArgs& a, uint32_t grid_blocks, bool count, bool use_grid, bool by_pixel, LaunchOn stream)
+// The pool kernel, <threads, slots, min waves, COUNT, HOSEK, NQ, GRID, FLATY>.  Its grid build (many-sphere scenes) has ONE scatter queue
+// (per-lane material switch) and one geometry per entry of kGridPoolSlotChoices, the first N of which -- largest first -- have the build
+// asked for.  LDS (scene + grid + pools) bounds it to a few blocks per CU, so the register budget is not the limit.
+template <uint32_t I> using GridPoolSlots = std::integral_constant<uint32_t, kGridPoolSlotChoices[I]>;
+template <uint32_t N, typename Build>
+static RenderKernel for_grid_pool_slots(uint32_t slots, Build build)
 {
-    const StripKernel k = strip_kernel(count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, use_grid, by_pixel, a.stream_samples != 0u, is_frame(a));
-    if (!k) return hipErrorInvalidValue;
-    return launch_with_lds(k, dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
+    static_assert(sizeof(kGridPoolSlotChoices) / sizeof(kGridPoolSlotChoices[0]) == 4 && N <= 4, "one line below per geometry");
+    if constexpr (N > 0) if (slots == kGridPoolSlotChoices[0]) return build(GridPoolSlots<0>{});
+    if constexpr (N > 1) if (slots == kGridPoolSlotChoices[1]) return build(GridPoolSlots<1>{});
+    if constexpr (N > 2) if (slots == kGridPoolSlotChoices[2]) return build(GridPoolSlots<2>{});
+    if constexpr (N > 3) if (slots == kGridPoolSlotChoices[3]) return build(GridPoolSlots<3>{});
+    return nullptr;
+}
+
+static RenderKernel grid_pool_kernel(const RenderPlan& p)
+{
+    return with_bools([&](auto Y) -> RenderKernel {                   // FLATY: the grid is one cell high (plan.grid_flat_y)
+        constexpr uint32_t T = kGridPoolThreads;
+        constexpr bool FLATY = decltype(Y)::value;
+        if (p.count) {
+#ifdef MIRT_FAST_MATH
+            return nullptr;                       // the fast library has no counting builds
+#else
+            // counting builds exist for the two largest geometries only, without a register bound
+            return for_grid_pool_slots<2>(p.grid_pool_slots, [&](auto sl) {
+                return with_bools([](auto H, auto F) { return pool_build<F.value, false, T, decltype(sl)::value, 1, true, H.value, 1, true, FLATY>(); }, p.hosek, p.frame);
+            });
+#endif
+        }
+        return for_grid_pool_slots<4>(p.grid_pool_slots, [&](auto sl) {
+            return with_bools([](auto H, auto F) { return pool_build<F.value, false, T, decltype(sl)::value, kGridPoolMinWaves, false, H.value, 1, true, FLATY>(); }, p.hosek, p.frame);
+        });
+    }, p.grid_flat_y != 0u);
+}
+
+// ... and its flat builds: geometry I of kPoolConfigs (the tile build: render_pt_pool_tile_kernel), by the queues of plan.pool
+template <uint32_t I> using PoolConfigIndex = std::integral_constant<uint32_t, I>;
+template <typename Build>
+static RenderKernel for_pool_config(uint32_t cfg, Build build)
+{
+    static_assert(sizeof(kPoolConfigs) / sizeof(kPoolConfigs[0]) == 6, "one line below per geometry");
+    switch (cfg) {
+    case 1:  return build(PoolConfigIndex<1>{});
+    case 2:  return build(PoolConfigIndex<2>{});
+    case 3:  return build(PoolConfigIndex<3>{});
+    case 4:  return build(PoolConfigIndex<4>{});
+    case 5:  return build(PoolConfigIndex<5>{});
+    default: return build(PoolConfigIndex<0>{});      // as pool_config: an index beyond the table is the default geometry
+    }
+}
+
+template <bool FEW, typename Build>
+static RenderKernel for_pool_queues(uint32_t queues, Build build)
+{
+    if constexpr (FEW) {
+        if (queues == 1) return build(std::integral_constant<uint32_t, 1>{});
+        if (queues == 2) return build(std::integral_constant<uint32_t, 2>{});
+        if (queues == 4) return build(std::integral_constant<uint32_t, 4>{});
+    }
+    if (queues == 3) return build(std::integral_constant<uint32_t, 3>{});
+    if (queues == 5) return build(std::integral_constant<uint32_t, 5>{});
+    return nullptr;
+}
+
+template <uint32_t I>
+static RenderKernel flat_pool_kernel(const RenderPlan& p)
+{
+    constexpr uint32_t T = kPoolConfigs[I].threads, SL = kPoolConfigs[I].slots, MW = kPoolConfigs[I].min_waves;
+    constexpr bool FEW = kPoolConfigs[I].few_queues, TILE = I == kTilePoolConfig;
+    if (p.pool.threads != T || p.pool.slots != SL || p.pool.min_waves != (p.count ? 1u : MW)) return nullptr;   // not the geometry of the plan's cfg
+    if (p.count) {
+#ifdef MIRT_FAST_MATH
+        return nullptr;                           // the fast library has no counting builds
+#else
+        // counting builds exist without a register bound and with five queues only
+        if (p.pool.queues != 5u) return nullptr;
+        return with_bools([](auto H, auto F) { return pool_build<F.value, TILE, T, SL, 1, true, H.value>(); }, p.hosek, p.frame);
+#endif
+    }
+    return for_pool_queues<FEW>(p.pool.queues, [&](auto nq) {
+        return with_bools([](auto H, auto F) { return pool_build<F.value, TILE, T, SL, MW, false, H.value, decltype(nq)::value>(); }, p.hosek, p.frame);
+    });
+}
+
+RenderKernel render_kernel(const RenderPlan& p)
+{
+    switch (p.kernel) {
+#ifndef MIRT_FAST_MATH
+    case kKernelParity:    return parity_kernel(p);
+    case kKernelParityHbm: return parity_hbm_kernel(p);
+#endif
+    case kKernelPtStrip:   return strip_kernel(p);
+    case kKernelPtHbm:     return hbm_kernel(p);
+    case kKernelPtPoolHbm: return pool_hbm_kernel(p);
+    case kKernelPtPool:    return p.use_grid ? grid_pool_kernel(p) : for_pool_config(p.pool_cfg, [&](auto i) { return flat_pool_kernel<decltype(i)::value>(p); });
+    default:               return nullptr;
+    }
+}
+
+#ifndef MIRT_FAST_MATH
+// the launch of a render kernel of either build: kernel<<<blocks, threads, a.lds_bytes, on>>>(a)
+hipError_t launch_with_lds(RenderKernel kernel, uint32_t blocks, uint32_t threads, const RenderArgs& a, LaunchOn on)
+{
+    return launch_with_lds<RenderKernel>(kernel, dim3(blocks), dim3(threads), a, on);
 }
 
 // Blocks of a kernel that are resident per CU at once (registers and LDS decide: the strip kernels use 59-106 VGPRs).  The
 // host sizes the persistent grids with it: a block that is launched but not resident holds its first work unit until some
 // other block exits, i.e. until the dispenser has run dry, and then runs that unit alone at the end of the launch.
-static uint32_t blocks_per_cu(const void* kernel, uint32_t threads, uint32_t lds_bytes)
+uint32_t blocks_per_cu(RenderKernel render_kernel, uint32_t threads, uint32_t lds_bytes)
 {
     // asked once per (kernel, LDS size): the interactive loop launches every frame
     struct Entry { const void* kernel; uint32_t lds, blocks; };
     static Entry cache[64];
     static uint32_t used = 0;
     static std::mutex lock;
+    const void* const kernel = reinterpret_cast<const void*>(render_kernel);
     std::lock_guard<std::mutex> guard(lock);
     for (uint32_t i = 0; i < used; ++i)
         if (cache[i].kernel == kernel && cache[i].lds == lds_bytes) return cache[i].blocks;
@@ -2474,306 +2681,6 @@ static uint32_t blocks_per_cu(const void* kernel, uint32_t threads, uint32_t lds
     return blocks;
 }
 
-uint32_t strip_blocks_per_cu(bool hosek, bool count, bool use_grid, bool by_pixel, uint32_t lds_bytes, bool stream, bool frame)
-{
-    const StripKernel k = strip_kernel(count, hosek, use_grid, by_pixel, stream, frame);
-    return k ? blocks_per_cu(reinterpret_cast<const void*>(k), kBlockThreads, lds_bytes) : 1u;
-}
-
-#ifndef MIRT_FAST_MATH
-uint32_t parity_blocks_per_cu(bool count, bool by_pixel, uint32_t lds_bytes)
-{
-    return blocks_per_cu(reinterpret_cast<const void*>(parity_kernel(count, by_pixel)), kBlockThreads, lds_bytes);
-}
-#endif
-
-// ---- MIRT_SCENE_HBM scenes ----
-#ifdef MIRT_FAST_MATH
-#define MIRT_HBM_COUNT_TREE(K) if (count) return nullptr;                    /* the counting builds exist in the exact build only */
-#else
-#define MIRT_HBM_COUNT_TREE(K)                                                                                                     \
-    if (count) {                                                                                                                   \
-        if (bvh) return by_pixel ? (hosek ? K<true, true, true, true> : K<true, false, true, true>)                                \
-                                 : (hosek ? K<true, true, true, false> : K<true, false, true, false>);                             \
-        return by_pixel ? (hosek ? K<true, true, false, true> : K<true, false, false, true>)                                       \
-                        : (hosek ? K<true, true, false, false> : K<true, false, false, false>);                                    \
-    }
-#endif
-#define MIRT_HBM_TREE(K)                                                                                                           \
-    MIRT_HBM_COUNT_TREE(K)                                                                                                         \
-    if (bvh) return hosek ? K<false, true, true, true> : K<false, false, true, true>;   /* lane = pixel only */                    \
-    return by_pixel ? (hosek ? K<false, true, false, true> : K<false, false, false, true>)                                         \
-                    : (hosek ? K<false, true, false, false> : K<false, false, false, false>);
-
-static StripKernel hbm_kernel(bool count, bool hosek, bool bvh, bool by_pixel, bool frame = false)
-{
-    if (frame) { MIRT_HBM_TREE(render_pt_hbm_frame_kernel) }
-    MIRT_HBM_TREE(render_pt_hbm_kernel)
-}
-
-hipError_t launch_pt_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool bvh, bool by_pixel, LaunchOn stream)
-{
-    const StripKernel k = hbm_kernel(count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, bvh, by_pixel, is_frame(a));
-    if (!k) return hipErrorInvalidValue;
-    return launch_with_lds(k, dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
-}
-
-uint32_t hbm_blocks_per_cu(bool hosek, bool count, bool bvh, bool by_pixel, uint32_t threads, uint32_t lds_bytes, bool frame)
-{
-    const StripKernel k = hbm_kernel(count, hosek, bvh, by_pixel, frame);
-    return k ? blocks_per_cu(reinterpret_cast<const void*>(k), threads, lds_bytes) : 1u;
-}
-
-#ifndef MIRT_FAST_MATH
-static ParityKernel parity_hbm_kernel(bool count, bool by_pixel)
-{
-    if (by_pixel) return count ? render_parity_hbm_kernel<true, true> : render_parity_hbm_kernel<false, true>;
-    return count ? render_parity_hbm_kernel<true, false> : render_parity_hbm_kernel<false, false>;
-}
-
-hipError_t launch_parity_hbm(const RenderArgs& a, uint32_t grid_blocks, bool count, bool by_pixel, LaunchOn stream)
-{
-    return launch_with_lds(parity_hbm_kernel(count, by_pixel), dim3(grid_blocks), dim3(a.launch_threads ? a.launch_threads : kBlockThreads), a, stream);
-}
-
-uint32_t parity_hbm_blocks_per_cu(bool count, bool by_pixel, uint32_t threads, uint32_t lds_bytes)
-{
-    return blocks_per_cu(reinterpret_cast<const void*>(parity_hbm_kernel(count, by_pixel)), threads, lds_bytes);
-}
-#endif
-
-// ---- MIRT_SCENE_HBM scenes, pooled (MIRT_FLAG_KERNEL_POOL): one build per geometry of kBvhPoolSlotChoices ----
-template <uint32_t SL>
-static StripKernel hbm_pool_kernel_(bool count, bool hosek, bool frame)
-{
-    constexpr uint32_t T = kBvhPoolThreads, MW = kBvhPoolMinWaves;
-#ifdef MIRT_FAST_MATH
-    if (count) return nullptr;                   // the counting builds exist in the exact build only
-#else
-    if (count) return frame ? (hosek ? render_pt_pool_hbm_frame_kernel<T, SL, 1, true, true> : render_pt_pool_hbm_frame_kernel<T, SL, 1, true, false>)
-                            : (hosek ? render_pt_pool_hbm_kernel<T, SL, 1, true, true> : render_pt_pool_hbm_kernel<T, SL, 1, true, false>);
-#endif
-    return frame ? (hosek ? render_pt_pool_hbm_frame_kernel<T, SL, MW, false, true> : render_pt_pool_hbm_frame_kernel<T, SL, MW, false, false>)
-                 : (hosek ? render_pt_pool_hbm_kernel<T, SL, MW, false, true> : render_pt_pool_hbm_kernel<T, SL, MW, false, false>);
-}
-
-static StripKernel hbm_pool_kernel(uint32_t slots, bool count, bool hosek, bool frame)
-{
-    return for_bvh_pool_slots(slots, [=](auto sl) { return hbm_pool_kernel_<decltype(sl)::value>(count, hosek, frame); });
-}
-
-hipError_t launch_pt_pool_hbm(const RenderArgs& a, uint32_t grid_blocks, uint32_t slots, bool count, LaunchOn stream)
-{
-    const StripKernel k = hbm_pool_kernel(slots, count, (a.flags & MIRT_FLAG_SKY_HOSEK) != 0, is_frame(a));
-    if (!k) return hipErrorInvalidValue;
-    return launch_with_lds(k, dim3(grid_blocks), dim3(kBvhPoolThreads), a, stream);
-}
-
-uint32_t hbm_pool_blocks_per_cu(uint32_t slots, bool hosek, bool count, uint32_t lds_bytes, bool frame)
-{
-    const StripKernel k = hbm_pool_kernel(slots, count, hosek, frame);
-    return k ? blocks_per_cu(reinterpret_cast<const void*>(k), kBvhPoolThreads, lds_bytes) : 0u;
-}
-
-// builds of the pool kernel by scatter queues: 3 and 5 for every geometry; 1, 2 and 4 as well (FEW = true) for the default and the
-// tile geometry -- a scene with fewer shading routines than queues would carry empty queues through every pick and push
-// (two routines, config 4: -1.2 %)
-// the pool kernel a launcher below starts: the progressive-frame build of the same geometry when the launch is a frame (`frame`)
-#define MIRT_POOL_K(...)      (frame ? render_pt_pool_frame_kernel<__VA_ARGS__> : render_pt_pool_kernel<__VA_ARGS__>)
-#define MIRT_POOL_TILE_K(...) (frame ? render_pt_pool_tile_frame_kernel<__VA_ARGS__> : render_pt_pool_tile_kernel<__VA_ARGS__>)
-template <uint32_t T, uint32_t SL, uint32_t MW = 1, bool FEW = false>
-static hipError_t launch_pool_cfg(const RenderArgs& a, uint32_t grid_blocks, bool count, bool hosek, uint32_t nq, LaunchOn stream)
-{
-    const dim3 g(grid_blocks), b(T);
-    const bool frame = is_frame(a);
-#ifdef MIRT_FAST_MATH
-    if (count) return hipErrorInvalidValue;
-#else
-    if (count) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, 1, true, true), g, b, a, stream)
-                            : launch_with_lds(MIRT_POOL_K(T, SL, 1, true, false), g, b, a, stream);
-#endif
-    if constexpr (FEW) {
-        if (nq == 1) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 1), g, b, a, stream)
-                                  : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 1), g, b, a, stream);
-        if (nq == 2) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 2), g, b, a, stream)
-                                  : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 2), g, b, a, stream);
-        if (nq == 4) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 4), g, b, a, stream)
-                                  : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 4), g, b, a, stream);
-    }
-    if (nq <= 3) return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true, 3), g, b, a, stream)
-                              : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false, 3), g, b, a, stream);
-    return hosek ? launch_with_lds(MIRT_POOL_K(T, SL, MW, false, true), g, b, a, stream)
-                 : launch_with_lds(MIRT_POOL_K(T, SL, MW, false, false), g, b, a, stream);
-}
-
-// the tile build (MIRT_FLAG_TEXEL_TILES): fewer slots, a texel window per wave
-template <uint32_t T, uint32_t SL, uint32_t MW>
-static hipError_t launch_pool_tile(const RenderArgs& a, uint32_t grid_blocks, bool count, bool hosek, uint32_t nq, LaunchOn stream)
-{
-    const dim3 g(grid_blocks), b(T);
-    const bool frame = is_frame(a);
-#ifdef MIRT_FAST_MATH
-    if (count) return hipErrorInvalidValue;
-#else
-    if (count) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, 1, true, true), g, b, a, stream)
-                            : launch_with_lds(MIRT_POOL_TILE_K(T, SL, 1, true, false), g, b, a, stream);
-#endif
-    if (nq == 1) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 1), g, b, a, stream)
-                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 1), g, b, a, stream);
-    if (nq == 2) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 2), g, b, a, stream)
-                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 2), g, b, a, stream);
-    if (nq == 4) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 4), g, b, a, stream)
-                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 4), g, b, a, stream);
-    if (nq <= 3) return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true, 3), g, b, a, stream)
-                              : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false, 3), g, b, a, stream);
-    return hosek ? launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, true), g, b, a, stream)
-                 : launch_with_lds(MIRT_POOL_TILE_K(T, SL, MW, false, false), g, b, a, stream);
-}
-
-// grid build of the default pool geometry: LDS (scene + grid + pools) bounds it to a few blocks per CU, so the
-// register budget is not the limit
-template <bool FLATY>
-static hipError_t launch_pool_grid_(const RenderArgs& a, uint32_t grid_blocks, bool count, bool hosek, LaunchOn stream)
-{
-    const dim3 g(grid_blocks), b(kGridPoolThreads);
-    const bool frame = is_frame(a);
-    const uint32_t slots = a.grid_pool_slots;
-#ifdef MIRT_FAST_MATH
-    if (count) return hipErrorInvalidValue;
-#else
-    if (count) {                                // counting builds exist for the two largest geometries
-        if (slots == kGridPoolSlotChoices[0])
-            return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], 1, true, true, 1, true, FLATY), g, b, a, stream)
-                         : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], 1, true, false, 1, true, FLATY), g, b, a, stream);
-        if (slots == kGridPoolSlotChoices[1])
-            return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], 1, true, true, 1, true, FLATY), g, b, a, stream)
-                         : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], 1, true, false, 1, true, FLATY), g, b, a, stream);
-        return hipErrorInvalidValue;
-    }
-#endif
-    if (slots == kGridPoolSlotChoices[0])
-        return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
-                     : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[0], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
-    if (slots == kGridPoolSlotChoices[1])
-        return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
-                     : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[1], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
-    if (slots == kGridPoolSlotChoices[2])
-        return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[2], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
-                     : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[2], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
-    return hosek ? launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[3], kGridPoolMinWaves, false, true, 1, true, FLATY), g, b, a, stream)
-                 : launch_with_lds(MIRT_POOL_K(kGridPoolThreads, kGridPoolSlotChoices[3], kGridPoolMinWaves, false, false, 1, true, FLATY), g, b, a, stream);
-}
-
-// grid builds have ONE scatter queue (per-lane material switch); FLATY = the grid is one cell high (RenderArgs.grid_flat_y)
-static hipError_t launch_pool_grid(const RenderArgs& a, uint32_t grid_blocks, bool count, bool hosek, uint32_t nq, LaunchOn stream)
-{
-    (void)nq;
-    return a.grid_flat_y ? launch_pool_grid_<true>(a, grid_blocks, count, hosek, stream) : launch_pool_grid_<false>(a, grid_blocks, count, hosek, stream);
-}
-
-// pool geometries {threads per block, slots per wave}; [0] is the default.  The kernel is held to 80 VGPRs
-// (6 waves per SIMD = 24 per CU); 112 slots x 48 B + rings + accumulators = 6.4 KB per wave keeps all 24
-// resident in a CU's 160 KB of LDS.  Measured on config 3 (DESIGN.md 4.2): 128 slots (5 waves/SIMD)
-// +2.5 % time; 64 slots -> 68 % lane use, 1.4x; 256 slots -> 8 waves per CU, 1.7x; 88 slots at 7
-// waves per SIMD (72 VGPRs, spills) +10 %.
-// [kTilePoolConfig] is the tile build: the default geometry + a texel window per wave in the spare LDS of its 6 blocks per CU.
-static const PoolConfig kPoolConfigs[] = { { 256, 112, 0 }, { 256, 128, 0 }, { 256, 64, 0 }, { 256, 256, 0 }, { 256, 96, 0 }, { 256, kTilePoolSlots, 0 } };
-
-uint32_t pool_config_count() { return (uint32_t)(sizeof(kPoolConfigs) / sizeof(kPoolConfigs[0])); }
-
-template <uint32_t NQ>
-static uint32_t pool_bytes_per_wave(uint32_t slots)
-{
-    return (slots == 64) ? WavePoolLayout<64, NQ>::kBytes : (slots == 96) ? WavePoolLayout<96, NQ>::kBytes
-         : (slots == 112) ? WavePoolLayout<112, NQ>::kBytes : (slots == 128) ? WavePoolLayout<128, NQ>::kBytes : WavePoolLayout<256, NQ>::kBytes;
-}
-
-// the build that runs for a geometry: 1 / 2 queues exist for the default and the tile geometry only
-static uint32_t built_queues(uint32_t cfg, uint32_t nq)
-{
-    const bool few = cfg == kDefaultPoolConfig || cfg == kTilePoolConfig;
-    if (few && nq >= 1 && nq <= 4) return nq;
-    return nq <= 3 ? 3u : 5u;
-}
-
-// nq = scatter queues the scene needs (pool_scatter_queues); the LDS layout is that of the build that runs
-PoolConfig pool_config(uint32_t i, uint32_t nq)
-{
-    if (i >= pool_config_count()) i = 0;
-    PoolConfig c = kPoolConfigs[i];
-    const uint32_t q = built_queues(i, nq);
-    const uint32_t per_wave = q == 1 ? pool_bytes_per_wave<1>(c.slots) : q == 2 ? pool_bytes_per_wave<2>(c.slots)
-                            : q == 3 ? pool_bytes_per_wave<3>(c.slots) : q == 4 ? pool_bytes_per_wave<4>(c.slots) : pool_bytes_per_wave<5>(c.slots);
-    c.lds_bytes = per_wave * (c.threads / 64);
-    if (i == kTilePoolConfig) {
-        const uint32_t tw = q == 1 ? WavePoolLayout<kTilePoolSlots, 1, false, true>::kBytes : q == 2 ? WavePoolLayout<kTilePoolSlots, 2, false, true>::kBytes
-                          : q == 3 ? WavePoolLayout<kTilePoolSlots, 3, false, true>::kBytes : q == 4 ? WavePoolLayout<kTilePoolSlots, 4, false, true>::kBytes
-                          : WavePoolLayout<kTilePoolSlots, 5, false, true>::kBytes;
-        c.lds_bytes = tw * (c.threads / 64);
-    }
-    return c;
-}
-
-// the grid build's geometry: 512 threads, 112 slots, one more queue (OP_WALK) and a cell word per slot
-PoolConfig pool_config_grid(size_t lds_for_pools)
-{
-    const uint32_t waves = kGridPoolThreads / 64;
-    const uint32_t bytes[4] = { WavePoolLayout<kGridPoolSlotChoices[0], 1, true>::kBytes * waves, WavePoolLayout<kGridPoolSlotChoices[1], 1, true>::kBytes * waves,
-                                WavePoolLayout<kGridPoolSlotChoices[2], 1, true>::kBytes * waves, WavePoolLayout<kGridPoolSlotChoices[3], 1, true>::kBytes * waves };
-    for (int i = 0; i < 4; ++i)
-        if (bytes[i] <= lds_for_pools) return PoolConfig{ kGridPoolThreads, kGridPoolSlotChoices[i], bytes[i] };
-    return PoolConfig{ kGridPoolThreads, 0, 0 };
-}
-
-// scatter queues a scene needs: one per shading routine (builds exist for 1 ... 5); the counting build always has 5
-uint32_t pool_scatter_queues(uint32_t n_routines, bool count)
-{
-    if (count || n_routines > 4) return 5u;
-    return n_routines < 1 ? 1u : n_routines;
-}
-
-hipError_t launch_pt_pool(const RenderArgs& a, uint32_t grid_blocks, uint32_t cfg, bool count, uint32_t nq, LaunchOn stream)
-{
-    const bool hosek = (a.flags & MIRT_FLAG_SKY_HOSEK) != 0;
-    if (a.grid) return launch_pool_grid(a, grid_blocks, count, hosek, nq, stream);     // host: default geometry only
-    switch (cfg) {
-    case 1:  return launch_pool_cfg<256, 128>(a, grid_blocks, count, hosek, nq, stream);
-    case 2:  return launch_pool_cfg<256, 64>(a, grid_blocks, count, hosek, nq, stream);
-    case 3:  return launch_pool_cfg<256, 256>(a, grid_blocks, count, hosek, nq, stream);
-    case 4:  return launch_pool_cfg<256, 96, 7>(a, grid_blocks, count, hosek, nq, stream);     // 7 waves per SIMD: <= 72 VGPRs
-    case kTilePoolConfig: return launch_pool_tile<256, kTilePoolSlots, 6>(a, grid_blocks, count, hosek, nq, stream);
-    default: return launch_pool_cfg<256, 112, 6, true>(a, grid_blocks, count, hosek, nq, stream);   // 6 waves per SIMD: <= 80 VGPRs
-    }
-}
-
-// mirrors the dispatch of launch_pt_pool / launch_pool_cfg / launch_pool_grid above
-void pool_kernel_name(const RenderArgs& a, uint32_t cfg, bool count, uint32_t nq, char* out, size_t out_len)
-{
-    const bool hosek = (a.flags & MIRT_FLAG_SKY_HOSEK) != 0;
-    const char* tf[2] = { "false", "true" };
-    const char* frame = is_frame(a) ? "_frame" : "";
-    uint32_t slots = 112, minw = 6, threads = 256;
-    if (a.grid) { threads = kGridPoolThreads; slots = a.grid_pool_slots; minw = count ? 1 : kGridPoolMinWaves; nq = 1; }
-    else {
-        switch (cfg) {
-        case 1: slots = 128; minw = 1; break;
-        case 2: slots = 64; minw = 1; break;
-        case 3: slots = 256; minw = 1; break;
-        case 4: slots = 96; minw = 7; break;
-        case kTilePoolConfig: slots = kTilePoolSlots; break;
-        default: break;
-        }
-        if (count) { minw = 1; nq = 5; } else nq = built_queues(cfg, nq);
-        if (cfg == kTilePoolConfig) {
-            snprintf(out, out_len, "render_pt_pool_tile%s_kernel<%u,%u,%u,%s,%s,%u,false>", frame, threads, slots, minw, tf[count], tf[hosek], nq);
-            return;
-        }
-    }
-    snprintf(out, out_len, "render_pt_pool%s_kernel<%u,%u,%u,%s,%s,%u,%s,%s>", frame, threads, slots, minw, tf[count], tf[hosek], nq, tf[a.grid != nullptr],
-             tf[a.grid != nullptr && a.grid_flat_y != 0u]);
-}
-
-#ifndef MIRT_FAST_MATH
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on)
 {
     const uint32_t blocks = a.band_rows < 4096u ? (a.band_rows ? a.band_rows : 1u) : 4096u;

@@ -1,9 +1,11 @@
 // mirt_launch_plan.h — the launch plan of a render call: which kernel runs, in which geometry and with which schedule, as plain
-// data computed by two pure functions (mirt_launch_plan.hip).  No HIP call, no context, no getenv, no allocation: host arithmetic
-// over a handful of numbers, so that a machine without a GPU can check it (host/plan_check.cpp, tests/test_launch_plan.py).
+// data computed by two pure functions, and a third that prints the kernel's name (mirt_launch_plan.hip).  No HIP call, no context, no
+// getenv, no allocation: host arithmetic over a handful of numbers, so that a machine without a GPU can check it (host/plan_check.cpp,
+// tests/test_launch_plan.py, tests/test_launch_kernels.py).
 // Plain C++ on top of include/mirt.h: g++ compiles it.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/mirt.h"
@@ -36,7 +38,9 @@ constexpr uint32_t kPoolMinSpp           = 32;
 constexpr uint32_t kPoolMinSppOneRoutine = 800;
 constexpr uint32_t kPoolMinSppGrid       = 16;
 
-struct PoolConfig { uint32_t threads, slots, lds_bytes; };
+// The geometry of a pool kernel's build, which is every number among its template arguments: threads per block, path slots per wave, the
+// waves per SIMD it is held to (launch bounds) and its scatter queues (0: pooled HBM, which has no such argument); and the LDS of a block's pools.
+struct PoolConfig { uint32_t threads, slots, lds_bytes, min_waves, queues; };
 
 // Tuning / experiment knobs.  They are read from the environment ONCE, when a context is created
 // (mirt_ctx_create), never inside a render call: a shipped library must not change its schedule
@@ -81,8 +85,9 @@ struct PlanFacts {
     bool     camera_is_pinhole;                   // camera
 };
 
-// The kernel a plan runs.  Together with the bits below it names one template instance; occupancy, dispatch and the name reported by
-// mirt_ctx_last_kernel are functions of it (mirt_api.hip).
+// The kernel a plan runs.  Together with the bits below it names one template instance: render_kernel(plan) of the plan's build
+// (mirt_kernels.h) is that instance -- what the occupancy question is asked of and what is dispatched (mirt_api.hip) --, and
+// plan_kernel_name(plan) prints it for mirt_ctx_last_kernel.  Both read the plan and nothing else.
 enum PlanKernel : uint32_t { kKernelParity, kKernelParityHbm, kKernelPtStrip, kKernelPtHbm, kKernelPtPool, kKernelPtPoolHbm };
 
 struct RenderPlan {
@@ -92,7 +97,7 @@ struct RenderPlan {
     PlanKernel kernel;
     bool       fast, count, hosek, frame, use_grid, hbm_bvh, by_pixel, stream;
     uint32_t   pool_cfg, pool_nq;
-    PoolConfig pool;                  // geometry of the pool kernel that runs: threads / slots / lds (zero for the other kernels)
+    PoolConfig pool;                  // geometry of the pool kernel that runs (zero for the other kernels)
     // the schedule (the RenderArgs fields of the same names)
     uint32_t out_rows, n_units, lvl_unit[kStripLevels + 1], lvl_pix[kStripLevels + 1];
     uint32_t px_groups_log2, static_units, stream_samples, strip_cand, grid_flat_y, grid_pool_slots;
@@ -125,5 +130,8 @@ uint32_t out_rows(const MirtParams* p);
 RenderPlan plan_render(const PlanFacts& f, const Tuning& tune, const MirtParams& p, bool frame);
 // The caps that need the occupancy answer -- blocks of the chosen kernel resident per CU (0: no answer) --, then the dispenser's start.
 void plan_blocks(RenderPlan& plan, uint32_t resident_per_cu);
+// The name mirt_ctx_last_kernel reports: the plan's kernel template and its arguments, without spaces, as the tests and tools read them;
+// "fast_build::" in front of the fast-math build's.
+void plan_kernel_name(const RenderPlan& plan, char* out, size_t out_len);
 
 }  // namespace mirt

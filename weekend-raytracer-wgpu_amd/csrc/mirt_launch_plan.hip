@@ -1,5 +1,7 @@
-// mirt_launch_plan.hip — the launch plan of a render call (mirt_launch_plan.h): host arithmetic only.  launch_render (mirt_api.hip)
-// is its one caller in the library; host/plan_check.cpp calls it without a device.
+// mirt_launch_plan.hip — the launch plan of a render call and the name of its kernel (mirt_launch_plan.h): host arithmetic only.
+// launch_render (mirt_api.hip) is its one caller in the library; host/plan_check.cpp calls it without a device.
+#include <cstdio>
+
 #include "mirt_kernels.h"
 
 namespace kx = mirt::exact_build;
@@ -72,7 +74,7 @@ RenderPlan plan_render(const PlanFacts& f, const Tuning& tune, const MirtParams&
     const bool tiles = pt && (p.flags & MIRT_FLAG_TEXEL_TILES) && f.has_image_texture && tune.pool_config < 0;
     const uint32_t pool_cfg = tune.pool_config >= 0 ? (uint32_t)tune.pool_config : (tiles ? kTilePoolConfig : kDefaultPoolConfig);
     const uint32_t pool_nq = kx::pool_scatter_queues(f.n_shading_routines, count);
-    const PoolConfig pc = kx::pool_config(pool_cfg, pool_nq);
+    const PoolConfig pc = kx::pool_config(pool_cfg, pool_nq, count);
     // Default schedule: the pooled kernel pays off when a strip holds enough samples to keep the pool full and the
     // pools still leave >= 16 waves per CU resident beside the scene tables; the sample counts from which it does are
     // measured crossovers against the strip kernel's lane-per-pixel schedule (mirt_kernels.h: kPoolMinSpp*): 28 for scenes
@@ -105,7 +107,7 @@ RenderPlan plan_render(const PlanFacts& f, const Tuning& tune, const MirtParams&
     // the largest geometry only)
     const size_t lds_beside = scene_lds_g + f.grid_bytes;
     const size_t lds_grid_block = (size_t)f.lds_per_block / kGridPoolBlocksPerCu;
-    PoolConfig pcg = kx::pool_config_grid(lds_grid_block > lds_beside ? lds_grid_block - lds_beside : 0);
+    PoolConfig pcg = kx::pool_config_grid(lds_grid_block > lds_beside ? lds_grid_block - lds_beside : 0, count);
     if (count && pcg.slots != kGridPoolSlotChoices[0] && pcg.slots != kGridPoolSlotChoices[1]) pcg.slots = 0;
     const size_t lds_pool_grid_block = lds_beside + pcg.lds_bytes;
     const uint32_t pool_grid_waves_per_cu = pcg.slots ? (uint32_t)(f.lds_per_cu / lds_pool_grid_block) * (pcg.threads / 64u) : 0u;
@@ -128,7 +130,9 @@ RenderPlan plan_render(const PlanFacts& f, const Tuning& tune, const MirtParams&
     const bool pool_hbm = hbm_plan.slots != 0u;
     if (pool_hbm) pool = true;
     // the geometry of the pool kernel that will run
-    const PoolConfig pcu = pool_hbm ? PoolConfig{ hbm_plan.threads, hbm_plan.slots, hbm_plan.lds_bytes_per_block } : pool_grid ? pcg : pc;
+    // (the pooled HBM builds: the counting ones carry no register bound; no queue argument)
+    const PoolConfig pcu = pool_hbm ? PoolConfig{ hbm_plan.threads, hbm_plan.slots, hbm_plan.lds_bytes_per_block, count ? 1u : kBvhPoolMinWaves, 0u }
+                         : pool_grid ? pcg : pc;
     const uint32_t resident_pool_waves = pool_hbm ? hbm_plan.waves_per_cu : pool_grid ? pool_grid_waves_per_cu : pool_waves_per_cu;
 
     // the kernels' pinhole shortcut (generate_primary): the flag travels in the padding word beside lower_left_corner of
@@ -313,6 +317,33 @@ void plan_blocks(RenderPlan& a, uint32_t resident_per_cu)
     const uint32_t launched_waves = blocks * ((pool ? a.pool.threads : (a.launch_threads ? a.launch_threads : kBlockThreads)) / 64u);
     a.first_dispensed = launched_waves;          // the words themselves are zero (retire_slots): no memset node in front of the kernel
     for (uint32_t x = 0; x < 8u; ++x) a.disp_taken[x] = launched_waves > x ? (launched_waves - x + 7u) / 8u : 0u;
+}
+
+void plan_kernel_name(const RenderPlan& pl, char* out, size_t n)
+{
+    const char* const tf[2] = { "false", "true" };
+    const char* const fast = pl.fast ? "fast_build::" : "", *const kframe = pl.frame ? "_frame" : "";
+    const char* const count = tf[pl.count], *const hosek = tf[pl.hosek];
+    const PoolConfig& g = pl.pool;
+    switch (pl.kernel) {
+    case kKernelParity:    snprintf(out, n, "render_parity_kernel<%s,%s>", count, tf[pl.by_pixel]); break;
+    case kKernelParityHbm: snprintf(out, n, "render_parity_hbm_kernel<%s,%s>", count, tf[pl.by_pixel]); break;
+    case kKernelPtStrip:   // (a counting grid build is lane = sample whatever by_pixel says: render_kernel)
+        if (pl.stream) snprintf(out, n, "%srender_pt_stream%s_kernel<%s>", fast, kframe, hosek);
+        else snprintf(out, n, "%srender_pt_strip%s_kernel<%s,%s,%s,%s>", fast, kframe, count, hosek, tf[pl.use_grid], tf[pl.by_pixel && !(pl.count && pl.use_grid)]);
+        break;
+    case kKernelPtHbm:     // (the non-counting BVH build is lane = pixel whatever by_pixel says)
+        snprintf(out, n, "%srender_pt_hbm%s_kernel<%s,%s,%s,%s>", fast, kframe, count, hosek, tf[pl.hbm_bvh], tf[pl.by_pixel || (pl.hbm_bvh && !pl.count)]);
+        break;
+    case kKernelPtPoolHbm: snprintf(out, n, "%srender_pt_pool_hbm%s_kernel<%u,%u,%u,%s,%s>", fast, kframe, g.threads, g.slots, g.min_waves, count, hosek); break;
+    case kKernelPtPool:    // <threads, slots, min waves, COUNT, HOSEK, NQ, GRID, FLATY>; the tile build's name has always stopped at GRID
+        if (!pl.use_grid && pl.pool_cfg == kTilePoolConfig)
+            snprintf(out, n, "%srender_pt_pool_tile%s_kernel<%u,%u,%u,%s,%s,%u,false>", fast, kframe, g.threads, g.slots, g.min_waves, count, hosek, g.queues);
+        else
+            snprintf(out, n, "%srender_pt_pool%s_kernel<%u,%u,%u,%s,%s,%u,%s,%s>", fast, kframe, g.threads, g.slots, g.min_waves, count, hosek, g.queues, tf[pl.use_grid],
+                     tf[pl.use_grid && pl.grid_flat_y != 0u]);
+        break;
+    }
 }
 
 }  // namespace mirt

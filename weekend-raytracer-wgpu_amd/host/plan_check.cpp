@@ -9,11 +9,27 @@
 //   w h spp nb mode fl(hex) rb re tr np part sb fspp fb     MirtParams
 //   t.<field>                              a Tuning field that differs from its default (t.pool_min_spp=40)
 //   frame res                              the frame bit of plan_render; resident_per_cu of plan_blocks
+//
+// plan_check --kernels CASES.txt prints the kernel of every case instead (tests/test_launch_kernels.py), four words per line: the case, the name
+// mirt_ctx_last_kernel would report (plan_kernel_name), the template instance render_kernel selects in the plan's build -- the symbol of
+// its kernel handle in libmirt.so, demangled and written as the reported names are --, and that symbol itself.  "-": no such instance.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+
+#include <cxxabi.h>
+#include <dlfcn.h>
 
 #include "../csrc/mirt_launch_plan.h"
+
+// mirt_kernels.h (not included: it needs the HIP headers) declares these; a kernel's handle is all this program wants of them
+namespace mirt {
+struct RenderArgs;
+using RenderKernel = void (*)(RenderArgs);
+namespace exact_build { RenderKernel render_kernel(const RenderPlan& plan); }
+namespace fast_build { RenderKernel render_kernel(const RenderPlan& plan); }
+}
 
 static const char* const kKernelNames[] = { "parity", "parity-hbm", "pt-strip", "pt-hbm", "pt-pool", "pt-pool-hbm" };
 
@@ -41,6 +57,45 @@ static void print_plan(FILE* out, const char* name, const mirt::RenderPlan& p)
             p.spread_units, p.pinhole, p.grid_pool_slots, p.launch_threads, p.lds_bytes, p.bvh_stack_entries, p.blocks, p.first_dispensed);
     print_list(out, "dt", p.disp_taken, 8);
     fputc('\n', out);
+}
+
+static void erase_all(std::string& s, const char* what)
+{
+    for (size_t at; (at = s.find(what)) != std::string::npos;) s.erase(at, std::strlen(what));
+}
+
+// "void mirt::exact_build::render_pt_pool_kernel<256u, 112u, 6u, false, false, 3u, false, false>(mirt::RenderArgs)" as a reported name is
+// written: no return type, no argument list, no "mirt::exact_build::" (the fast build keeps "fast_build::"), no spaces, no unsigned suffixes
+static std::string as_reported(const char* demangled)
+{
+    std::string s = demangled;
+    if (s.rfind("void ", 0) == 0) s.erase(0, 5);
+    const size_t args = s.rfind('(');
+    if (args != std::string::npos) s.erase(args);
+    erase_all(s, "mirt::exact_build::");
+    erase_all(s, "mirt::");
+    erase_all(s, "__device_stub__");
+    erase_all(s, " ");
+    for (size_t i = 1; i + 1 < s.size(); ++i)
+        if (s[i] == 'u' && s[i - 1] >= '0' && s[i - 1] <= '9' && (s[i + 1] == ',' || s[i + 1] == '>')) s.erase(i, 1);
+    return s;
+}
+
+static void print_kernel(FILE* out, const char* name, const mirt::RenderPlan& p)
+{
+    if (p.status != MIRT_OK) { fprintf(out, "%s status=%d %s\n", name, p.status, p.message); return; }
+    char reported[128];
+    mirt::plan_kernel_name(p, reported, sizeof reported);
+    const mirt::RenderKernel k = p.fast ? mirt::fast_build::render_kernel(p) : mirt::exact_build::render_kernel(p);
+    Dl_info info{};
+    if (!k || !dladdr(reinterpret_cast<const void*>(k), &info) || !info.dli_sname || info.dli_saddr != reinterpret_cast<const void*>(k)) {
+        fprintf(out, "%s %s - -\n", name, reported);
+        return;
+    }
+    int status = 0;
+    char* const demangled = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+    fprintf(out, "%s %s %s %s\n", name, reported, status == 0 ? as_reported(demangled).c_str() : "-", info.dli_sname);
+    std::free(demangled);
 }
 
 struct Case {
@@ -91,9 +146,10 @@ static bool set_field(Case& c, const char* key, const char* val)
 
 int main(int argc, char** argv)
 {
-    if (argc != 2) { fprintf(stderr, "usage: plan_check CASES.txt\n"); return 2; }
-    FILE* in = std::fopen(argv[1], "r");
-    if (!in) { fprintf(stderr, "plan_check: cannot open %s\n", argv[1]); return 2; }
+    const bool kernels = argc == 3 && std::strcmp(argv[1], "--kernels") == 0;
+    if (argc != 2 && !kernels) { fprintf(stderr, "usage: plan_check [--kernels] CASES.txt\n"); return 2; }
+    FILE* in = std::fopen(argv[argc - 1], "r");
+    if (!in) { fprintf(stderr, "plan_check: cannot open %s\n", argv[argc - 1]); return 2; }
     char line[2048];
     for (int n = 1; std::fgets(line, sizeof line, in); ++n) {
         if (char* hash = std::strchr(line, '#')) *hash = '\0';
@@ -110,7 +166,8 @@ int main(int argc, char** argv)
         if (!any) continue;
         mirt::RenderPlan plan = mirt::plan_render(c.f, c.t, c.p, c.frame != 0u);
         if (plan.status == MIRT_OK) mirt::plan_blocks(plan, c.res);
-        print_plan(stdout, c.name, plan);
+        if (kernels) print_kernel(stdout, c.name, plan);
+        else print_plan(stdout, c.name, plan);
     }
     std::fclose(in);
     return 0;
