@@ -804,6 +804,48 @@ int mirt_ctx_adapt_stats(MirtContext* ctx, MirtAdaptStats* out);
  *                      lds_bytes_per_block = 96 (+ 144) + threads / 64 * (50 * slots + 896 + 256 * max_depth). */
 int mirt_adapt_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtBvhPoolPlan* out);
 
+/* ---- adaptive runs: a whole loop per call, step sizes chosen on the device ----
+ * mirt_ctx_adapt_run_device queues run->max_steps adaptive steps in order on hip_stream (NULL = the context's), with no host
+ * synchronisation, no allocation and no read of the count in between.  Step j selects exactly as mirt_ctx_adapt_step_device does (the
+ * same rule, the ascending list, the count); its scan stage then chooses the step's sample count ON THE DEVICE, from the count it has
+ * just summed, by an integer rule:
+ *   the step size    base = params->spp (even, at least 2, as for a step); cap = run->max_spp, 0 meaning base.  spp_j = 0 when count_j is 0,
+ *                    otherwise base << k with k the smallest k >= 0 for which count_j * (base << k) >= run->min_items or
+ *                    (base << k) == cap; the product is 64 bit.  min_items == 0 never grows.  mirt_adapt_run_spp is that rule for one
+ *                    count, HOST ONLY (no device, no context; it is the function the scan stage's thread runs: csrc/mirt_adapt_rule.h).
+ *                    Its errors: MIRT_ERR_NULL_POINTER (run or out), MIRT_ERR_BAD_MODE (run->flags != 0), MIRT_ERR_SPP_RANGE (spp is 0,
+ *                    odd or above MIRT_MAX_SPP_PER_CALL, or max_spp as below).
+ *   a step of a run  every listed pixel receives samples n .. n + spp_j - 1 of ITS stream: `sum` grows by every sample, `even` by the
+ *                    samples whose OWN index is even, samples = n + spp_j, the pads are written as 0; the 64-bit counter grows by
+ *                    count_j * spp_j, and entry j of a run log in device memory receives {count_j, spp_j}.  A pixel may overshoot
+ *                    max_samples by less than spp_j <= cap: the caller bounds that through max_spp.  The render kernels are builds of
+ *                    their own, adapt_pixels_run_kernel<HOSEK,BVH> and adapt_pixels_pool_run_kernel<THREADS,SLOTS,MINW,HOSEK>, which read
+ *                    spp_j as a wave-uniform word next to the count.  A run of max_steps = 1, min_items = 0, max_spp = 0 leaves the bytes
+ *                    of one mirt_ctx_adapt_step_device.
+ *   empty steps      once a step lists nothing every later step of the run lists nothing either (the records did not change).  Such
+ *                    steps are queued and run as empty steps do today -- the select stage runs, the render stage's blocks return at once
+ *                    -- and leave records, list, count (0) and counter as they are; they log {0, 0}.
+ *   state            mirt_ctx_adapt_list_read and mirt_ctx_adapt_stats().active describe the run's LAST step; steps grows by max_steps.
+ *                    One event pair around the whole run: kernel_ms spans it.  mirt_ctx_last_kernel names the run's render kernel.  The
+ *                    launch ring, MirtStats and the accumulation are untouched; ordering against set_scene*, update_spheres*,
+ *                    set_spheres*, resolves, reads and writes is that of a step.  The log (MIRT_ADAPT_RUN_MAX_STEPS entries) is part of the
+ *                    buffer mirt_ctx_adapt_reset sizes and clears.
+ *   honoured         MIRT_ADAPT_POOL in adapt->flags (the same hint, the same fall-backs), MIRT_FLAG_SKY_HOSEK, MIRT_FLAG_NO_GRID, bands
+ *                    and tile partitions.
+ *   errors           MIRT_ERR_NULL_POINTER: ctx, params, adapt or run is null; then every check and code of a step, in a step's order; then
+ *                    MIRT_ERR_BAD_MODE: run->flags != 0;  MIRT_ERR_BAD_ROWS: max_steps is 0 or above MIRT_ADAPT_RUN_MAX_STEPS;
+ *                    MIRT_ERR_SPP_RANGE: max_spp is neither 0 nor params->spp << m, or exceeds MIRT_MAX_SPP_PER_CALL.  A refused call queues
+ *                    nothing and writes nothing.
+ *   mirt_ctx_adapt_run_read   blocking, for tests and hosts: the log of the LAST run, entries 0 .. max_steps - 1 of it, and *n_steps =
+ *                    its max_steps.  MIRT_ERR_NO_SCENE before the first run since the reset; MIRT_ERR_OUT_BUFFER if len < that max_steps
+ *                    (*n_steps is set all the same). */
+typedef struct MirtAdaptRun     { uint32_t max_steps, min_items, max_spp, flags; } MirtAdaptRun;      /* 16 B */
+typedef struct MirtAdaptRunStep { uint32_t count, spp; } MirtAdaptRunStep;                           /*  8 B */
+#define MIRT_ADAPT_RUN_MAX_STEPS 256u
+int mirt_adapt_run_spp(uint32_t count, uint32_t spp, const MirtAdaptRun* run, uint32_t* out);
+int mirt_ctx_adapt_run_device(MirtContext* ctx, const MirtParams* params, const MirtAdaptParams* adapt, const MirtAdaptRun* run, void* hip_stream);
+int mirt_ctx_adapt_run_read(MirtContext* ctx, MirtAdaptRunStep* out, size_t len, uint32_t* n_steps);
+
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE
  * expansions over ALL 2^32 binary32 bit patterns.  Writes the two mismatch counts (sqrt, 1/x);
@@ -952,6 +994,8 @@ static_assert(sizeof(MirtRadianceParams) == 24, "MirtRadianceParams is four u32 
 static_assert(sizeof(MirtAdaptPixel) == 64, "MirtAdaptPixel is four 16-byte accesses");
 static_assert(sizeof(MirtAdaptParams) == 16, "MirtAdaptParams is four u32");
 static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32 and a double");
+static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
+static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -969,6 +1013,8 @@ _Static_assert(sizeof(MirtRadianceParams) == 24, "MirtRadianceParams is four u32
 _Static_assert(sizeof(MirtAdaptPixel) == 64, "MirtAdaptPixel is four 16-byte accesses");
 _Static_assert(sizeof(MirtAdaptParams) == 16, "MirtAdaptParams is four u32");
 _Static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32 and a double");
+_Static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
+_Static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
 #endif
 
 #endif /* MIRT_H */

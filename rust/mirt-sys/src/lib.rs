@@ -300,6 +300,29 @@ pub struct MirtAdaptStats {
 /// The rule's floor: 0.125 of radiance per sample, summed over the channels, in 2^-20 units.
 pub const MIRT_ADAPT_FLOOR: u32 = 1 << 17;
 
+/// An adaptive run (`mirt_ctx_adapt_run_device`): `max_steps` steps queued by one call; a step that lists `count` pixels takes
+/// `spp << k` samples of each, `k` the smallest for which `count * (spp << k) >= min_items` or `spp << k == max_spp` (0: `spp`).
+/// `flags` must be 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtAdaptRun {
+    pub max_steps: u32,
+    pub min_items: u32,
+    pub max_spp: u32,
+    pub flags: u32,
+}
+
+/// One entry of a run's log (`mirt_ctx_adapt_run_read`): the pixels the step listed and the samples each of them received.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtAdaptRunStep {
+    pub count: u32,
+    pub spp: u32,
+}
+
+/// The most steps one run queues, and the entries of its log.
+pub const MIRT_ADAPT_RUN_MAX_STEPS: u32 = 256;
+
 /// What a `mirt_ctx_trace_radiance*` call traces: samples `sample_begin .. sample_begin + spp - 1` of every ray's stream.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -449,6 +472,10 @@ extern "C" {
     pub fn mirt_ctx_adapt_write(ctx: *mut MirtContext, input: *const MirtAdaptPixel, len: usize) -> c_int;
     pub fn mirt_ctx_adapt_list_read(ctx: *mut MirtContext, list: *mut u32, len: usize, count: *mut u32) -> c_int;
     pub fn mirt_ctx_adapt_stats(ctx: *mut MirtContext, out: *mut MirtAdaptStats) -> c_int;
+    // adaptive runs: a whole loop per call, step sizes chosen on the device
+    pub fn mirt_adapt_run_spp(count: u32, spp: u32, run: *const MirtAdaptRun, out: *mut u32) -> c_int;
+    pub fn mirt_ctx_adapt_run_device(ctx: *mut MirtContext, params: *const MirtParams, adapt: *const MirtAdaptParams, run: *const MirtAdaptRun, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ctx_adapt_run_read(ctx: *mut MirtContext, out: *mut MirtAdaptRunStep, len: usize, n_steps: *mut u32) -> c_int;
     pub fn mirt_ctx_selftest_math(ctx: *mut MirtContext, out_mismatches: *mut u64) -> c_int;
     pub fn mirt_ctx_selftest_checker_sign(ctx: *mut MirtContext, out_counts: *mut u64) -> c_int;
     pub fn mirt_render(scene: *const MirtScene, params: *const MirtParams, device: c_int, out_rgba8: *mut u8, out_len: usize) -> c_int;

@@ -16,6 +16,13 @@ the median of --reps windows after a warm-up of each variant, every window's fig
   c  mirt_ctx_adapt_resolve_device against resolve_accum_kernel (mirt_ctx_accum_frame_device with spp = 0), the same kind of windows.
   e  the empty step (--pool only): the records of a finished run, so that a step lists nothing and its render launch is a grid of blocks
      that return at once -- the whole step (select, scan, compact, render) with and without MIRT_ADAPT_POOL, windows as in c.
+  r  (--run) the adaptive RUN, mirt_ctx_adapt_run_device: one call queues max_spp / step + 1 steps and the host waits
+     once.  Per --tolerances entry, in alternating windows like case a: `uniform`; `loop_pool`, the host-driven pooled loop of case a;
+     `run_0`, the same steps as one run (min_items 0: nothing grows, only the host's reads are gone); `run_<min_items>_<cap>` for every
+     --min-items entry (`auto`: half of, once and twice the paths the device keeps in flight, compute units x the plan's waves x slots)
+     and every --caps entry, with the samples each takes beside its time (growth spends samples) and its log.  All with MIRT_ADAPT_POOL.
+     `tail`: the records of a converged run, then a run of 32 steps that all list nothing -- the price of the steps behind the empty
+     one, pooled and unpooled, per step.  Lines go to profiles/r18_adaptive_run_rates.jsonl.
 --pool     adds the twin of every adaptive variant with MIRT_ADAPT_POOL (a: adaptive_<tolerance>_pool, b: adapt_pool) in
            the same alternating windows, compares their records with the unpooled variant's, and enables case e.
 --fold-trace FILE   no device: reads the *_kernel_trace.csv of a rocprofv3 --kernel-trace --stats run and appends one line with the calls
@@ -23,7 +30,7 @@ the median of --reps windows after a warm-up of each variant, every window's fig
 
 Run every world and case as a process of its own under its own time limit, e.g.
   timeout -k 10 300 python tools/adaptive_rates.py --spheres 484 --cases a
-usage: python tools/adaptive_rates.py [--pool] [--spheres 484,1000000] [--cases a,b,c,e] [--reps 5] [--max-spp 256] [--step 8] [--tolerances 4096,1024]
+usage: python tools/adaptive_rates.py [--pool] [--run] [--min-items auto] [--caps 32,64] [--spheres 484,1000000] [--cases a,b,c,e] [--reps 5] [--max-spp 256] [--step 8] [--tolerances 4096,1024]
                                       [--machinery-spp 32] [--window-ms 200] [--out profiles/r16_adaptive_rates.jsonl] [--fold-trace FILE]"""
 from __future__ import annotations
 
@@ -70,12 +77,17 @@ def main():
     ap.add_argument("--machinery-spp", type=int, default=32)
     ap.add_argument("--window-ms", type=float, default=200.0)
     ap.add_argument("--pool", action="store_true", help="also time every adaptive variant with MIRT_ADAPT_POOL")
+    ap.add_argument("--run", action="store_true", help="case r: adaptive runs (mirt_ctx_adapt_run_device) against the host-driven loop")
+    ap.add_argument("--min-items", default="auto")
+    ap.add_argument("--caps", default="32,64")
     ap.add_argument("--out", default="")
     ap.add_argument("--fold-trace", default="")
     ap.add_argument("--note", default="", help="copied into every line")
     a = ap.parse_args()
+    if a.run:
+        a.cases = "r"
     if not a.out:
-        a.out = str(ROOT / "profiles" / ("r17_adaptive_pool_rates.jsonl" if a.pool else "r16_adaptive_rates.jsonl"))
+        a.out = str(ROOT / "profiles" / ("r18_adaptive_run_rates.jsonl" if a.run else "r17_adaptive_pool_rates.jsonl" if a.pool else "r16_adaptive_rates.jsonl"))
 
     def emit(line):
         if a.note:
@@ -173,6 +185,86 @@ def main():
                   "last_run_pixels_at_max": int((counts >= a.max_spp).sum()), "last_run_median_samples": int(np.median(counts)),
                   **({"pooled_records_equal": same, "time_over_unpooled": {k: round(med[k] / med[k[:-5]], 3) for k in same}} if a.pool else {}),
                   "kernels": {k: last[k]["kernel"] for k in runs}, "all_ms": {k: [round(x, 2) for x in v] for k, v in t.items()}})
+
+        if "r" in cases:
+            p_step, p_all = pt(a.step), pt(a.max_spp)
+            max_steps = a.max_spp // a.step + 1
+            plan = m.adapt_pool_plan(base["max_depth"])
+            in_flight = torch.cuda.get_device_properties(0).multi_processor_count * plan["waves_per_cu"] * plan["slots"]
+            min_items = [in_flight // 2, in_flight, 2 * in_flight] if a.min_items == "auto" else [int(x) for x in a.min_items.split(",") if x]
+            caps = [int(x) for x in a.caps.split(",") if x]
+
+            def uniform():
+                ctx.accum_reset(p_all)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                ctx.accum_add(p_all)
+                ctx.synchronize()
+                return {"ms": (time.perf_counter() - t0) * 1e3, "samples": npix * a.max_spp, "kernel": ctx.last_kernel()}
+
+            def loop(tol):
+                adapt = m.make_adapt_params(a.step, a.max_spp, tol, True)
+                ctx.adapt_reset(p_step)
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                while True:
+                    ctx.adapt_step(p_step, adapt)
+                    st = ctx.adapt_stats()                          # waits for the step: the host must know whether to go on
+                    if st["active"] == 0:
+                        break
+                return {"ms": (time.perf_counter() - t0) * 1e3, "samples": st["total_samples"], "steps": st["steps"], "kernel": ctx.last_kernel()}
+
+            def one_run(tol, items, cap, steps=max_steps, pool=True, reset=True):
+                adapt, run = m.make_adapt_params(a.step, a.max_spp, tol, pool), m.make_adapt_run(steps, items, cap)
+                if reset:
+                    ctx.adapt_reset(p_step)
+                ctx.synchronize()
+                before = ctx.adapt_stats()["total_samples"]
+                t0 = time.perf_counter()
+                ctx.adapt_run(p_step, adapt, run)
+                st = ctx.adapt_stats()                              # the one wait
+                ms = (time.perf_counter() - t0) * 1e3
+                log = ctx.adapt_run_log()
+                return {"ms": ms, "samples": st["total_samples"] - before, "steps": int((log[:, 0] != 0).sum()), "device_ms": st["kernel_ms"], "active": st["active"],
+                        "log": log[log[:, 0] != 0].tolist(), "kernel": ctx.last_kernel()}
+
+            for tol in [int(x) for x in a.tolerances.split(",") if x]:
+                runs = {"uniform": uniform, "loop_pool": lambda: loop(tol), "run_0": lambda: one_run(tol, 0, 0)}
+                for cap in caps:
+                    for items in min_items:
+                        runs[f"run_{items}_{cap}"] = lambda items=items, cap=cap: one_run(tol, items, cap)
+                # the tail: behind run_0's converged records, 32 steps that list nothing
+                runs["tail32_pool"] = lambda: one_run(tol, 0, 0, 32, True, False)
+                runs["tail32_plain"] = lambda: one_run(tol, 0, 0, 32, False, False)
+                last, recs = {}, {}
+                for k, fn in runs.items():                             # warm-up; the records of the loop and of the run that repeats it
+                    if k.startswith("tail"):
+                        one_run(tol, 0, 0)
+                    last[k] = fn()
+                    if k in ("loop_pool", "run_0"):
+                        recs[k] = ctx.adapt_read()
+                same = bool(np.array_equal(recs["loop_pool"].view(np.uint8), recs["run_0"].view(np.uint8)))
+                t = {k: [] for k in runs}
+                for _ in range(a.reps):
+                    for k, fn in runs.items():
+                        if k.startswith("tail"):
+                            one_run(tol, 0, 0)                         # converged records, outside the window
+                        last[k] = fn()
+                        assert last[k].get("active", 0) == 0, (k, last[k])      # every run converged within max_steps
+                        t[k].append(last[k]["ms"])
+                med = {k: statistics.median(v) for k, v in t.items()}
+                assert last["tail32_pool"]["samples"] == 0 and last["tail32_plain"]["samples"] == 0
+                emit({**base, "case": "r_adaptive_run", "tolerance": tol, "max_spp": a.max_spp, "step": a.step, "min_samples": a.step, "max_steps": max_steps,
+                      "paths_in_flight": in_flight, "ms": {k: round(v, 2) for k, v in med.items()},
+                      "spread_ms": {k: [round(min(v), 2), round(max(v), 2)] for k, v in t.items()},
+                      "samples": {k: int(last[k]["samples"]) for k in runs}, "time_over_loop": {k: round(med[k] / med["loop_pool"], 3) for k in runs},
+                      "time_over_uniform": {k: round(med[k] / med["uniform"], 3) for k in runs},
+                      "samples_over_uniform": {k: round(last[k]["samples"] / last["uniform"]["samples"], 4) for k in runs},
+                      "sampling_steps": {k: last[k]["steps"] for k in runs if "steps" in last[k]},
+                      "device_ms_of_the_run": {k: round(last[k]["device_ms"], 2) for k in runs if "device_ms" in last[k]},
+                      "us_per_empty_step": {k: round(med[k] / 32 * 1e3, 1) for k in runs if k.startswith("tail")},
+                      "run_0_records_equal_the_loops": same, "logs": {k: last[k]["log"] for k in runs if last[k].get("log")},
+                      "kernels": {k: last[k]["kernel"] for k in runs}, "all_ms": {k: [round(x, 2) for x in v] for k, v in t.items()}})
 
         if "b" in cases:
             n_steps = a.machinery_spp // a.step

@@ -54,6 +54,7 @@ MIRT_RAY_SORT_DIRECTION_BITS = 8
 # mirt_ctx_adapt_*: the rule's floor, 0.125 of radiance per sample summed over the channels, in 2^-20 units
 MIRT_ADAPT_FLOOR = 1 << 17
 MIRT_ADAPT_POOL = 1 << 1                # MirtAdaptParams.flags; bit 0 is unassigned
+MIRT_ADAPT_RUN_MAX_STEPS = 256          # mirt_ctx_adapt_run_device: steps of one run, entries of its log
 
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
@@ -223,6 +224,14 @@ class MirtAdaptParams(C.Structure):
     _fields_ = [("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("tolerance", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class MirtAdaptRun(C.Structure):
+    _fields_ = [("max_steps", C.c_uint32), ("min_items", C.c_uint32), ("max_spp", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MirtAdaptRunStep(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("spp", C.c_uint32)]
+
+
 class MirtAdaptStats(C.Structure):
     _fields_ = [("pixels", C.c_uint64), ("total_samples", C.c_uint64), ("active", C.c_uint32), ("steps", C.c_uint32), ("kernel_ms", C.c_double)]
 
@@ -308,6 +317,9 @@ SYMBOLS = {
     "mirt_ctx_adapt_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mirt_ctx_adapt_list_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint32)]),
     "mirt_ctx_adapt_stats": (C.c_int, [C.c_void_p, _P(MirtAdaptStats)]),
+    "mirt_adapt_run_spp": (C.c_int, [C.c_uint32, C.c_uint32, _P(MirtAdaptRun), _P(C.c_uint32)]),
+    "mirt_ctx_adapt_run_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtAdaptParams), _P(MirtAdaptRun), C.c_void_p]),
+    "mirt_ctx_adapt_run_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint32)]),
     "mirt_ctx_selftest_math": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "mirt_ctx_selftest_checker_sign": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "mirt_ctx_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

@@ -290,6 +290,31 @@ def adapt_active(records, adapt: _abi.MirtAdaptParams) -> np.ndarray:
     return out.reshape(records.shape)
 
 
+def make_adapt_run(max_steps: int, min_items: int = 0, max_spp: int = 0) -> _abi.MirtAdaptRun:
+    """MirtAdaptRun for Context.adapt_run: `max_steps` steps (1 .. MIRT_ADAPT_RUN_MAX_STEPS) queued by one call.  A step that lists `count`
+    pixels takes spp << k samples of each, k the smallest for which count x (spp << k) reaches `min_items` or spp << k is `max_spp`
+    (0: params.spp, i.e. steps never grow; otherwise params.spp << m).  min_items = 0 never grows (include/mirt.h has the rule)."""
+    for name, v in (("max_steps", max_steps), ("min_items", min_items), ("max_spp", max_spp)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    r = _abi.MirtAdaptRun()
+    r.max_steps, r.min_items, r.max_spp, r.flags = int(max_steps), int(min_items), int(max_spp), 0
+    return r
+
+
+def adapt_run_spp(count: int, spp: int, run: _abi.MirtAdaptRun) -> int:
+    """mirt_adapt_run_spp: the sample count a step of `run` takes when it lists `count` pixels and params.spp is `spp` -- the function
+    the scan stage runs on the device.  Needs no device."""
+    if not isinstance(run, _abi.MirtAdaptRun):
+        raise ValueError(f"run must be a MirtAdaptRun (make_adapt_run builds one), not {type(run).__name__}")
+    for name, v in (("count", count), ("spp", spp)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    out = C.c_uint32()
+    check(lib().mirt_adapt_run_spp(int(count), int(spp), C.byref(run), C.byref(out)))
+    return int(out.value)
+
+
 def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort=False, pool=False) -> _abi.MirtRadianceParams:
     for name, v in (("spp", spp), ("sample_begin", sample_begin), ("num_bounces", num_bounces)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
@@ -611,6 +636,23 @@ class Context:
         if not isinstance(adapt, _abi.MirtAdaptParams):
             raise ValueError(f"adapt must be a MirtAdaptParams (make_adapt_params builds one), not {type(adapt).__name__}")
         check(lib().mirt_ctx_adapt_step_device(self._h, C.byref(_check_params(params)), C.byref(adapt), _stream_arg(stream)))
+
+    def adapt_run(self, params: _abi.MirtParams, adapt: _abi.MirtAdaptParams, run: _abi.MirtAdaptRun, stream: Optional[int] = None) -> None:
+        """mirt_ctx_adapt_run_device: run.max_steps adaptive steps queued on `stream` (see _stream_arg) by ONE call, no host
+        synchronisation -- every step selects as adapt_step does and its sample count is chosen on the device from the list it has
+        just built (make_adapt_run); steps behind an empty one change nothing.  adapt_run_log() has the counts and step sizes."""
+        if not isinstance(adapt, _abi.MirtAdaptParams):
+            raise ValueError(f"adapt must be a MirtAdaptParams (make_adapt_params builds one), not {type(adapt).__name__}")
+        if not isinstance(run, _abi.MirtAdaptRun):
+            raise ValueError(f"run must be a MirtAdaptRun (make_adapt_run builds one), not {type(run).__name__}")
+        check(lib().mirt_ctx_adapt_run_device(self._h, C.byref(_check_params(params)), C.byref(adapt), C.byref(run), _stream_arg(stream)))
+
+    def adapt_run_log(self) -> np.ndarray:
+        """mirt_ctx_adapt_run_read: the last run's log -> uint32 [max_steps, 2], {count, spp} per step; blocking."""
+        n = C.c_uint32()
+        buf = np.zeros((_abi.MIRT_ADAPT_RUN_MAX_STEPS, 2), np.uint32)
+        check(lib().mirt_ctx_adapt_run_read(self._h, C.c_void_p(buf.ctypes.data), len(buf), C.byref(n)))
+        return buf[:n.value].copy()
 
     def adapt_resolve(self, params: _abi.MirtParams) -> np.ndarray:
         """mirt_ctx_adapt_resolve: every pixel's mean over ITS samples, tone curves per params.flags -> uint8 [rows, width, 4]; blocking."""

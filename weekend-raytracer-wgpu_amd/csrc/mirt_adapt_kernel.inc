@@ -23,6 +23,12 @@
 //                         writes the record back with four 16-byte stores.  Lanes of the last wave beyond the count load nothing, take
 //                         part in the wave's loops with their tests masked off and store nothing.
 //   adapt_resolve_kernel  per pixel resolve_channel(sum[k], samples, flags); samples == 0: black, A = 255.
+//
+// A step of a RUN (mirt_ctx_adapt_run_device; DESIGN.md 10.14) is the same four kernels with two of them in a second build: the scan
+// stage's thread 0 also chooses the step's sample count from the count it has just summed (adapt_run_spp of mirt_adapt_rule.h), writes
+// it into head[1] and {count, spp} into the run log (adapt_scan_run_kernel), and the render stage reads that word next to the count in
+// the place of A.spp (adapt_pixels_run_kernel<HOSEK, BVH>).  The second builds share their TEXT with the first
+// (mirt_adapt_scan_text.inc, mirt_adapt_pixels_text.inc), so a step's kernels keep their names and their code.
 
 typedef uint32_t adapt_u4 __attribute__((ext_vector_type(4)));        // a record's quarter, 16-byte aligned (the buffer is the context's own)
 
@@ -55,38 +61,13 @@ __global__ __launch_bounds__(kAdaptSelectThreads) void adapt_select_kernel(const
     }
 }
 
-// head[0] = the step's count; the 64-bit word at head + 2 = samples added since the reset
-__global__ __launch_bounds__(kAdaptScanThreads) void adapt_scan_kernel(uint32_t* block_counts, uint32_t n_blocks, uint32_t* head, uint32_t spp)
-{
-    __shared__ uint32_t wave_total[kAdaptScanThreads / 64u];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < n_blocks; base += kAdaptScanThreads) {      // (base stays below 2^24: at most 2^32 / 256 blocks)
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_blocks ? block_counts[i] : 0u;
-        uint32_t incl = v;
-        for (uint32_t off = 1; off < 64u; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63u) wave_total[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < kAdaptScanThreads / 64u; ++w) {
-            const uint32_t t = wave_total[w];
-            if (w < wave) before += t;
-            all += t;
-        }
-        if (i < n_blocks) block_counts[i] = carry + before + incl - v;
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0u) {
-        head[0] = carry;
-        unsigned long long* total = reinterpret_cast<unsigned long long*>(head + 2);
-        *total += (unsigned long long)carry * spp;
-    }
-}
+// adapt_scan_kernel (a step: spp is the launch's) and adapt_scan_run_kernel (a step of a run: thread 0 chooses spp and logs it), one text
+#define MIRT_ADAPT_RUN 0
+#include "mirt_adapt_scan_text.inc"
+#undef MIRT_ADAPT_RUN
+#define MIRT_ADAPT_RUN 1
+#include "mirt_adapt_scan_text.inc"
+#undef MIRT_ADAPT_RUN
 
 __global__ __launch_bounds__(kAdaptSelectThreads) void adapt_compact_kernel(const unsigned char* flags, uint32_t n, const uint32_t* block_offsets, uint32_t* list)
 {
@@ -104,52 +85,18 @@ __global__ __launch_bounds__(kAdaptSelectThreads) void adapt_compact_kernel(cons
     }
 }
 
-template <bool HOSEK, bool BVH>
-__global__ __launch_bounds__(kAdaptThreads, 5) void adapt_pixels_kernel(RenderArgs A, adapt_u4* recs, const uint32_t* list, const uint32_t* count_word)
-{
-    constexpr uint32_t SRC = BVH ? kSrcBvh : kSrcHbmFlat;
-    const uint32_t count = __builtin_amdgcn_readfirstlane(*count_word);
-    if (blockIdx.x * kAdaptThreads >= count) return;                   // the whole block (one wave): nothing staged, no barrier met
-    extern __shared__ __align__(16) unsigned char smem[];
-    const SceneLds S = stage_scene<true, false>(A, smem, HOSEK);
-    const GridLds G{};
-    uint32_t* bvh_stack = nullptr;
-    if constexpr (BVH)
-        bvh_stack = reinterpret_cast<uint32_t*>(smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, HOSEK, false)) + (threadIdx.x >> 6) * (kBvhStackBytesPerWave / 4u);      // (one wave per block: + 0)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t slot = blockIdx.x * kAdaptThreads + threadIdx.x;    // < 2^32: the grid covers out_rows x width <= 2^32 - 1 pixels
-    const bool alive = slot < count;
-    const uint64_t pi = alive ? list[slot] : 0u;                       // the record's place in the band; < out_rows x width (adapt_compact_kernel)
-    const uint32_t ci = (uint32_t)pi / A.width;
-    const uint32_t x = (uint32_t)pi - ci * A.width;
-    const uint32_t y = abs_row(A, ci);
-    adapt_u4 q0 = { 0u, 0u, 0u, 0u }, q1 = q0, q2 = q0, q3 = q0;
-    if (alive) { q0 = recs[4u * pi]; q1 = recs[4u * pi + 1u]; q2 = recs[4u * pi + 2u]; q3 = recs[4u * pi + 3u]; }
-    const uint32_t n = q3.x;
-
-    Work<false> work;
-    work.clear();
-    unsigned long long sum_r = adapt_u64(q0.x, q0.y), sum_g = adapt_u64(q0.z, q0.w), sum_b = adapt_u64(q1.x, q1.y);
-    unsigned long long even_r = adapt_u64(q1.z, q1.w), even_g = adapt_u64(q2.x, q2.y), even_b = adapt_u64(q2.z, q2.w);
-    for (uint32_t s = 0; s < A.spp; ++s) {
-        Rng rng;
-        f3 ro, rd;
-        {   // camera constants are re-read from LDS per sample instead of living in 21 VGPRs (strip_kernel_body)
-            const CamRegs C = load_camera(S, A);
-            generate_primary(A, C, x, y, n + s, rng, ro, rd);
-        }
-        const f3 c = path_radiance<false, HOSEK, false, SRC>(A, S, G, alive, rng, ro, rd, work, lane, nullptr, kNoCand, bvh_stack);
-        const unsigned long long fr = to_fixed(c.x), fg = to_fixed(c.y), fb = to_fixed(c.z);
-        sum_r += fr; sum_g += fg; sum_b += fb;
-        if (((n + s) & 1u) == 0u) { even_r += fr; even_g += fg; even_b += fb; }
-    }
-    if (alive) {
-        recs[4u * pi] = adapt_u4{ (uint32_t)sum_r, (uint32_t)(sum_r >> 32), (uint32_t)sum_g, (uint32_t)(sum_g >> 32) };
-        recs[4u * pi + 1u] = adapt_u4{ (uint32_t)sum_b, (uint32_t)(sum_b >> 32), (uint32_t)even_r, (uint32_t)(even_r >> 32) };
-        recs[4u * pi + 2u] = adapt_u4{ (uint32_t)even_g, (uint32_t)(even_g >> 32), (uint32_t)even_b, (uint32_t)(even_b >> 32) };
-        recs[4u * pi + 3u] = adapt_u4{ n + A.spp, 0u, 0u, 0u };
-    }
-}
+// adapt_pixels_kernel<HOSEK, BVH> (a step: spp is the launch's) and adapt_pixels_run_kernel<HOSEK, BVH> (a step of a run: spp is the word
+// behind the count), one text
+#define MIRT_ADAPT_PIXELS_KERNEL adapt_pixels_kernel
+#define MIRT_ADAPT_RUN 0
+#include "mirt_adapt_pixels_text.inc"
+#undef MIRT_ADAPT_RUN
+#undef MIRT_ADAPT_PIXELS_KERNEL
+#define MIRT_ADAPT_PIXELS_KERNEL adapt_pixels_run_kernel
+#define MIRT_ADAPT_RUN 1
+#include "mirt_adapt_pixels_text.inc"
+#undef MIRT_ADAPT_RUN
+#undef MIRT_ADAPT_PIXELS_KERNEL
 
 __global__ __launch_bounds__(256) void adapt_resolve_kernel(const adapt_u4* recs, uint32_t* out, uint64_t n_pixels, uint32_t flags)
 {
@@ -176,14 +123,31 @@ hipError_t launch_adapt_select(const void* d_recs, uint32_t n, const MirtAdaptPa
     return hipGetLastError();
 }
 
+// The select stage of a step of a run: the same three kernels with adapt_scan_run_kernel in the middle, which derives the step's sample
+// count (base_spp, min_items, cap_spp: adapt_run_spp's arguments) and writes {count, spp} to d_log_entry, 8-byte aligned.
+hipError_t launch_adapt_select_run(const void* d_recs, uint32_t n, const MirtAdaptParams& adapt, uint32_t base_spp, uint32_t min_items, uint32_t cap_spp,
+                                   unsigned char* d_flags, uint32_t* d_block_counts, uint32_t* d_list, uint32_t* d_head, void* d_log_entry, hipStream_t stream)
+{
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + kAdaptSelectThreads - 1u) / kAdaptSelectThreads);
+    hipLaunchKernelGGL(adapt_select_kernel, dim3(blocks), dim3(kAdaptSelectThreads), 0, stream, static_cast<const adapt_u4*>(d_recs), n, adapt, d_flags, d_block_counts);
+    hipLaunchKernelGGL(adapt_scan_run_kernel, dim3(1), dim3(kAdaptScanThreads), 0, stream, d_block_counts, blocks, d_head, base_spp, min_items, cap_spp,
+                       static_cast<uint2*>(d_log_entry));
+    hipLaunchKernelGGL(adapt_compact_kernel, dim3(blocks), dim3(kAdaptSelectThreads), 0, stream, d_flags, n, d_block_counts, d_list);
+    return hipGetLastError();
+}
+
 // The render stage: one thread per pixel of the buffer (a.n_units of them), one wave per block; a.lds_bytes = stage_scene's image without
 // the tables + the wave's traversal stacks (BVH build); `a` carries the camera, the tables, the sky, the tree, the row fields, spp,
 // num_bounces and seed_mix as a render launch's does.
-hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, hipStream_t stream)
+// run: adapt_pixels_run_kernel, which takes the step's sample count from d_count[1] and not from a.spp.
+hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, bool run, hipStream_t stream)
 {
     const uint32_t blocks = (uint32_t)(((uint64_t)a.n_units + kAdaptThreads - 1u) / kAdaptThreads);
     auto k = hosek ? (bvh ? adapt_pixels_kernel<true, true> : adapt_pixels_kernel<true, false>)
                    : (bvh ? adapt_pixels_kernel<false, true> : adapt_pixels_kernel<false, false>);
+    if (run)
+        k = hosek ? (bvh ? adapt_pixels_run_kernel<true, true> : adapt_pixels_run_kernel<true, false>)
+                  : (bvh ? adapt_pixels_run_kernel<false, true> : adapt_pixels_run_kernel<false, false>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(kAdaptThreads), a.lds_bytes, stream, a, static_cast<adapt_u4*>(d_recs), d_list, d_count);
     return hipGetLastError();
 }

@@ -25,4 +25,17 @@ __host__ __device__ inline bool adapt_active(const uint64_t sum[3], const uint64
     return !converged;
 }
 
+// The step size of an adaptive RUN (mirt_ctx_adapt_run_device), ONE function for the host (mirt_adapt_run_spp) and the
+// device (thread 0 of adapt_scan_run_kernel): a step that lists `count` pixels takes base << k samples of each, k the smallest for which
+// count x (base << k) reaches min_items or base << k is the cap (cap = base << m, or 0 for base: the caller has checked it).  The
+// product is 64 bit: count < 2^32 and base << k <= cap <= 2^24.
+__host__ __device__ inline uint32_t adapt_run_spp(uint32_t count, uint32_t base, uint32_t min_items, uint32_t cap)
+{
+    if (count == 0u) return 0u;
+    if (cap == 0u) cap = base;
+    uint32_t spp = base;
+    while ((uint64_t)count * spp < (uint64_t)min_items && spp < cap) spp <<= 1;
+    return spp;
+}
+
 }  // namespace mirt

@@ -441,9 +441,11 @@ struct MirtContext {
     // mirt_ctx_adapt_* (DESIGN.md 10.12): the records and the select stage's storage, state of their own like the ray queries'; both grow, never shrink
     unsigned char*      d_adapt = nullptr;         // [adapt_pixels] MirtAdaptPixel
     size_t              cap_adapt = 0;
-    unsigned char*      d_adapt_sel = nullptr;     // head {count, -, u64 samples added} | list [pixels] u32 | block counts [ceil(pixels / 256)] u32 | flags [pixels] u8
+    unsigned char*      d_adapt_sel = nullptr;     // head {count, spp of a run's step, u64 samples added} | list [pixels] u32 | block counts [ceil(pixels / 256)] u32 | flags [pixels] u8 | run log
     size_t              cap_adapt_sel = 0;
     size_t              adapt_off_counts = 0, adapt_off_flags = 0;
+    size_t              adapt_off_log = 0;         // behind the flags, 8-byte aligned: the run log, MIRT_ADAPT_RUN_MAX_STEPS x MirtAdaptRunStep (10.14)
+    uint32_t            adapt_run_steps = 0;       // max_steps of the last run since the reset; 0: none
     uint64_t            adapt_pixels = 0;
     uint32_t            adapt_width = 0, adapt_rows = 0;
     uint32_t            adapt_steps = 0;           // since the reset
@@ -2055,13 +2057,16 @@ int mirt_ctx_adapt_reset(MirtContext* c, const MirtParams* p)
     // head 16 bytes | list | block counts | flags
     const uint64_t n_blocks = (npix + 255u) / 256u;
     const size_t off_counts = 16u + (size_t)npix * 4u, off_flags = off_counts + (size_t)n_blocks * 4u;
+    const size_t off_log = (off_flags + (size_t)npix + 7u) & ~(size_t)7u, sel_bytes = off_log + MIRT_ADAPT_RUN_MAX_STEPS * sizeof(MirtAdaptRunStep);   // | run log
+    c->adapt_run_steps = 0;
     if ((rc = ensure_capacity(&c->d_adapt, &c->cap_adapt, (size_t)npix * sizeof(MirtAdaptPixel))) != MIRT_OK) return rc;
-    if ((rc = ensure_capacity(&c->d_adapt_sel, &c->cap_adapt_sel, off_flags + (size_t)npix)) != MIRT_OK) return rc;
+    if ((rc = ensure_capacity(&c->d_adapt_sel, &c->cap_adapt_sel, sel_bytes)) != MIRT_OK) return rc;
     HIP_TRY(hipMemsetAsync(c->d_adapt, 0, (size_t)npix * sizeof(MirtAdaptPixel), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_adapt_sel, 0, off_flags + (size_t)npix, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_adapt_sel, 0, sel_bytes, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->adapt_off_counts = off_counts;
     c->adapt_off_flags = off_flags;
+    c->adapt_off_log = off_log;
     c->adapt_pixels = npix;
     c->adapt_width = p->width;
     c->adapt_rows = out_rows(p);
@@ -2091,11 +2096,9 @@ static int check_adapt_step(const MirtContext* c, const MirtParams* p, const Mir
     return MIRT_OK;
 }
 
-int mirt_ctx_adapt_step_device(MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, void* hip_stream)
+// A step (run == nullptr) or the run->max_steps steps of a run, queued on one stream between one event pair; `q` has passed check_adapt_step.
+static int queue_adapt_steps(MirtContext* c, const MirtParams& q, const MirtAdaptParams* adapt, const MirtAdaptRun* run, void* hip_stream)
 {
-    MirtParams q;
-    const int rc = check_adapt_step(c, p, adapt, &q);
-    if (rc != MIRT_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const bool bvh = !(q.flags & MIRT_FLAG_NO_GRID), hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
@@ -2120,21 +2123,89 @@ int mirt_ctx_adapt_step_device(MirtContext* c, const MirtParams* p, const MirtAd
     uint32_t* list = reinterpret_cast<uint32_t*>(c->d_adapt_sel + 16u);
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_adapt_begin, st));
-    HIP_TRY(kx::launch_adapt_select(c->d_adapt, (uint32_t)c->adapt_pixels, *adapt, q.spp, c->d_adapt_sel + c->adapt_off_flags,
-                                    reinterpret_cast<uint32_t*>(c->d_adapt_sel + c->adapt_off_counts), list, head, st));
-    const char* tf[2] = { "false", "true" };
-    if (pooled) {
-        HIP_TRY(kx::launch_adapt_pixels_pool(a, c->d_adapt, list, head, pool_blocks, plan.slots, hosek, st));
-        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_pool_kernel<%u,%u,%u,%s>", plan.threads, plan.slots, mirt::kBvhPoolMinWaves, tf[hosek]);
-    } else {
-        HIP_TRY(kx::launch_adapt_pixels(a, c->d_adapt, list, head, hosek, bvh, st));
-        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_kernel<%s,%s>", tf[hosek], tf[bvh]);
+    unsigned char* flags = c->d_adapt_sel + c->adapt_off_flags;
+    uint32_t* counts = reinterpret_cast<uint32_t*>(c->d_adapt_sel + c->adapt_off_counts);
+    const uint32_t n_steps = run ? run->max_steps : 1u;
+    for (uint32_t j = 0; j < n_steps; ++j) {
+        // a step of a run: its scan stage chooses the sample count and logs {count, spp}; the render stage reads it from head[1] (10.14).
+        // Steps behind an empty one are queued like the others: their select stage finds nothing and their blocks return at once.
+        if (run)
+            HIP_TRY(kx::launch_adapt_select_run(c->d_adapt, (uint32_t)c->adapt_pixels, *adapt, q.spp, run->min_items, run->max_spp, flags, counts, list, head,
+                                                c->d_adapt_sel + c->adapt_off_log + (size_t)j * sizeof(MirtAdaptRunStep), st));
+        else
+            HIP_TRY(kx::launch_adapt_select(c->d_adapt, (uint32_t)c->adapt_pixels, *adapt, q.spp, flags, counts, list, head, st));
+        if (pooled) HIP_TRY(kx::launch_adapt_pixels_pool(a, c->d_adapt, list, head, pool_blocks, plan.slots, hosek, run != nullptr, st));
+        else HIP_TRY(kx::launch_adapt_pixels(a, c->d_adapt, list, head, hosek, bvh, run != nullptr, st));
     }
+    const char* tf[2] = { "false", "true" };
+    if (pooled)
+        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_pool%s_kernel<%u,%u,%u,%s>", run ? "_run" : "", plan.threads, plan.slots, mirt::kBvhPoolMinWaves, tf[hosek]);
+    else
+        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels%s_kernel<%s,%s>", run ? "_run" : "", tf[hosek], tf[bvh]);
     HIP_TRY(hipEventRecord(c->ev_adapt_end, st));
     c->adapt_pending = true;
     c->adapt_timed = timed;
     c->adapt_ms = 0.0;
-    c->adapt_steps += 1;
+    c->adapt_steps += n_steps;
+    if (run) c->adapt_run_steps = n_steps;
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_step_device(MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, void* hip_stream)
+{
+    MirtParams q;
+    const int rc = check_adapt_step(c, p, adapt, &q);
+    if (rc != MIRT_OK) return rc;
+    return queue_adapt_steps(c, q, adapt, nullptr, hip_stream);
+}
+
+// ---- adaptive runs (include/mirt.h) ----
+// what a run's own fields are refused for; spp has passed a step's checks or mirt_adapt_run_spp's
+static int check_adapt_run(const MirtAdaptRun* run, uint32_t spp, bool with_steps)
+{
+    if (run->flags != 0u) return fail(MIRT_ERR_BAD_MODE, "unknown MirtAdaptRun.flags bits 0x%x", run->flags);
+    if (with_steps && (run->max_steps == 0u || run->max_steps > MIRT_ADAPT_RUN_MAX_STEPS))
+        return fail(MIRT_ERR_BAD_ROWS, "max_steps %u is out of range: 1 .. %u", run->max_steps, (unsigned)MIRT_ADAPT_RUN_MAX_STEPS);
+    if (run->max_spp != 0u) {
+        uint64_t s = spp;
+        while (s < run->max_spp) s <<= 1;
+        if (s != run->max_spp || run->max_spp > MIRT_MAX_SPP_PER_CALL)
+            return fail(MIRT_ERR_SPP_RANGE, "max_spp %u is neither 0 nor spp %u << m, or above %u", run->max_spp, spp, (unsigned)MIRT_MAX_SPP_PER_CALL);
+    }
+    return MIRT_OK;
+}
+
+int mirt_adapt_run_spp(uint32_t count, uint32_t spp, const MirtAdaptRun* run, uint32_t* out)
+{
+    if (!run || !out) return fail(MIRT_ERR_NULL_POINTER, "run/out is null");
+    if (spp == 0u || (spp & 1u) || spp > MIRT_MAX_SPP_PER_CALL) return fail(MIRT_ERR_SPP_RANGE, "spp %u: a step's size is even, 2 .. %u", spp, (unsigned)MIRT_MAX_SPP_PER_CALL);
+    const int rc = check_adapt_run(run, spp, false);
+    if (rc != MIRT_OK) return rc;
+    *out = mirt::adapt_run_spp(count, spp, run->min_items, run->max_spp);
+    return MIRT_OK;
+}
+
+int mirt_ctx_adapt_run_device(MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, const MirtAdaptRun* run, void* hip_stream)
+{
+    if (!c || !p || !adapt || !run) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/adapt/run is null");
+    MirtParams q;
+    int rc = check_adapt_step(c, p, adapt, &q);
+    if (rc != MIRT_OK) return rc;
+    if ((rc = check_adapt_run(run, q.spp, true)) != MIRT_OK) return rc;
+    return queue_adapt_steps(c, q, adapt, run, hip_stream);
+}
+
+int mirt_ctx_adapt_run_read(MirtContext* c, MirtAdaptRunStep* out, size_t len, uint32_t* n_steps)
+{
+    if (!c || !n_steps) return fail(MIRT_ERR_NULL_POINTER, "ctx/n_steps is null");
+    if (!c->d_adapt_sel || c->adapt_pixels == 0 || c->adapt_run_steps == 0) return fail(MIRT_ERR_NO_SCENE, "no adaptive run has been queued since the reset");
+    *n_steps = c->adapt_run_steps;
+    if (len < c->adapt_run_steps) return fail(MIRT_ERR_OUT_BUFFER, "the log holds %u steps, room for %zu", c->adapt_run_steps, len);
+    if (!out) return fail(MIRT_ERR_NULL_POINTER, "out is null");
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = adapt_await(c);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpy(out, c->d_adapt_sel + c->adapt_off_log, sizeof(MirtAdaptRunStep) * (size_t)c->adapt_run_steps, hipMemcpyDeviceToHost));
     return MIRT_OK;
 }
 

@@ -290,15 +290,21 @@ hipError_t launch_radiance_pool(const RenderArgs& a, const void* d_rays, void* d
 // four words {count of the step, unused, 64-bit counter of samples added (+= count x spp)}, 8-byte aligned.
 hipError_t launch_adapt_select(const void* d_recs, uint32_t n, const MirtAdaptParams& adapt, uint32_t spp, unsigned char* d_flags, uint32_t* d_block_counts,
                                uint32_t* d_list, uint32_t* d_head, hipStream_t stream);
+// The select stage of a step of a RUN (mirt_ctx_adapt_run_device): adapt_scan_run_kernel in the middle, whose thread 0 chooses the
+// step's sample count on the device -- adapt_run_spp(count, base_spp, min_items, cap_spp) of mirt_adapt_rule.h -- writes it to d_head[1], adds
+// count x that to the counter and writes {count, spp} to d_log_entry (8-byte aligned).
+hipError_t launch_adapt_select_run(const void* d_recs, uint32_t n, const MirtAdaptParams& adapt, uint32_t base_spp, uint32_t min_items, uint32_t cap_spp,
+                                   unsigned char* d_flags, uint32_t* d_block_counts, uint32_t* d_list, uint32_t* d_head, void* d_log_entry, hipStream_t stream);
 // ... and its render stage: adapt_pixels_kernel<hosek, bvh>, one thread per pixel of the buffer (a.n_units = out_rows x width), one wave per block; blocks
 // beyond *d_count return at once.  `a` carries the camera (with the pinhole word set), the tables, the sky, the tree, the row fields, width, height, spp,
-// num_bounces and seed_mix as a render launch's does; lds_bytes as launch_radiance wants them.
-hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, hipStream_t stream);
+// num_bounces and seed_mix as a render launch's does; lds_bytes as launch_radiance wants them.  run: adapt_pixels_run_kernel<hosek, bvh>, the same text
+// with the sample count read from d_count[1] (wave-uniform) in the place of a.spp.
+hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, bool run, hipStream_t stream);
 // MIRT_ADAPT_POOL: adapt_pixels_pool_kernel<kBvhPoolThreads, slots, kBvhPoolMinWaves, hosek> (mirt_adapt_pool_kernel.inc), the pooled schedule on units of
 // 16 list entries.  `a` as for launch_adapt_pixels, but bvh_stack_entries / lds_bytes as mirt_adapt_pool_plan gives them; grid_blocks blocks of
-// kBvhPoolThreads, whose waves stride over the units; blocks beyond ceil(*d_count / 16) units return at once.
+// kBvhPoolThreads, whose waves stride over the units; blocks beyond ceil(*d_count / 16) units return at once.  run: adapt_pixels_pool_run_kernel, as above.
 hipError_t launch_adapt_pixels_pool(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, uint32_t slots, bool hosek,
-                                    hipStream_t stream);
+                                    bool run, hipStream_t stream);
 // adapt_resolve_kernel: n_pixels records -> RGBA8, every pixel over its own sample count
 hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);

@@ -190,6 +190,28 @@ inline std::vector<uint32_t> adapt_list(MirtContext* ctx)
     list.resize(count);
     return list;
 }
+// Adaptive runs (mirt_ctx_adapt_run_device): run.max_steps steps queued by one call on `hip_stream`, every step's sample count chosen on the
+// device from the list it has just built.  adapt_run_spp is that rule for one count, host only; adapt_run_log blocks.
+static_assert(sizeof(MirtAdaptRun) == 16 && sizeof(MirtAdaptRunStep) == 8 && MIRT_ADAPT_RUN_MAX_STEPS == 256u, "the adaptive run of include/mirt.h");
+inline uint32_t adapt_run_spp(uint32_t count, uint32_t spp, const MirtAdaptRun& run)
+{
+    uint32_t out = 0;
+    check(mirt_adapt_run_spp(count, spp, &run, &out));
+    return out;
+}
+inline void adapt_run(MirtContext* ctx, const MirtParams& params, const MirtAdaptParams& adapt, const MirtAdaptRun& run, void* hip_stream = nullptr)
+{
+    check(mirt_ctx_adapt_run_device(ctx, &params, &adapt, &run, hip_stream));
+}
+// {count, spp} of every step of the last run
+inline std::vector<MirtAdaptRunStep> adapt_run_log(MirtContext* ctx)
+{
+    std::vector<MirtAdaptRunStep> log(MIRT_ADAPT_RUN_MAX_STEPS);
+    uint32_t n_steps = 0;
+    check(mirt_ctx_adapt_run_read(ctx, log.data(), log.size(), &n_steps));
+    log.resize(n_steps);
+    return log;
+}
 // the pinhole ray through the centre of pixel (x, y), row 0 on top: cameraMakeRay with a zero lens
 inline MirtRay pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float t_max = 1000.0f)
 {

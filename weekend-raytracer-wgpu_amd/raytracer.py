@@ -830,16 +830,44 @@ class Raytracer:
             spp = self.render_params.sampling.num_samples_per_pixel
         return _radiance(self, rays, spp, seed, self.render_params.sampling.num_bounces, self.sky_state is not None, self.scene_data, sort, pool)
 
-    def render_adaptive(self, tolerance: int, max_spp: int, step: int = 4, min_spp: int = 4, *, seed: int = 0, flags: int = 0, pool: bool = False) -> tuple:
+    def _default_adapt_run(self, ctx, step: int, max_spp: int, pool: bool, hosek: bool):
+        """The MirtAdaptRun of render_adaptive(run=True): enough steps for a pixel that takes `step` samples at a time to reach `max_spp`
+        and one more, steps that may grow to 8 x step, and min_items = the paths the device keeps in flight at once, times 2 --
+        compute units x resident waves per unit x paths per wave (the pool's slots, or 64 lanes of 20 waves without a pool).  The
+        factors 8 and 2 are guesses: nobody has tuned them."""
+        import torch
+        from .context import adapt_pool_plan, make_adapt_run
+        cus = int(torch.cuda.get_device_properties(int(ctx.device)).multi_processor_count)
+        plan = adapt_pool_plan(ctx.bvh_info()["plan"]["max_depth"], hosek) if pool else {"slots": 0}
+        in_flight = cus * (plan["waves_per_cu"] * plan["slots"] if plan["slots"] else 20 * 64)
+        max_steps = -(-int(max_spp) // int(step)) + 1
+        if max_steps > _abi.MIRT_ADAPT_RUN_MAX_STEPS:
+            raise ValueError(f"max_spp {max_spp} in steps of {step} needs {max_steps} steps: a run holds {_abi.MIRT_ADAPT_RUN_MAX_STEPS}; pass a MirtAdaptRun")
+        cap = int(step)
+        while cap < 8 * int(step) and 2 * cap <= _abi.MIRT_MAX_SPP_PER_CALL:
+            cap *= 2
+        return make_adapt_run(max_steps, min(2 * in_flight, 0xffffffff), cap)
+
+    def render_adaptive(self, tolerance: int, max_spp: int, step: int = 4, min_spp: int = 4, *, seed: int = 0, flags: int = 0, pool: bool = False,
+                        run=None) -> tuple:
         """Adaptive sampling of the current viewport (mirt_ctx_adapt_*): steps of `step` (even) samples for the pixels that have not
         converged -- fewer than `min_spp` samples, or even and odd halves further apart than tolerance x 2^-16 of the mean -- until no
         pixel below `max_spp` is left -> (RGBA8 [h][w][4], samples per pixel uint32 [h][w]).  One RNG stream per sample whatever
         `reference_stream` says (a pixel's samples must be independent).  A scene held in LDS is set again as a MIRT_SCENE_HBM scene
         first and stays one; on a node member 0's context renders the whole viewport.  The accumulation is not touched.  The mean of
         a pixel that a stopping rule has stopped is slightly biased.  pool=True asks for the pooled schedule
-        (MIRT_ADAPT_POOL, a hint): the image and the counts are the same."""
+        (MIRT_ADAPT_POOL, a hint): the image and the counts are the same.
+
+        run: None is the loop above, driven by the host: a step, a read of the count, the next step.  A MirtAdaptRun (make_adapt_run)
+        replaces it by ONE call that queues run.max_steps steps (mirt_ctx_adapt_run_device) whose sample counts the device chooses --
+        `step` << k, growing as the list shrinks, up to run.max_spp -- and the method waits once, in the resolve.  Steps behind the
+        first empty one change nothing; a run that is too short leaves pixels unconverged (Context.adapt_run_log() tells).  A pixel may
+        end above `max_spp` by less than run.max_spp.  run=True builds a default (_default_adapt_run): min_items from the device's
+        compute units and the plan's resident waves and slots, times a small factor that nobody has tuned."""
         from .context import make_adapt_params
         adapt = make_adapt_params(min_spp, max_spp, tolerance, pool)
+        if run is not None and run is not True and not isinstance(run, _abi.MirtAdaptRun):
+            raise ValueError(f"run must be None, True or a MirtAdaptRun (make_adapt_run builds one), not {run!r}")
         if not isinstance(step, (int, np.integer)) or isinstance(step, bool) or int(step) < 2 or int(step) % 2:
             raise ValueError(f"step must be an even sample count >= 2, not {step!r}")
         target = self._pick_target()
@@ -854,6 +882,11 @@ class Raytracer:
         w, h = int(rp.viewport_size[0]), int(rp.viewport_size[1])
         params = make_params(w, h, int(step), mode=_abi.MIRT_MODE_PT, num_bounces=rp.sampling.num_bounces, flags=flags, seed=seed)
         ctx.adapt_reset(params)
+        if run is not None:
+            if run is True:
+                run = self._default_adapt_run(ctx, int(step), int(max_spp), bool(pool), self.sky_state is not None)
+            ctx.adapt_run(params, adapt, run)
+            return ctx.adapt_resolve(params), ctx.adapt_read()["samples"].reshape(h, w).copy()
         while True:
             ctx.adapt_step(params, adapt)
             if ctx.adapt_stats()["active"] == 0:
