@@ -846,6 +846,45 @@ int mirt_adapt_run_spp(uint32_t count, uint32_t spp, const MirtAdaptRun* run, ui
 int mirt_ctx_adapt_run_device(MirtContext* ctx, const MirtParams* params, const MirtAdaptParams* adapt, const MirtAdaptRun* run, void* hip_stream);
 int mirt_ctx_adapt_run_read(MirtContext* ctx, MirtAdaptRunStep* out, size_t len, uint32_t* n_steps);
 
+/* ---- adaptive steps on a scene that lives in LDS: MIRT_ADAPT_LDS in MirtAdaptParams.flags ----
+ * Without the flag an adaptive step needs a MIRT_SCENE_HBM scene.  With it mirt_ctx_adapt_step_device and mirt_ctx_adapt_run_device also
+ * accept a context whose scene lives in LDS (mirt_ctx_set_scene, or mirt_ctx_set_scene_ex with flags 0), where it stays: the select
+ * stage is unchanged, the render stage is adapt_pixels_lds_kernel<HOSEK,GRID> (a run: adapt_pixels_lds_run_kernel<HOSEK,GRID>).
+ *   same bytes       after a step or run with the flag on an LDS scene the list and its count, the 64-bit sample counter, the run log and
+ *                    all 64 bytes of every record (pads written as 0, unlisted records untouched) equal what the same call leaves on a
+ *                    context that holds the same world as a MIRT_SCENE_HBM scene: integer sums of the same samples.
+ *   an HBM scene     ignores the flag: same kernel, same name in mirt_ctx_last_kernel, same bytes as without it.
+ *   an LDS scene     without the flag: MIRT_ERR_NO_SCENE, as ever.  With it MIRT_ADAPT_POOL is a hint that is ignored (there is no pooled
+ *                    LDS build); any other bit of adapt->flags is MIRT_ERR_BAD_MODE.  Every other check and code of a step, in a step's
+ *                    order; last of all the layout, below.  A refused call queues nothing and writes nothing.
+ *   the layout       the scene's uniform grid when it has one (mirt_grid_plan) and MIRT_FLAG_NO_GRID is not set; otherwise the flat
+ *                    layout if the scene fits it; otherwise MIRT_ERR_SCENE_TOO_LARGE, the code a render with MIRT_FLAG_NO_GRID gives on
+ *                    such a scene.  MIRT_FLAG_SKY_HOSEK is honoured; schedule hints are ignored.
+ *   the kernel       blocks of 256 threads whose four waves share one staged scene, in a PERSISTENT grid of
+ *                    min(ceil(pixels / 256), CUs x blocks_per_cu) blocks, blocks_per_cu the smaller of mirt_adapt_lds_plan's and the
+ *                    occupancy query's answer.  A unit is 64 >> g consecutive list entries, their spp samples dealt to 1 << g groups of
+ *                    lanes; waves stride over the units.  g is chosen ON THE DEVICE from the count:  g_cap = min(2, trailing zero bits
+ *                    of spp);  g = the smallest of 0 .. g_cap with ceil(count / (64 >> g)) >= grid_waves = blocks x 4, else g_cap; 0 for
+ *                    an empty list.  In a run spp is the step's spp_j.  A short late list is then four times as many waves.
+ *   state            as for every adaptive step: one event pair; the launch ring, MirtStats and the accumulation untouched.
+ *   mirt_adapt_lds_plan    HOST-ONLY, the function the launch itself uses.  grid_bytes = MirtGridPlan.blob_bytes of the scene, 0 for the
+ *                    flat layout; lds_bytes_per_cu == 0 means gfx950's 163 840.  threads = 256; grid = 1 for the grid layout, else 0;
+ *                      lds_bytes_per_block = 96 (+ 144 with hosek) + (grid_bytes ? grid_bytes : 32 * n_spheres + 48 * n_materials)
+ *                      blocks_per_cu       = min(8, lds_bytes_per_cu / lds_bytes_per_block)
+ *                    A layout the render launches refuse -- with the sky's 144 bytes counted, as mirt_ctx_set_scene counts them: more
+ *                    than 122 880 bytes, or a grid over more than 4 095 spheres -- or one that exceeds lds_bytes_per_cu gives all
+ *                    fields 0.  A large flat scene gets one or two blocks per CU: four or eight waves.  That is documented, not tuned.
+ *                    MIRT_ERR_NULL_POINTER for a null `out`.
+ *   mirt_adapt_lds_groups  HOST-ONLY: the rule for g above, for one count (the function every wave runs: csrc/mirt_adapt_rule.h).
+ *                    MIRT_ERR_NULL_POINTER: out_log2 is null;  MIRT_ERR_SPP_RANGE: spp is 0, odd or above MIRT_MAX_SPP_PER_CALL;
+ *                    MIRT_ERR_BAD_ROWS: grid_waves is 0.
+ * Knobs, read once in mirt_ctx_create (tests, A/B runs): MIRT_ADAPT_LDS_BLOCKS=n launches at most n blocks; MIRT_ADAPT_LDS_GROUPS=1|2|3
+ * forces g = 0|1|2, still capped by spp. */
+enum { MIRT_ADAPT_LDS = 1u << 3 };    /* MirtAdaptParams.flags; bit 2: unassigned */
+typedef struct MirtAdaptLdsPlan { uint32_t threads, grid, lds_bytes_per_block, blocks_per_cu; } MirtAdaptLdsPlan;   /* 16 B */
+int mirt_adapt_lds_plan(uint32_t n_spheres, uint32_t n_materials, uint32_t grid_bytes, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtAdaptLdsPlan* out);
+int mirt_adapt_lds_groups(uint32_t count, uint32_t spp, uint32_t grid_waves, uint32_t* out_log2);
+
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE
  * expansions over ALL 2^32 binary32 bit patterns.  Writes the two mismatch counts (sqrt, 1/x);
@@ -996,6 +1035,7 @@ static_assert(sizeof(MirtAdaptParams) == 16, "MirtAdaptParams is four u32");
 static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32 and a double");
 static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
 static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
+static_assert(sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptLdsPlan is four words");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -1015,6 +1055,7 @@ _Static_assert(sizeof(MirtAdaptParams) == 16, "MirtAdaptParams is four u32");
 _Static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32 and a double");
 _Static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
 _Static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
+_Static_assert(sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptLdsPlan is four words");
 #endif
 
 #endif /* MIRT_H */

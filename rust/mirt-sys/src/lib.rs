@@ -320,6 +320,16 @@ pub struct MirtAdaptRunStep {
     pub spp: u32,
 }
 
+/// `mirt_adapt_lds_plan`: the geometry an adaptive step with `MIRT_ADAPT_LDS` runs on a scene in LDS (host only; all fields 0: no such layout).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtAdaptLdsPlan {
+    pub threads: u32,
+    pub grid: u32,
+    pub lds_bytes_per_block: u32,
+    pub blocks_per_cu: u32,
+}
+
 /// The most steps one run queues, and the entries of its log.
 pub const MIRT_ADAPT_RUN_MAX_STEPS: u32 = 256;
 
@@ -344,6 +354,8 @@ pub const MIRT_RADIANCE_SORT: u32 = 1 << 4;
 pub const MIRT_RADIANCE_POOL: u32 = 1 << 6;
 /// `MirtAdaptParams.flags`: the pooled schedule for the step's render stage (a hint: same records); bit 0 is unassigned.
 pub const MIRT_ADAPT_POOL: u32 = 1 << 1;
+/// `MirtAdaptParams.flags`: a step or run also accepts a scene that lives in LDS, where it stays (an HBM scene ignores it); bit 2 is unassigned.
+pub const MIRT_ADAPT_LDS: u32 = 1 << 3;
 
 pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
 /// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.
@@ -476,6 +488,9 @@ extern "C" {
     pub fn mirt_adapt_run_spp(count: u32, spp: u32, run: *const MirtAdaptRun, out: *mut u32) -> c_int;
     pub fn mirt_ctx_adapt_run_device(ctx: *mut MirtContext, params: *const MirtParams, adapt: *const MirtAdaptParams, run: *const MirtAdaptRun, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_ctx_adapt_run_read(ctx: *mut MirtContext, out: *mut MirtAdaptRunStep, len: usize, n_steps: *mut u32) -> c_int;
+    // adaptive steps on a scene that lives in LDS (MIRT_ADAPT_LDS): the launch's geometry and the device's rule for the sample groups, host only
+    pub fn mirt_adapt_lds_plan(n_spheres: u32, n_materials: u32, grid_bytes: u32, hosek: u32, lds_bytes_per_cu: u64, out: *mut MirtAdaptLdsPlan) -> c_int;
+    pub fn mirt_adapt_lds_groups(count: u32, spp: u32, grid_waves: u32, out_log2: *mut u32) -> c_int;
     pub fn mirt_ctx_selftest_math(ctx: *mut MirtContext, out_mismatches: *mut u64) -> c_int;
     pub fn mirt_ctx_selftest_checker_sign(ctx: *mut MirtContext, out_counts: *mut u64) -> c_int;
     pub fn mirt_render(scene: *const MirtScene, params: *const MirtParams, device: c_int, out_rgba8: *mut u8, out_len: usize) -> c_int;

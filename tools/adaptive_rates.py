@@ -23,6 +23,14 @@ the median of --reps windows after a warm-up of each variant, every window's fig
      and every --caps entry, with the samples each takes beside its time (growth spends samples) and its log.  All with MIRT_ADAPT_POOL.
      `tail`: the records of a converged run, then a run of 32 steps that all list nothing -- the price of the steps behind the empty
      one, pooled and unpooled, per step.  Lines go to profiles/r18_adaptive_run_rates.jsonl.
+  l  (--lds) the world once as a scene in LDS and once as a MIRT_SCENE_HBM scene, two contexts in ONE process, per
+     --tolerances entry in alternating windows like case a: `uniform_lds`, mirt_ctx_accum_add of --max-spp samples on the LDS scene with
+     its default schedule; `lds_loop`, the host-driven loop with MIRT_ADAPT_LDS; `lds_run_0` and `lds_run_<min_items>_<cap>`, runs with it
+     (--min-items / --caps: one pair, 10.14's best grown parameters by default); `hbm_loop_pool`, `hbm_run_0`, `hbm_run_<min_items>_<cap>`,
+     the same on the HBM scene with MIRT_ADAPT_POOL.  The records of every LDS variant are compared with its HBM twin's once.
+  m  (--lds) the price of the machinery on the LDS scene: tolerance 0 and min = max = --machinery-spp, every pixel in every step, with
+     MIRT_ADAPT_LDS against mirt_ctx_accum_add of the same samples in the same steps on the same context; windows as in b.
+     Lines go to profiles/r20_adaptive_lds_rates.jsonl.
 --pool     adds the twin of every adaptive variant with MIRT_ADAPT_POOL (a: adaptive_<tolerance>_pool, b: adapt_pool) in
            the same alternating windows, compares their records with the unpooled variant's, and enables case e.
 --fold-trace FILE   no device: reads the *_kernel_trace.csv of a rocprofv3 --kernel-trace --stats run and appends one line with the calls
@@ -30,7 +38,7 @@ the median of --reps windows after a warm-up of each variant, every window's fig
 
 Run every world and case as a process of its own under its own time limit, e.g.
   timeout -k 10 300 python tools/adaptive_rates.py --spheres 484 --cases a
-usage: python tools/adaptive_rates.py [--pool] [--run] [--min-items auto] [--caps 32,64] [--spheres 484,1000000] [--cases a,b,c,e] [--reps 5] [--max-spp 256] [--step 8] [--tolerances 4096,1024]
+usage: python tools/adaptive_rates.py [--pool] [--run] [--lds] [--min-items auto] [--caps 32,64] [--spheres 484,1000000] [--cases a,b,c,e] [--reps 5] [--max-spp 256] [--step 8] [--tolerances 4096,1024]
                                       [--machinery-spp 32] [--window-ms 200] [--out profiles/r16_adaptive_rates.jsonl] [--fold-trace FILE]"""
 from __future__ import annotations
 
@@ -58,7 +66,7 @@ def fold_trace(path: str) -> dict:
     with open(path, newline="") as f:
         for r in csv.DictReader(f):
             name = r["Kernel_Name"]
-            if "adapt_" in name or "render_pt_hbm" in name or "resolve_accum" in name:
+            if "adapt_" in name or "render_pt_" in name or "resolve_accum" in name:
                 short = name.replace("mirt::exact_build::", "").replace("void ", "").split("(")[0]
                 durations.setdefault(short, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     return {"case": "kernel_trace", "source": Path(path).name,
@@ -78,6 +86,7 @@ def main():
     ap.add_argument("--window-ms", type=float, default=200.0)
     ap.add_argument("--pool", action="store_true", help="also time every adaptive variant with MIRT_ADAPT_POOL")
     ap.add_argument("--run", action="store_true", help="case r: adaptive runs (mirt_ctx_adapt_run_device) against the host-driven loop")
+    ap.add_argument("--lds", action="store_true", help="cases l, m: MIRT_ADAPT_LDS on the world held in LDS against the HBM builds and against uniform sampling in LDS")
     ap.add_argument("--min-items", default="auto")
     ap.add_argument("--caps", default="32,64")
     ap.add_argument("--out", default="")
@@ -86,8 +95,13 @@ def main():
     a = ap.parse_args()
     if a.run:
         a.cases = "r"
+    if a.lds:
+        a.cases = a.cases if set(a.cases.split(",")) <= {"l", "m"} else "l,m"
+        a.spheres = "484" if a.spheres == "484,1000000" else a.spheres       # the world must fit LDS
+        a.min_items = "917504" if a.min_items == "auto" else a.min_items     # 10.14's best grown run on this world
+        a.caps = "32" if a.caps == "32,64" else a.caps
     if not a.out:
-        a.out = str(ROOT / "profiles" / ("r18_adaptive_run_rates.jsonl" if a.run else "r17_adaptive_pool_rates.jsonl" if a.pool else "r16_adaptive_rates.jsonl"))
+        a.out = str(ROOT / "profiles" / ("r20_adaptive_lds_rates.jsonl" if a.lds else "r18_adaptive_run_rates.jsonl" if a.run else "r17_adaptive_pool_rates.jsonl" if a.pool else "r16_adaptive_rates.jsonl"))
 
     def emit(line):
         if a.note:
@@ -129,6 +143,123 @@ def main():
         base = {"world": f"rtiow_field({n})", "n_spheres": n, "max_depth": ctx.bvh_info()["plan"]["max_depth"], "width": W, "height": H,
                 "num_bounces": BOUNCES, "reps": a.reps}
         pt = lambda spp: m.make_params(W, H, spp, mode=m.MIRT_MODE_PT, num_bounces=BOUNCES)
+
+        if "l" in cases or "m" in cases:
+            lds_ctx = m.Context(0)
+            lds_ctx.set_scene(sd)                                       # the same world, in LDS
+
+        if "l" in cases:
+            p_step, p_all = pt(a.step), pt(a.max_spp)
+            max_steps = a.max_spp // a.step + 1
+            items, cap = int(a.min_items.split(",")[0]), int(a.caps.split(",")[0])
+
+            def uniform_lds():
+                lds_ctx.accum_reset(p_all)
+                lds_ctx.synchronize()
+                t0 = time.perf_counter()
+                lds_ctx.accum_add(p_all)
+                lds_ctx.synchronize()
+                return {"ms": (time.perf_counter() - t0) * 1e3, "samples": npix * a.max_spp, "kernel": lds_ctx.last_kernel()}
+
+            def loop_on(c, adapt):
+                c.adapt_reset(p_step)
+                c.synchronize()
+                t0 = time.perf_counter()
+                while True:
+                    c.adapt_step(p_step, adapt)
+                    st = c.adapt_stats()                                # waits for the step: the host must know whether to go on
+                    if st["active"] == 0:
+                        break
+                return {"ms": (time.perf_counter() - t0) * 1e3, "samples": st["total_samples"], "steps": st["steps"], "kernel": c.last_kernel()}
+
+            def run_on(c, adapt, min_items, max_spp):
+                c.adapt_reset(p_step)
+                c.synchronize()
+                t0 = time.perf_counter()
+                c.adapt_run(p_step, adapt, m.make_adapt_run(max_steps, min_items, max_spp))
+                st = c.adapt_stats()                                    # the one wait
+                ms = (time.perf_counter() - t0) * 1e3
+                log = c.adapt_run_log()
+                return {"ms": ms, "samples": st["total_samples"], "steps": int((log[:, 0] != 0).sum()), "device_ms": st["kernel_ms"], "active": st["active"],
+                        "log": log[log[:, 0] != 0].tolist(), "kernel": c.last_kernel()}
+
+            for tol in [int(x) for x in a.tolerances.split(",") if x]:
+                on_lds = m.make_adapt_params(a.step, a.max_spp, tol, lds=True)
+                on_hbm = m.make_adapt_params(a.step, a.max_spp, tol, pool=True)
+                grown = f"run_{items}_{cap}"
+                runs = {"uniform_lds": (None, uniform_lds),
+                        "lds_loop": (lds_ctx, lambda: loop_on(lds_ctx, on_lds)), "hbm_loop_pool": (ctx, lambda: loop_on(ctx, on_hbm)),
+                        "lds_run_0": (lds_ctx, lambda: run_on(lds_ctx, on_lds, 0, 0)), "hbm_run_0": (ctx, lambda: run_on(ctx, on_hbm, 0, 0)),
+                        "lds_" + grown: (lds_ctx, lambda: run_on(lds_ctx, on_lds, items, cap)), "hbm_" + grown: (ctx, lambda: run_on(ctx, on_hbm, items, cap))}
+                last, recs = {}, {}
+                for k, (c, fn) in runs.items():                         # warm-up; the records of every adaptive variant, once
+                    last[k] = fn()
+                    if c is not None:
+                        recs[k] = c.adapt_read()
+                same = {k: bool(np.array_equal(recs[k].view(np.uint8), recs[("hbm_loop_pool" if k == "lds_loop" else "hbm" + k[3:])].view(np.uint8)))
+                        for k in recs if k.startswith("lds_")}
+                assert all(same.values()), same                         # the contract: the same bytes in LDS and in HBM
+                t = {k: [] for k in runs}
+                for _ in range(a.reps):
+                    for k, (_, fn) in runs.items():
+                        last[k] = fn()
+                        assert last[k].get("active", 0) == 0, (k, last[k])      # every run converged within max_steps
+                        t[k].append(last[k]["ms"])
+                med = {k: statistics.median(v) for k, v in t.items()}
+                emit({**base, "case": "l_adaptive_lds", "tolerance": tol, "max_spp": a.max_spp, "step": a.step, "min_samples": a.step, "max_steps": max_steps,
+                      "ms": {k: round(v, 2) for k, v in med.items()}, "spread_ms": {k: [round(min(v), 2), round(max(v), 2)] for k, v in t.items()},
+                      "samples": {k: int(last[k]["samples"]) for k in runs},
+                      "time_over_uniform_lds": {k: round(med[k] / med["uniform_lds"], 3) for k in runs},
+                      "lds_over_hbm": {k: round(med[k] / med["hbm_loop_pool" if k == "lds_loop" else "hbm" + k[3:]], 3) for k in runs if k.startswith("lds_")},
+                      "samples_over_uniform": {k: round(last[k]["samples"] / last["uniform_lds"]["samples"], 4) for k in runs},
+                      "sampling_steps": {k: last[k]["steps"] for k in runs if "steps" in last[k]},
+                      "device_ms_of_the_run": {k: round(last[k]["device_ms"], 2) for k in runs if "device_ms" in last[k]},
+                      "lds_records_equal_hbm": same, "logs": {k: last[k]["log"] for k in runs if last[k].get("log")},
+                      "kernels": {k: last[k]["kernel"] for k in runs}, "all_ms": {k: [round(x, 2) for x in v] for k, v in t.items()}})
+
+        if "m" in cases:
+            n_steps = a.machinery_spp // a.step
+            p_step = pt(a.step)
+            adapt = m.make_adapt_params(a.machinery_spp, a.machinery_spp, 0, lds=True)
+
+            def run_adapt_lds():
+                for _ in range(n_steps):
+                    lds_ctx.adapt_step(p_step, adapt, stream=stream.cuda_stream)
+
+            def run_accum_lds():
+                for _ in range(n_steps):
+                    lds_ctx.accum_add(p_step, stream=stream.cuda_stream)
+
+            lds_ctx.adapt_reset(p_step)
+            lds_ctx.accum_reset(p_step)
+            run_adapt_lds()
+            kernels = {"adapt_lds": lds_ctx.last_kernel()}
+            run_accum_lds()
+            kernels["accum_lds"] = lds_ctx.last_kernel()
+            torch.cuda.synchronize()
+            same = bool(np.array_equal(lds_ctx.adapt_read()["sum"], lds_ctx.accum_read(p_step).reshape(-1, 3)))
+            lds_ctx.set_timing(False)
+
+            def fresh_lds(fn, reset):
+                reset(p_step)
+                torch.cuda.synchronize()
+                return window(fn, 1)
+
+            variants = {"adapt_lds": (run_adapt_lds, lds_ctx.adapt_reset), "accum_lds": (run_accum_lds, lds_ctx.accum_reset)}
+            for fn, reset in variants.values():
+                fresh_lds(fn, reset)
+            t = {k: [] for k in variants}
+            for _ in range(a.reps):
+                for k, (fn, reset) in variants.items():
+                    t[k].append(fresh_lds(fn, reset))
+            lds_ctx.set_timing(True)
+            med = {k: statistics.median(v) for k, v in t.items()}
+            emit({**base, "case": "m_price_of_the_machinery_lds", "samples_per_pixel": a.machinery_spp, "step": a.step, "steps": n_steps,
+                  "ms": {k: round(v, 3) for k, v in med.items()}, "adapt_over_accum": round(med["adapt_lds"] / med["accum_lds"], 3), "same_sums": same,
+                  "kernels": kernels, "all_ms": {k: [round(x, 3) for x in v] for k, v in t.items()}})
+
+        if "l" in cases or "m" in cases:
+            lds_ctx.close()
 
         if "a" in cases:
             p_step, p_all = pt(a.step), pt(a.max_spp)

@@ -54,6 +54,7 @@ MIRT_RAY_SORT_DIRECTION_BITS = 8
 # mirt_ctx_adapt_*: the rule's floor, 0.125 of radiance per sample summed over the channels, in 2^-20 units
 MIRT_ADAPT_FLOOR = 1 << 17
 MIRT_ADAPT_POOL = 1 << 1                # MirtAdaptParams.flags; bit 0 is unassigned
+MIRT_ADAPT_LDS = 1 << 3                 # MirtAdaptParams.flags: a step also runs on a scene that lives in LDS; bit 2 is unassigned
 MIRT_ADAPT_RUN_MAX_STEPS = 256          # mirt_ctx_adapt_run_device: steps of one run, entries of its log
 
 # mirt_node_create: members at most, and its flags
@@ -232,6 +233,13 @@ class MirtAdaptRunStep(C.Structure):
     _fields_ = [("count", C.c_uint32), ("spp", C.c_uint32)]
 
 
+class MirtAdaptLdsPlan(C.Structure):
+    _fields_ = [("threads", C.c_uint32), ("grid", C.c_uint32), ("lds_bytes_per_block", C.c_uint32), ("blocks_per_cu", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MirtAdaptStats(C.Structure):
     _fields_ = [("pixels", C.c_uint64), ("total_samples", C.c_uint64), ("active", C.c_uint32), ("steps", C.c_uint32), ("kernel_ms", C.c_double)]
 
@@ -318,6 +326,8 @@ SYMBOLS = {
     "mirt_ctx_adapt_list_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint32)]),
     "mirt_ctx_adapt_stats": (C.c_int, [C.c_void_p, _P(MirtAdaptStats)]),
     "mirt_adapt_run_spp": (C.c_int, [C.c_uint32, C.c_uint32, _P(MirtAdaptRun), _P(C.c_uint32)]),
+    "mirt_adapt_lds_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P(MirtAdaptLdsPlan)]),
+    "mirt_adapt_lds_groups": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
     "mirt_ctx_adapt_run_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtAdaptParams), _P(MirtAdaptRun), C.c_void_p]),
     "mirt_ctx_adapt_run_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint32)]),
     "mirt_ctx_selftest_math": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),

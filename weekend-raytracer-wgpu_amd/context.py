@@ -94,6 +94,29 @@ def adapt_pool_plan(max_depth: int, hosek: bool = False, lds_bytes_per_cu: int =
     return out.as_dict()
 
 
+def adapt_lds_plan(n_spheres: int, n_materials: int, grid_bytes: int = 0, hosek: bool = False, lds_bytes_per_cu: int = 0) -> dict:
+    """mirt_adapt_lds_plan: the geometry an adaptive step with MIRT_ADAPT_LDS runs on a scene that lives in LDS, host only: {"threads",
+    "grid", "lds_bytes_per_block", "blocks_per_cu"}.  grid_bytes = grid_plan()["blob_bytes"] for the grid layout, 0 for the flat one; all
+    fields 0: a layout the render launches refuse.  lds_bytes_per_cu = 0: gfx950's 163 840."""
+    for name, v in (("n_spheres", n_spheres), ("n_materials", n_materials), ("grid_bytes", grid_bytes)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    out = _abi.MirtAdaptLdsPlan()
+    check(lib().mirt_adapt_lds_plan(int(n_spheres), int(n_materials), int(grid_bytes), 1 if hosek else 0, int(lds_bytes_per_cu), C.byref(out)))
+    return out.as_dict()
+
+
+def adapt_lds_groups(count: int, spp: int, grid_waves: int) -> int:
+    """mirt_adapt_lds_groups: log2 of the sample groups an MIRT_ADAPT_LDS step deals a pixel's `spp` samples to when it lists `count`
+    pixels and its grid has `grid_waves` waves -- the function every wave runs on the device.  Needs no device."""
+    for name, v in (("count", count), ("spp", spp), ("grid_waves", grid_waves)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    out = C.c_uint32()
+    check(lib().mirt_adapt_lds_groups(int(count), int(spp), int(grid_waves), C.byref(out)))
+    return int(out.value)
+
+
 # one inner node as mirt_ctx_bvh_read returns it (csrc/mirt_bvh.h: BvhNode, 64 bytes)
 BVH_NODE_DTYPE = np.dtype([("lmin", "<f4", (3,)), ("lmax", "<f4", (3,)), ("rmin", "<f4", (3,)), ("rmax", "<f4", (3,)),
                            ("left", "<u4"), ("right", "<u4"), ("pad", "<u4", (2,))])
@@ -260,17 +283,20 @@ def radiance_ray_records(rays) -> np.ndarray:
 ADAPT_PIXEL_DTYPE = np.dtype([("sum", "<u8", (3,)), ("even", "<u8", (3,)), ("samples", "<u4"), ("_pad0", "<u4"), ("_pad1", "<u8")])
 
 
-def make_adapt_params(min_samples: int, max_samples: int, tolerance: int, pool: bool = False) -> _abi.MirtAdaptParams:
+def make_adapt_params(min_samples: int, max_samples: int, tolerance: int, pool: bool = False, lds: bool = False) -> _abi.MirtAdaptParams:
     """MirtAdaptParams: a pixel is sampled while it holds fewer than max_samples and either fewer than min_samples or its even and odd
     halves differ by more than tolerance x 2^-16 of its mean (include/mirt.h has the exact rule).  pool=True (MIRT_ADAPT_POOL): a hint
-    to run the step's render stage on the pooled schedule; the records, the list and the counters are the same."""
+    to run the step's render stage on the pooled schedule; the records, the list and the counters are the same.  lds=True
+    (MIRT_ADAPT_LDS): the step also runs on a scene that lives in LDS, where it stays; an HBM scene ignores it."""
     if not isinstance(pool, (bool, np.bool_)):
         raise ValueError(f"pool must be a bool, not {pool!r}")
+    if not isinstance(lds, (bool, np.bool_)):
+        raise ValueError(f"lds must be a bool, not {lds!r}")
     for name, v in (("min_samples", min_samples), ("max_samples", max_samples), ("tolerance", tolerance)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
             raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
     a = _abi.MirtAdaptParams()
-    a.min_samples, a.max_samples, a.tolerance, a.flags = int(min_samples), int(max_samples), int(tolerance), (_abi.MIRT_ADAPT_POOL if pool else 0)
+    a.min_samples, a.max_samples, a.tolerance, a.flags = int(min_samples), int(max_samples), int(tolerance), (_abi.MIRT_ADAPT_POOL if pool else 0) | (_abi.MIRT_ADAPT_LDS if lds else 0)
     return a
 
 

@@ -38,4 +38,19 @@ __host__ __device__ inline uint32_t adapt_run_spp(uint32_t count, uint32_t base,
     return spp;
 }
 
+// The sample groups of an MIRT_ADAPT_LDS step (adapt_pixels_lds_kernel), ONE function for the host (mirt_adapt_lds_groups)
+// and the device (every wave of the render stage): a unit is 64 >> g list entries, whose spp samples are dealt to 1 << g groups of lanes.
+// g is the smallest of 0 .. g_cap = min(2, trailing zero bits of spp) that gives each of the grid's `grid_waves` waves a unit, or g_cap
+// where none does; an empty list takes g = 0.  spp == 0 (an empty step of a run) has g_cap 0.
+__host__ __device__ inline uint32_t adapt_lds_groups(uint32_t count, uint32_t spp, uint32_t grid_waves)
+{
+    if (count == 0u) return 0u;
+    const uint32_t g_cap = (spp & 1u) || spp == 0u ? 0u : (spp & 2u) ? 1u : 2u;
+    for (uint32_t g = 0; g < g_cap; ++g) {
+        const uint32_t px = 64u >> g;
+        if (count / px + (count % px != 0u ? 1u : 0u) >= grid_waves) return g;
+    }
+    return g_cap;
+}
+
 }  // namespace mirt

@@ -282,6 +282,8 @@ Tuning read_tuning()
     }
     if (const char* e = std::getenv("MIRT_RADIANCE_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.radiance_pool_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_ADAPT_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_pool_blocks = (uint32_t)v; }
+    if (const char* e = std::getenv("MIRT_ADAPT_LDS_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_lds_blocks = (uint32_t)v; }
+    if (const char* e = std::getenv("MIRT_ADAPT_LDS_GROUPS")) { const int v = std::atoi(e); if (v >= 1 && v <= 3) t.adapt_lds_groups = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_GRID_BIG")) { const double v = std::atof(e); if (v >= 1.0 && v <= 1024.0) t.grid_big = v; }
     return t;
 }
@@ -604,6 +606,22 @@ int mirt_adapt_pool_plan(uint32_t max_depth, uint32_t hosek, uint64_t lds_bytes_
     *out = MirtBvhPoolPlan{};
     if (max_depth > MIRT_BVH_MAX_DEPTH) return fail(MIRT_ERR_BAD_ROWS, "max_depth %u exceeds MIRT_BVH_MAX_DEPTH (%u)", max_depth, (unsigned)MIRT_BVH_MAX_DEPTH);
     *out = plan_bvh_pool(max_depth, hosek != 0u, lds_bytes_per_cu ? lds_bytes_per_cu : (uint64_t)160 * 1024, 0u, mirt::kAdaptPoolExtraBytes);
+    return MIRT_OK;
+}
+
+int mirt_adapt_lds_plan(uint32_t n_spheres, uint32_t n_materials, uint32_t grid_bytes, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtAdaptLdsPlan* out)
+{
+    if (!out) return fail(MIRT_ERR_NULL_POINTER, "out is null");
+    *out = mirt::plan_adapt_lds(n_spheres, n_materials, grid_bytes, hosek != 0u, lds_bytes_per_cu ? lds_bytes_per_cu : (uint64_t)160 * 1024);
+    return MIRT_OK;
+}
+
+int mirt_adapt_lds_groups(uint32_t count, uint32_t spp, uint32_t grid_waves, uint32_t* out_log2)
+{
+    if (!out_log2) return fail(MIRT_ERR_NULL_POINTER, "out_log2 is null");
+    if (spp == 0u || (spp & 1u) || spp > MIRT_MAX_SPP_PER_CALL) return fail(MIRT_ERR_SPP_RANGE, "spp %u: a step's size is even, 2 .. %u", spp, (unsigned)MIRT_MAX_SPP_PER_CALL);
+    if (grid_waves == 0u) return fail(MIRT_ERR_BAD_ROWS, "grid_waves is 0");
+    *out_log2 = mirt::adapt_lds_groups(count, spp, grid_waves);
     return MIRT_OK;
 }
 
@@ -2075,13 +2093,27 @@ int mirt_ctx_adapt_reset(MirtContext* c, const MirtParams* p)
     return MIRT_OK;
 }
 
+// The layout of an MIRT_ADAPT_LDS step on the resident LDS scene: the scene's grid unless MIRT_FLAG_NO_GRID asks for the
+// flat scan, else the flat tables if they fit; plan_adapt_lds's geometry of it, or all fields 0 where neither fits a block's LDS.
+static MirtAdaptLdsPlan adapt_lds_layout(const MirtContext* c, const MirtParams& q)
+{
+    const bool hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
+    MirtAdaptLdsPlan plan{};
+    if (c->grid_bytes != 0u && !(q.flags & MIRT_FLAG_NO_GRID)) plan = mirt::plan_adapt_lds(c->n_spheres, c->n_mats, c->grid_bytes, hosek, c->lds_per_cu);
+    if (plan.lds_bytes_per_block > c->lds_per_block) plan = MirtAdaptLdsPlan{};
+    if (plan.threads == 0u && c->fits_flat) plan = mirt::plan_adapt_lds(c->n_spheres, c->n_mats, 0u, hosek, c->lds_per_cu);
+    if (plan.lds_bytes_per_block > c->lds_per_block) plan = MirtAdaptLdsPlan{};
+    return plan;
+}
+
 // What a step is refused for, in the header's order; *q = the params the launch runs with.  Nothing is queued before the last check has passed.
 static int check_adapt_step(const MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, MirtParams* q)
 {
     if (!c || !p || !adapt) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/adapt is null");
-    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (!c->have_scene || (!c->hbm && !(adapt->flags & MIRT_ADAPT_LDS)))
+        return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene (a scene in LDS takes MIRT_ADAPT_LDS)");
     if (p->mode != MIRT_MODE_PT) return fail(MIRT_ERR_BAD_MODE, "adaptive sampling exists in path-traced mode only");
-    if (adapt->flags & ~(uint32_t)MIRT_ADAPT_POOL) return fail(MIRT_ERR_BAD_MODE, "unknown MirtAdaptParams.flags bits 0x%x", adapt->flags);
+    if (adapt->flags & ~(uint32_t)(MIRT_ADAPT_POOL | MIRT_ADAPT_LDS)) return fail(MIRT_ERR_BAD_MODE, "unknown MirtAdaptParams.flags bits 0x%x", adapt->flags);
     if (p->flags & (MIRT_FLAG_COUNT_WORK | MIRT_FLAG_COUNT_GRID)) return fail(MIRT_ERR_BAD_MODE, "an adaptive step has no counting build");
     if (p->frame_spp != 0u) return fail(MIRT_ERR_FRAME_SPP, "frame_spp %u: an adaptive step needs independent samples (frame_spp 0)", p->frame_spp);
     *q = *p;
@@ -2093,6 +2125,9 @@ static int check_adapt_step(const MirtContext* c, const MirtParams* p, const Mir
         return fail(MIRT_ERR_SPP_RANGE, "max_samples %u is out of range: at most %u", adapt->max_samples, (unsigned)MIRT_MAX_SPP_PER_CALL);
     if (!c->d_adapt || c->adapt_pixels == 0 || c->adapt_width != p->width || c->adapt_rows != out_rows(p))
         return fail(MIRT_ERR_OUT_BUFFER, "the adaptive buffer does not match these params: call mirt_ctx_adapt_reset first");
+    if (!c->hbm && adapt_lds_layout(c, *q).threads == 0u)
+        return fail(MIRT_ERR_SCENE_TOO_LARGE, "this scene fits LDS in neither layout an MIRT_ADAPT_LDS step has%s",
+                    (q->flags & MIRT_FLAG_NO_GRID) ? " (MIRT_FLAG_NO_GRID: the flat one only)" : "");
     return MIRT_OK;
 }
 
@@ -2101,10 +2136,28 @@ static int queue_adapt_steps(MirtContext* c, const MirtParams& q, const MirtAdap
 {
     HIP_TRY(hipSetDevice(c->device));
     const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const bool bvh = !(q.flags & MIRT_FLAG_NO_GRID), hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
+    const bool bvh = c->hbm && !(q.flags & MIRT_FLAG_NO_GRID), hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
     mirt::RenderArgs a{};
     fill_common_args(c, &a, q, c->adapt_rows, pinhole_word(c));       // as launch_render
     a.n_units = (uint32_t)c->adapt_pixels;
+    // MIRT_ADAPT_LDS on a scene that lives in LDS (check_adapt_step has seen the flag and a layout): adapt_pixels_lds_kernel in a persistent
+    // grid of the blocks that are resident at once -- the plan's LDS bound and the occupancy answer, as plan_blocks -- or fewer, for fewer pixels
+    const bool lds = !c->hbm;
+    MirtAdaptLdsPlan lds_plan{};
+    uint32_t lds_blocks = 0;
+    if (lds) {
+        lds_plan = adapt_lds_layout(c, q);
+        a.lds_bytes = lds_plan.lds_bytes_per_block;
+        if (lds_plan.grid) { a.grid = c->d_grid; a.grid_bytes = c->grid_bytes; a.grid_flat_y = c->grid_flat_y ? 1u : 0u; }
+        for (int k = 0; k < 12; ++k) a.sph3[k] = c->sph3[k];
+        a.px_groups_log2 = c->tuning.adapt_lds_groups;
+        uint32_t per_cu = kx::adapt_lds_blocks_per_cu(hosek, lds_plan.grid != 0u, run != nullptr, a.lds_bytes);
+        if (per_cu > lds_plan.blocks_per_cu) per_cu = lds_plan.blocks_per_cu;
+        if (per_cu == 0u) per_cu = 1u;
+        const uint64_t all = (c->adapt_pixels + lds_plan.threads - 1u) / lds_plan.threads, resident = (uint64_t)c->cu_count * per_cu;
+        lds_blocks = (uint32_t)(all < resident ? all : resident);
+        if (c->tuning.adapt_lds_blocks != 0u && lds_blocks > c->tuning.adapt_lds_blocks) lds_blocks = c->tuning.adapt_lds_blocks;
+    }
     // MIRT_ADAPT_POOL on the BVH build: adapt_pixels_pool_kernel in the geometry mirt_adapt_pool_plan gives for the resident tree, where the
     // pool's own limits allow it -- 8-bit bounce counters, a geometry that fits beside the stacks of a tree this deep; otherwise the step
     // is the one without the flag.
@@ -2112,8 +2165,10 @@ static int queue_adapt_steps(MirtContext* c, const MirtParams& q, const MirtAdap
     if ((adapt->flags & MIRT_ADAPT_POOL) && bvh) plan = mirt::pooled_bvh_plan(plan_facts(c), c->tuning, hosek, mirt::kAdaptPoolExtraBytes, q.num_bounces);
     const bool pooled = plan.slots != 0u;
     // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
-    fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
-    a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
+    if (!lds) {
+        fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
+        a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
+    }
     uint32_t pool_blocks = 0;
     if (pooled) {                                           // units of 16 list entries; the host does not know the count: a grid for all pixels
         a.lds_bytes = plan.lds_bytes_per_block;             // camera words (+ sky), the block's pools, its waves' traversal stacks
@@ -2134,11 +2189,14 @@ static int queue_adapt_steps(MirtContext* c, const MirtParams& q, const MirtAdap
                                                 c->d_adapt_sel + c->adapt_off_log + (size_t)j * sizeof(MirtAdaptRunStep), st));
         else
             HIP_TRY(kx::launch_adapt_select(c->d_adapt, (uint32_t)c->adapt_pixels, *adapt, q.spp, flags, counts, list, head, st));
-        if (pooled) HIP_TRY(kx::launch_adapt_pixels_pool(a, c->d_adapt, list, head, pool_blocks, plan.slots, hosek, run != nullptr, st));
+        if (lds) HIP_TRY(kx::launch_adapt_pixels_lds(a, c->d_adapt, list, head, lds_blocks, hosek, lds_plan.grid != 0u, run != nullptr, st));
+        else if (pooled) HIP_TRY(kx::launch_adapt_pixels_pool(a, c->d_adapt, list, head, pool_blocks, plan.slots, hosek, run != nullptr, st));
         else HIP_TRY(kx::launch_adapt_pixels(a, c->d_adapt, list, head, hosek, bvh, run != nullptr, st));
     }
     const char* tf[2] = { "false", "true" };
-    if (pooled)
+    if (lds)
+        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_lds%s_kernel<%s,%s>", run ? "_run" : "", tf[hosek], tf[lds_plan.grid != 0u]);
+    else if (pooled)
         snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_pool%s_kernel<%u,%u,%u,%s>", run ? "_run" : "", plan.threads, plan.slots, mirt::kBvhPoolMinWaves, tf[hosek]);
     else
         snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels%s_kernel<%s,%s>", run ? "_run" : "", tf[hosek], tf[bvh]);

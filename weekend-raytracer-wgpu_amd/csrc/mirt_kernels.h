@@ -305,6 +305,13 @@ hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t
 // kBvhPoolThreads, whose waves stride over the units; blocks beyond ceil(*d_count / 16) units return at once.  run: adapt_pixels_pool_run_kernel, as above.
 hipError_t launch_adapt_pixels_pool(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, uint32_t slots, bool hosek,
                                     bool run, hipStream_t stream);
+// MIRT_ADAPT_LDS: adapt_pixels_lds_kernel<hosek, grid> (mirt_adapt_lds_kernel.inc), the render stage of a step on a scene that lives in LDS:
+// grid_blocks blocks of 256 threads that share one staged scene, their waves striding over units of 64 >> g list entries.  `a` as for launch_adapt_pixels plus
+// the grid fields (grid build) and sph3, px_groups_log2 = 0 (the device chooses g) or the forced g + 1, lds_bytes = plan_adapt_lds's bytes per block.
+// run: adapt_pixels_lds_run_kernel, as above.  adapt_lds_blocks_per_cu: the occupancy query's answer for that build and LDS size.
+hipError_t launch_adapt_pixels_lds(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, bool hosek, bool grid,
+                                   bool run, hipStream_t stream);
+uint32_t   adapt_lds_blocks_per_cu(bool hosek, bool grid, bool run, uint32_t lds_bytes);
 // adapt_resolve_kernel: n_pixels records -> RGBA8, every pixel over its own sample count
 hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);

@@ -2257,6 +2257,7 @@ static auto for_bvh_pool_slots(uint32_t slots, Build build) -> decltype(build(Bv
 #include "mirt_radiance_pool_kernel.inc"
 #include "mirt_adapt_kernel.inc"
 #include "mirt_adapt_pool_kernel.inc"
+#include "mirt_adapt_lds_kernel.inc"
 
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns

@@ -70,6 +70,8 @@ struct Tuning {
     uint32_t hbm_pool_slots = 0;      // MIRT_HBM_POOL_SLOTS=n (A/B runs): the pooled build of MIRT_SCENE_HBM scenes takes this one of kBvhPoolSlotChoices
     uint32_t radiance_pool_blocks = 0;    // MIRT_RADIANCE_POOL_BLOCKS=n (A/B runs, tests): a pooled radiance query launches at most n blocks, whose waves stride over the units
     uint32_t adapt_pool_blocks = 0;   // MIRT_ADAPT_POOL_BLOCKS=n (A/B runs, tests): a pooled adaptive step launches at most n blocks, whose waves stride over the units
+    uint32_t adapt_lds_blocks = 0;    // MIRT_ADAPT_LDS_BLOCKS=n (A/B runs, tests): an MIRT_ADAPT_LDS step launches at most n blocks
+    uint32_t adapt_lds_groups = 0;    // MIRT_ADAPT_LDS_GROUPS=1/2/3 (A/B runs, tests): an MIRT_ADAPT_LDS step deals samples to 1 / 2 / 4 groups of lanes (capped by spp)
     bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
 };
 
@@ -121,6 +123,12 @@ MirtBvhPoolPlan plan_bvh_pool(uint32_t max_depth, bool hosek, uint64_t lds_per_c
 // The gate every pooled BVH launch passes (render, radiance query, adaptive step): 8-bit bounce counters, and a geometry for the
 // resident tree that fits the block's LDS.  slots == 0: none, the launch is the one without the pool.
 MirtBvhPoolPlan pooled_bvh_plan(const PlanFacts& f, const Tuning& tune, bool hosek, uint32_t extra_per_wave, uint32_t num_bounces);
+
+// The geometry of an MIRT_ADAPT_LDS step (mirt_adapt_lds_plan; the launch calls this very function): 256-thread blocks that
+// stage camera (+ sky) and either the grid blob (grid_bytes != 0) or the sphere and material tables, at most 8 of them per CU.  All fields
+// 0: a layout the render launches refuse (mirt_ctx_set_scene's budget, which counts the sky; a grid over more than 4 095 spheres), or
+// not even one block per CU.
+MirtAdaptLdsPlan plan_adapt_lds(uint32_t n_spheres, uint32_t n_mats, uint32_t grid_bytes, bool hosek, uint64_t lds_per_cu);
 
 // MirtParams row selection: is it valid (then [*rb, *re) is the band), and the rows a call writes (mirt_params_out_rows)
 bool     rows_valid(const MirtParams* p, uint32_t* rb, uint32_t* re);

@@ -58,6 +58,17 @@ MirtBvhPoolPlan pooled_bvh_plan(const PlanFacts& f, const Tuning& tune, bool hos
     return plan.slots != 0u && plan.lds_bytes_per_block <= f.lds_per_block ? plan : MirtBvhPoolPlan{};
 }
 
+MirtAdaptLdsPlan plan_adapt_lds(uint32_t n_spheres, uint32_t n_mats, uint32_t grid_bytes, bool hosek, uint64_t lds_per_cu)
+{
+    const uint64_t tables = grid_bytes ? (uint64_t)grid_bytes : (uint64_t)kx::scene_lds_bytes(n_spheres, n_mats, true, false) - kx::scene_lds_bytes_grid(0u, false);
+    // what mirt_ctx_set_scene accepts of either layout: the budget with the sky counted, and 12-bit sphere ids in a grid
+    if (kx::scene_lds_bytes_grid(0u, true) + tables > kMaxLdsBytes || (grid_bytes != 0u && n_spheres > 4095u)) return MirtAdaptLdsPlan{};
+    const uint64_t block = kx::scene_lds_bytes_grid(0u, hosek) + tables;
+    const uint64_t per_cu = lds_per_cu / block;
+    if (per_cu == 0u) return MirtAdaptLdsPlan{};
+    return MirtAdaptLdsPlan{ 256u, grid_bytes ? 1u : 0u, (uint32_t)block, (uint32_t)(per_cu < 8u ? per_cu : 8u) };
+}
+
 RenderPlan plan_render(const PlanFacts& f, const Tuning& tune, const MirtParams& p, bool frame)
 {
     RenderPlan a{};

@@ -212,6 +212,23 @@ inline std::vector<MirtAdaptRunStep> adapt_run_log(MirtContext* ctx)
     log.resize(n_steps);
     return log;
 }
+// MIRT_ADAPT_LDS in MirtAdaptParams.flags: adapt_step and adapt_run also accept a scene that lives in LDS, where it stays (same records as on
+// the same world held as a MIRT_SCENE_HBM scene, which ignores the flag).  adapt_lds_plan is the geometry such a step runs (grid_bytes =
+// MirtGridPlan.blob_bytes, 0 for the flat layout; all fields 0: no such layout), adapt_lds_groups the rule by which the device deals a
+// pixel's samples to 1 << g groups of lanes; both host only.
+static_assert(MIRT_ADAPT_LDS == 1u << 3 && sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptParams.flags: adaptive steps on a scene in LDS");
+inline MirtAdaptLdsPlan adapt_lds_plan(uint32_t n_spheres, uint32_t n_materials, uint32_t grid_bytes = 0, bool hosek = false, uint64_t lds_bytes_per_cu = 0)
+{
+    MirtAdaptLdsPlan plan;
+    check(mirt_adapt_lds_plan(n_spheres, n_materials, grid_bytes, hosek ? 1u : 0u, lds_bytes_per_cu, &plan));
+    return plan;
+}
+inline uint32_t adapt_lds_groups(uint32_t count, uint32_t spp, uint32_t grid_waves)
+{
+    uint32_t out = 0;
+    check(mirt_adapt_lds_groups(count, spp, grid_waves, &out));
+    return out;
+}
 // the pinhole ray through the centre of pixel (x, y), row 0 on top: cameraMakeRay with a zero lens
 inline MirtRay pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float t_max = 1000.0f)
 {

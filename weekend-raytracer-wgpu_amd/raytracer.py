@@ -849,14 +849,16 @@ class Raytracer:
         return make_adapt_run(max_steps, min(2 * in_flight, 0xffffffff), cap)
 
     def render_adaptive(self, tolerance: int, max_spp: int, step: int = 4, min_spp: int = 4, *, seed: int = 0, flags: int = 0, pool: bool = False,
-                        run=None) -> tuple:
+                        run=None, lds: bool = False) -> tuple:
         """Adaptive sampling of the current viewport (mirt_ctx_adapt_*): steps of `step` (even) samples for the pixels that have not
         converged -- fewer than `min_spp` samples, or even and odd halves further apart than tolerance x 2^-16 of the mean -- until no
         pixel below `max_spp` is left -> (RGBA8 [h][w][4], samples per pixel uint32 [h][w]).  One RNG stream per sample whatever
         `reference_stream` says (a pixel's samples must be independent).  A scene held in LDS is set again as a MIRT_SCENE_HBM scene
         first and stays one; on a node member 0's context renders the whole viewport.  The accumulation is not touched.  The mean of
         a pixel that a stopping rule has stopped is slightly biased.  pool=True asks for the pooled schedule
-        (MIRT_ADAPT_POOL, a hint): the image and the counts are the same.
+        (MIRT_ADAPT_POOL, a hint): the image and the counts are the same.  lds=True (MIRT_ADAPT_LDS) leaves a scene held in LDS where it
+        is and runs the steps there -- the same image and counts, and later render() and progressive frames keep their LDS builds; on a
+        scene that is already an HBM scene it changes nothing, and `pool` is ignored on a scene in LDS.
 
         run: None is the loop above, driven by the host: a step, a read of the count, the next step.  A MirtAdaptRun (make_adapt_run)
         replaces it by ONE call that queues run.max_steps steps (mirt_ctx_adapt_run_device) whose sample counts the device chooses --
@@ -865,13 +867,13 @@ class Raytracer:
         end above `max_spp` by less than run.max_spp.  run=True builds a default (_default_adapt_run): min_items from the device's
         compute units and the plan's resident waves and slots, times a small factor that nobody has tuned."""
         from .context import make_adapt_params
-        adapt = make_adapt_params(min_spp, max_spp, tolerance, pool)
+        adapt = make_adapt_params(min_spp, max_spp, tolerance, pool, lds)
         if run is not None and run is not True and not isinstance(run, _abi.MirtAdaptRun):
             raise ValueError(f"run must be None, True or a MirtAdaptRun (make_adapt_run builds one), not {run!r}")
         if not isinstance(step, (int, np.integer)) or isinstance(step, bool) or int(step) < 2 or int(step) % 2:
             raise ValueError(f"step must be an even sample count >= 2, not {step!r}")
         target = self._pick_target()
-        if not self._hbm:
+        if not self._hbm and not lds:
             target.set_scene(self.scene_data(), hbm=True)
             self._hbm = True
         ctx = target.context(0) if hasattr(target, "context") else target
@@ -884,7 +886,7 @@ class Raytracer:
         ctx.adapt_reset(params)
         if run is not None:
             if run is True:
-                run = self._default_adapt_run(ctx, int(step), int(max_spp), bool(pool), self.sky_state is not None)
+                run = self._default_adapt_run(ctx, int(step), int(max_spp), bool(pool) and self._hbm, self.sky_state is not None)
             ctx.adapt_run(params, adapt, run)
             return ctx.adapt_resolve(params), ctx.adapt_read()["samples"].reshape(h, w).copy()
         while True:
