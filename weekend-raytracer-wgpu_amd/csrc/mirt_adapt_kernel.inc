@@ -32,7 +32,6 @@
 
 typedef uint32_t adapt_u4 __attribute__((ext_vector_type(4)));        // a record's quarter, 16-byte aligned (the buffer is the context's own)
 
-constexpr uint32_t kAdaptThreads = 64;              // adapt_pixels_kernel: one wave per block, as kRadianceThreads
 constexpr uint32_t kAdaptSelectThreads = 256;       // adapt_select_kernel / adapt_compact_kernel: records per block
 constexpr uint32_t kAdaptScanThreads = 1024;
 
@@ -136,20 +135,11 @@ hipError_t launch_adapt_select_run(const void* d_recs, uint32_t n, const MirtAda
     return hipGetLastError();
 }
 
-// The render stage: one thread per pixel of the buffer (a.n_units of them), one wave per block; a.lds_bytes = stage_scene's image without
-// the tables + the wave's traversal stacks (BVH build); `a` carries the camera, the tables, the sky, the tree, the row fields, spp,
-// num_bounces and seed_mix as a render launch's does.
-// run: adapt_pixels_run_kernel, which takes the step's sample count from d_count[1] and not from a.spp.
-hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, bool run, hipStream_t stream)
+// The render stage (run: adapt_pixels_run_kernel, which takes the step's sample count from the word behind the count and not from RenderArgs.spp)
+static QueryKernel adapt_kernel(const QueryPlan& p)
 {
-    const uint32_t blocks = (uint32_t)(((uint64_t)a.n_units + kAdaptThreads - 1u) / kAdaptThreads);
-    auto k = hosek ? (bvh ? adapt_pixels_kernel<true, true> : adapt_pixels_kernel<true, false>)
-                   : (bvh ? adapt_pixels_kernel<false, true> : adapt_pixels_kernel<false, false>);
-    if (run)
-        k = hosek ? (bvh ? adapt_pixels_run_kernel<true, true> : adapt_pixels_run_kernel<true, false>)
-                  : (bvh ? adapt_pixels_run_kernel<false, true> : adapt_pixels_run_kernel<false, false>);
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(kAdaptThreads), a.lds_bytes, stream, a, static_cast<adapt_u4*>(d_recs), d_list, d_count);
-    return hipGetLastError();
+    if (!p.run) return with_bools<QueryKernel>([](auto H, auto B) { return kernel_handle(adapt_pixels_kernel<H.value, B.value>); }, p.hosek, p.bvh);
+    return with_bools<QueryKernel>([](auto H, auto B) { return kernel_handle(adapt_pixels_run_kernel<H.value, B.value>); }, p.hosek, p.bvh);
 }
 
 hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream)

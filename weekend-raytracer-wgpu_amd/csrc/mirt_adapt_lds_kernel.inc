@@ -20,7 +20,6 @@
 // build 5; only <false,false> fits as it is.  So the bound stays 4, and where LDS allows more blocks (mirt_adapt_lds_plan: up to 8) the
 // occupancy answer is the smaller number.  A large flat table allows one or two blocks per CU: documented, not tuned.
 
-constexpr uint32_t kAdaptLdsThreads = 256;          // four waves share one staged scene
 #ifndef MIRT_ADAPT_LDS_MINW
 #define MIRT_ADAPT_LDS_MINW 4                       // (experiment builds: -DMIRT_ADAPT_LDS_MINW=6)
 #endif
@@ -37,31 +36,8 @@ constexpr uint32_t kAdaptLdsMinWaves = MIRT_ADAPT_LDS_MINW;     // waves per SIM
 #undef MIRT_ADAPT_RUN
 #undef MIRT_ADAPT_LDS_KERNEL
 
-using AdaptLdsKernel = void (*)(RenderArgs, adapt_u4*, const uint32_t*, const uint32_t*);
-
-static AdaptLdsKernel adapt_lds_kernel(bool hosek, bool grid, bool run)
+static QueryKernel adapt_lds_kernel(const QueryPlan& p)
 {
-    if (run)
-        return hosek ? (grid ? adapt_pixels_lds_run_kernel<true, true> : adapt_pixels_lds_run_kernel<true, false>)
-                     : (grid ? adapt_pixels_lds_run_kernel<false, true> : adapt_pixels_lds_run_kernel<false, false>);
-    return hosek ? (grid ? adapt_pixels_lds_kernel<true, true> : adapt_pixels_lds_kernel<true, false>)
-                 : (grid ? adapt_pixels_lds_kernel<false, true> : adapt_pixels_lds_kernel<false, false>);
-}
-
-// blocks of the build that are resident per CU at once with lds_bytes of LDS each (the occupancy query, asked once per kernel and size)
-uint32_t adapt_lds_blocks_per_cu(bool hosek, bool grid, bool run, uint32_t lds_bytes)
-{
-    // (blocks_per_cu keys its cache on the kernel's address and never calls through the pointer)
-    return blocks_per_cu(reinterpret_cast<RenderKernel>(reinterpret_cast<void*>(adapt_lds_kernel(hosek, grid, run))), kAdaptLdsThreads, lds_bytes);
-}
-
-// The render stage of an MIRT_ADAPT_LDS step: grid_blocks blocks of kAdaptLdsThreads; `a` carries the camera (with the pinhole word set), the
-// tables, the sky, the grid (grid build: grid, grid_bytes, grid_flat_y), sph3, the row fields, width, height, spp, num_bounces and seed_mix as
-// a render launch's does, px_groups_log2 = 0 or the forced g + 1, and lds_bytes = mirt_adapt_lds_plan's bytes per block.
-// run: adapt_pixels_lds_run_kernel, which takes the step's sample count from d_count[1] and not from a.spp.
-hipError_t launch_adapt_pixels_lds(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, bool hosek, bool grid,
-                                   bool run, hipStream_t stream)
-{
-    return launch_with_lds(adapt_lds_kernel(hosek, grid, run), dim3(grid_blocks), dim3(kAdaptLdsThreads), a, LaunchOn(stream), static_cast<adapt_u4*>(d_recs), d_list,
-                           d_count);
+    if (p.run) return with_bools<QueryKernel>([](auto H, auto G) { return kernel_handle(adapt_pixels_lds_run_kernel<H.value, G.value>); }, p.hosek, p.grid);
+    return with_bools<QueryKernel>([](auto H, auto G) { return kernel_handle(adapt_pixels_lds_kernel<H.value, G.value>); }, p.hosek, p.grid);
 }

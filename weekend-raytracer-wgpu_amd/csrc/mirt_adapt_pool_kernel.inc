@@ -45,27 +45,12 @@ struct AdaptPoolState {
 #undef MIRT_ADAPT_POOL_KERNEL
 
 // ---- one build per geometry of kBvhPoolSlotChoices (the pooled HBM render's table) x HOSEK ----
-using AdaptPoolKernel = void (*)(RenderArgs, adapt_u4*, const uint32_t*, const uint32_t*);
-template <uint32_t SL>
-static AdaptPoolKernel adapt_pool_kernel_(bool hosek, bool run)
+static QueryKernel adapt_pool_kernel(const QueryPlan& p)
 {
-    constexpr uint32_t T = kBvhPoolThreads, MW = kBvhPoolMinWaves;
-    if (run) return hosek ? adapt_pixels_pool_run_kernel<T, SL, MW, true> : adapt_pixels_pool_run_kernel<T, SL, MW, false>;
-    return hosek ? adapt_pixels_pool_kernel<T, SL, MW, true> : adapt_pixels_pool_kernel<T, SL, MW, false>;
-}
-
-static AdaptPoolKernel adapt_pool_kernel(uint32_t slots, bool hosek, bool run)
-{
-    return for_bvh_pool_slots(slots, [=](auto sl) { return adapt_pool_kernel_<decltype(sl)::value>(hosek, run); });
-}
-
-// The render stage of a pooled step: grid_blocks blocks of kBvhPoolThreads, whose waves stride over the units of 16 list entries; a.lds_bytes =
-// mirt_adapt_pool_plan's bytes per block, a.bvh_stack_entries its stack entries.  run: adapt_pixels_pool_run_kernel, which takes the step's sample
-// count from d_count[1] and not from a.spp
-hipError_t launch_adapt_pixels_pool(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, uint32_t slots, bool hosek,
-                                    bool run, hipStream_t stream)
-{
-    const AdaptPoolKernel k = adapt_pool_kernel(slots, hosek, run);
-    if (!k) return hipErrorInvalidValue;
-    return launch_with_lds(k, dim3(grid_blocks), dim3(kBvhPoolThreads), a, LaunchOn(stream), static_cast<adapt_u4*>(d_recs), d_list, d_count);
+    if (p.threads != kBvhPoolThreads || p.min_waves != kBvhPoolMinWaves) return nullptr;      // not a geometry of plan_bvh_pool
+    return for_bvh_pool_slots(p.slots, [&](auto sl) -> QueryKernel {
+        constexpr uint32_t T = kBvhPoolThreads, SL = decltype(sl)::value, MW = kBvhPoolMinWaves;
+        if (p.run) return with_bools<QueryKernel>([](auto H) { return kernel_handle(adapt_pixels_pool_run_kernel<T, SL, MW, H.value>); }, p.hosek);
+        return with_bools<QueryKernel>([](auto H) { return kernel_handle(adapt_pixels_pool_kernel<T, SL, MW, H.value>); }, p.hosek);
+    });
 }

@@ -1228,31 +1228,16 @@ static void fill_bvh_args(const MirtContext* c, mirt::RenderArgs* a, uint32_t st
     a->bvh_stack_entries = stack_entries;
 }
 
-// The tree and the traversal stacks of the query kernels that run one thread per ray or pixel in kBlockThreads blocks (ray queries, feature
-// frames): the stacks hold as many node references per lane as the resident tree is deep (a push happens at inner nodes only, at
-// most one per level): 256 x depth bytes per wave, as in the pooled kernel -- at most 32 KB per block (MIRT_BVH_MAX_DEPTH)
-static void fill_query_stacks(const MirtContext* c, mirt::RenderArgs* a, bool bvh)
+// The kernel arguments a query plan decides (mirt_launch_plan.h: QueryPlan) and what of the context goes with them -- the tree, the grid,
+// sph3 --, behind fill_common_args: the counterpart of fill_render_args for the query launches.
+static void fill_query_args(const MirtContext* c, const mirt::QueryPlan& pl, mirt::RenderArgs* a)
 {
-    const uint32_t entries = bvh ? (c->bvh_plan.max_depth ? c->bvh_plan.max_depth : 1u) : 0u;
-    fill_bvh_args(c, a, entries);
-    a->lds_bytes = (mirt::kBlockThreads / 64u) * 64u * 4u * entries;
-}
-
-// Blocks of a pooled query launch (radiance query, adaptive step) over `units` units of 16, one unit per wave; `at_most` != 0
-// (MIRT_*_POOL_BLOCKS): no more blocks than that, their waves stride over the units
-static uint32_t pooled_query_blocks(uint64_t units, uint32_t threads, uint32_t at_most)
-{
-    const uint64_t waves = threads / 64u, blocks = (units + waves - 1u) / waves;
-    return (uint32_t)(at_most != 0u && blocks > at_most ? at_most : blocks);
-}
-
-// a query kernel is queued behind ev_trace_begin / before ev_trace_end: what mirt_ctx_trace_stats will wait for and fold
-static void mark_trace_queued(MirtContext* c, bool timed, bool counted)
-{
-    c->trace_pending = true;
-    c->trace_timed = timed;
-    c->trace_counted = counted;
-    c->trace_stats = MirtRayStats{};
+    const bool lds_scene = pl.family == mirt::kQueryAdaptLds;
+    if (!lds_scene) fill_bvh_args(c, a, pl.bvh_stack_entries);
+    else for (int k = 0; k < 12; ++k) a->sph3[k] = c->sph3[k];
+    if (pl.grid) { a->grid = c->d_grid; a->grid_bytes = c->grid_bytes; a->grid_flat_y = c->grid_flat_y ? 1u : 0u; }
+    if (pl.rays_as_row) { a->width = pl.n_rays; a->height = 1u; }
+    a->lds_bytes = pl.lds_bytes; a->n_units = pl.n_units; a->px_groups_log2 = pl.px_groups_log2;
 }
 
 // jenkins-folds a caller's 64-bit seed into the 32-bit key of a launch's RNG streams (RenderArgs.seed_mix)
@@ -1587,32 +1572,39 @@ static int queue_ray_sort(MirtContext* c, const void* d_rays, uint32_t n, hipStr
     return MIRT_OK;
 }
 
+// The tail of a ray query, a feature frame and a radiance query: the plan's kernel on `st` behind ev_trace_begin, its name, ev_trace_end, and
+// what mirt_ctx_trace_stats will wait for and fold.
+static int queue_query(MirtContext* c, const mirt::QueryPlan& pl, const mirt::RenderArgs& a, const mirt::QueryBuffers& b, hipStream_t st, bool timed)
+{
+    HIP_TRY(kx::launch_query(pl, a, b, st));
+    mirt::query_kernel_name(pl, c->last_kernel, sizeof c->last_kernel);
+    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
+    c->trace_pending = true;
+    c->trace_timed = timed;
+    c->trace_counted = pl.count;
+    c->trace_stats = MirtRayStats{};
+    return MIRT_OK;
+}
+
 // Queue trace_rays_kernel<bvh, any, count> (trace_rays_sorted_kernel behind the code kernel and the sort with MIRT_RAYS_SORT) for n > 0 rays in
 // device memory on `st`.  No host synchronisation.
 static int launch_trace(MirtContext* c, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, hipStream_t st)
 {
-    const bool bvh = !(flags & MIRT_RAYS_FLAT), any = (flags & MIRT_RAYS_ANY_HIT) != 0, count = (flags & MIRT_RAYS_COUNT) != 0;
-    const bool sort = (flags & MIRT_RAYS_SORT) != 0;
+    const mirt::QueryPlan pl = mirt::plan_trace(plan_facts(c), c->tuning, n, flags);
     mirt::RenderArgs a{};
     fill_common_args(c, &a, MirtParams{}, 0u, -1);
     a.counters = c->d_trace_counters;
-    fill_query_stacks(c, &a, bvh);
+    fill_query_args(c, pl, &a);
     const bool timed = c->timing;
-    const uint32_t* d_order = nullptr;
-    if (sort) {           // first: a failed allocation leaves nothing queued
+    mirt::QueryBuffers b{ d_rays, d_hits, nullptr, nullptr };
+    if (pl.sorted) {      // first: a failed allocation leaves nothing queued
         if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
-        const int rc = queue_ray_sort(c, d_rays, n, st, &d_order);
+        const int rc = queue_ray_sort(c, d_rays, n, st, &b.order);
         if (rc != MIRT_OK) return rc;
     }
-    if (count) HIP_TRY(hipMemsetAsync(c->d_trace_counters, 0, sizeof(unsigned long long) * mirt::kNumCounters, st));
-    if (timed && !sort) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
-    if (sort) HIP_TRY(kx::launch_trace_rays_sorted(a, d_rays, d_hits, n, d_order, bvh, any, count, st));
-    else HIP_TRY(kx::launch_trace_rays(a, d_rays, d_hits, n, bvh, any, count, st));
-    const char* tf[2] = { "false", "true" };
-    snprintf(c->last_kernel, sizeof c->last_kernel, "trace_rays%s_kernel<%s,%s,%s>", sort ? "_sorted" : "", tf[bvh], tf[any], tf[count]);
-    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
-    mark_trace_queued(c, timed, count);
-    return MIRT_OK;
+    if (pl.count) HIP_TRY(hipMemsetAsync(c->d_trace_counters, 0, sizeof(unsigned long long) * mirt::kNumCounters, st));
+    if (timed && !pl.sorted) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    return queue_query(c, pl, a, b, st, timed);
 }
 
 int mirt_ctx_trace_rays_device(MirtContext* c, const void* d_rays, uint32_t n_rays, uint32_t flags, void* d_hits, void* hip_stream)
@@ -1713,17 +1705,13 @@ static int check_features(const MirtContext* c, const MirtParams* p, uint32_t fl
 // accumulation stay as they are; the event pair and the pending flag are the ray queries' (mirt_ctx_trace_stats folds the time).
 static int launch_features(MirtContext* c, const MirtParams* p, uint32_t flags, void* d_out, hipStream_t st)
 {
-    const bool bvh = !(flags & MIRT_FEATURES_FLAT);
+    const mirt::QueryPlan pl = mirt::plan_features(plan_facts(c), c->tuning, *p, flags);
     mirt::RenderArgs a{};
     fill_common_args(c, &a, *p, out_rows(p), pinhole_word(c));     // the camera with generate_primary's pinhole word, as in launch_render
-    fill_query_stacks(c, &a, bvh);                                 // traversal stacks as for ray queries
+    fill_query_args(c, pl, &a);                                    // traversal stacks as for ray queries
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
-    HIP_TRY(kx::launch_features(a, d_out, bvh, st));
-    snprintf(c->last_kernel, sizeof c->last_kernel, "feature_frame_kernel<%s>", bvh ? "true" : "false");
-    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
-    mark_trace_queued(c, timed, false);
-    return MIRT_OK;
+    return queue_query(c, pl, a, mirt::QueryBuffers{ nullptr, d_out, nullptr, nullptr }, st, timed);
 }
 
 int mirt_ctx_render_features_device(MirtContext* c, const MirtParams* p, uint32_t flags, void* d_out, size_t out_len, void* hip_stream)
@@ -1795,45 +1783,20 @@ static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, co
 // deep; otherwise the launch is the one without the flag.
 static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const MirtRadianceParams* p, void* d_out, hipStream_t st)
 {
-    const bool bvh = !(p->flags & MIRT_RADIANCE_FLAT), hosek = (p->flags & MIRT_RADIANCE_SKY_HOSEK) != 0, sort = (p->flags & MIRT_RADIANCE_SORT) != 0;
-    MirtBvhPoolPlan plan{};
-    if ((p->flags & MIRT_RADIANCE_POOL) && bvh) plan = mirt::pooled_bvh_plan(plan_facts(c), c->tuning, hosek, 0u, p->num_bounces);
-    const bool pooled = plan.slots != 0u;
+    const mirt::QueryPlan pl = mirt::plan_radiance(plan_facts(c), c->tuning, n, *p);
     MirtParams q{};                                       // the query's sampling fields as a render call's; no frame, no rows
     q.spp = p->spp; q.num_bounces = p->num_bounces; q.flags = p->flags; q.seed = p->seed; q.sample_begin = p->sample_begin;
     mirt::RenderArgs a{};
     fill_common_args(c, &a, q, 0u, -1);                   // (the camera stays zero: a query has none)
-    a.n_units = n;
-    // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
-    fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
-    a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
-    uint32_t pool_blocks = 0;
-    if (pooled) {                                         // units of 16 slots of the batch, one unit per wave: the hardware's dispatcher is the balancer
-        a.width = n;
-        a.height = 1u;
-        a.n_units = (uint32_t)(((uint64_t)n + mirt::kStripPixels - 1u) / mirt::kStripPixels);
-        a.lds_bytes = plan.lds_bytes_per_block;           // camera words (+ sky), the block's pools, its waves' traversal stacks
-        pool_blocks = pooled_query_blocks(a.n_units, plan.threads, c->tuning.radiance_pool_blocks);
-    }
+    fill_query_args(c, pl, &a);
     const bool timed = c->timing;
     if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
-    const uint32_t* d_order = nullptr;
-    if (sort) {
-        const int rc = queue_ray_sort(c, d_rays, n, st, &d_order);
+    mirt::QueryBuffers b{ d_rays, d_out, nullptr, nullptr };
+    if (pl.sorted) {
+        const int rc = queue_ray_sort(c, d_rays, n, st, &b.order);
         if (rc != MIRT_OK) return rc;
     }
-    const char* tf[2] = { "false", "true" };
-    if (pooled) {
-        HIP_TRY(kx::launch_radiance_pool(a, d_rays, d_out, d_order, pool_blocks, plan.slots, hosek, st));
-        snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays_pool_kernel<%u,%u,%u,%s,%s>", plan.threads, plan.slots, mirt::kBvhPoolMinWaves, tf[hosek], tf[sort]);
-    } else {
-        if (sort) HIP_TRY(kx::launch_radiance_sorted(a, d_rays, d_out, d_order, hosek, bvh, st));
-        else HIP_TRY(kx::launch_radiance(a, d_rays, d_out, hosek, bvh, st));
-        snprintf(c->last_kernel, sizeof c->last_kernel, "radiance_rays%s_kernel<%s,%s>", sort ? "_sorted" : "", tf[hosek], tf[bvh]);
-    }
-    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
-    mark_trace_queued(c, timed, false);
-    return MIRT_OK;
+    return queue_query(c, pl, a, b, st, timed);
 }
 
 int mirt_ctx_trace_radiance_device(MirtContext* c, const void* d_rays, uint32_t n_rays, const MirtRadianceParams* p, void* d_out, void* hip_stream)
@@ -2093,21 +2056,9 @@ int mirt_ctx_adapt_reset(MirtContext* c, const MirtParams* p)
     return MIRT_OK;
 }
 
-// The layout of an MIRT_ADAPT_LDS step on the resident LDS scene: the scene's grid unless MIRT_FLAG_NO_GRID asks for the
-// flat scan, else the flat tables if they fit; plan_adapt_lds's geometry of it, or all fields 0 where neither fits a block's LDS.
-static MirtAdaptLdsPlan adapt_lds_layout(const MirtContext* c, const MirtParams& q)
-{
-    const bool hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
-    MirtAdaptLdsPlan plan{};
-    if (c->grid_bytes != 0u && !(q.flags & MIRT_FLAG_NO_GRID)) plan = mirt::plan_adapt_lds(c->n_spheres, c->n_mats, c->grid_bytes, hosek, c->lds_per_cu);
-    if (plan.lds_bytes_per_block > c->lds_per_block) plan = MirtAdaptLdsPlan{};
-    if (plan.threads == 0u && c->fits_flat) plan = mirt::plan_adapt_lds(c->n_spheres, c->n_mats, 0u, hosek, c->lds_per_cu);
-    if (plan.lds_bytes_per_block > c->lds_per_block) plan = MirtAdaptLdsPlan{};
-    return plan;
-}
-
-// What a step is refused for, in the header's order; *q = the params the launch runs with.  Nothing is queued before the last check has passed.
-static int check_adapt_step(const MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, MirtParams* q)
+// What a step (`run`: the steps of a run) is refused for, in the header's order; *q = the params the launch runs with, *pl = its plan, made
+// once per call.  Nothing is queued before the last check has passed.
+static int check_adapt_step(const MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, bool run, MirtParams* q, mirt::QueryPlan* pl)
 {
     if (!c || !p || !adapt) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/adapt is null");
     if (!c->have_scene || (!c->hbm && !(adapt->flags & MIRT_ADAPT_LDS)))
@@ -2125,55 +2076,23 @@ static int check_adapt_step(const MirtContext* c, const MirtParams* p, const Mir
         return fail(MIRT_ERR_SPP_RANGE, "max_samples %u is out of range: at most %u", adapt->max_samples, (unsigned)MIRT_MAX_SPP_PER_CALL);
     if (!c->d_adapt || c->adapt_pixels == 0 || c->adapt_width != p->width || c->adapt_rows != out_rows(p))
         return fail(MIRT_ERR_OUT_BUFFER, "the adaptive buffer does not match these params: call mirt_ctx_adapt_reset first");
-    if (!c->hbm && adapt_lds_layout(c, *q).threads == 0u)
-        return fail(MIRT_ERR_SCENE_TOO_LARGE, "this scene fits LDS in neither layout an MIRT_ADAPT_LDS step has%s",
-                    (q->flags & MIRT_FLAG_NO_GRID) ? " (MIRT_FLAG_NO_GRID: the flat one only)" : "");
+    // the plan: MIRT_ADAPT_POOL where the pool's own limits allow it, otherwise the step without the flag; a scene in LDS needs a layout that fits
+    *pl = mirt::plan_adapt(plan_facts(c), c->tuning, *q, adapt->flags, run, c->adapt_pixels);
+    if (pl->status != MIRT_OK) return fail(pl->status, "%s", pl->message);
     return MIRT_OK;
 }
 
-// A step (run == nullptr) or the run->max_steps steps of a run, queued on one stream between one event pair; `q` has passed check_adapt_step.
-static int queue_adapt_steps(MirtContext* c, const MirtParams& q, const MirtAdaptParams* adapt, const MirtAdaptRun* run, void* hip_stream)
+// A step (run == nullptr) or the run->max_steps steps of a run, queued on one stream between one event pair; `q` and its plan have passed
+// check_adapt_step.
+static int queue_adapt_steps(MirtContext* c, const MirtParams& q, mirt::QueryPlan pl, const MirtAdaptParams* adapt, const MirtAdaptRun* run, void* hip_stream)
 {
     HIP_TRY(hipSetDevice(c->device));
     const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const bool bvh = c->hbm && !(q.flags & MIRT_FLAG_NO_GRID), hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
+    // an MIRT_ADAPT_LDS step runs a persistent grid: its kernel's occupancy bounds the blocks, as a render launch's does (plan_blocks)
+    if (pl.family == mirt::kQueryAdaptLds) mirt::query_plan_blocks(pl, kx::blocks_per_cu(kx::query_kernel(pl), pl.threads, pl.lds_bytes));
     mirt::RenderArgs a{};
     fill_common_args(c, &a, q, c->adapt_rows, pinhole_word(c));       // as launch_render
-    a.n_units = (uint32_t)c->adapt_pixels;
-    // MIRT_ADAPT_LDS on a scene that lives in LDS (check_adapt_step has seen the flag and a layout): adapt_pixels_lds_kernel in a persistent
-    // grid of the blocks that are resident at once -- the plan's LDS bound and the occupancy answer, as plan_blocks -- or fewer, for fewer pixels
-    const bool lds = !c->hbm;
-    MirtAdaptLdsPlan lds_plan{};
-    uint32_t lds_blocks = 0;
-    if (lds) {
-        lds_plan = adapt_lds_layout(c, q);
-        a.lds_bytes = lds_plan.lds_bytes_per_block;
-        if (lds_plan.grid) { a.grid = c->d_grid; a.grid_bytes = c->grid_bytes; a.grid_flat_y = c->grid_flat_y ? 1u : 0u; }
-        for (int k = 0; k < 12; ++k) a.sph3[k] = c->sph3[k];
-        a.px_groups_log2 = c->tuning.adapt_lds_groups;
-        uint32_t per_cu = kx::adapt_lds_blocks_per_cu(hosek, lds_plan.grid != 0u, run != nullptr, a.lds_bytes);
-        if (per_cu > lds_plan.blocks_per_cu) per_cu = lds_plan.blocks_per_cu;
-        if (per_cu == 0u) per_cu = 1u;
-        const uint64_t all = (c->adapt_pixels + lds_plan.threads - 1u) / lds_plan.threads, resident = (uint64_t)c->cu_count * per_cu;
-        lds_blocks = (uint32_t)(all < resident ? all : resident);
-        if (c->tuning.adapt_lds_blocks != 0u && lds_blocks > c->tuning.adapt_lds_blocks) lds_blocks = c->tuning.adapt_lds_blocks;
-    }
-    // MIRT_ADAPT_POOL on the BVH build: adapt_pixels_pool_kernel in the geometry mirt_adapt_pool_plan gives for the resident tree, where the
-    // pool's own limits allow it -- 8-bit bounce counters, a geometry that fits beside the stacks of a tree this deep; otherwise the step
-    // is the one without the flag.
-    MirtBvhPoolPlan plan{};
-    if ((adapt->flags & MIRT_ADAPT_POOL) && bvh) plan = mirt::pooled_bvh_plan(plan_facts(c), c->tuning, hosek, mirt::kAdaptPoolExtraBytes, q.num_bounces);
-    const bool pooled = plan.slots != 0u;
-    // path_radiance walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky)
-    if (!lds) {
-        fill_bvh_args(c, &a, pooled ? plan.stack_entries : 0u);
-        a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(c->n_spheres, hosek) + (bvh ? mirt::kBvhStackBytesPerWave : 0u));     // one wave per block
-    }
-    uint32_t pool_blocks = 0;
-    if (pooled) {                                           // units of 16 list entries; the host does not know the count: a grid for all pixels
-        a.lds_bytes = plan.lds_bytes_per_block;             // camera words (+ sky), the block's pools, its waves' traversal stacks
-        pool_blocks = pooled_query_blocks((c->adapt_pixels + mirt::kStripPixels - 1u) / mirt::kStripPixels, plan.threads, c->tuning.adapt_pool_blocks);
-    }
+    fill_query_args(c, pl, &a);
     uint32_t* head = reinterpret_cast<uint32_t*>(c->d_adapt_sel);
     uint32_t* list = reinterpret_cast<uint32_t*>(c->d_adapt_sel + 16u);
     const bool timed = c->timing;
@@ -2189,17 +2108,9 @@ static int queue_adapt_steps(MirtContext* c, const MirtParams& q, const MirtAdap
                                                 c->d_adapt_sel + c->adapt_off_log + (size_t)j * sizeof(MirtAdaptRunStep), st));
         else
             HIP_TRY(kx::launch_adapt_select(c->d_adapt, (uint32_t)c->adapt_pixels, *adapt, q.spp, flags, counts, list, head, st));
-        if (lds) HIP_TRY(kx::launch_adapt_pixels_lds(a, c->d_adapt, list, head, lds_blocks, hosek, lds_plan.grid != 0u, run != nullptr, st));
-        else if (pooled) HIP_TRY(kx::launch_adapt_pixels_pool(a, c->d_adapt, list, head, pool_blocks, plan.slots, hosek, run != nullptr, st));
-        else HIP_TRY(kx::launch_adapt_pixels(a, c->d_adapt, list, head, hosek, bvh, run != nullptr, st));
+        HIP_TRY(kx::launch_query(pl, a, mirt::QueryBuffers{ nullptr, c->d_adapt, list, head }, st));
     }
-    const char* tf[2] = { "false", "true" };
-    if (lds)
-        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_lds%s_kernel<%s,%s>", run ? "_run" : "", tf[hosek], tf[lds_plan.grid != 0u]);
-    else if (pooled)
-        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels_pool%s_kernel<%u,%u,%u,%s>", run ? "_run" : "", plan.threads, plan.slots, mirt::kBvhPoolMinWaves, tf[hosek]);
-    else
-        snprintf(c->last_kernel, sizeof c->last_kernel, "adapt_pixels%s_kernel<%s,%s>", run ? "_run" : "", tf[hosek], tf[bvh]);
+    mirt::query_kernel_name(pl, c->last_kernel, sizeof c->last_kernel);
     HIP_TRY(hipEventRecord(c->ev_adapt_end, st));
     c->adapt_pending = true;
     c->adapt_timed = timed;
@@ -2212,9 +2123,10 @@ static int queue_adapt_steps(MirtContext* c, const MirtParams& q, const MirtAdap
 int mirt_ctx_adapt_step_device(MirtContext* c, const MirtParams* p, const MirtAdaptParams* adapt, void* hip_stream)
 {
     MirtParams q;
-    const int rc = check_adapt_step(c, p, adapt, &q);
+    mirt::QueryPlan pl;
+    const int rc = check_adapt_step(c, p, adapt, false, &q, &pl);
     if (rc != MIRT_OK) return rc;
-    return queue_adapt_steps(c, q, adapt, nullptr, hip_stream);
+    return queue_adapt_steps(c, q, pl, adapt, nullptr, hip_stream);
 }
 
 // ---- adaptive runs (include/mirt.h) ----
@@ -2247,10 +2159,11 @@ int mirt_ctx_adapt_run_device(MirtContext* c, const MirtParams* p, const MirtAda
 {
     if (!c || !p || !adapt || !run) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/adapt/run is null");
     MirtParams q;
-    int rc = check_adapt_step(c, p, adapt, &q);
+    mirt::QueryPlan pl;
+    int rc = check_adapt_step(c, p, adapt, true, &q, &pl);
     if (rc != MIRT_OK) return rc;
     if ((rc = check_adapt_run(run, q.spp, true)) != MIRT_OK) return rc;
-    return queue_adapt_steps(c, q, adapt, run, hip_stream);
+    return queue_adapt_steps(c, q, pl, adapt, run, hip_stream);
 }
 
 int mirt_ctx_adapt_run_read(MirtContext* c, MirtAdaptRunStep* out, size_t len, uint32_t* n_steps)

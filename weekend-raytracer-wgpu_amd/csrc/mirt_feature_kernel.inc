@@ -118,12 +118,7 @@ __global__ __launch_bounds__(kBlockThreads) void feature_frame_kernel(RenderArgs
     }
 }
 
-// one thread per pixel of the rows the launch selects; a.lds_bytes = the block's traversal stacks (0 for the flat scan)
-hipError_t launch_features(const RenderArgs& a, void* d_out, bool bvh, hipStream_t stream)
+static QueryKernel feature_kernel(const QueryPlan& p)
 {
-    const uint64_t npix = (uint64_t)a.out_rows * a.width;
-    const uint32_t blocks = (uint32_t)((npix + kBlockThreads - 1u) / kBlockThreads);
-    hipLaunchKernelGGL(bvh ? feature_frame_kernel<true> : feature_frame_kernel<false>, dim3(blocks), dim3(kBlockThreads), a.lds_bytes, stream,
-                       a, static_cast<trace_u4*>(d_out));
-    return hipGetLastError();
+    return with_bools<QueryKernel>([](auto B) { return kernel_handle(feature_frame_kernel<B.value>); }, p.bvh);
 }

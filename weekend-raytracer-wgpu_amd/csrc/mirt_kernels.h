@@ -242,6 +242,8 @@ struct LaunchOn {
 // where the build has none (parity mode and every counting launch in fast_build).  mirt_ctx_last_kernel reports the same instance
 // (plan_kernel_name, mirt_launch_plan.h).
 using RenderKernel = void (*)(RenderArgs);
+using QueryKernel = const void*;      // a query kernel's handle: what the runtime's launch, attribute and occupancy calls take
+struct QueryBuffers { const void* in; void* out; const uint32_t* order; const uint32_t* count; };
 namespace fast_build {
 RenderKernel render_kernel(const RenderPlan& plan);
 }
@@ -262,29 +264,16 @@ hipError_t launch_resolve(const unsigned long long* accum, uint32_t* out, uint64
 hipError_t launch_selftest_math(unsigned long long* d_mismatches, hipStream_t stream);
 // d_counts[3]: decided inputs, parity mismatches and zeros among them (mirt_ctx_selftest_checker_sign)
 hipError_t launch_selftest_checker_sign(unsigned long long* d_counts, hipStream_t stream);
-// mirt_ctx_trace_rays*: trace_rays_kernel<bvh, any, count> (mirt_trace_kernel.inc), one thread per ray.  `a` carries the tree exactly as a render
-// launch's does, bvh_stack_entries = the stack entries per lane, lds_bytes = 256 x that per wave of the block (0 for the flat scan), and
-// `counters`; d_rays / d_hits: [n_rays] MirtRay / MirtRayHit in device memory, 4-byte aligned.
-hipError_t launch_trace_rays(const RenderArgs& a, const void* d_rays, void* d_hits, uint32_t n_rays, bool bvh, bool any, bool count, hipStream_t stream);
-// MIRT_RAYS_SORT: trace_rays_sorted_kernel<bvh, any, count>, the same launch with slot k working on record d_order[k] ([n_rays] uint32 in device memory)
-hipError_t launch_trace_rays_sorted(const RenderArgs& a, const void* d_rays, void* d_hits, uint32_t n_rays, const uint32_t* d_order, bool bvh, bool any, bool count,
-                                    hipStream_t stream);
-// mirt_ctx_render_features*: feature_frame_kernel<bvh> (mirt_feature_kernel.inc), one thread per pixel of a.out_rows x a.width.  `a` carries the
-// camera (with the pinhole word set), the tables, the tree, seed_mix, spp, sample_begin and the row fields as a render launch's does,
-// bvh_stack_entries and lds_bytes as launch_trace_rays wants them; d_out: [out_rows x width] MirtFeaturePixel in device memory, 4-byte aligned.
-hipError_t launch_features(const RenderArgs& a, void* d_out, bool bvh, hipStream_t stream);
-// mirt_ctx_trace_radiance*: radiance_rays_kernel<hosek, bvh> (mirt_radiance_kernel.inc), one thread per ray, one wave per block.  `a` carries the tables, the sky and
-// the tree as a render launch's does, spp, sample_begin, num_bounces and seed_mix, n_units = the number of rays, flags = the caller's
-// MIRT_RADIANCE_* bits, lds_bytes = scene_lds_bytes_grid(n_spheres, hosek) + kBvhStackBytesPerWave (BVH build);
-// d_rays / d_out: [n_units] MirtRadianceRay / MirtRadiance in device memory, 4-byte aligned.
-hipError_t launch_radiance(const RenderArgs& a, const void* d_rays, void* d_out, bool hosek, bool bvh, hipStream_t stream);
-// MIRT_RADIANCE_SORT: radiance_rays_sorted_kernel<hosek, bvh>, slot k working on record d_order[k] ([n_units] uint32 in device memory)
-hipError_t launch_radiance_sorted(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, bool hosek, bool bvh, hipStream_t stream);
-// MIRT_RADIANCE_POOL: radiance_rays_pool_kernel<kBvhPoolThreads, slots, kBvhPoolMinWaves, hosek, d_order != nullptr> (mirt_radiance_pool_kernel.inc),
-// the pooled HBM render's schedule on units of 16 rays.  `a` as for launch_radiance, but n_units = ceil(n_rays / 16), width = n_rays, and
-// bvh_stack_entries / lds_bytes as the pooled render's (mirt_bvh_pool_plan); grid_blocks blocks of kBvhPoolThreads, whose waves stride over the units.
-hipError_t launch_radiance_pool(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, uint32_t grid_blocks, uint32_t slots, bool hosek,
-                                hipStream_t stream);
+// The query launches (ray queries, feature frames, radiance queries, the render stage of an adaptive step): query_kernel is the one template
+// instance a QueryPlan names (mirt_launch_plan.h, which also says what `a` must carry), nullptr where there is none; launch_query dispatches
+// it in the plan's geometry with `a` and the family's buffers, all in device memory:
+//   trace                 in: [n_rays] MirtRay, out: [n_rays] MirtRayHit, 4-byte aligned; order: the permutation of a sorted launch, [n_rays] words
+//   features              out: [out_rows x width] MirtFeaturePixel, 4-byte aligned
+//   radiance(-pool)       in: [n_rays] MirtRadianceRay, out: [n_rays] MirtRadiance, 4-byte aligned; order: as above (nullptr: the caller's order)
+//   adapt(-pool, -lds)    out: the buffer's MirtAdaptPixel records, 16-byte aligned; order: the step's list; count: its head words {count, a run's spp}
+QueryKernel query_kernel(const QueryPlan& plan);
+hipError_t  launch_query(const QueryPlan& plan, const RenderArgs& a, const QueryBuffers& b, hipStream_t stream);
+uint32_t    blocks_per_cu(QueryKernel kernel, uint32_t threads, uint32_t lds_bytes);        // as above, of a query kernel
 // mirt_ctx_adapt_* (mirt_adapt_kernel.inc).  The select stage of a step over n >= 1 records (MirtAdaptPixel, 16-byte aligned):
 // adapt_select_kernel, adapt_scan_kernel, adapt_compact_kernel -- d_flags [n] bytes, d_block_counts [ceil(n / 256)] words, d_list [n] words, d_head
 // four words {count of the step, unused, 64-bit counter of samples added (+= count x spp)}, 8-byte aligned.
@@ -295,23 +284,6 @@ hipError_t launch_adapt_select(const void* d_recs, uint32_t n, const MirtAdaptPa
 // count x that to the counter and writes {count, spp} to d_log_entry (8-byte aligned).
 hipError_t launch_adapt_select_run(const void* d_recs, uint32_t n, const MirtAdaptParams& adapt, uint32_t base_spp, uint32_t min_items, uint32_t cap_spp,
                                    unsigned char* d_flags, uint32_t* d_block_counts, uint32_t* d_list, uint32_t* d_head, void* d_log_entry, hipStream_t stream);
-// ... and its render stage: adapt_pixels_kernel<hosek, bvh>, one thread per pixel of the buffer (a.n_units = out_rows x width), one wave per block; blocks
-// beyond *d_count return at once.  `a` carries the camera (with the pinhole word set), the tables, the sky, the tree, the row fields, width, height, spp,
-// num_bounces and seed_mix as a render launch's does; lds_bytes as launch_radiance wants them.  run: adapt_pixels_run_kernel<hosek, bvh>, the same text
-// with the sample count read from d_count[1] (wave-uniform) in the place of a.spp.
-hipError_t launch_adapt_pixels(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, bool hosek, bool bvh, bool run, hipStream_t stream);
-// MIRT_ADAPT_POOL: adapt_pixels_pool_kernel<kBvhPoolThreads, slots, kBvhPoolMinWaves, hosek> (mirt_adapt_pool_kernel.inc), the pooled schedule on units of
-// 16 list entries.  `a` as for launch_adapt_pixels, but bvh_stack_entries / lds_bytes as mirt_adapt_pool_plan gives them; grid_blocks blocks of
-// kBvhPoolThreads, whose waves stride over the units; blocks beyond ceil(*d_count / 16) units return at once.  run: adapt_pixels_pool_run_kernel, as above.
-hipError_t launch_adapt_pixels_pool(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, uint32_t slots, bool hosek,
-                                    bool run, hipStream_t stream);
-// MIRT_ADAPT_LDS: adapt_pixels_lds_kernel<hosek, grid> (mirt_adapt_lds_kernel.inc), the render stage of a step on a scene that lives in LDS:
-// grid_blocks blocks of 256 threads that share one staged scene, their waves striding over units of 64 >> g list entries.  `a` as for launch_adapt_pixels plus
-// the grid fields (grid build) and sph3, px_groups_log2 = 0 (the device chooses g) or the forced g + 1, lds_bytes = plan_adapt_lds's bytes per block.
-// run: adapt_pixels_lds_run_kernel, as above.  adapt_lds_blocks_per_cu: the occupancy query's answer for that build and LDS size.
-hipError_t launch_adapt_pixels_lds(const RenderArgs& a, void* d_recs, const uint32_t* d_list, const uint32_t* d_count, uint32_t grid_blocks, bool hosek, bool grid,
-                                   bool run, hipStream_t stream);
-uint32_t   adapt_lds_blocks_per_cu(bool hosek, bool grid, bool run, uint32_t lds_bytes);
 // adapt_resolve_kernel: n_pixels records -> RGBA8, every pixel over its own sample count
 hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);

@@ -2211,26 +2211,8 @@ struct PoolHbmState {
 #undef MIRT_POOL_HBM_KERNEL_FRAME
 
 // ------------------------------------------------------------------------------------------
-// launch helpers (host side; the launchers of the .inc files below use them too)
+// selector helpers (host side; the kernel selectors of the .inc files below and of the end of this file use them)
 // ------------------------------------------------------------------------------------------
-
-// kernel<<<g, b, a.lds_bytes, stream>>>(a, more...): the launch of every kernel whose first argument is RenderArgs.  `more` by
-// reference: a deduced value parameter drops the typedef of a pointer to 4-byte aligned vectors (trace_u4) and with it the alignment
-template <typename K, typename... More>
-static hipError_t launch_with_lds(K kernel, dim3 g, dim3 b, const RenderArgs& a, LaunchOn stream, const More&... more)
-{
-    if (a.lds_bytes > 48u * 1024u) {        // more than the default dynamic-LDS window: ask for it
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    if (stream.end != nullptr) {                   // the launch's event pair rides on the dispatch
-        hipExtLaunchKernelGGL(kernel, g, b, a.lds_bytes, stream.stream, stream.begin, stream.end, 0u, a, more...);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(kernel, g, b, a.lds_bytes, stream.stream, a, more...);
-    return hipGetLastError();
-}
 
 // The build of a pooled BVH kernel for `slots` path slots per wave: build(std::integral_constant<uint32_t, SLOTS>) for the entry of
 // kBvhPoolSlotChoices that equals `slots`, nullptr for every other number.  The one place that knows the table's length.
@@ -2245,6 +2227,22 @@ static auto for_bvh_pool_slots(uint32_t slots, Build build) -> decltype(build(Bv
     if (slots == kBvhPoolSlotChoices[3]) return build(BvhPoolSlots<3>{});
     return nullptr;
 }
+
+// run-time bools as compile-time ones: build(std::true_type / std::false_type ...), the first bool outermost.  K: what the build returns --
+// RenderKernel for the render selectors at the end of this file, QueryKernel for those of the .inc files below.  (K is named, not deduced:
+// a deduced result is instantiated where it is used, and the order of instantiation is the order of the kernels in the code object.)
+template <typename K = RenderKernel, typename Build>
+static K with_bools(Build build) { return build(); }
+template <typename K = RenderKernel, typename Build, typename... Rest>
+static K with_bools(Build build, bool b, Rest... rest)
+{
+    return b ? with_bools<K>([=](auto... more) { return build(std::true_type{}, more...); }, rest...)
+             : with_bools<K>([=](auto... more) { return build(std::false_type{}, more...); }, rest...);
+}
+
+// a kernel as the runtime knows it: the address of its handle (what hipLaunchKernel, hipFuncSetAttribute and the occupancy query take)
+template <typename K>
+static QueryKernel kernel_handle(K kernel) { return reinterpret_cast<QueryKernel>(kernel); }
 
 #ifdef MIRT_ISA_PROBES
 #include "mirt_isa_probes.inc"       // tools/isa_mix.py; never part of libmirt.so
@@ -2461,16 +2459,6 @@ uint32_t pool_scatter_queues(uint32_t n_routines, bool count)
 // same bits.  What the functions below can return is exactly what the library carries: the set is sparse on purpose, and each gap is
 // noted where it lies.  They are written in the order, outermost choice first and `true` first, in which the builds stand in the code object.
 
-// run-time bools as compile-time ones: build(std::true_type / std::false_type ...), the first bool outermost
-template <typename Build>
-static RenderKernel with_bools(Build build) { return build(); }
-template <typename Build, typename... Rest>
-static RenderKernel with_bools(Build build, bool b, Rest... rest)
-{
-    return b ? with_bools([=](auto... more) { return build(std::true_type{}, more...); }, rest...)
-             : with_bools([=](auto... more) { return build(std::false_type{}, more...); }, rest...);
-}
-
 // a family's render build, or its progressive-frame build (mirt_ctx_accum_frame_device: the *_frame_kernel of the same arguments)
 template <bool FRAME, auto... A> static RenderKernel strip_build() { if constexpr (FRAME) return render_pt_strip_frame_kernel<A...>; else return render_pt_strip_kernel<A...>; }
 template <bool FRAME, auto... A> static RenderKernel stream_build() { if constexpr (FRAME) return render_pt_stream_frame_kernel<A...>; else return render_pt_stream_kernel<A...>; }
@@ -2652,31 +2640,80 @@ RenderKernel render_kernel(const RenderPlan& p)
 }
 
 #ifndef MIRT_FAST_MATH
+// more dynamic LDS than the default window: the kernel is told before it is launched with it
+static hipError_t allow_lds(const void* kernel, uint32_t lds_bytes)
+{
+    return lds_bytes > 48u * 1024u ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) : hipSuccess;
+}
+
 // the launch of a render kernel of either build: kernel<<<blocks, threads, a.lds_bytes, on>>>(a)
 hipError_t launch_with_lds(RenderKernel kernel, uint32_t blocks, uint32_t threads, const RenderArgs& a, LaunchOn on)
 {
-    return launch_with_lds<RenderKernel>(kernel, dim3(blocks), dim3(threads), a, on);
+    const hipError_t e = allow_lds(reinterpret_cast<const void*>(kernel), a.lds_bytes);
+    if (e != hipSuccess) return e;
+    if (on.end != nullptr) {                       // the launch's event pair rides on the dispatch
+        hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), a.lds_bytes, on.stream, on.begin, on.end, 0u, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), a.lds_bytes, on.stream, a);
+    return hipGetLastError();
+}
+
+// ---- the kernel of a query launch, and its launch ----
+// query_kernel(plan) is the template instance a query plan names (mirt_launch_plan.h), nullptr where there is none (a pooled plan in a
+// geometry plan_bvh_pool does not make).  The selectors stand in the .inc files, where the builds are instantiated.
+QueryKernel query_kernel(const QueryPlan& p)
+{
+    switch (p.family) {
+    case kQueryTrace:        return trace_kernel(p);
+    case kQueryFeatures:     return feature_kernel(p);
+    case kQueryRadiance:     return radiance_kernel(p);
+    case kQueryRadiancePool: return radiance_pool_kernel(p);
+    case kQueryAdapt:        return adapt_kernel(p);
+    case kQueryAdaptPool:    return adapt_pool_kernel(p);
+    case kQueryAdaptLds:     return adapt_lds_kernel(p);
+    default:                 return nullptr;
+    }
+}
+
+// kernel<<<plan.blocks, plan.threads, a.lds_bytes, stream>>>(a, the family's buffers).  Only the pooled and the LDS families can pass the
+// default LDS window (the others' stacks and sky stay below it), so only they ever pay allow_lds's call.
+hipError_t launch_query(const QueryPlan& p, const RenderArgs& a, const QueryBuffers& b, hipStream_t stream)
+{
+    const QueryKernel k = query_kernel(p);
+    if (!k) return hipErrorInvalidValue;
+    const hipError_t e = allow_lds(k, a.lds_bytes);
+    if (e != hipSuccess) return e;
+    // the kernels' arguments behind RenderArgs, in their order (hipLaunchKernel copies as many as the kernel has, each by its own size)
+    const void* args[5] = { &a };
+    switch (p.family) {
+    case kQueryTrace:        args[1] = &b.in; args[2] = &b.out; args[3] = &p.n_rays; args[4] = &b.order; break;     // (rays, hits, n_rays[, order])
+    case kQueryFeatures:     args[1] = &b.out; break;                                                               // (pixels)
+    case kQueryRadiance:
+    case kQueryRadiancePool: args[1] = &b.in; args[2] = &b.out; args[3] = &b.order; break;                          // (rays, records[, order])
+    default:                 args[1] = &b.out; args[2] = &b.order; args[3] = &b.count; break;                       // (records, list, head words)
+    }
+    (void)hipLaunchKernel(k, dim3(p.blocks), dim3(p.threads), const_cast<void**>(args), a.lds_bytes, stream);
+    return hipGetLastError();
 }
 
 // Blocks of a kernel that are resident per CU at once (registers and LDS decide: the strip kernels use 59-106 VGPRs).  The
 // host sizes the persistent grids with it: a block that is launched but not resident holds its first work unit until some
 // other block exits, i.e. until the dispenser has run dry, and then runs that unit alone at the end of the launch.
-uint32_t blocks_per_cu(RenderKernel render_kernel, uint32_t threads, uint32_t lds_bytes)
+uint32_t blocks_per_cu(RenderKernel kernel, uint32_t threads, uint32_t lds_bytes) { return blocks_per_cu(reinterpret_cast<QueryKernel>(kernel), threads, lds_bytes); }
+uint32_t blocks_per_cu(QueryKernel kernel, uint32_t threads, uint32_t lds_bytes)
 {
     // asked once per (kernel, LDS size): the interactive loop launches every frame
     struct Entry { const void* kernel; uint32_t lds, blocks; };
     static Entry cache[64];
     static uint32_t used = 0;
     static std::mutex lock;
-    const void* const kernel = reinterpret_cast<const void*>(render_kernel);
     std::lock_guard<std::mutex> guard(lock);
     for (uint32_t i = 0; i < used; ++i)
         if (cache[i].kernel == kernel && cache[i].lds == lds_bytes) return cache[i].blocks;
     uint32_t blocks = 1u;
     int n = 0;
-    if ((lds_bytes <= 48u * 1024u ||
-         hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess) &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, (int)threads, lds_bytes) == hipSuccess && n >= 1)
+    if (allow_lds(kernel, lds_bytes) == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, (int)threads, lds_bytes) == hipSuccess && n >= 1)
         blocks = (uint32_t)n;
     if (used < 64u) cache[used++] = Entry{ kernel, lds_bytes, blocks };
     return blocks;

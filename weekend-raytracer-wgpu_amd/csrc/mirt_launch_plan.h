@@ -1,7 +1,7 @@
 // mirt_launch_plan.h — the launch plan of a render call: which kernel runs, in which geometry and with which schedule, as plain
-// data computed by two pure functions, and a third that prints the kernel's name (mirt_launch_plan.hip).  No HIP call, no context, no
-// getenv, no allocation: host arithmetic over a handful of numbers, so that a machine without a GPU can check it (host/plan_check.cpp,
-// tests/test_launch_plan.py, tests/test_launch_kernels.py).
+// data computed by two pure functions, and a third that prints the kernel's name (mirt_launch_plan.hip); below it the same for the query
+// launches (QueryPlan).  No HIP call, no context, no getenv, no allocation: host arithmetic over a handful of numbers, so that a machine
+// without a GPU can check it (host/plan_check.cpp, tests/test_launch_plan.py, tests/test_launch_kernels.py, tests/test_query_plan.py).
 // Plain C++ on top of include/mirt.h: g++ compiles it.
 #pragma once
 
@@ -141,5 +141,57 @@ void plan_blocks(RenderPlan& plan, uint32_t resident_per_cu);
 // The name mirt_ctx_last_kernel reports: the plan's kernel template and its arguments, without spaces, as the tests and tools read them;
 // "fast_build::" in front of the fast-math build's.
 void plan_kernel_name(const RenderPlan& plan, char* out, size_t out_len);
+
+// ---- query launches: ray queries, feature frames, radiance queries, adaptive steps and runs ----
+constexpr uint32_t kRadianceThreads = 64;    // radiance_rays_kernel: one wave per block (mirt_radiance_kernel.inc has the measurement)
+constexpr uint32_t kAdaptThreads    = 64;    // adapt_pixels_kernel: one wave per block, as kRadianceThreads
+constexpr uint32_t kAdaptLdsThreads = 256;   // adapt_pixels_lds_kernel: four waves share one staged scene
+
+// The kernel family of a query launch; with the bits below it names one template instance of the exact build: query_kernel(plan)
+// (mirt_kernels.h) is that instance and query_kernel_name(plan) prints it for mirt_ctx_last_kernel.
+//   trace          trace_rays[_sorted]_kernel<bvh, any, count>                      one thread per ray, kBlockThreads
+//   features       feature_frame_kernel<bvh>                                        one thread per pixel, kBlockThreads
+//   radiance       radiance_rays[_sorted]_kernel<hosek, bvh>                        one thread per ray, one wave per block
+//   radiance-pool  radiance_rays_pool_kernel<threads, slots, min waves, hosek, sorted>   units of 16 rays, one per wave, or the waves stride
+//   adapt          adapt_pixels[_run]_kernel<hosek, bvh>                            one thread per pixel of the buffer, one wave per block
+//   adapt-pool     adapt_pixels_pool[_run]_kernel<threads, slots, min waves, hosek>  units of 16 pixels of the buffer, as radiance-pool
+//   adapt-lds      adapt_pixels_lds[_run]_kernel<hosek, grid>                       a persistent grid of the blocks resident at once
+enum QueryFamily : uint32_t { kQueryTrace, kQueryFeatures, kQueryRadiance, kQueryRadiancePool, kQueryAdapt, kQueryAdaptPool, kQueryAdaptLds };
+
+// What a query launch decides, and the contract between it and its kernel: fill_query_args (mirt_api.hip) copies the fields of the
+// second group into RenderArgs beside what every launch carries (fill_common_args), launch_query dispatches `blocks` x `threads`.
+struct QueryPlan {
+    int         status;               // MIRT_OK, or the one refusal (adapt-lds: MIRT_ERR_SCENE_TOO_LARGE, no layout fits a block's LDS) with its message
+    const char* message;
+    // the kernel
+    QueryFamily family;
+    bool        bvh, any, count, sorted, hosek, grid, run;
+    uint32_t    threads, slots, min_waves;   // threads per block of the launch; pooled families: with slots and min waves the build's template arguments
+    // RenderArgs
+    uint32_t    lds_bytes;            // trace, features: the block's traversal stacks, 256 bytes x bvh_stack_entries per wave; radiance, adapt: the staged camera
+                                      // (+ sky) and, walking the tree, the wave's kBvhStackBytesPerWave; pooled: plan_bvh_pool's block; adapt-lds: plan_adapt_lds's
+    uint32_t    bvh_stack_entries;    // trace, features: the depth of the resident tree (at least 1), 0 for the flat scan; pooled: the tree's depth; else 0 =
+                                      // MIRT_BVH_MAX_DEPTH, the strip kernels' stacks.  adapt-lds has no tree: its launch leaves every bvh_* field zero
+    uint32_t    n_units;              // radiance: rays; radiance-pool: units of 16 rays; adapt families: pixels of the buffer; else 0
+    uint32_t    px_groups_log2;       // adapt-lds: 0 (the device chooses) or the forced g + 1 (Tuning.adapt_lds_groups); else 0
+    bool        rays_as_row;          // radiance-pool: RenderArgs.width = n_rays, height = 1.  (`grid`: grid, grid_bytes, grid_flat_y travel; adapt-lds: sph3 too)
+    uint32_t    n_rays;               // trace: the kernel's own argument behind the buffers; radiance(-pool): the batch's length
+    uint32_t    blocks;               // the grid of the launch; adapt-lds: before the occupancy cap (query_plan_blocks)
+    uint32_t    cu_count, blocks_per_cu, at_most_blocks;     // adapt-lds, for query_plan_blocks: the layout's own bound (plan_adapt_lds), Tuning.adapt_lds_blocks
+};
+
+// flags: the caller's MIRT_RAYS_* / MIRT_FEATURES_* bits; adapt_flags: MirtAdaptParams.flags; n_rays > 0; `p`, `rows` (= out_rows(&p)): the
+// params of a feature frame as checked; `q`: those of an adaptive step as check_adapt_step leaves them; `run`: a step of a run (planned
+// once per call); buffer_pixels: records in the context's adaptive buffer.  A pooled request that pooled_bvh_plan gives no geometry
+// plans the launch without the pool.
+QueryPlan plan_trace(const PlanFacts& f, const Tuning& tune, uint32_t n_rays, uint32_t flags);
+QueryPlan plan_features(const PlanFacts& f, const Tuning& tune, const MirtParams& p, uint32_t flags);
+QueryPlan plan_radiance(const PlanFacts& f, const Tuning& tune, uint32_t n_rays, const MirtRadianceParams& p);
+QueryPlan plan_adapt(const PlanFacts& f, const Tuning& tune, const MirtParams& q, uint32_t adapt_flags, bool run, uint64_t buffer_pixels);
+// adapt-lds, shaped like plan_blocks: a persistent grid of the blocks resident at once -- the smaller of the occupancy answer and the layout's
+// bound, at least one per CU --, or fewer for fewer pixels or Tuning.adapt_lds_blocks; the other families' grids need no answer: nothing
+void query_plan_blocks(QueryPlan& plan, uint32_t resident_per_cu);
+// The name mirt_ctx_last_kernel reports, written as plan_kernel_name writes a render kernel's
+void query_kernel_name(const QueryPlan& plan, char* out, size_t out_len);
 
 }  // namespace mirt

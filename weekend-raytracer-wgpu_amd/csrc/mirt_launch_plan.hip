@@ -1,5 +1,5 @@
-// mirt_launch_plan.hip — the launch plan of a render call and the name of its kernel (mirt_launch_plan.h): host arithmetic only.
-// launch_render (mirt_api.hip) is its one caller in the library; host/plan_check.cpp calls it without a device.
+// mirt_launch_plan.hip — the launch plan of a render call, of a query launch, and the names of their kernels (mirt_launch_plan.h): host
+// arithmetic only.  The launch functions of mirt_api.hip are its callers in the library; host/plan_check.cpp calls it without a device.
 #include <cstdio>
 
 #include "mirt_kernels.h"
@@ -354,6 +354,141 @@ void plan_kernel_name(const RenderPlan& pl, char* out, size_t n)
             snprintf(out, n, "%srender_pt_pool%s_kernel<%u,%u,%u,%s,%s,%u,%s,%s>", fast, kframe, g.threads, g.slots, g.min_waves, count, hosek, g.queues, tf[pl.use_grid],
                      tf[pl.use_grid && pl.grid_flat_y != 0u]);
         break;
+    }
+}
+
+// ---- query launches ----
+// The tree and the traversal stacks of the query kernels that run one thread per ray or pixel in kBlockThreads blocks (ray queries, feature
+// frames): the stacks hold as many node references per lane as the resident tree is deep (a push happens at inner nodes only, at
+// most one per level): 256 x depth bytes per wave, as in the pooled kernel -- at most 32 KB per block (MIRT_BVH_MAX_DEPTH)
+static QueryPlan plan_block_query(const PlanFacts& f, QueryFamily family, bool bvh, uint64_t items)
+{
+    QueryPlan a{};
+    a.family = family; a.bvh = bvh; a.threads = kBlockThreads;
+    a.bvh_stack_entries = bvh ? (f.bvh_max_depth ? f.bvh_max_depth : 1u) : 0u;
+    a.lds_bytes = (kBlockThreads / 64u) * 64u * 4u * a.bvh_stack_entries;
+    a.blocks = (uint32_t)((items + kBlockThreads - 1u) / kBlockThreads);
+    return a;
+}
+
+QueryPlan plan_trace(const PlanFacts& f, const Tuning&, uint32_t n_rays, uint32_t flags)
+{
+    QueryPlan a = plan_block_query(f, kQueryTrace, !(flags & MIRT_RAYS_FLAT), n_rays);
+    a.any = (flags & MIRT_RAYS_ANY_HIT) != 0; a.count = (flags & MIRT_RAYS_COUNT) != 0; a.sorted = (flags & MIRT_RAYS_SORT) != 0;
+    a.n_rays = n_rays;
+    return a;
+}
+
+QueryPlan plan_features(const PlanFacts& f, const Tuning&, const MirtParams& p, uint32_t flags)
+{
+    return plan_block_query(f, kQueryFeatures, !(flags & MIRT_FEATURES_FLAT), (uint64_t)out_rows(&p) * p.width);
+}
+
+// What the radiance query and the adaptive step share.  Unpooled: `items` rays or pixels, one per thread, one wave per block; path_radiance
+// walks the tree as the strip kernels do, with a stack of MIRT_BVH_MAX_DEPTH entries per lane behind the staged camera (+ sky).
+// Pooled (`pool` has slots): units of 16 items, one unit per wave -- the hardware's dispatcher is the balancer --; `at_most` != 0
+// (MIRT_*_POOL_BLOCKS): no more blocks than that, their waves stride over the units.  LDS: camera words (+ sky), the block's pools, its
+// waves' traversal stacks.
+static QueryPlan plan_path_query(const PlanFacts& f, QueryFamily unpooled, QueryFamily pooled, bool bvh, bool hosek, uint64_t items, uint32_t wave_threads,
+                                 const MirtBvhPoolPlan& pool, uint32_t at_most)
+{
+    QueryPlan a{};
+    a.bvh = bvh; a.hosek = hosek;
+    if (pool.slots == 0u) {
+        a.family = unpooled; a.threads = wave_threads;
+        a.lds_bytes = (uint32_t)(kx::scene_lds_bytes_grid(f.n_spheres, hosek) + (bvh ? kBvhStackBytesPerWave : 0u));
+        a.n_units = (uint32_t)items;
+        a.blocks = (uint32_t)(((uint64_t)a.n_units + wave_threads - 1u) / wave_threads);
+        return a;
+    }
+    a.family = pooled;
+    a.threads = pool.threads; a.slots = pool.slots; a.min_waves = kBvhPoolMinWaves;
+    a.lds_bytes = pool.lds_bytes_per_block; a.bvh_stack_entries = pool.stack_entries;
+    const uint64_t units = (items + kStripPixels - 1u) / kStripPixels, waves = pool.threads / 64u, blocks = (units + waves - 1u) / waves;
+    a.n_units = (uint32_t)units;
+    a.blocks = (uint32_t)(at_most != 0u && blocks > at_most ? at_most : blocks);
+    return a;
+}
+
+QueryPlan plan_radiance(const PlanFacts& f, const Tuning& tune, uint32_t n_rays, const MirtRadianceParams& p)
+{
+    const bool bvh = !(p.flags & MIRT_RADIANCE_FLAT), hosek = (p.flags & MIRT_RADIANCE_SKY_HOSEK) != 0;
+    MirtBvhPoolPlan pool{};
+    if ((p.flags & MIRT_RADIANCE_POOL) && bvh) pool = pooled_bvh_plan(f, tune, hosek, 0u, p.num_bounces);
+    QueryPlan a = plan_path_query(f, kQueryRadiance, kQueryRadiancePool, bvh, hosek, n_rays, kRadianceThreads, pool, tune.radiance_pool_blocks);
+    a.sorted = (p.flags & MIRT_RADIANCE_SORT) != 0;
+    a.rays_as_row = a.family == kQueryRadiancePool;       // its units are slots of the batch: the kernel reads the batch's length where a render reads the width
+    a.n_rays = n_rays;
+    return a;
+}
+
+// The layout of an MIRT_ADAPT_LDS step on the resident LDS scene: the scene's grid unless MIRT_FLAG_NO_GRID asks for the
+// flat scan, else the flat tables if they fit; plan_adapt_lds's geometry of it, or all fields 0 where neither fits a block's LDS.
+static MirtAdaptLdsPlan adapt_lds_layout(const PlanFacts& f, uint32_t flags, bool hosek)
+{
+    MirtAdaptLdsPlan plan{};
+    if (f.grid_bytes != 0u && !(flags & MIRT_FLAG_NO_GRID)) plan = plan_adapt_lds(f.n_spheres, f.n_mats, f.grid_bytes, hosek, f.lds_per_cu);
+    if (plan.lds_bytes_per_block > f.lds_per_block) plan = MirtAdaptLdsPlan{};
+    if (plan.threads == 0u && f.fits_flat) plan = plan_adapt_lds(f.n_spheres, f.n_mats, 0u, hosek, f.lds_per_cu);
+    if (plan.lds_bytes_per_block > f.lds_per_block) plan = MirtAdaptLdsPlan{};
+    return plan;
+}
+
+QueryPlan plan_adapt(const PlanFacts& f, const Tuning& tune, const MirtParams& q, uint32_t adapt_flags, bool run, uint64_t buffer_pixels)
+{
+    const bool hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
+    QueryPlan a{};
+    if (!f.hbm) {
+        // a scene that lives in LDS (the caller has seen MIRT_ADAPT_LDS): adapt_pixels_lds_kernel over the staged scene of the layout
+        const MirtAdaptLdsPlan lds = adapt_lds_layout(f, q.flags, hosek);
+        a.family = kQueryAdaptLds;
+        a.hosek = hosek; a.grid = lds.grid != 0u;
+        if (lds.threads == 0u) {
+            a.status = MIRT_ERR_SCENE_TOO_LARGE;
+            a.message = (q.flags & MIRT_FLAG_NO_GRID) ? "this scene fits LDS in neither layout an MIRT_ADAPT_LDS step has (MIRT_FLAG_NO_GRID: the flat one only)"
+                                                      : "this scene fits LDS in neither layout an MIRT_ADAPT_LDS step has";
+            return a;
+        }
+        a.threads = lds.threads; a.lds_bytes = lds.lds_bytes_per_block;
+        a.n_units = (uint32_t)buffer_pixels; a.px_groups_log2 = tune.adapt_lds_groups;
+        a.blocks = (uint32_t)((buffer_pixels + lds.threads - 1u) / lds.threads);
+        a.cu_count = f.cu_count; a.blocks_per_cu = lds.blocks_per_cu; a.at_most_blocks = tune.adapt_lds_blocks;
+    } else {
+        // MIRT_ADAPT_POOL on the BVH build: adapt_pixels_pool_kernel in the geometry mirt_adapt_pool_plan gives for the resident tree
+        const bool bvh = !(q.flags & MIRT_FLAG_NO_GRID);
+        MirtBvhPoolPlan pool{};
+        if ((adapt_flags & MIRT_ADAPT_POOL) && bvh) pool = pooled_bvh_plan(f, tune, hosek, kAdaptPoolExtraBytes, q.num_bounces);
+        a = plan_path_query(f, kQueryAdapt, kQueryAdaptPool, bvh, hosek, buffer_pixels, kAdaptThreads, pool, tune.adapt_pool_blocks);
+        // (the host does not know the step's count: either grid is for all pixels, n_units the buffer's in both)
+        a.n_units = (uint32_t)buffer_pixels;
+    }
+    a.run = run;
+    return a;
+}
+
+void query_plan_blocks(QueryPlan& a, uint32_t resident_per_cu)
+{
+    if (a.family != kQueryAdaptLds) return;
+    uint32_t per_cu = resident_per_cu;
+    if (per_cu > a.blocks_per_cu) per_cu = a.blocks_per_cu;
+    if (per_cu == 0u) per_cu = 1u;
+    const uint64_t resident = (uint64_t)a.cu_count * per_cu;
+    if (a.blocks > resident) a.blocks = (uint32_t)resident;
+    if (a.at_most_blocks != 0u && a.blocks > a.at_most_blocks) a.blocks = a.at_most_blocks;
+}
+
+void query_kernel_name(const QueryPlan& pl, char* out, size_t n)
+{
+    const char* const tf[2] = { "false", "true" };
+    const char* const sorted = pl.sorted ? "_sorted" : "", *const run = pl.run ? "_run" : "", *const hosek = tf[pl.hosek];
+    switch (pl.family) {
+    case kQueryTrace:        snprintf(out, n, "trace_rays%s_kernel<%s,%s,%s>", sorted, tf[pl.bvh], tf[pl.any], tf[pl.count]); break;
+    case kQueryFeatures:     snprintf(out, n, "feature_frame_kernel<%s>", tf[pl.bvh]); break;
+    case kQueryRadiance:     snprintf(out, n, "radiance_rays%s_kernel<%s,%s>", sorted, hosek, tf[pl.bvh]); break;
+    case kQueryRadiancePool: snprintf(out, n, "radiance_rays_pool_kernel<%u,%u,%u,%s,%s>", pl.threads, pl.slots, pl.min_waves, hosek, tf[pl.sorted]); break;
+    case kQueryAdapt:        snprintf(out, n, "adapt_pixels%s_kernel<%s,%s>", run, hosek, tf[pl.bvh]); break;
+    case kQueryAdaptPool:    snprintf(out, n, "adapt_pixels_pool%s_kernel<%u,%u,%u,%s>", run, pl.threads, pl.slots, pl.min_waves, hosek); break;
+    case kQueryAdaptLds:     snprintf(out, n, "adapt_pixels_lds%s_kernel<%s,%s>", run, hosek, tf[pl.grid]); break;
     }
 }
 

@@ -25,7 +25,6 @@
 //   A record (MirtRadiance, 32 bytes: three u64 sums, samples, _pad) leaves as two 16-byte stores; with MIRT_RADIANCE_ACCUMULATE
 // (RenderArgs.flags, wave-uniform) two 16-byte loads precede them and the lane adds.
 
-constexpr uint32_t kRadianceThreads = 64;
 constexpr uint32_t kRadianceFlat = 1u << 0, kRadianceAccumulate = 1u << 1, kRadianceHosek = 1u << 2;     // MIRT_RADIANCE_* (include/mirt.h)
 static_assert(kRadianceFlat == MIRT_RADIANCE_FLAT && kRadianceAccumulate == MIRT_RADIANCE_ACCUMULATE && kRadianceHosek == MIRT_RADIANCE_SKY_HOSEK,
               "RenderArgs.flags of a radiance launch are the caller's MIRT_RADIANCE_* bits");
@@ -52,22 +51,8 @@ __global__ __launch_bounds__(kRadianceThreads, 5) void radiance_rays_sorted_kern
 #undef MIRT_RAY_OF_SLOT
 }
 
-// one thread per ray (a.n_units of them), one wave per block; a.lds_bytes = stage_scene's image without the tables + the wave's traversal stacks (BVH build)
-hipError_t launch_radiance(const RenderArgs& a, const void* d_rays, void* d_out, bool hosek, bool bvh, hipStream_t stream)
+static QueryKernel radiance_kernel(const QueryPlan& p)
 {
-    const uint32_t blocks = (uint32_t)(((uint64_t)a.n_units + kRadianceThreads - 1u) / kRadianceThreads);
-    auto k = hosek ? (bvh ? radiance_rays_kernel<true, true> : radiance_rays_kernel<true, false>)
-                   : (bvh ? radiance_rays_kernel<false, true> : radiance_rays_kernel<false, false>);
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(kRadianceThreads), a.lds_bytes, stream, a, static_cast<const trace_u4*>(d_rays), static_cast<trace_u4*>(d_out));
-    return hipGetLastError();
-}
-
-// the same launch in the order d_order gives ([a.n_units] uint32 in device memory, a permutation)
-hipError_t launch_radiance_sorted(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, bool hosek, bool bvh, hipStream_t stream)
-{
-    const uint32_t blocks = (uint32_t)(((uint64_t)a.n_units + kRadianceThreads - 1u) / kRadianceThreads);
-    auto k = hosek ? (bvh ? radiance_rays_sorted_kernel<true, true> : radiance_rays_sorted_kernel<true, false>)
-                   : (bvh ? radiance_rays_sorted_kernel<false, true> : radiance_rays_sorted_kernel<false, false>);
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(kRadianceThreads), a.lds_bytes, stream, a, static_cast<const trace_u4*>(d_rays), static_cast<trace_u4*>(d_out), d_order);
-    return hipGetLastError();
+    if (!p.sorted) return with_bools<QueryKernel>([](auto H, auto B) { return kernel_handle(radiance_rays_kernel<H.value, B.value>); }, p.hosek, p.bvh);
+    return with_bools<QueryKernel>([](auto H, auto B) { return kernel_handle(radiance_rays_sorted_kernel<H.value, B.value>); }, p.hosek, p.bvh);
 }

@@ -127,26 +127,11 @@ __global__ __launch_bounds__(THREADS, MINW) void radiance_rays_pool_kernel(Rende
 }
 
 // ---- one build per geometry of kBvhPoolSlotChoices (the pooled HBM render's table) x HOSEK x SORTED ----
-using RadiancePoolKernel = void (*)(RenderArgs, const trace_u4*, trace_u4*, const uint32_t*);
-template <uint32_t SL>
-static RadiancePoolKernel radiance_pool_kernel_(bool hosek, bool sorted)
+static QueryKernel radiance_pool_kernel(const QueryPlan& p)
 {
-    constexpr uint32_t T = kBvhPoolThreads, MW = kBvhPoolMinWaves;
-    return hosek ? (sorted ? radiance_rays_pool_kernel<T, SL, MW, true, true> : radiance_rays_pool_kernel<T, SL, MW, true, false>)
-                 : (sorted ? radiance_rays_pool_kernel<T, SL, MW, false, true> : radiance_rays_pool_kernel<T, SL, MW, false, false>);
-}
-
-static RadiancePoolKernel radiance_pool_kernel(uint32_t slots, bool hosek, bool sorted)
-{
-    return for_bvh_pool_slots(slots, [=](auto sl) { return radiance_pool_kernel_<decltype(sl)::value>(hosek, sorted); });
-}
-
-// a.n_units units of 16 slots (a.width rays), grid_blocks blocks of kBvhPoolThreads; a.lds_bytes = mirt_bvh_pool_plan's bytes per block,
-// a.bvh_stack_entries its stack entries; d_order: the permutation (MIRT_RADIANCE_SORT) or nullptr
-hipError_t launch_radiance_pool(const RenderArgs& a, const void* d_rays, void* d_out, const uint32_t* d_order, uint32_t grid_blocks, uint32_t slots, bool hosek,
-                                hipStream_t stream)
-{
-    const RadiancePoolKernel k = radiance_pool_kernel(slots, hosek, d_order != nullptr);
-    if (!k) return hipErrorInvalidValue;
-    return launch_with_lds(k, dim3(grid_blocks), dim3(kBvhPoolThreads), a, LaunchOn(stream), static_cast<const trace_u4*>(d_rays), static_cast<trace_u4*>(d_out), d_order);
+    if (p.threads != kBvhPoolThreads || p.min_waves != kBvhPoolMinWaves) return nullptr;      // not a geometry of plan_bvh_pool
+    return for_bvh_pool_slots(p.slots, [&](auto sl) -> QueryKernel {
+        constexpr uint32_t T = kBvhPoolThreads, SL = decltype(sl)::value, MW = kBvhPoolMinWaves;
+        return with_bools<QueryKernel>([](auto H, auto S) { return kernel_handle(radiance_rays_pool_kernel<T, SL, MW, H.value, S.value>); }, p.hosek, p.sorted);
+    });
 }

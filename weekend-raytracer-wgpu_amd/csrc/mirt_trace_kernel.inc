@@ -42,39 +42,9 @@ __global__ __launch_bounds__(kBlockThreads) void trace_rays_sorted_kernel(Render
 #undef MIRT_RAY_OF_SLOT
 }
 
-using TraceKernel = void (*)(RenderArgs, const trace_f4*, trace_u4*, uint32_t);
-static TraceKernel trace_kernel(bool bvh, bool any, bool count)
+static QueryKernel trace_kernel(const QueryPlan& p)
 {
-    if (bvh) return any ? (count ? trace_rays_kernel<true, true, true> : trace_rays_kernel<true, true, false>)
-                        : (count ? trace_rays_kernel<true, false, true> : trace_rays_kernel<true, false, false>);
-    return any ? (count ? trace_rays_kernel<false, true, true> : trace_rays_kernel<false, true, false>)
-               : (count ? trace_rays_kernel<false, false, true> : trace_rays_kernel<false, false, false>);
+    if (!p.sorted) return with_bools<QueryKernel>([](auto B, auto A, auto C) { return kernel_handle(trace_rays_kernel<B.value, A.value, C.value>); }, p.bvh, p.any, p.count);
+    return with_bools<QueryKernel>([](auto B, auto A, auto C) { return kernel_handle(trace_rays_sorted_kernel<B.value, A.value, C.value>); }, p.bvh, p.any, p.count);
 }
 
-// one thread per ray; a.lds_bytes = the block's traversal stacks (0 for the flat scan)
-hipError_t launch_trace_rays(const RenderArgs& a, const void* d_rays, void* d_hits, uint32_t n_rays, bool bvh, bool any, bool count, hipStream_t stream)
-{
-    const uint32_t blocks = (uint32_t)(((uint64_t)n_rays + kBlockThreads - 1u) / kBlockThreads);
-    hipLaunchKernelGGL(trace_kernel(bvh, any, count), dim3(blocks), dim3(kBlockThreads), a.lds_bytes, stream, a,
-                       static_cast<const trace_f4*>(d_rays), static_cast<trace_u4*>(d_hits), n_rays);
-    return hipGetLastError();
-}
-
-using TraceSortedKernel = void (*)(RenderArgs, const trace_f4*, trace_u4*, uint32_t, const uint32_t*);
-static TraceSortedKernel trace_sorted_kernel(bool bvh, bool any, bool count)
-{
-    if (bvh) return any ? (count ? trace_rays_sorted_kernel<true, true, true> : trace_rays_sorted_kernel<true, true, false>)
-                        : (count ? trace_rays_sorted_kernel<true, false, true> : trace_rays_sorted_kernel<true, false, false>);
-    return any ? (count ? trace_rays_sorted_kernel<false, true, true> : trace_rays_sorted_kernel<false, true, false>)
-               : (count ? trace_rays_sorted_kernel<false, false, true> : trace_rays_sorted_kernel<false, false, false>);
-}
-
-// the same launch in the order d_order gives ([n_rays] uint32 in device memory, a permutation)
-hipError_t launch_trace_rays_sorted(const RenderArgs& a, const void* d_rays, void* d_hits, uint32_t n_rays, const uint32_t* d_order, bool bvh, bool any, bool count,
-                                    hipStream_t stream)
-{
-    const uint32_t blocks = (uint32_t)(((uint64_t)n_rays + kBlockThreads - 1u) / kBlockThreads);
-    hipLaunchKernelGGL(trace_sorted_kernel(bvh, any, count), dim3(blocks), dim3(kBlockThreads), a.lds_bytes, stream, a,
-                       static_cast<const trace_f4*>(d_rays), static_cast<trace_u4*>(d_hits), n_rays, d_order);
-    return hipGetLastError();
-}

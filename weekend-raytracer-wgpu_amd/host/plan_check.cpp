@@ -13,6 +13,12 @@
 // plan_check --kernels CASES.txt prints the kernel of every case instead (tests/test_launch_kernels.py), four words per line: the case, the name
 // mirt_ctx_last_kernel would report (plan_kernel_name), the template instance render_kernel selects in the plan's build -- the symbol of
 // its kernel handle in libmirt.so, demangled and written as the reported names are --, and that symbol itself.  "-": no such instance.
+//
+// plan_check --queries CASES.txt / --query-kernels CASES.txt do the same for the query launches (QueryPlan, query_kernel; tests/test_query_plan.py).
+// A case gives the facts, the tuning and res as above and
+//   q                                      trace / features / radiance / adapt: the planning function (the plan chooses the pooled and LDS families)
+//   n  qf(hex)                             rays; the MIRT_RAYS_* / MIRT_FEATURES_* / MIRT_RADIANCE_* bits (radiance: spp, sb, nb as MirtParams')
+//   af(hex) run px                         adapt: MirtAdaptParams.flags, a step of a run, pixels in the buffer; fl = the step's MIRT_FLAG_* bits
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,7 +33,7 @@
 namespace mirt {
 struct RenderArgs;
 using RenderKernel = void (*)(RenderArgs);
-namespace exact_build { RenderKernel render_kernel(const RenderPlan& plan); }
+namespace exact_build { RenderKernel render_kernel(const RenderPlan& plan); const void* query_kernel(const QueryPlan& plan); }
 namespace fast_build { RenderKernel render_kernel(const RenderPlan& plan); }
 }
 
@@ -70,7 +76,7 @@ static std::string as_reported(const char* demangled)
 {
     std::string s = demangled;
     if (s.rfind("void ", 0) == 0) s.erase(0, 5);
-    const size_t args = s.rfind('(');
+    const size_t args = s.find('(');       // (template arguments are numbers and bools; a query kernel's argument list has parentheses of its own)
     if (args != std::string::npos) s.erase(args);
     erase_all(s, "mirt::exact_build::");
     erase_all(s, "mirt::");
@@ -81,14 +87,11 @@ static std::string as_reported(const char* demangled)
     return s;
 }
 
-static void print_kernel(FILE* out, const char* name, const mirt::RenderPlan& p)
+// case, reported name, the instance behind the handle `k` written as a reported name, its symbol
+static void print_handle(FILE* out, const char* name, const char* reported, const void* k)
 {
-    if (p.status != MIRT_OK) { fprintf(out, "%s status=%d %s\n", name, p.status, p.message); return; }
-    char reported[128];
-    mirt::plan_kernel_name(p, reported, sizeof reported);
-    const mirt::RenderKernel k = p.fast ? mirt::fast_build::render_kernel(p) : mirt::exact_build::render_kernel(p);
     Dl_info info{};
-    if (!k || !dladdr(reinterpret_cast<const void*>(k), &info) || !info.dli_sname || info.dli_saddr != reinterpret_cast<const void*>(k)) {
+    if (!k || !dladdr(k, &info) || !info.dli_sname || info.dli_saddr != k) {
         fprintf(out, "%s %s - -\n", name, reported);
         return;
     }
@@ -98,13 +101,59 @@ static void print_kernel(FILE* out, const char* name, const mirt::RenderPlan& p)
     std::free(demangled);
 }
 
+static void print_kernel(FILE* out, const char* name, const mirt::RenderPlan& p)
+{
+    if (p.status != MIRT_OK) { fprintf(out, "%s status=%d %s\n", name, p.status, p.message); return; }
+    char reported[128];
+    mirt::plan_kernel_name(p, reported, sizeof reported);
+    print_handle(out, name, reported, reinterpret_cast<const void*>(p.fast ? mirt::fast_build::render_kernel(p) : mirt::exact_build::render_kernel(p)));
+}
+
+static void print_query_kernel(FILE* out, const char* name, const mirt::QueryPlan& p)
+{
+    if (p.status != MIRT_OK) { fprintf(out, "%s status=%d %s\n", name, p.status, p.message); return; }
+    char reported[128];
+    mirt::query_kernel_name(p, reported, sizeof reported);
+    print_handle(out, name, reported, mirt::exact_build::query_kernel(p));
+}
+
+// ---- query launches (plan_check --queries / --query-kernels; tests/test_query_plan.py) ----
+static const char* const kFamilyNames[] = { "trace", "features", "radiance", "radiance-pool", "adapt", "adapt-pool", "adapt-lds" };
+
+// The query plan in its fixed one-line format.  id = bvh any count sorted hosek grid run; geo = threads/slots/min waves; bse = bvh_stack_entries;
+// pxg = px_groups_log2; row = rays_as_row; cap = cu_count/blocks_per_cu/at_most_blocks.  A refused launch prints its status and message instead.
+static void print_query_plan(FILE* out, const char* name, const mirt::QueryPlan& p)
+{
+    if (p.status != MIRT_OK) { fprintf(out, "%s status=%d %s\n", name, p.status, p.message); return; }
+    fprintf(out, "%s %s id=%d%d%d%d%d%d%d geo=%u/%u/%u lds=%u bse=%u units=%u pxg=%u row=%d n=%u blocks=%u cap=%u/%u/%u\n", name, kFamilyNames[p.family], p.bvh, p.any,
+            p.count, p.sorted, p.hosek, p.grid, p.run, p.threads, p.slots, p.min_waves, p.lds_bytes, p.bvh_stack_entries, p.n_units, p.px_groups_log2, p.rays_as_row,
+            p.n_rays, p.blocks, p.cu_count, p.blocks_per_cu, p.at_most_blocks);
+}
+
 struct Case {
     char             name[64] = "?";
     mirt::PlanFacts  f{};
     mirt::Tuning     t;
     MirtParams       p{};
     uint32_t         frame = 0, res = 0;
+    // a query case: q = trace / features / radiance / adapt; n rays; qf = the MIRT_RAYS_* / MIRT_FEATURES_* / MIRT_RADIANCE_* bits (radiance: spp,
+    // sb and nb are the params'); adapt: fl = the step's MIRT_FLAG_* bits, af = MirtAdaptParams.flags, run, px = pixels in the buffer
+    char             q[16] = "";
+    uint32_t         n = 0, qf = 0, af = 0, run = 0;
+    uint64_t         px = 0;
 };
+
+static bool plan_query(const Case& c, mirt::QueryPlan* plan)
+{
+    const MirtRadianceParams rp{ c.p.spp, c.p.sample_begin, c.p.num_bounces, c.qf, c.p.seed };
+    if (std::strcmp(c.q, "trace") == 0) *plan = mirt::plan_trace(c.f, c.t, c.n, c.qf);
+    else if (std::strcmp(c.q, "features") == 0) *plan = mirt::plan_features(c.f, c.t, c.p, c.qf);
+    else if (std::strcmp(c.q, "radiance") == 0) *plan = mirt::plan_radiance(c.f, c.t, c.n, rp);
+    else if (std::strcmp(c.q, "adapt") == 0) *plan = mirt::plan_adapt(c.f, c.t, c.p, c.af, c.run != 0u, c.px);
+    else return false;
+    if (plan->status == MIRT_OK) mirt::query_plan_blocks(*plan, c.res);
+    return true;
+}
 
 enum FieldType { kU32, kU64, kInt, kBool, kDouble, kHex };
 struct Field { const char* key; FieldType type; void* at; };
@@ -127,7 +176,10 @@ static bool set_field(Case& c, const char* key, const char* val)
         { "t.static_units", kInt, &t.static_units }, { "t.pool_min_spp", kInt, &t.pool_min_spp }, { "t.stream", kInt, &t.stream },
         { "t.px_groups", kInt, &t.px_groups }, { "t.strip_cand", kInt, &t.strip_cand }, { "t.static_block", kU32, &t.static_block },
         { "t.static_grid", kInt, &t.static_grid }, { "t.hbm_pool_slots", kU32, &t.hbm_pool_slots },
+        { "t.radiance_pool_blocks", kU32, &t.radiance_pool_blocks }, { "t.adapt_pool_blocks", kU32, &t.adapt_pool_blocks },
+        { "t.adapt_lds_blocks", kU32, &t.adapt_lds_blocks }, { "t.adapt_lds_groups", kU32, &t.adapt_lds_groups },
         { "frame", kU32, &c.frame }, { "res", kU32, &c.res },
+        { "n", kU32, &c.n }, { "qf", kHex, &c.qf }, { "af", kHex, &c.af }, { "run", kU32, &c.run }, { "px", kU64, &c.px },
     };
     for (const Field& fd : fields) {
         if (std::strcmp(fd.key, key) != 0) continue;
@@ -146,8 +198,10 @@ static bool set_field(Case& c, const char* key, const char* val)
 
 int main(int argc, char** argv)
 {
-    const bool kernels = argc == 3 && std::strcmp(argv[1], "--kernels") == 0;
-    if (argc != 2 && !kernels) { fprintf(stderr, "usage: plan_check [--kernels] CASES.txt\n"); return 2; }
+    const char* const mode = argc == 3 ? argv[1] : "";
+    const bool query_kernels = std::strcmp(mode, "--query-kernels") == 0, queries = query_kernels || std::strcmp(mode, "--queries") == 0;
+    const bool kernels = std::strcmp(mode, "--kernels") == 0;
+    if (argc != 2 && !kernels && !queries) { fprintf(stderr, "usage: plan_check [--kernels | --queries | --query-kernels] CASES.txt\n"); return 2; }
     FILE* in = std::fopen(argv[argc - 1], "r");
     if (!in) { fprintf(stderr, "plan_check: cannot open %s\n", argv[argc - 1]); return 2; }
     char line[2048];
@@ -161,9 +215,17 @@ int main(int argc, char** argv)
             *eq = '\0';
             any = true;
             if (std::strcmp(word, "name") == 0) snprintf(c.name, sizeof c.name, "%s", eq + 1);
+            else if (std::strcmp(word, "q") == 0) snprintf(c.q, sizeof c.q, "%s", eq + 1);
             else if (!set_field(c, word, eq + 1)) { fprintf(stderr, "plan_check: line %d: unknown key '%s'\n", n, word); return 2; }
         }
         if (!any) continue;
+        if (queries) {
+            mirt::QueryPlan plan{};
+            if (!plan_query(c, &plan)) { fprintf(stderr, "plan_check: line %d: q='%s' is no query\n", n, c.q); return 2; }
+            if (query_kernels) print_query_kernel(stdout, c.name, plan);
+            else print_query_plan(stdout, c.name, plan);
+            continue;
+        }
         mirt::RenderPlan plan = mirt::plan_render(c.f, c.t, c.p, c.frame != 0u);
         if (plan.status == MIRT_OK) mirt::plan_blocks(plan, c.res);
         if (kernels) print_kernel(stdout, c.name, plan);
