@@ -885,6 +885,34 @@ typedef struct MirtAdaptLdsPlan { uint32_t threads, grid, lds_bytes_per_block, b
 int mirt_adapt_lds_plan(uint32_t n_spheres, uint32_t n_materials, uint32_t grid_bytes, uint32_t hosek, uint64_t lds_bytes_per_cu, MirtAdaptLdsPlan* out);
 int mirt_adapt_lds_groups(uint32_t count, uint32_t spp, uint32_t grid_waves, uint32_t* out_log2);
 
+/* ---- ray, feature and radiance queries on a scene that lives in LDS: MIRT_QUERY_LDS ----
+ * One bit, accepted in three flag words: the `flags` of mirt_ctx_trace_rays*, the `flags` of mirt_ctx_render_features* and
+ * MirtRadianceParams.flags.  Without it those calls answer MIRT_ERR_NO_SCENE on a scene that is not a MIRT_SCENE_HBM one, as ever.
+ *   an HBM scene     ignores the flag: the kernel, the name in mirt_ctx_last_kernel and the bytes are those of the call without it.
+ *   an LDS scene     every other check keeps its place and its code; the layout is checked last.  The call uses the scene's uniform
+ *                    grid when it has one and the family's _FLAT bit (MIRT_RAYS_FLAT, MIRT_FEATURES_FLAT, MIRT_RADIANCE_FLAT) is not
+ *                    set; otherwise the flat tables, if the scene fits them; otherwise it answers MIRT_ERR_SCENE_TOO_LARGE, the code a
+ *                    render with MIRT_FLAG_NO_GRID gives on a grid-only scene.  A refused call queues nothing and writes nothing.
+ *   same bytes       every record of every family, for every float bit pattern in a ray, equals the record of the same call without
+ *                    the flag on a context that holds the same world as a MIRT_SCENE_HBM scene (either tree builder), whose bytes
+ *                    are in turn those of its _FLAT build.  MIRT_RAYS_ANY_HIT, MIRT_RAYS_COUNT, MIRT_RADIANCE_ACCUMULATE and
+ *                    MIRT_RADIANCE_SKY_HOSEK are honoured.
+ *   schedule hints   MIRT_RAYS_SORT, MIRT_RADIANCE_SORT and MIRT_RADIANCE_POOL are accepted and ignored on an LDS scene (there is no
+ *                    tree to take bounds from and no pooled LDS query build); the bytes are the same by those flags' own contracts.
+ *                    Such a call is no sorted launch: mirt_ctx_trace_order_read keeps describing the last launch that really sorted.
+ *   counters         under MIRT_RAYS_COUNT, flat layout: rays, sphere_tests, roots and hits are those of MIRT_RAYS_FLAT |
+ *                    MIRT_RAYS_COUNT on the HBM twin, nodes and wave_nodes 0.  Grid: rays and hits are the twin's, sphere_tests and
+ *                    roots count what the lanes really perform, nodes counts grid cells visited summed over lanes, wave_nodes
+ *                    cell-loop iterations summed over waves.
+ *   state            as for every query: the launch ring, MirtStats and the accumulation are untouched, mirt_ctx_trace_stats().kernel_ms
+ *                    spans the kernel, mirt_ctx_synchronize and mirt_ctx_destroy wait for it.  mirt_ctx_last_kernel names
+ *                    trace_rays_lds_kernel<grid,any,count>, feature_frame_lds_kernel<grid> or radiance_rays_lds_kernel<hosek,grid>.
+ *   geometry         mirt_adapt_lds_plan's for the layout (hosek = 0 for ray and feature queries, which stage no sky): 256-thread
+ *                    blocks, a persistent grid of min(ceil(items / 256), CUs x blocks per CU), the blocks per CU the smaller of the
+ *                    plan's bound and the kernel's occupancy.  MIRT_QUERY_LDS_BLOCKS=n (read once in mirt_ctx_create; tests, A/B runs)
+ *                    launches at most n blocks. */
+enum { MIRT_QUERY_LDS = 1u << 8 };
+
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE
  * expansions over ALL 2^32 binary32 bit patterns.  Writes the two mismatch counts (sqrt, 1/x);

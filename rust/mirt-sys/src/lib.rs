@@ -356,6 +356,9 @@ pub const MIRT_RADIANCE_POOL: u32 = 1 << 6;
 pub const MIRT_ADAPT_POOL: u32 = 1 << 1;
 /// `MirtAdaptParams.flags`: a step or run also accepts a scene that lives in LDS, where it stays (an HBM scene ignores it); bit 2 is unassigned.
 pub const MIRT_ADAPT_LDS: u32 = 1 << 3;
+/// The `flags` of `mirt_ctx_trace_rays*` and `mirt_ctx_render_features*`, and `MirtRadianceParams.flags`: the query also accepts a scene
+/// that lives in LDS, where it stays (the same records as on the same world held as an HBM scene, which ignores the flag).
+pub const MIRT_QUERY_LDS: u32 = 1 << 8;
 
 pub const MIRT_RAY_MISS: u32 = 0xffff_ffff;
 /// `mirt_ctx_trace_rays*` flags: the flat scan instead of the tree; stop at the first hit (occlusion); the counting build.

@@ -55,6 +55,7 @@ MIRT_RAY_SORT_DIRECTION_BITS = 8
 MIRT_ADAPT_FLOOR = 1 << 17
 MIRT_ADAPT_POOL = 1 << 1                # MirtAdaptParams.flags; bit 0 is unassigned
 MIRT_ADAPT_LDS = 1 << 3                 # MirtAdaptParams.flags: a step also runs on a scene that lives in LDS; bit 2 is unassigned
+MIRT_QUERY_LDS = 1 << 8                 # the flags of mirt_ctx_trace_rays*, mirt_ctx_render_features* and MirtRadianceParams.flags: the query also runs on a scene that lives in LDS
 MIRT_ADAPT_RUN_MAX_STEPS = 256          # mirt_ctx_adapt_run_device: steps of one run, entries of its log
 
 # mirt_node_create: members at most, and its flags

@@ -188,12 +188,19 @@ def ray_records(rays) -> np.ndarray:
     raise ValueError(f"rays must be a one-dimensional RAY_DTYPE array or float32 [n, 8], not {rays.dtype} of shape {rays.shape}")
 
 
-def _check_rays_flags(flags, sort=False) -> int:
+def _lds_flag(lds) -> int:
+    """MIRT_QUERY_LDS for lds=True: the query also runs on a scene that lives in LDS, where it stays (an HBM scene ignores it)."""
+    if not isinstance(lds, (bool, np.bool_)):
+        raise ValueError(f"lds must be a bool, not {lds!r}")
+    return _abi.MIRT_QUERY_LDS if lds else 0
+
+
+def _check_rays_flags(flags, sort=False, lds=False) -> int:
     if not isinstance(flags, (int, np.integer)) or isinstance(flags, bool) or int(flags) & ~RAYS_FLAGS or int(flags) < 0:
         raise ValueError(f"flags must be a combination of MIRT_RAYS_FLAT, MIRT_RAYS_ANY_HIT, MIRT_RAYS_COUNT and MIRT_RAYS_SORT, not {flags!r}")
     if not isinstance(sort, (bool, np.bool_)):
         raise ValueError(f"sort must be a bool, not {sort!r}")
-    return int(flags) | (_abi.MIRT_RAYS_SORT if sort else 0)
+    return int(flags) | (_abi.MIRT_RAYS_SORT if sort else 0) | _lds_flag(lds)
 
 
 def ray_sort_codes(centre, radius, rays) -> np.ndarray:
@@ -341,7 +348,7 @@ def adapt_run_spp(count: int, spp: int, run: _abi.MirtAdaptRun) -> int:
     return int(out.value)
 
 
-def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort=False, pool=False) -> _abi.MirtRadianceParams:
+def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort=False, pool=False, lds=False) -> _abi.MirtRadianceParams:
     for name, v in (("spp", spp), ("sample_begin", sample_begin), ("num_bounces", num_bounces)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
             raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
@@ -351,7 +358,7 @@ def _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumula
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError(f"{name} must be a bool, not {v!r}")
     flags = (_abi.MIRT_RADIANCE_FLAT if flat else 0) | (_abi.MIRT_RADIANCE_SKY_HOSEK if hosek else 0) | (_abi.MIRT_RADIANCE_ACCUMULATE if accumulate else 0) \
-        | (_abi.MIRT_RADIANCE_SORT if sort else 0) | (_abi.MIRT_RADIANCE_POOL if pool else 0)
+        | (_abi.MIRT_RADIANCE_SORT if sort else 0) | (_abi.MIRT_RADIANCE_POOL if pool else 0) | _lds_flag(lds)
     return _abi.MirtRadianceParams(int(spp), int(sample_begin), int(num_bounces), flags, int(seed))
 
 
@@ -428,6 +435,7 @@ class Context:
         else:
             check(lib().mirt_ctx_set_scene(self._h, C.byref(c)))
         self._scene = scene
+        self._scene_hbm = bool(hbm)
 
     def bvh_info(self) -> dict:
         """mirt_ctx_bvh_info: the tree this context holds -- {"plan": counts as bvh_plan() reports them, "root", "built_on_device",
@@ -482,25 +490,27 @@ class Context:
         check(lib().mirt_ctx_set_spheres_device(self._h, C.c_void_p(int(d_ptr)) if int(count) else None, int(count)))
 
     # ---- ray queries against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
-    def trace_rays(self, rays, flags: int = 0, sort: bool = False) -> np.ndarray:
+    def trace_rays(self, rays, flags: int = 0, sort: bool = False, lds: bool = False) -> np.ndarray:
         """mirt_ctx_trace_rays: the flat scan's answer for every ray, by the renderer's own arithmetic -> a RAY_HIT_DTYPE array, one
         record per ray in the caller's order; `sphere` == MIRT_RAY_MISS (and everything else 0) for a miss.  `rays`: see ray_records
         (make_rays builds them); flags: MIRT_RAYS_FLAT / _ANY_HIT / _COUNT / _SORT; sort=True sets MIRT_RAYS_SORT: the batch is traced
-        in an order derived on the device, the records are the same.  Needs a scene set with hbm=True.  Blocking."""
+        in an order derived on the device, the records are the same.  Needs a scene set with hbm=True, or lds=True (MIRT_QUERY_LDS):
+        then a scene that lives in LDS answers too, with the same records -- through its uniform grid, or with MIRT_RAYS_FLAT through
+        its flat tables; `sort` is then ignored, and an HBM scene ignores `lds`.  Blocking."""
         recs = ray_records(rays)
-        flags = _check_rays_flags(flags, sort)
+        flags = _check_rays_flags(flags, sort, lds)
         hits = np.zeros(len(recs), RAY_HIT_DTYPE)
         check(lib().mirt_ctx_trace_rays(self._h, C.c_void_p(recs.ctypes.data) if len(recs) else None, len(recs), flags,
                                         C.c_void_p(hits.ctypes.data) if len(recs) else None))
         self._note_sorted(flags & _abi.MIRT_RAYS_SORT, len(recs))
         return hits
 
-    def trace_rays_device(self, d_rays: int, n: int, d_hits: int, flags: int = 0, stream: Optional[int] = None, sort: bool = False) -> None:
+    def trace_rays_device(self, d_rays: int, n: int, d_hits: int, flags: int = 0, stream: Optional[int] = None, sort: bool = False, lds: bool = False) -> None:
         """mirt_ctx_trace_rays_device: `n` 32-byte MirtRay records at device address `d_rays` -> `n` MirtRayHit records at `d_hits`
         (e.g. torch tensors' data_ptr()), asynchronously on `stream` (see _stream_arg); no host synchronisation (sort=True: unless the
-        context's sort scratch must grow; sorted launches of one context are kept in order by the caller)."""
+        context's sort scratch must grow; sorted launches of one context are kept in order by the caller).  lds: as in trace_rays."""
         _check_range(0, n)
-        flags = _check_rays_flags(flags, sort)
+        flags = _check_rays_flags(flags, sort, lds)
         if int(n):
             d_rays, d_hits = _check_address("d_rays", d_rays), _check_address("d_hits", d_hits)
         check(lib().mirt_ctx_trace_rays_device(self._h, C.c_void_p(d_rays) if int(n) else None, int(n), flags,
@@ -515,7 +525,7 @@ class Context:
         return st.as_dict()
 
     def _note_sorted(self, sort, n: int) -> None:
-        if sort and n:       # the length trace_order reads: that of the last sorted launch the library accepted
+        if sort and n and getattr(self, "_scene_hbm", True):       # (a scene in LDS, reached with lds=True, ignores the hint: no sorted launch)
             self._sorted_n = n
 
     def trace_order(self) -> np.ndarray:
@@ -528,7 +538,7 @@ class Context:
 
     # ---- path-traced radiance for a caller's rays against the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
     def trace_radiance(self, rays, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0, flat: bool = False,
-                       hosek: bool = False, into: Optional[np.ndarray] = None, sort: bool = False, pool: bool = False) -> np.ndarray:
+                       hosek: bool = False, into: Optional[np.ndarray] = None, sort: bool = False, pool: bool = False, lds: bool = False) -> np.ndarray:
         """mirt_ctx_trace_radiance: `spp` samples of the path tracer for every ray -> a RADIANCE_DTYPE array {"sum" [3] in 2^-20 units,
         "samples"}, one record per ray in the caller's order (radiance_mean gives the means).  A sample is the renderer's from its
         primary ray on: samples sample_begin .. sample_begin + spp - 1 of the RNG stream a pixel of index `stream` has under `seed`.
@@ -537,9 +547,11 @@ class Context:
         returned -- a progressive probe passes sample_begin = the samples it holds.  sort=True (MIRT_RADIANCE_SORT): the batch runs in
         an order derived on the device, for batches that are not in a coherent order; the records are the same.  pool=True (MIRT_RADIANCE_POOL): a hint to run the
         pooled schedule, which deals the samples of 16 rays to a wave's lanes (Context.last_kernel tells whether it ran); the records are
-        the same.  Needs a scene set with hbm=True.  Blocking."""
+        the same.  Needs a scene set with hbm=True, or lds=True (MIRT_QUERY_LDS): then a scene that lives in LDS answers too, with the
+        same records (its grid, or with flat=True its flat tables; `sort` and `pool` are then ignored); an HBM scene ignores `lds`.
+        Blocking."""
         recs = radiance_ray_records(rays)
-        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, into is not None, sort, pool)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, into is not None, sort, pool, lds)
         if into is None:
             out = np.zeros(len(recs), RADIANCE_DTYPE)
         else:
@@ -553,13 +565,14 @@ class Context:
 
     def trace_radiance_device(self, d_rays: int, n: int, d_out: int, spp: int, *, sample_begin: int = 0, num_bounces: int = 8, seed: int = 0,
                               flat: bool = False, hosek: bool = False, accumulate: bool = False, stream: Optional[int] = None,
-                              sort: bool = False, pool: bool = False) -> None:
+                              sort: bool = False, pool: bool = False, lds: bool = False) -> None:
         """mirt_ctx_trace_radiance_device: `n` 32-byte MirtRadianceRay records at device address `d_rays` -> `n` MirtRadiance records at
         `d_out` (e.g. torch tensors' data_ptr()), one kernel queued on `stream` (see _stream_arg); no host synchronisation.
         accumulate=True adds to the records already at `d_out`.  sort=True: the code kernel and the sort are queued in front of it (sorted
-        launches of one context are kept in order by the caller).  pool=True: the pooled schedule (a hint, as in trace_radiance)."""
+        launches of one context are kept in order by the caller).  pool=True: the pooled schedule (a hint, as in trace_radiance).
+        lds: as in trace_radiance."""
         _check_range(0, n)
-        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort, pool)
+        params = _radiance_params(spp, sample_begin, num_bounces, seed, flat, hosek, accumulate, sort, pool, lds)
         if int(n):
             d_rays, d_out = _check_address("d_rays", d_rays), _check_address("d_out", d_out)
         check(lib().mirt_ctx_trace_radiance_device(self._h, C.c_void_p(d_rays) if int(n) else None, int(n), C.byref(params),
@@ -567,30 +580,34 @@ class Context:
         self._note_sorted(sort, int(n))
 
     # ---- first-hit feature frames of the resident MIRT_SCENE_HBM scene (include/mirt.h) ----
-    def render_features(self, params: _abi.MirtParams, flat: bool = False) -> np.ndarray:
+    def render_features(self, params: _abi.MirtParams, flat: bool = False, lds: bool = False) -> np.ndarray:
         """mirt_ctx_render_features: what the camera sees first at every pixel of the rows `params` selects -> a FEATURE_DTYPE array
         [rows, width] {"albedo", "t", "normal", "sphere"}; `sphere` == MIRT_RAY_MISS and `t` == 0 where the centre ray leaves the scene.
         params.spp == 0: the centre ray alone; spp >= 1: albedo and normal are means over the renderer's own primary rays of those
-        samples.  flat=True runs the flat scan instead of the tree (the comparison build).  Needs a scene set with hbm=True.  Blocking."""
+        samples.  flat=True runs the flat scan instead of the tree (the comparison build).  Needs a scene set with hbm=True, or
+        lds=True (MIRT_QUERY_LDS): then a scene that lives in LDS answers too, with the same records (its grid, or with flat=True its
+        flat tables); an HBM scene ignores `lds`.  Blocking."""
         params = _check_params(params)
         if not isinstance(flat, (bool, np.bool_)):
             raise ValueError(f"flat must be a bool, not {flat!r}")
+        lds_flag = _lds_flag(lds)
         rows, width = max(params_out_rows(params), 0), int(params.width)
         buf = np.zeros(max(rows * width, 1), FEATURE_DTYPE)              # (never a null pointer: a part may own no row)
-        check(lib().mirt_ctx_render_features(self._h, C.byref(params), _abi.MIRT_FEATURES_FLAT if flat else 0,
+        check(lib().mirt_ctx_render_features(self._h, C.byref(params), (_abi.MIRT_FEATURES_FLAT if flat else 0) | lds_flag,
                                              C.c_void_p(buf.ctypes.data), rows * width * FEATURE_DTYPE.itemsize))
         return buf[:rows * width].reshape(rows, width)
 
-    def render_features_device(self, params: _abi.MirtParams, d_ptr: int, nbytes: int, flat: bool = False, stream: Optional[int] = None) -> None:
+    def render_features_device(self, params: _abi.MirtParams, d_ptr: int, nbytes: int, flat: bool = False, stream: Optional[int] = None, lds: bool = False) -> None:
         """mirt_ctx_render_features_device: the same records into `nbytes` of device memory at `d_ptr` (4-byte aligned, e.g. a torch
-        tensor's data_ptr()), one kernel queued on `stream` (see _stream_arg); no host synchronisation."""
+        tensor's data_ptr()), one kernel queued on `stream` (see _stream_arg); no host synchronisation.  lds: as in render_features."""
         params = _check_params(params)
         if not isinstance(flat, (bool, np.bool_)):
             raise ValueError(f"flat must be a bool, not {flat!r}")
+        lds_flag = _lds_flag(lds)
         d_ptr = _check_address("d_ptr", d_ptr)
         if not isinstance(nbytes, (int, np.integer)) or isinstance(nbytes, bool) or int(nbytes) < 0:
             raise ValueError(f"nbytes must be a byte count, not {nbytes!r}")
-        check(lib().mirt_ctx_render_features_device(self._h, C.byref(params), _abi.MIRT_FEATURES_FLAT if flat else 0, C.c_void_p(d_ptr),
+        check(lib().mirt_ctx_render_features_device(self._h, C.byref(params), (_abi.MIRT_FEATURES_FLAT if flat else 0) | lds_flag, C.c_void_p(d_ptr),
                                                     int(nbytes), _stream_arg(stream)))
 
     def bvh_refits(self) -> int:

@@ -283,6 +283,7 @@ Tuning read_tuning()
     if (const char* e = std::getenv("MIRT_RADIANCE_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.radiance_pool_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_ADAPT_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_pool_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_ADAPT_LDS_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_lds_blocks = (uint32_t)v; }
+    if (const char* e = std::getenv("MIRT_QUERY_LDS_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.query_lds_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_ADAPT_LDS_GROUPS")) { const int v = std::atoi(e); if (v >= 1 && v <= 3) t.adapt_lds_groups = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_GRID_BIG")) { const double v = std::atof(e); if (v >= 1.0 && v <= 1024.0) t.grid_big = v; }
     return t;
@@ -1232,7 +1233,7 @@ static void fill_bvh_args(const MirtContext* c, mirt::RenderArgs* a, uint32_t st
 // sph3 --, behind fill_common_args: the counterpart of fill_render_args for the query launches.
 static void fill_query_args(const MirtContext* c, const mirt::QueryPlan& pl, mirt::RenderArgs* a)
 {
-    const bool lds_scene = pl.family == mirt::kQueryAdaptLds;
+    const bool lds_scene = mirt::query_family_lds(pl.family);
     if (!lds_scene) fill_bvh_args(c, a, pl.bvh_stack_entries);
     else for (int k = 0; k < 12; ++k) a->sph3[k] = c->sph3[k];
     if (pl.grid) { a->grid = c->d_grid; a->grid_bytes = c->grid_bytes; a->grid_flat_y = c->grid_flat_y ? 1u : 0u; }
@@ -1552,9 +1553,13 @@ static int check_trace(const MirtContext* c, const void* rays, uint32_t n, uint3
 {
     *go = false;
     if (!c) return fail(MIRT_ERR_NULL_POINTER, "ctx is null");
-    if (flags & ~(uint32_t)(MIRT_RAYS_FLAT | MIRT_RAYS_ANY_HIT | MIRT_RAYS_COUNT | MIRT_RAYS_SORT)) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RAYS_* bits 0x%x", flags);
+    if (flags & ~(uint32_t)(MIRT_RAYS_FLAT | MIRT_RAYS_ANY_HIT | MIRT_RAYS_COUNT | MIRT_RAYS_SORT | MIRT_QUERY_LDS)) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RAYS_* bits 0x%x", flags);
     if (n && (!rays || !hits)) return fail(MIRT_ERR_NULL_POINTER, "rays/hits is null");
-    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (!c->have_scene || (!c->hbm && !(flags & MIRT_QUERY_LDS))) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene (a scene in LDS takes MIRT_QUERY_LDS)");
+    if (!c->hbm) {                                           // MIRT_QUERY_LDS on a scene in LDS: the layout, last
+        const mirt::QueryPlan pl = mirt::plan_trace(plan_facts(c), c->tuning, n, flags);
+        if (pl.status != MIRT_OK) return fail(pl.status, "%s", pl.message);
+    }
     *go = n != 0u;
     return MIRT_OK;
 }
@@ -1586,11 +1591,18 @@ static int queue_query(MirtContext* c, const mirt::QueryPlan& pl, const mirt::Re
     return MIRT_OK;
 }
 
+// An MIRT_QUERY_LDS launch runs a persistent grid: its kernel's occupancy bounds the blocks, as an MIRT_ADAPT_LDS step's does (queue_adapt_steps)
+static void size_query_grid(mirt::QueryPlan& pl)
+{
+    if (mirt::query_family_lds(pl.family)) mirt::query_plan_blocks(pl, kx::blocks_per_cu(kx::query_kernel(pl), pl.threads, pl.lds_bytes));
+}
+
 // Queue trace_rays_kernel<bvh, any, count> (trace_rays_sorted_kernel behind the code kernel and the sort with MIRT_RAYS_SORT) for n > 0 rays in
 // device memory on `st`.  No host synchronisation.
 static int launch_trace(MirtContext* c, const void* d_rays, uint32_t n, uint32_t flags, void* d_hits, hipStream_t st)
 {
-    const mirt::QueryPlan pl = mirt::plan_trace(plan_facts(c), c->tuning, n, flags);
+    mirt::QueryPlan pl = mirt::plan_trace(plan_facts(c), c->tuning, n, flags);
+    size_query_grid(pl);
     mirt::RenderArgs a{};
     fill_common_args(c, &a, MirtParams{}, 0u, -1);
     a.counters = c->d_trace_counters;
@@ -1684,8 +1696,8 @@ int mirt_ctx_trace_stats(MirtContext* c, MirtRayStats* out)
 static int check_features(const MirtContext* c, const MirtParams* p, uint32_t flags, const void* out, size_t out_len)
 {
     if (!c || !p || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/out is null");
-    if (flags & ~(uint32_t)MIRT_FEATURES_FLAT) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_FEATURES_* bits 0x%x", flags);
-    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (flags & ~(uint32_t)(MIRT_FEATURES_FLAT | MIRT_QUERY_LDS)) return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_FEATURES_* bits 0x%x", flags);
+    if (!c->have_scene || (!c->hbm && !(flags & MIRT_QUERY_LDS))) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene (a scene in LDS takes MIRT_QUERY_LDS)");
     if (p->width == 0 || p->height == 0)
         return fail(MIRT_ERR_VIEWPORT_SIZE, "viewport_size elements cannot be zero: (%u, %u)", p->width, p->height);
     uint32_t rb, re;
@@ -1698,6 +1710,10 @@ static int check_features(const MirtContext* c, const MirtParams* p, uint32_t fl
     const size_t need = (size_t)out_rows(p) * p->width * sizeof(MirtFeaturePixel);
     if (out_len < need) return fail(MIRT_ERR_OUT_BUFFER, "output buffer holds %zu bytes, %zu needed", out_len, need);
     if (c->pt_scene_status != MIRT_OK) return fail(c->pt_scene_status, "scene tables are inconsistent: %s", mirt_status_string(c->pt_scene_status));
+    if (!c->hbm) {                                           // MIRT_QUERY_LDS on a scene in LDS: the layout, last
+        const mirt::QueryPlan pl = mirt::plan_features(plan_facts(c), c->tuning, *p, flags);
+        if (pl.status != MIRT_OK) return fail(pl.status, "%s", pl.message);
+    }
     return MIRT_OK;
 }
 
@@ -1705,7 +1721,8 @@ static int check_features(const MirtContext* c, const MirtParams* p, uint32_t fl
 // accumulation stay as they are; the event pair and the pending flag are the ray queries' (mirt_ctx_trace_stats folds the time).
 static int launch_features(MirtContext* c, const MirtParams* p, uint32_t flags, void* d_out, hipStream_t st)
 {
-    const mirt::QueryPlan pl = mirt::plan_features(plan_facts(c), c->tuning, *p, flags);
+    mirt::QueryPlan pl = mirt::plan_features(plan_facts(c), c->tuning, *p, flags);
+    size_query_grid(pl);
     mirt::RenderArgs a{};
     fill_common_args(c, &a, *p, out_rows(p), pinhole_word(c));     // the camera with generate_primary's pinhole word, as in launch_render
     fill_query_args(c, pl, &a);                                    // traversal stacks as for ray queries
@@ -1762,15 +1779,19 @@ static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, co
     *go = false;
     if (!c || !p) return fail(MIRT_ERR_NULL_POINTER, "ctx/params is null");
     if (n && (!rays || !out)) return fail(MIRT_ERR_NULL_POINTER, "rays/out is null");
-    if (p->flags & ~(uint32_t)(MIRT_RADIANCE_FLAT | MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_SKY_HOSEK | MIRT_RADIANCE_SORT | MIRT_RADIANCE_POOL))
+    if (p->flags & ~(uint32_t)(MIRT_RADIANCE_FLAT | MIRT_RADIANCE_ACCUMULATE | MIRT_RADIANCE_SKY_HOSEK | MIRT_RADIANCE_SORT | MIRT_RADIANCE_POOL | MIRT_QUERY_LDS))
         return fail(MIRT_ERR_BAD_MODE, "unknown MIRT_RADIANCE_* bits 0x%x", p->flags);
-    if (!c->have_scene || !c->hbm) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene");
+    if (!c->have_scene || (!c->hbm && !(p->flags & MIRT_QUERY_LDS))) return fail(MIRT_ERR_NO_SCENE, "the context holds no MIRT_SCENE_HBM scene (a scene in LDS takes MIRT_QUERY_LDS)");
     if (p->spp == 0) return fail(MIRT_ERR_SPP_ZERO, "spp is zero");
     if (p->spp > MIRT_MAX_SPP_PER_CALL || (uint64_t)p->sample_begin + p->spp > 0xffffffffull)
         return fail(MIRT_ERR_SPP_RANGE, "spp %u (from sample %u) is out of range: at most %u samples per ray in one call, sample indices below 2^32",
                     p->spp, p->sample_begin, (unsigned)MIRT_MAX_SPP_PER_CALL);
     if (c->pt_scene_status != MIRT_OK) return fail(c->pt_scene_status, "scene tables are inconsistent: %s", mirt_status_string(c->pt_scene_status));
     if ((p->flags & MIRT_RADIANCE_SKY_HOSEK) && !c->have_sky) return fail(MIRT_ERR_SKY, "MIRT_RADIANCE_SKY_HOSEK needs scene.sky");
+    if (!c->hbm) {                                           // MIRT_QUERY_LDS on a scene in LDS: the layout, last
+        const mirt::QueryPlan pl = mirt::plan_radiance(plan_facts(c), c->tuning, n, *p);
+        if (pl.status != MIRT_OK) return fail(pl.status, "%s", pl.message);
+    }
     *go = n != 0u;
     return MIRT_OK;
 }
@@ -1783,7 +1804,8 @@ static int check_radiance(const MirtContext* c, const void* rays, uint32_t n, co
 // deep; otherwise the launch is the one without the flag.
 static int launch_radiance(MirtContext* c, const void* d_rays, uint32_t n, const MirtRadianceParams* p, void* d_out, hipStream_t st)
 {
-    const mirt::QueryPlan pl = mirt::plan_radiance(plan_facts(c), c->tuning, n, *p);
+    mirt::QueryPlan pl = mirt::plan_radiance(plan_facts(c), c->tuning, n, *p);
+    size_query_grid(pl);
     MirtParams q{};                                       // the query's sampling fields as a render call's; no frame, no rows
     q.spp = p->spp; q.num_bounces = p->num_bounces; q.flags = p->flags; q.seed = p->seed; q.sample_begin = p->sample_begin;
     mirt::RenderArgs a{};

@@ -2256,6 +2256,9 @@ static QueryKernel kernel_handle(K kernel) { return reinterpret_cast<QueryKernel
 #include "mirt_adapt_kernel.inc"
 #include "mirt_adapt_pool_kernel.inc"
 #include "mirt_adapt_lds_kernel.inc"
+#include "mirt_trace_lds_kernel.inc"
+#include "mirt_feature_lds_kernel.inc"
+#include "mirt_radiance_lds_kernel.inc"
 
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns
@@ -2672,6 +2675,9 @@ QueryKernel query_kernel(const QueryPlan& p)
     case kQueryAdapt:        return adapt_kernel(p);
     case kQueryAdaptPool:    return adapt_pool_kernel(p);
     case kQueryAdaptLds:     return adapt_lds_kernel(p);
+    case kQueryTraceLds:     return trace_lds_kernel(p);
+    case kQueryFeaturesLds:  return feature_lds_kernel(p);
+    case kQueryRadianceLds:  return radiance_lds_kernel(p);
     default:                 return nullptr;
     }
 }
@@ -2687,9 +2693,12 @@ hipError_t launch_query(const QueryPlan& p, const RenderArgs& a, const QueryBuff
     // the kernels' arguments behind RenderArgs, in their order (hipLaunchKernel copies as many as the kernel has, each by its own size)
     const void* args[5] = { &a };
     switch (p.family) {
-    case kQueryTrace:        args[1] = &b.in; args[2] = &b.out; args[3] = &p.n_rays; args[4] = &b.order; break;     // (rays, hits, n_rays[, order])
-    case kQueryFeatures:     args[1] = &b.out; break;                                                               // (pixels)
+    case kQueryTrace:
+    case kQueryTraceLds:     args[1] = &b.in; args[2] = &b.out; args[3] = &p.n_rays; args[4] = &b.order; break;     // (rays, hits, n_rays[, order])
+    case kQueryFeatures:
+    case kQueryFeaturesLds:  args[1] = &b.out; break;                                                               // (pixels)
     case kQueryRadiance:
+    case kQueryRadianceLds:
     case kQueryRadiancePool: args[1] = &b.in; args[2] = &b.out; args[3] = &b.order; break;                          // (rays, records[, order])
     default:                 args[1] = &b.out; args[2] = &b.order; args[3] = &b.count; break;                       // (records, list, head words)
     }

@@ -71,6 +71,7 @@ struct Tuning {
     uint32_t radiance_pool_blocks = 0;    // MIRT_RADIANCE_POOL_BLOCKS=n (A/B runs, tests): a pooled radiance query launches at most n blocks, whose waves stride over the units
     uint32_t adapt_pool_blocks = 0;   // MIRT_ADAPT_POOL_BLOCKS=n (A/B runs, tests): a pooled adaptive step launches at most n blocks, whose waves stride over the units
     uint32_t adapt_lds_blocks = 0;    // MIRT_ADAPT_LDS_BLOCKS=n (A/B runs, tests): an MIRT_ADAPT_LDS step launches at most n blocks
+    uint32_t query_lds_blocks = 0;    // MIRT_QUERY_LDS_BLOCKS=n (A/B runs, tests): an MIRT_QUERY_LDS launch (ray, feature or radiance query on a scene in LDS) launches at most n blocks
     uint32_t adapt_lds_groups = 0;    // MIRT_ADAPT_LDS_GROUPS=1/2/3 (A/B runs, tests): an MIRT_ADAPT_LDS step deals samples to 1 / 2 / 4 groups of lanes (capped by spp)
     bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
 };
@@ -146,6 +147,7 @@ void plan_kernel_name(const RenderPlan& plan, char* out, size_t out_len);
 constexpr uint32_t kRadianceThreads = 64;    // radiance_rays_kernel: one wave per block (mirt_radiance_kernel.inc has the measurement)
 constexpr uint32_t kAdaptThreads    = 64;    // adapt_pixels_kernel: one wave per block, as kRadianceThreads
 constexpr uint32_t kAdaptLdsThreads = 256;   // adapt_pixels_lds_kernel: four waves share one staged scene
+constexpr uint32_t kQueryLdsThreads = 256;   // trace_rays_lds_kernel, feature_frame_lds_kernel, radiance_rays_lds_kernel: the same shape
 
 // The kernel family of a query launch; with the bits below it names one template instance of the exact build: query_kernel(plan)
 // (mirt_kernels.h) is that instance and query_kernel_name(plan) prints it for mirt_ctx_last_kernel.
@@ -156,12 +158,17 @@ constexpr uint32_t kAdaptLdsThreads = 256;   // adapt_pixels_lds_kernel: four wa
 //   adapt          adapt_pixels[_run]_kernel<hosek, bvh>                            one thread per pixel of the buffer, one wave per block
 //   adapt-pool     adapt_pixels_pool[_run]_kernel<threads, slots, min waves, hosek>  units of 16 pixels of the buffer, as radiance-pool
 //   adapt-lds      adapt_pixels_lds[_run]_kernel<hosek, grid>                       a persistent grid of the blocks resident at once
-enum QueryFamily : uint32_t { kQueryTrace, kQueryFeatures, kQueryRadiance, kQueryRadiancePool, kQueryAdapt, kQueryAdaptPool, kQueryAdaptLds };
+//   trace-lds      trace_rays_lds_kernel<grid, any, count>                          MIRT_QUERY_LDS on a scene in LDS: adapt-lds's shape,
+//   features-lds   feature_frame_lds_kernel<grid>                                   units of 64 consecutive rays or pixels, lane = ray or pixel
+//   radiance-lds   radiance_rays_lds_kernel<hosek, grid>
+enum QueryFamily : uint32_t { kQueryTrace, kQueryFeatures, kQueryRadiance, kQueryRadiancePool, kQueryAdapt, kQueryAdaptPool, kQueryAdaptLds,
+                              kQueryTraceLds, kQueryFeaturesLds, kQueryRadianceLds };
+constexpr bool query_family_lds(QueryFamily f) { return f == kQueryAdaptLds || f == kQueryTraceLds || f == kQueryFeaturesLds || f == kQueryRadianceLds; }
 
 // What a query launch decides, and the contract between it and its kernel: fill_query_args (mirt_api.hip) copies the fields of the
 // second group into RenderArgs beside what every launch carries (fill_common_args), launch_query dispatches `blocks` x `threads`.
 struct QueryPlan {
-    int         status;               // MIRT_OK, or the one refusal (adapt-lds: MIRT_ERR_SCENE_TOO_LARGE, no layout fits a block's LDS) with its message
+    int         status;               // MIRT_OK, or the one refusal (the LDS families: MIRT_ERR_SCENE_TOO_LARGE, no layout fits a block's LDS) with its message
     const char* message;
     // the kernel
     QueryFamily family;
@@ -172,24 +179,26 @@ struct QueryPlan {
                                       // (+ sky) and, walking the tree, the wave's kBvhStackBytesPerWave; pooled: plan_bvh_pool's block; adapt-lds: plan_adapt_lds's
     uint32_t    bvh_stack_entries;    // trace, features: the depth of the resident tree (at least 1), 0 for the flat scan; pooled: the tree's depth; else 0 =
                                       // MIRT_BVH_MAX_DEPTH, the strip kernels' stacks.  adapt-lds has no tree: its launch leaves every bvh_* field zero
-    uint32_t    n_units;              // radiance: rays; radiance-pool: units of 16 rays; adapt families: pixels of the buffer; else 0
+    uint32_t    n_units;              // radiance, radiance-lds: rays; radiance-pool: units of 16 rays; adapt families: pixels of the buffer; else 0
     uint32_t    px_groups_log2;       // adapt-lds: 0 (the device chooses) or the forced g + 1 (Tuning.adapt_lds_groups); else 0
-    bool        rays_as_row;          // radiance-pool: RenderArgs.width = n_rays, height = 1.  (`grid`: grid, grid_bytes, grid_flat_y travel; adapt-lds: sph3 too)
+    bool        rays_as_row;          // radiance-pool: RenderArgs.width = n_rays, height = 1.  (`grid`: grid, grid_bytes, grid_flat_y travel; the LDS families: sph3 too)
     uint32_t    n_rays;               // trace: the kernel's own argument behind the buffers; radiance(-pool): the batch's length
-    uint32_t    blocks;               // the grid of the launch; adapt-lds: before the occupancy cap (query_plan_blocks)
-    uint32_t    cu_count, blocks_per_cu, at_most_blocks;     // adapt-lds, for query_plan_blocks: the layout's own bound (plan_adapt_lds), Tuning.adapt_lds_blocks
+    uint32_t    blocks;               // the grid of the launch; the LDS families: before the occupancy cap (query_plan_blocks)
+    uint32_t    cu_count, blocks_per_cu, at_most_blocks;     // the LDS families, for query_plan_blocks: the layout's own bound (plan_adapt_lds), Tuning.adapt_lds_blocks / query_lds_blocks
 };
 
 // flags: the caller's MIRT_RAYS_* / MIRT_FEATURES_* bits; adapt_flags: MirtAdaptParams.flags; n_rays > 0; `p`, `rows` (= out_rows(&p)): the
 // params of a feature frame as checked; `q`: those of an adaptive step as check_adapt_step leaves them; `run`: a step of a run (planned
 // once per call); buffer_pixels: records in the context's adaptive buffer.  A pooled request that pooled_bvh_plan gives no geometry
-// plans the launch without the pool.
+// plans the launch without the pool.  MIRT_QUERY_LDS in the flags of a ray, feature or radiance query on a scene that lives in LDS (!f.hbm; the
+// caller has checked the flag) plans the family's LDS kernel over plan_adapt_lds's geometry of the layout: the scene's grid unless the family's
+// _FLAT bit is set, else the flat tables if they fit, else MIRT_ERR_SCENE_TOO_LARGE.  An HBM scene ignores the flag.
 QueryPlan plan_trace(const PlanFacts& f, const Tuning& tune, uint32_t n_rays, uint32_t flags);
 QueryPlan plan_features(const PlanFacts& f, const Tuning& tune, const MirtParams& p, uint32_t flags);
 QueryPlan plan_radiance(const PlanFacts& f, const Tuning& tune, uint32_t n_rays, const MirtRadianceParams& p);
 QueryPlan plan_adapt(const PlanFacts& f, const Tuning& tune, const MirtParams& q, uint32_t adapt_flags, bool run, uint64_t buffer_pixels);
-// adapt-lds, shaped like plan_blocks: a persistent grid of the blocks resident at once -- the smaller of the occupancy answer and the layout's
-// bound, at least one per CU --, or fewer for fewer pixels or Tuning.adapt_lds_blocks; the other families' grids need no answer: nothing
+// The LDS families (query_family_lds), shaped like plan_blocks: a persistent grid of the blocks resident at once -- the smaller of the occupancy answer and the layout's
+// bound, at least one per CU --, or fewer for fewer items or Tuning.adapt_lds_blocks / query_lds_blocks; the other families' grids need no answer: nothing
 void query_plan_blocks(QueryPlan& plan, uint32_t resident_per_cu);
 // The name mirt_ctx_last_kernel reports, written as plan_kernel_name writes a render kernel's
 void query_kernel_name(const QueryPlan& plan, char* out, size_t out_len);

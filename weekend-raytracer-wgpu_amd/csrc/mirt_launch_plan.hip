@@ -371,16 +371,55 @@ static QueryPlan plan_block_query(const PlanFacts& f, QueryFamily family, bool b
     return a;
 }
 
-QueryPlan plan_trace(const PlanFacts& f, const Tuning&, uint32_t n_rays, uint32_t flags)
+// The layout of an MIRT_ADAPT_LDS step or an MIRT_QUERY_LDS query on the resident LDS scene: the scene's grid unless
+// `flat` asks for the flat scan (MIRT_FLAG_NO_GRID; a query family's _FLAT bit), else the flat tables if they fit; plan_adapt_lds's geometry of
+// it, or all fields 0 where neither fits a block's LDS.
+static MirtAdaptLdsPlan adapt_lds_layout(const PlanFacts& f, bool flat, bool hosek)
 {
+    MirtAdaptLdsPlan plan{};
+    if (f.grid_bytes != 0u && !flat) plan = plan_adapt_lds(f.n_spheres, f.n_mats, f.grid_bytes, hosek, f.lds_per_cu);
+    if (plan.lds_bytes_per_block > f.lds_per_block) plan = MirtAdaptLdsPlan{};
+    if (plan.threads == 0u && f.fits_flat) plan = plan_adapt_lds(f.n_spheres, f.n_mats, 0u, hosek, f.lds_per_cu);
+    if (plan.lds_bytes_per_block > f.lds_per_block) plan = MirtAdaptLdsPlan{};
+    return plan;
+}
+
+// An MIRT_QUERY_LDS query over `items` rays or pixels: the family's LDS kernel in the layout's geometry, a persistent grid before its
+// occupancy cap (query_plan_blocks), or the refusal a render with MIRT_FLAG_NO_GRID gives on a grid-only scene.
+static QueryPlan plan_lds_query(const PlanFacts& f, const Tuning& tune, QueryFamily family, bool flat, bool hosek, uint64_t items)
+{
+    QueryPlan a{};
+    const MirtAdaptLdsPlan lds = adapt_lds_layout(f, flat, hosek);
+    a.family = family; a.hosek = hosek; a.grid = lds.grid != 0u;
+    if (lds.threads == 0u) {
+        a.status = MIRT_ERR_SCENE_TOO_LARGE;
+        a.message = flat ? "this scene fits LDS in neither layout an MIRT_QUERY_LDS query has (the _FLAT bit: the flat one only)"
+                         : "this scene fits LDS in neither layout an MIRT_QUERY_LDS query has";
+        return a;
+    }
+    a.threads = kQueryLdsThreads; a.lds_bytes = lds.lds_bytes_per_block;
+    a.blocks = (uint32_t)((items + kQueryLdsThreads - 1u) / kQueryLdsThreads);
+    a.cu_count = f.cu_count; a.blocks_per_cu = lds.blocks_per_cu; a.at_most_blocks = tune.query_lds_blocks;
+    return a;
+}
+
+QueryPlan plan_trace(const PlanFacts& f, const Tuning& tune, uint32_t n_rays, uint32_t flags)
+{
+    if (!f.hbm && (flags & MIRT_QUERY_LDS)) {      // the schedule hint MIRT_RAYS_SORT is accepted and ignored: no tree to take bounds from
+        QueryPlan a = plan_lds_query(f, tune, kQueryTraceLds, (flags & MIRT_RAYS_FLAT) != 0, false, n_rays);
+        a.any = (flags & MIRT_RAYS_ANY_HIT) != 0; a.count = (flags & MIRT_RAYS_COUNT) != 0;
+        a.n_rays = n_rays;
+        return a;
+    }
     QueryPlan a = plan_block_query(f, kQueryTrace, !(flags & MIRT_RAYS_FLAT), n_rays);
     a.any = (flags & MIRT_RAYS_ANY_HIT) != 0; a.count = (flags & MIRT_RAYS_COUNT) != 0; a.sorted = (flags & MIRT_RAYS_SORT) != 0;
     a.n_rays = n_rays;
     return a;
 }
 
-QueryPlan plan_features(const PlanFacts& f, const Tuning&, const MirtParams& p, uint32_t flags)
+QueryPlan plan_features(const PlanFacts& f, const Tuning& tune, const MirtParams& p, uint32_t flags)
 {
+    if (!f.hbm && (flags & MIRT_QUERY_LDS)) return plan_lds_query(f, tune, kQueryFeaturesLds, (flags & MIRT_FEATURES_FLAT) != 0, false, (uint64_t)out_rows(&p) * p.width);
     return plan_block_query(f, kQueryFeatures, !(flags & MIRT_FEATURES_FLAT), (uint64_t)out_rows(&p) * p.width);
 }
 
@@ -413,6 +452,11 @@ static QueryPlan plan_path_query(const PlanFacts& f, QueryFamily unpooled, Query
 QueryPlan plan_radiance(const PlanFacts& f, const Tuning& tune, uint32_t n_rays, const MirtRadianceParams& p)
 {
     const bool bvh = !(p.flags & MIRT_RADIANCE_FLAT), hosek = (p.flags & MIRT_RADIANCE_SKY_HOSEK) != 0;
+    if (!f.hbm && (p.flags & MIRT_QUERY_LDS)) {    // the schedule hints MIRT_RADIANCE_SORT and _POOL are accepted and ignored: no tree, no pooled LDS query build
+        QueryPlan a = plan_lds_query(f, tune, kQueryRadianceLds, !bvh, hosek, n_rays);
+        a.n_units = n_rays; a.n_rays = n_rays;
+        return a;
+    }
     MirtBvhPoolPlan pool{};
     if ((p.flags & MIRT_RADIANCE_POOL) && bvh) pool = pooled_bvh_plan(f, tune, hosek, 0u, p.num_bounces);
     QueryPlan a = plan_path_query(f, kQueryRadiance, kQueryRadiancePool, bvh, hosek, n_rays, kRadianceThreads, pool, tune.radiance_pool_blocks);
@@ -422,25 +466,13 @@ QueryPlan plan_radiance(const PlanFacts& f, const Tuning& tune, uint32_t n_rays,
     return a;
 }
 
-// The layout of an MIRT_ADAPT_LDS step on the resident LDS scene: the scene's grid unless MIRT_FLAG_NO_GRID asks for the
-// flat scan, else the flat tables if they fit; plan_adapt_lds's geometry of it, or all fields 0 where neither fits a block's LDS.
-static MirtAdaptLdsPlan adapt_lds_layout(const PlanFacts& f, uint32_t flags, bool hosek)
-{
-    MirtAdaptLdsPlan plan{};
-    if (f.grid_bytes != 0u && !(flags & MIRT_FLAG_NO_GRID)) plan = plan_adapt_lds(f.n_spheres, f.n_mats, f.grid_bytes, hosek, f.lds_per_cu);
-    if (plan.lds_bytes_per_block > f.lds_per_block) plan = MirtAdaptLdsPlan{};
-    if (plan.threads == 0u && f.fits_flat) plan = plan_adapt_lds(f.n_spheres, f.n_mats, 0u, hosek, f.lds_per_cu);
-    if (plan.lds_bytes_per_block > f.lds_per_block) plan = MirtAdaptLdsPlan{};
-    return plan;
-}
-
 QueryPlan plan_adapt(const PlanFacts& f, const Tuning& tune, const MirtParams& q, uint32_t adapt_flags, bool run, uint64_t buffer_pixels)
 {
     const bool hosek = (q.flags & MIRT_FLAG_SKY_HOSEK) != 0;
     QueryPlan a{};
     if (!f.hbm) {
         // a scene that lives in LDS (the caller has seen MIRT_ADAPT_LDS): adapt_pixels_lds_kernel over the staged scene of the layout
-        const MirtAdaptLdsPlan lds = adapt_lds_layout(f, q.flags, hosek);
+        const MirtAdaptLdsPlan lds = adapt_lds_layout(f, (q.flags & MIRT_FLAG_NO_GRID) != 0, hosek);
         a.family = kQueryAdaptLds;
         a.hosek = hosek; a.grid = lds.grid != 0u;
         if (lds.threads == 0u) {
@@ -468,7 +500,7 @@ QueryPlan plan_adapt(const PlanFacts& f, const Tuning& tune, const MirtParams& q
 
 void query_plan_blocks(QueryPlan& a, uint32_t resident_per_cu)
 {
-    if (a.family != kQueryAdaptLds) return;
+    if (!query_family_lds(a.family)) return;
     uint32_t per_cu = resident_per_cu;
     if (per_cu > a.blocks_per_cu) per_cu = a.blocks_per_cu;
     if (per_cu == 0u) per_cu = 1u;
@@ -489,6 +521,9 @@ void query_kernel_name(const QueryPlan& pl, char* out, size_t n)
     case kQueryAdapt:        snprintf(out, n, "adapt_pixels%s_kernel<%s,%s>", run, hosek, tf[pl.bvh]); break;
     case kQueryAdaptPool:    snprintf(out, n, "adapt_pixels_pool%s_kernel<%u,%u,%u,%s>", run, pl.threads, pl.slots, pl.min_waves, hosek); break;
     case kQueryAdaptLds:     snprintf(out, n, "adapt_pixels_lds%s_kernel<%s,%s>", run, hosek, tf[pl.grid]); break;
+    case kQueryTraceLds:     snprintf(out, n, "trace_rays_lds_kernel<%s,%s,%s>", tf[pl.grid], tf[pl.any], tf[pl.count]); break;
+    case kQueryFeaturesLds:  snprintf(out, n, "feature_frame_lds_kernel<%s>", tf[pl.grid]); break;
+    case kQueryRadianceLds:  snprintf(out, n, "radiance_rays_lds_kernel<%s,%s>", hosek, tf[pl.grid]); break;
     }
 }
 

@@ -217,6 +217,10 @@ inline std::vector<MirtAdaptRunStep> adapt_run_log(MirtContext* ctx)
 // MirtGridPlan.blob_bytes, 0 for the flat layout; all fields 0: no such layout), adapt_lds_groups the rule by which the device deals a
 // pixel's samples to 1 << g groups of lanes; both host only.
 static_assert(MIRT_ADAPT_LDS == 1u << 3 && sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptParams.flags: adaptive steps on a scene in LDS");
+// MIRT_QUERY_LDS in the flags of trace_rays / render_features and in MirtRadianceParams.flags: the query also accepts a scene that lives in
+// LDS, where it stays (same records as on the same world held as a MIRT_SCENE_HBM scene, which ignores the flag); geometry: adapt_lds_plan.
+constexpr uint32_t kQueryLds = MIRT_QUERY_LDS;
+static_assert(kQueryLds == 1u << 8, "ray, feature and radiance queries on a scene in LDS");
 inline MirtAdaptLdsPlan adapt_lds_plan(uint32_t n_spheres, uint32_t n_materials, uint32_t grid_bytes = 0, bool hosek = false, uint64_t lds_bytes_per_cu = 0)
 {
     MirtAdaptLdsPlan plan;

@@ -118,7 +118,7 @@ static void print_query_kernel(FILE* out, const char* name, const mirt::QueryPla
 }
 
 // ---- query launches (plan_check --queries / --query-kernels; tests/test_query_plan.py) ----
-static const char* const kFamilyNames[] = { "trace", "features", "radiance", "radiance-pool", "adapt", "adapt-pool", "adapt-lds" };
+static const char* const kFamilyNames[] = { "trace", "features", "radiance", "radiance-pool", "adapt", "adapt-pool", "adapt-lds", "trace-lds", "features-lds", "radiance-lds" };
 
 // The query plan in its fixed one-line format.  id = bvh any count sorted hosek grid run; geo = threads/slots/min waves; bse = bvh_stack_entries;
 // pxg = px_groups_log2; row = rays_as_row; cap = cu_count/blocks_per_cu/at_most_blocks.  A refused launch prints its status and message instead.
@@ -178,6 +178,7 @@ static bool set_field(Case& c, const char* key, const char* val)
         { "t.static_grid", kInt, &t.static_grid }, { "t.hbm_pool_slots", kU32, &t.hbm_pool_slots },
         { "t.radiance_pool_blocks", kU32, &t.radiance_pool_blocks }, { "t.adapt_pool_blocks", kU32, &t.adapt_pool_blocks },
         { "t.adapt_lds_blocks", kU32, &t.adapt_lds_blocks }, { "t.adapt_lds_groups", kU32, &t.adapt_lds_groups },
+        { "t.query_lds_blocks", kU32, &t.query_lds_blocks },
         { "frame", kU32, &c.frame }, { "res", kU32, &c.res },
         { "n", kU32, &c.n }, { "qf", kHex, &c.qf }, { "af", kHex, &c.af }, { "run", kU32, &c.run }, { "px", kU64, &c.px },
     };

@@ -424,49 +424,51 @@ def pixel_ray(camera: _abi.MirtGpuCamera, width: int, height: int, x: int, y: in
     return eye, d.astype(f32)
 
 
-def _pick(owner, x: int, y: int, width: int, height: int, camera: _abi.MirtGpuCamera, scene_data) -> Optional[dict]:
-    """Layer.pick / Raytracer.pick: the sphere under pixel (x, y) by Context.trace_rays with t_max = 1000 (what a path of the renderer
-    would hit first).  Ray queries need the world in device memory: a resident LDS scene -- or none yet -- is set again as a
-    MIRT_SCENE_HBM scene first (the images do not change; owner._hbm is True afterwards).  On a node the query runs on member 0's
-    context."""
-    o, d = pixel_ray(camera, width, height, x, y)              # refuses a pixel outside the viewport before anything is set
+def _query_target(owner, scene_data, lds):
+    """The context a query of Layer / Raytracer runs on (member 0's on a node).  lds=False: the query needs the world in device memory,
+    so a resident LDS scene -- or none yet -- is set again as a MIRT_SCENE_HBM scene first (owner._hbm is True afterwards).  lds=True
+    (MIRT_QUERY_LDS): whatever is resident stays where it is -- a scene held in LDS answers from there, and later renders keep their
+    LDS builds --; with nothing resident yet the library answers MIRT_ERR_NO_SCENE."""
+    if not isinstance(lds, (bool, np.bool_)):
+        raise ValueError(f"lds must be a bool, not {lds!r}")
     target = owner._pick_target()
-    if not owner._hbm:
+    if not owner._hbm and not lds:
         target.set_scene(scene_data(), hbm=True)
         owner._hbm = True
-    ctx = target.context(0) if hasattr(target, "context") else target
-    hit = ctx.trace_rays(make_rays(o, d[None, :], 1000.0))[0]
+    return target.context(0) if hasattr(target, "context") else target
+
+
+def _pick(owner, x: int, y: int, width: int, height: int, camera: _abi.MirtGpuCamera, scene_data, lds: bool = False) -> Optional[dict]:
+    """Layer.pick / Raytracer.pick: the sphere under pixel (x, y) by Context.trace_rays with t_max = 1000 (what a path of the renderer
+    would hit first).  Ray queries need the world in device memory: a resident LDS scene -- or none yet -- is set again as a
+    MIRT_SCENE_HBM scene first (the images do not change; owner._hbm is True afterwards) unless lds=True (_query_target).  On a node
+    the query runs on member 0's context."""
+    o, d = pixel_ray(camera, width, height, x, y)              # refuses a pixel outside the viewport before anything is set
+    ctx = _query_target(owner, scene_data, lds)
+    hit = ctx.trace_rays(make_rays(o, d[None, :], 1000.0), lds=bool(lds))[0]
     if int(hit["sphere"]) == _abi.MIRT_RAY_MISS:
         return None
     return {"sphere": int(hit["sphere"]), "t": float(hit["t"]), "point": hit["point"].copy(), "normal": hit["normal"].copy()}
 
 
-def _features(owner, spp: int, seed: int, width: int, height: int, camera: _abi.MirtGpuCamera, scene_data) -> dict:
+def _features(owner, spp: int, seed: int, width: int, height: int, camera: _abi.MirtGpuCamera, scene_data, lds: bool = False) -> dict:
     """Layer.features / Raytracer.features: Context.render_features of the whole viewport with `camera` -> the planes {"albedo"
     [h, w, 3], "normal" [h, w, 3], "t" [h, w], "sphere" [h, w]}.  Like _pick: a resident LDS scene -- or none yet -- is set again as a
-    MIRT_SCENE_HBM scene first, and on a node member 0's context renders the whole band."""
+    MIRT_SCENE_HBM scene first unless lds=True (_query_target), and on a node member 0's context renders the whole band."""
     if not isinstance(spp, (int, np.integer)) or isinstance(spp, bool) or int(spp) < 0:
         raise ValueError(f"spp must be a sample count >= 0, not {spp!r}")
-    target = owner._pick_target()
-    if not owner._hbm:
-        target.set_scene(scene_data(), hbm=True)
-        owner._hbm = True
-    ctx = target.context(0) if hasattr(target, "context") else target
+    ctx = _query_target(owner, scene_data, lds)
     ctx.set_camera(camera)                                     # Layer.update_camera changes the camera without a device call
-    rec = ctx.render_features(make_params(width, height, int(spp), mode=_abi.MIRT_MODE_PT, seed=seed))
+    rec = ctx.render_features(make_params(width, height, int(spp), mode=_abi.MIRT_MODE_PT, seed=seed), lds=bool(lds))
     return {k: rec[k].copy() for k in ("albedo", "normal", "t", "sphere")}
 
 
-def _radiance(owner, rays, spp: int, seed: int, num_bounces: int, hosek: bool, scene_data, sort: bool = False, pool: bool = False) -> np.ndarray:
+def _radiance(owner, rays, spp: int, seed: int, num_bounces: int, hosek: bool, scene_data, sort: bool = False, pool: bool = False, lds: bool = False) -> np.ndarray:
     """Layer.radiance / Raytracer.radiance: Context.trace_radiance of `rays` (RADIANCE_RAY_DTYPE: make_radiance_rays) -> float64 means
     [n, 3]; sort=True: in an order derived on the device (MIRT_RADIANCE_SORT), the same means.  Like _pick: a resident LDS scene -- or none yet -- is set again as a MIRT_SCENE_HBM scene first, and on a node the query
-    runs on member 0's context."""
-    target = owner._pick_target()
-    if not owner._hbm:
-        target.set_scene(scene_data(), hbm=True)
-        owner._hbm = True
-    ctx = target.context(0) if hasattr(target, "context") else target
-    return radiance_mean(ctx.trace_radiance(rays, spp, num_bounces=num_bounces, seed=seed, hosek=hosek, sort=sort, pool=pool))
+    runs on member 0's context.  lds=True: _query_target."""
+    ctx = _query_target(owner, scene_data, lds)
+    return radiance_mean(ctx.trace_radiance(rays, spp, num_bounces=num_bounces, seed=seed, hosek=hosek, sort=sort, pool=pool, lds=bool(lds)))
 
 
 def _jpeg_check(rc: int) -> None:
@@ -616,30 +618,33 @@ class Layer:
             self._ctx = Context(self._device)
         return self._ctx
 
-    def pick(self, x: int, y: int) -> Optional[dict]:
+    def pick(self, x: int, y: int, *, lds: bool = False) -> Optional[dict]:
         """The sphere of `world` under pixel (x, y) of the viewport (row 0 on top): {"sphere": index into `world`, "t", "point",
         "normal"} -- exactly the record Context.trace_rays returns for the pinhole ray through the pixel's centre (pixel_ray) with
         t_max = 1000 -- or None where the ray leaves the scene.  Ray queries need the world in device memory: if the resident scene is
         not a MIRT_SCENE_HBM one (or nothing is resident yet, before the first set_data) the world is set as one first, and
         move_spheres / set_world then work on it in place; the next set_data sets the scene by its own rule again (a small world goes
-        back to LDS), so a pick after it pays for one more set_scene."""
-        return _pick(self, x, y, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data)
+        back to LDS), so a pick after it pays for one more set_scene.  lds=True (MIRT_QUERY_LDS): a world held in LDS stays there and
+        answers from there, the same record; it needs a resident scene (after the first set_data)."""
+        return _pick(self, x, y, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data, lds)
 
-    def features(self, spp: int = 0, *, seed: int = 0) -> dict:
+    def features(self, spp: int = 0, *, seed: int = 0, lds: bool = False) -> dict:
         """What the camera sees first at every pixel of the viewport: {"albedo" [h, w, 3], "normal" [h, w, 3], "t" [h, w], "sphere"
         [h, w] (index into `world`, MIRT_RAY_MISS where the pixel's centre ray leaves the scene)} by Context.render_features with the
         layer's current camera.  spp = 0: the centre rays alone (an id and depth buffer for picking, exact guides); spp >= 1: albedo
         and normal are means over the path tracer's own primary rays of samples 0 .. spp - 1 (its pixel filter and depth of field).
-        Like pick, it needs the world in device memory and sets it as a MIRT_SCENE_HBM scene first where it is not."""
-        return _features(self, spp, seed, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data)
+        Like pick, it needs the world in device memory and sets it as a MIRT_SCENE_HBM scene first where it is not, unless lds=True
+        (as in pick: the same planes from the scene in LDS)."""
+        return _features(self, spp, seed, int(self.vp_size[0]), int(self.vp_size[1]), self.camera.c, self.scene_data, lds)
 
-    def radiance(self, rays, spp: int = 16, *, seed: int = 0, num_bounces: int = 8, sort: bool = False, pool: bool = False) -> np.ndarray:
+    def radiance(self, rays, spp: int = 16, *, seed: int = 0, num_bounces: int = 8, sort: bool = False, pool: bool = False, lds: bool = False) -> np.ndarray:
         """Path-traced radiance of `world` along rays the caller chooses (make_radiance_rays: panorama and fisheye cameras, probes)
         -> float64 means [n, 3] over samples 0 .. spp - 1 of every ray's stream, by Context.trace_radiance.  Like pick, it needs the
         world in device memory and sets it as a MIRT_SCENE_HBM scene first where it is not.  sort=True traces the batch in an order
         derived on the device: for rays that are not in a coherent order (probe grids, shuffled batches); the means are the same.
-        pool=True asks for the pooled schedule (MIRT_RADIANCE_POOL, a hint): the means are the same."""
-        return _radiance(self, rays, spp, seed, num_bounces, False, self.scene_data, sort, pool)
+        pool=True asks for the pooled schedule (MIRT_RADIANCE_POOL, a hint): the means are the same.  lds=True: as in pick -- the same
+        means from the scene in LDS, where `sort` and `pool` are ignored."""
+        return _radiance(self, rays, spp, seed, num_bounces, False, self.scene_data, sort, pool, lds)
 
     def register_texture(self) -> np.ndarray:         # layer.rs:150-176: the RGBA8 bytes imgui would receive
         if self._rgba is None:
@@ -805,30 +810,34 @@ class Raytracer:
     def _pick_target(self):
         return self._ctx
 
-    def pick(self, x: int, y: int) -> Optional[dict]:
+    def pick(self, x: int, y: int, *, lds: bool = False) -> Optional[dict]:
         """The sphere of the scene under pixel (x, y) of the viewport, as Layer.pick: {"sphere", "t", "point", "normal"} of the pinhole
         ray through the pixel's centre (the lens is ignored), or None.  A scene held in LDS is set again as a MIRT_SCENE_HBM scene
-        first and stays one; the accumulation is not touched (the images are the same either way)."""
+        first and stays one; the accumulation is not touched (the images are the same either way).  lds=True (MIRT_QUERY_LDS) leaves
+        a scene held in LDS where it is and asks it there -- the same record, and later render() and progressive frames keep their
+        LDS builds; on a scene that is already an HBM scene it changes nothing."""
         w, h = self.render_params.viewport_size
-        return _pick(self, x, y, int(w), int(h), self.camera.c, self.scene_data)
+        return _pick(self, x, y, int(w), int(h), self.camera.c, self.scene_data, lds)
 
-    def features(self, spp: Optional[int] = None, *, seed: int = 0) -> dict:
+    def features(self, spp: Optional[int] = None, *, seed: int = 0, lds: bool = False) -> dict:
         """First-hit guides of the current viewport and camera, as Layer.features: {"albedo", "normal", "t", "sphere"} planes.
         spp = None takes `sampling.num_samples_per_pixel`, the samples of one displayed frame (samples 0 .. spp - 1 of `seed`, one RNG
         stream per sample whatever `reference_stream` says: a guide needs the frame's pixel filter, not its draws); spp = 0 the centre
-        rays alone.  A scene held in LDS is set again as a MIRT_SCENE_HBM scene first and stays one; the accumulation is not touched."""
+        rays alone.  A scene held in LDS is set again as a MIRT_SCENE_HBM scene first and stays one; the accumulation is not touched.
+        lds=True: as in pick -- the same planes from the scene in LDS, which stays there."""
         w, h = self.render_params.viewport_size
         if spp is None:
             spp = self.render_params.sampling.num_samples_per_pixel
-        return _features(self, spp, seed, int(w), int(h), self.camera.c, self.scene_data)
+        return _features(self, spp, seed, int(w), int(h), self.camera.c, self.scene_data, lds)
 
-    def radiance(self, rays, spp: Optional[int] = None, *, seed: int = 0, sort: bool = False, pool: bool = False) -> np.ndarray:
+    def radiance(self, rays, spp: Optional[int] = None, *, seed: int = 0, sort: bool = False, pool: bool = False, lds: bool = False) -> np.ndarray:
         """Path-traced radiance of the scene along rays the caller chooses (make_radiance_rays) -> float64 means [n, 3], as
         Layer.radiance.  spp = None takes `sampling.num_samples_per_pixel`; the bounces are `sampling.num_bounces` and the sky is the
-        scene's (the Hosek blob where there is one).  The accumulation is not touched.  sort, pool: as Layer.radiance."""
+        scene's (the Hosek blob where there is one).  The accumulation is not touched.  sort, pool: as Layer.radiance.  lds=True: as in
+        pick -- the same means from the scene in LDS, which stays there (`sort` and `pool` are ignored on it)."""
         if spp is None:
             spp = self.render_params.sampling.num_samples_per_pixel
-        return _radiance(self, rays, spp, seed, self.render_params.sampling.num_bounces, self.sky_state is not None, self.scene_data, sort, pool)
+        return _radiance(self, rays, spp, seed, self.render_params.sampling.num_bounces, self.sky_state is not None, self.scene_data, sort, pool, lds)
 
     def _default_adapt_run(self, ctx, step: int, max_spp: int, pool: bool, hosek: bool):
         """The MirtAdaptRun of render_adaptive(run=True): enough steps for a pixel that takes `step` samples at a time to reach `max_spp`
