@@ -25,13 +25,9 @@ __global__ __launch_bounds__(kAdaptLdsThreads, kAdaptLdsMinWaves) void MIRT_ADAP
     }
     const uint32_t unit_px = 64u >> g;
     const uint32_t units = count / unit_px + (count % unit_px != 0u ? 1u : 0u);      // <= 2^30
-    if (blockIdx.x * kWaves >= units) return;                          // the whole block: nothing staged, no barrier met
-    extern __shared__ __align__(16) unsigned char smem[];
-    const SceneLds S = stage_scene<true, !GRID>(A, smem, HOSEK);
-    GridLds G{};
-    if constexpr (GRID) G = stage_grid(A, smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, HOSEK, false));
-    // no block barrier from here on: a wave without units leaves, the others stride over theirs
-    const uint32_t lane = threadIdx.x & 63u;
+#define MIRT_LDS_SKY HOSEK
+#include "mirt_lds_block_text.inc"
+#undef MIRT_LDS_SKY
     const uint32_t grp = lane >> (6u - g);                             // which share of the samples this lane takes
     const uint32_t n_mine = spp >> g;                                  // wave-uniform: 1 << g divides spp
     Work<false> work;

@@ -3,7 +3,7 @@
 // fast_build:: copy and no counting build.
 //
 // feature_frame_kernel<BVH>: lane = pixel, 64 consecutive COMPACT pixels per wave, kBlockThreads threads per block, one pixel per thread
-// and no loop over pixels.  Lanes of the last wave beyond out_rows x width are not alive: they take part in the wave's loops with their
+// and no loop over pixels; the pixel itself is mirt_feature_item_text.inc.  Lanes of the last wave beyond out_rows x width are not alive: they take part in the wave's loops with their
 // tests masked off and store nothing.  A pixel traces the CENTRE ray first -- generate_primary with both jitter draws replaced by 0.5
 // and a zero lens, no random draw -- whose nearest hit is the record's `sphere` and `t`, and then its sample set: the centre ray alone
 // for spp == 0, else the renderer's own primary rays of samples sample_begin .. sample_begin + spp - 1 (generate_primary itself: jitter,
@@ -54,6 +54,8 @@ MIRT_DEV int feature_nearest_hit(const RenderArgs& A, f3 ro, f3 rd, bool alive, 
 
 // What a hit adds to the sums: sphereIntersection's normal (wgsl:431-440, not turned towards the ray) and the attenuation of the
 // material's scatter routine (scatterRay's switch, wgsl:174-202) without its direction.  Runs in the lanes that hit.
+// (feature_of_hit_lds, mirt_feature_lds_kernel.inc, is this body with the staged tables: one body for both changes the code objects,
+// profiles/r25_isa_identity.md.)
 MIRT_DEV void feature_of_hit(const RenderArgs& A, int best, float t, f3 ro, f3 rd, f3& hn, f3& albedo)
 {
     const PreparedSphere sp = A.spheres[best];
@@ -84,38 +86,11 @@ __global__ __launch_bounds__(kBlockThreads) void feature_frame_kernel(RenderArgs
     Work<false> work;
     work.clear();
 
-    // the centre ray
-    const float u = ((float)x + 0.5f) * C.inv_w;
-    const float v = 1.0f - ((float)y + 0.5f) * C.inv_h;
-    f3 ro = C.eye;
-    f3 rd = fma3(v, C.ver, fma3(u, C.hor, C.llc)) - C.eye;
-    float closest;
-    int best = feature_nearest_hit<BVH>(A, ro, rd, alive, closest, work, lane, stack);
-    const uint32_t sphere = best >= 0 ? (uint32_t)best : kTraceMiss;
-    const float t = best >= 0 ? closest : 0.0f;
-
-    // the sample set: wave-uniform trip count; for spp == 0 the one sample is the centre ray and its hit above
-    f3 sum_n = mk(0, 0, 0), sum_a = mk(0, 0, 0);
-    const uint32_t n = A.spp ? A.spp : 1u;
-    Rng rng;
-    rng.state = 0u;
-    for (uint32_t s = 0; s < n; ++s) {
-        if (A.spp != 0u) {
-            generate_primary(A, C, x, y, A.sample_begin + s, rng, ro, rd);
-            best = feature_nearest_hit<BVH>(A, ro, rd, alive, closest, work, lane, stack);
-        }
-        if (alive && best >= 0) {
-            f3 hn, al;
-            feature_of_hit(A, best, closest, ro, rd, hn, al);
-            sum_n = sum_n + hn;
-            sum_a = sum_a + al;
-        }
-    }
-    if (alive) {
-        const float fn = (float)n;
-        out[2u * i] = trace_u4{ bits(sum_a.x / fn), bits(sum_a.y / fn), bits(sum_a.z / fn), bits(t) };
-        out[2u * i + 1u] = trace_u4{ bits(sum_n.x / fn), bits(sum_n.y / fn), bits(sum_n.z / fn), sphere };
-    }
+#define MIRT_FEATURE_NEAREST feature_nearest_hit<BVH>(A, ro, rd, alive, closest, work, lane, stack)
+#define MIRT_FEATURE_OF_HIT feature_of_hit(A, best, closest, ro, rd, hn, al)
+#include "mirt_feature_item_text.inc"
+#undef MIRT_FEATURE_NEAREST
+#undef MIRT_FEATURE_OF_HIT
 }
 
 static QueryKernel feature_kernel(const QueryPlan& p)

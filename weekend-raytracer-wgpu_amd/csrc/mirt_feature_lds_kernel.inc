@@ -7,7 +7,8 @@
 // consecutive COMPACT pixels, unit = blockIdx.x * 4 + wave, + gridDim.x * 4: lane = pixel, the wave composition of feature_frame_kernel.
 // A block whose first unit does not exist returns before anything is staged; in a live block every wave passes the staging barriers and
 // there is no block barrier behind them.
-// The body is feature_frame_kernel's -- centre ray first, then the sample set, float sums from +0 -- with the nearest hit replaced:
+// The block begins with mirt_lds_block_text.inc; a pixel is mirt_feature_item_text.inc, the text feature_frame_kernel includes -- centre
+// ray first, then the sample set, float sums from +0 -- with this layout's nearest hit:
 //   GRID = false: nearest_hit over the staged sphere table, original index order (the strip kernels' flat scan);
 //   GRID = true : nearest_hit_grid, the strip kernels' walk, two-dimensional where the grid is one cell high.
 // Both start at kMaxT and are held to the flat scan of the HBM build bit for bit (test_sphere's (f, id) tie-break and the builder's
@@ -28,7 +29,7 @@ MIRT_DEV int feature_nearest_hit_lds(const RenderArgs& A, const SceneLds& S, con
     }
 }
 
-// feature_of_hit with the tables where this layout keeps them
+// feature_of_hit (mirt_feature_kernel.inc) with the tables where this layout keeps them; a fix to one is a fix to both
 template <bool GRID>
 MIRT_DEV void feature_of_hit_lds(const RenderArgs& A, const SceneLds& S, int best, float t, f3 ro, f3 rd, f3& hn, f3& albedo)
 {
@@ -53,13 +54,9 @@ __global__ __launch_bounds__(kQueryLdsThreads, kQueryLdsMinWaves) void feature_f
     constexpr uint32_t kWaves = kQueryLdsThreads / 64u;
     const uint64_t n_pix = (uint64_t)A.out_rows * A.width;                  // < 2^32 (check_features)
     const uint32_t units = (uint32_t)((n_pix + 63u) / 64u);
-    if (blockIdx.x * kWaves >= units) return;                               // the whole block: nothing staged, no barrier met
-    extern __shared__ __align__(16) unsigned char smem[];
-    const SceneLds S = stage_scene<true, !GRID>(A, smem, false);
-    GridLds G{};
-    if constexpr (GRID) G = stage_grid(A, smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, false, false));
-    // no block barrier from here on: a wave without units leaves, the others stride over theirs
-    const uint32_t lane = threadIdx.x & 63u;
+#define MIRT_LDS_SKY false
+#include "mirt_lds_block_text.inc"
+#undef MIRT_LDS_SKY
     const uint32_t grid_waves = gridDim.x * kWaves;
     const CamRegs C = feature_camera(A);
     Work<false> work;
@@ -71,38 +68,11 @@ __global__ __launch_bounds__(kQueryLdsThreads, kQueryLdsMinWaves) void feature_f
         const uint32_t ci = pi / A.width;
         const uint32_t x = pi - ci * A.width, y = abs_row(A, ci);
 
-        // the centre ray
-        const float u = ((float)x + 0.5f) * C.inv_w;
-        const float v = 1.0f - ((float)y + 0.5f) * C.inv_h;
-        f3 ro = C.eye;
-        f3 rd = fma3(v, C.ver, fma3(u, C.hor, C.llc)) - C.eye;
-        float closest;
-        int best = feature_nearest_hit_lds<GRID>(A, S, G, ro, rd, alive, closest, work, lane);
-        const uint32_t sphere = best >= 0 ? (uint32_t)best : kTraceMiss;
-        const float t = best >= 0 ? closest : 0.0f;
-
-        // the sample set: wave-uniform trip count; for spp == 0 the one sample is the centre ray and its hit above
-        f3 sum_n = mk(0, 0, 0), sum_a = mk(0, 0, 0);
-        const uint32_t n = A.spp ? A.spp : 1u;
-        Rng rng;
-        rng.state = 0u;
-        for (uint32_t s = 0; s < n; ++s) {
-            if (A.spp != 0u) {
-                generate_primary(A, C, x, y, A.sample_begin + s, rng, ro, rd);
-                best = feature_nearest_hit_lds<GRID>(A, S, G, ro, rd, alive, closest, work, lane);
-            }
-            if (alive && best >= 0) {
-                f3 hn, al;
-                feature_of_hit_lds<GRID>(A, S, best, closest, ro, rd, hn, al);
-                sum_n = sum_n + hn;
-                sum_a = sum_a + al;
-            }
-        }
-        if (alive) {
-            const float fn = (float)n;
-            out[2u * i] = trace_u4{ bits(sum_a.x / fn), bits(sum_a.y / fn), bits(sum_a.z / fn), bits(t) };
-            out[2u * i + 1u] = trace_u4{ bits(sum_n.x / fn), bits(sum_n.y / fn), bits(sum_n.z / fn), sphere };
-        }
+#define MIRT_FEATURE_NEAREST feature_nearest_hit_lds<GRID>(A, S, G, ro, rd, alive, closest, work, lane)
+#define MIRT_FEATURE_OF_HIT feature_of_hit_lds<GRID>(A, S, best, closest, ro, rd, hn, al)
+#include "mirt_feature_item_text.inc"
+#undef MIRT_FEATURE_NEAREST
+#undef MIRT_FEATURE_OF_HIT
     }
 }
 

@@ -10,8 +10,7 @@
 //   * OP_GEN loads the item's ray from memory as radiance_rays_kernel does (two 16-byte loads: {origin, stream} {direction, _pad}), seeds
 //     the stream of (stream, sample) and skips the four draws of a primary ray.  A lane without an item loads nothing.
 //   * there is no dispenser: a wave takes unit first_unit(), then every grid_waves-th behind it.  The epilogue writes MirtRadiance
-//     records (two 16-byte stores per ray, two loads in front of them under MIRT_RADIANCE_ACCUMULATE, as mirt_radiance_ray_body.inc):
-//     no resolve, no counters.
+//     records through mirt_radiance_record_text.inc, the text the per-lane kernels include: no resolve, no counters.
 // The sums are exact integers, so the order in which a unit's (ray, sample) items are served cannot change a byte: the records are those
 // of radiance_rays_kernel.  LDS of a block is the pooled render's: camera words (+ sky) | THREADS / 64 pools | THREADS / 64 x 64 stacks
 // of RenderArgs.bvh_stack_entries words -- mirt_bvh_pool_plan is the plan of this kernel too.
@@ -112,16 +111,9 @@ __global__ __launch_bounds__(THREADS, MINW) void radiance_rays_pool_kernel(Rende
             uint64_t i = base_slot + lane;
             if constexpr (SORTED) i = order[i];
             unsigned long long acc_r = L_acc[lane * 3 + 0], acc_g = L_acc[lane * 3 + 1], acc_b = L_acc[lane * 3 + 2];
-            uint32_t samples = AS.spp;
-            if (AS.flags & kRadianceAccumulate) {
-                const trace_u4 o0 = out[2u * i], o1 = out[2u * i + 1u];
-                acc_r += (unsigned long long)o0.x | ((unsigned long long)o0.y << 32);
-                acc_g += (unsigned long long)o0.z | ((unsigned long long)o0.w << 32);
-                acc_b += (unsigned long long)o1.x | ((unsigned long long)o1.y << 32);
-                samples += o1.z;
-            }
-            out[2u * i] = trace_u4{ (uint32_t)acc_r, (uint32_t)(acc_r >> 32), (uint32_t)acc_g, (uint32_t)(acc_g >> 32) };
-            out[2u * i + 1u] = trace_u4{ (uint32_t)acc_b, (uint32_t)(acc_b >> 32), samples, 0u };
+#define MIRT_RADIANCE_ARGS AS
+#include "mirt_radiance_record_text.inc"
+#undef MIRT_RADIANCE_ARGS
         }
     }
 }

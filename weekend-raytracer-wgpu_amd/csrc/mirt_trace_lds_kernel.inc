@@ -6,9 +6,10 @@
 // four waves share ONE staged scene, a persistent grid of min(ceil(rays / 256), CUs x resident blocks) blocks whose waves stride over
 // units of 64 consecutive rays, unit = blockIdx.x * 4 + wave, + gridDim.x * 4: lane = ray, the wave composition of trace_rays_kernel.
 // A block whose first unit does not exist returns before anything is staged; in a live block every wave passes the staging barriers and
-// there is no block barrier behind them.  Records travel as in trace_rays_kernel; `closest` starts at the ray's t_max.
-//   GRID = false: the flat scan of trace_rays_kernel<false, ...> (mirt_trace_ray_body.inc) over the STAGED sphere table: test_sphere in
-//                 original index order, ANY with the same early exit, so the per-lane counters are the twin's.
+// there is no block barrier behind them (mirt_lds_block_text.inc).  The ray load, the flat scan and the hit record are the parts of
+// mirt_trace_ray_text.inc that trace_rays_kernel includes; `closest` starts at the ray's t_max.
+//   GRID = false: that flat scan over the STAGED sphere table: test_sphere in original index order, ANY with the same early exit, so
+//                 the per-lane counters are the twin's.
 //   GRID = true : nearest_hit_grid_query below.
 //   COUNT       : Work<true>, flushed once per wave at its end: rays, the sphere tests a lane really performs, roots, rays with a hit;
 //                 on the grid also cells visited per lane / cell-loop iterations per wave (MirtRayStats.nodes / wave_nodes).
@@ -165,23 +166,20 @@ __global__ __launch_bounds__(kQueryLdsThreads, kQueryLdsMinWaves) void trace_ray
 {
     constexpr uint32_t kWaves = kQueryLdsThreads / 64u;
     const uint32_t units = n_rays / 64u + (n_rays % 64u != 0u ? 1u : 0u);
-    if (blockIdx.x * kWaves >= units) return;                               // the whole block: nothing staged, no barrier met
-    extern __shared__ __align__(16) unsigned char smem[];
-    const SceneLds S = stage_scene<true, !GRID>(A, smem, false);
-    GridLds G{};
-    if constexpr (GRID) G = stage_grid(A, smem + scene_lds_bytes_dev(A.n_spheres, A.n_mats, false, false));
-    // no block barrier from here on: a wave without units leaves, the others stride over theirs
-    const uint32_t lane = threadIdx.x & 63u;
+#define MIRT_LDS_SKY false
+#include "mirt_lds_block_text.inc"
+#undef MIRT_LDS_SKY
     const uint32_t grid_waves = gridDim.x * kWaves;
     Work<COUNT> work;
     work.clear();
+#define MIRT_TRACE_SPHERES S.spheres
+#define MIRT_TRACE_HIT_SPHERE (GRID ? A.spheres : S.spheres)[best]         // grid layout: one global read per hit
     for (uint32_t unit = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6)); unit < units; unit += grid_waves) {
         const uint64_t i = (uint64_t)unit * 64u + lane;
         const bool alive = i < n_rays;
-        trace_f4 r0 = { 0.0f, 0.0f, 0.0f, 0.0f }, r1 = { 0.0f, 0.0f, 0.0f, 0.0f };
-        if (alive) { r0 = rays[2u * i]; r1 = rays[2u * i + 1u]; }          // {origin, t_max} {direction, _pad}
-        const f3 ro = mk(r0.x, r0.y, r0.z), rd = mk(r1.x, r1.y, r1.z);
-        const float t_max = r0.w;
+#define MIRT_TRACE_PART 1
+#include "mirt_trace_ray_text.inc"
+#undef MIRT_TRACE_PART
 
         float closest;
         int best;
@@ -189,44 +187,17 @@ __global__ __launch_bounds__(kQueryLdsThreads, kQueryLdsMinWaves) void trace_ray
             best = A.grid_flat_y ? nearest_hit_grid_query<COUNT, ANY, true>(G, ro, rd, t_max, alive, closest, work, lane)
                                  : nearest_hit_grid_query<COUNT, ANY, false>(G, ro, rd, t_max, alive, closest, work, lane);
         } else {
-            const float a = dot(rd, rd);
-            const float inv_a = rcp_(a);
-            closest = t_max;
-            best = -1;
-            if (alive) work.add(kCntRays);
-            const float4* sph = reinterpret_cast<const float4*>(S.spheres);      // {centre, r^2}: the first half of PreparedSphere i, in LDS
-            const uint32_t n = A.n_spheres;
-            bool go = alive;
-            for (uint32_t s = 0; s < n; ++s) {
-                test_sphere<COUNT>(sph[2u * s], s, ro, rd, a, inv_a, go, closest, best, work);
-                if constexpr (ANY) {
-                    go = go && best < 0;
-                    if (!ballot_(go)) break;
-                }
-            }
+#define MIRT_TRACE_PART 2
+#include "mirt_trace_ray_text.inc"
+#undef MIRT_TRACE_PART
         }
-        if (alive) {
-            trace_u4 h0 = { 0u, kTraceMiss, 0u, 0u }, h1 = { 0u, 0u, 0u, 0u };
-            if (best >= 0) {
-                work.add(kCntHits);
-                if constexpr (ANY) {
-                    h0.y = 0u;
-                } else {
-                    // sphereIntersection (wgsl:431-440) as path_radiance computes it: the normal is not turned towards the ray
-                    PreparedSphere sp;
-                    if constexpr (GRID) sp = A.spheres[best];               // grid layout: one global read per hit
-                    else sp = S.spheres[best];
-                    const f3 hp = fma3(closest, rd, ro);
-                    const f3 hn = sp.inv_r * (hp - mk(sp.cx, sp.cy, sp.cz));
-                    h0 = trace_u4{ bits(closest), (uint32_t)best, bits(hp.x), bits(hp.y) };
-                    h1 = trace_u4{ bits(hp.z), bits(hn.x), bits(hn.y), bits(hn.z) };
-                }
-            }
-            hits[2u * i] = h0;
-            hits[2u * i + 1u] = h1;
-        }
+#define MIRT_TRACE_PART 3
+#include "mirt_trace_ray_text.inc"
+#undef MIRT_TRACE_PART
     }
     work.flush(A.counters, lane);
+#undef MIRT_TRACE_SPHERES
+#undef MIRT_TRACE_HIT_SPHERE
 }
 
 static QueryKernel trace_lds_kernel(const QueryPlan& p)
