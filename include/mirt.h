@@ -913,6 +913,58 @@ int mirt_adapt_lds_groups(uint32_t count, uint32_t spp, uint32_t grid_waves, uin
  *                    launches at most n blocks. */
 enum { MIRT_QUERY_LDS = 1u << 8 };
 
+/* ---- denoise a progressive or an adaptive frame on the device: an edge-avoiding a-trous filter ----
+ * Filters the mean of the context's exact sums with the caller's feature frame as guide.  No scene is read: the call works on HBM and
+ * LDS scenes alike, and on a context whose scene has been replaced since.  It is a fixed spatial filter, not a learned denoiser.
+ *   source       MIRT_DENOISE_SRC_ACCUM: the accumulation buffer, sum[3] per pixel, n = mirt_ctx_accum_samples for every pixel;
+ *                MIRT_DENOISE_SRC_ADAPT: the adaptive records, sum[3] and n = samples per pixel.
+ *   guides       one MirtFeaturePixel per pixel of the same compact band, device memory (the _device form) or host memory: what
+ *                mirt_ctx_render_features* wrote for the same width, height and rows.  4-byte aligned; every bit pattern is defined.
+ *   params       read: width, height and the row fields (checked against the source's reset), MIRT_FLAG_NO_TONEMAP and
+ *                MIRT_FLAG_NO_SRGB of flags.  Nothing else.
+ *   output       row-major over the band.  RGBA8 with A = 255, 4 bytes per pixel; with MIRT_DENOISE_OUT_F32 {r, g, b, 1.0f} as
+ *                float32, 16 bytes per pixel: the linear mean before the tone curves.
+ *   arithmetic   float32, every operation a single IEEE operation in the order written, no contraction.  p a pixel, k a channel,
+ *                W x R the band.
+ *                  m[k]   = (float)((double)sum[k] / ((double)n * 1048576.0)), 0 for n == 0       (the mean of the resolves)
+ *                  den[k] = albedo[k] if sphere != MIRT_RAY_MISS and 0.015625f <= albedo[k] <= 64.0f, else 1.0f
+ *                  c[k]   = m[k] / den[k]
+ *                  level i = 0 .. levels - 1, s = 1 << i:  inv_i = 1.0f / (sg * sg), sg = sigma_colour * 2^-i (host, float32);
+ *                    taps q = p + s * (dx, dy), dy = -2..2 outer, dx = -2..2 inner, a tap outside [0, W) x [0, R) skipped;
+ *                    kern = b[dx + 2] * b[dy + 2], b = {1, 4, 6, 4, 1}; the centre tap has w = 36; every other tap
+ *                      wg = 1 if both sphere fields are MIRT_RAY_MISS, 0 if they differ, otherwise x = (n_p[0] * n_q[0] +
+ *                           n_p[1] * n_q[1]) + n_p[2] * n_q[2], x = (x > 0) ? ((x < 1) ? x : 1) : 0, x = x * x normal_log2 times
+ *                      wc = 1 if sigma_colour == 0, otherwise d[k] = c_p[k] - c_q[k], d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2],
+ *                           wc = exp(-(d2 * inv_i)) with mirt-math's exp
+ *                      w  = (kern * wg) * wc
+ *                    wsum = wsum + w, acc[k] = acc[k] + w * c_q[k], both from +0 in tap order; c'[k] = acc[k] / wsum
+ *                  r[k]   = c[k] * den[k];  F32 stores {r[0], r[1], r[2], 1.0f}; RGBA8 stores the resolve of the 2^-20 fixed-point
+ *                           value of r[k] at one sample, per params->flags
+ *   errors       in this order.  MIRT_ERR_NULL_POINTER: ctx, params, denoise, guides or out is null.  MIRT_ERR_BAD_MODE: unknown
+ *                source or flag bit, levels outside 1..8, normal_log2 above 8, sigma_colour negative or NaN, or positive with an
+ *                inv_i that is not finite and positive.  MIRT_ERR_BAD_ROWS: a tile partition (n_parts > 1 with tile_rows != 0): its
+ *                compact rows are not neighbours in the image.  MIRT_ERR_OUT_BUFFER: no buffer of that source, another width or row
+ *                count than its reset, guides_len < pixels * 32, out_len too small.  MIRT_ERR_NO_SCENE: nothing accumulated, or no
+ *                adaptive step since the reset (the codes of the two resolves).  MIRT_ERR_ALLOC: scratch could not be grown.  A
+ *                refused call queues nothing and writes nothing.
+ *   state        the sums, records, guides, launch ring, MirtStats and sample counts are untouched.  mirt_ctx_trace_stats().kernel_ms
+ *                spans the first through the last kernel, mirt_ctx_last_kernel names the a-trous kernel, mirt_ctx_synchronize and
+ *                mirt_ctx_destroy wait for it.
+ *   scratch      two colour planes and one guide plane, 16 bytes per pixel each; the context's, grows only.  A call that must grow it
+ *                waits for the device first.  All denoise launches of a context share it: the caller keeps them in order among
+ *                themselves, as for sorted launches.
+ *   ordering     an ACCUM denoise is a reading link of the progressive frame chain, exactly as mirt_ctx_accum_frame_device with
+ *                spp == 0: ordered after the last frame on whatever stream, and mirt_ctx_accum_reset / _resolve / _read wait for it.
+ *                An ADAPT denoise is ordered by the caller against steps, like mirt_ctx_adapt_resolve_device.  The _device form has
+ *                no host synchronisation (unless the scratch grows). */
+typedef struct MirtDenoiseParams { uint32_t source, levels, normal_log2, flags; float sigma_colour; uint32_t _pad[3]; } MirtDenoiseParams; /* 32 B; _pad is not read */
+enum { MIRT_DENOISE_SRC_ACCUM = 0, MIRT_DENOISE_SRC_ADAPT = 1 };   /* source */
+enum { MIRT_DENOISE_OUT_F32 = 1u << 0 };                            /* flags  */
+int mirt_ctx_denoise_device(MirtContext* ctx, const MirtParams* params, const MirtDenoiseParams* denoise, const void* d_guides, size_t guides_len,
+                            void* d_out, size_t out_len, void* hip_stream);
+int mirt_ctx_denoise(MirtContext* ctx, const MirtParams* params, const MirtDenoiseParams* denoise, const MirtFeaturePixel* guides, size_t guides_len,
+                     void* out, size_t out_len);    /* host memory; blocking */
+
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE
  * expansions over ALL 2^32 binary32 bit patterns.  Writes the two mismatch counts (sqrt, 1/x);
@@ -1064,6 +1116,7 @@ static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32 
 static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
 static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
 static_assert(sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptLdsPlan is four words");
+static_assert(sizeof(MirtDenoiseParams) == 32, "MirtDenoiseParams is eight words");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -1084,6 +1137,7 @@ _Static_assert(sizeof(MirtAdaptStats) == 32, "MirtAdaptStats is two u64, two u32
 _Static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
 _Static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
 _Static_assert(sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptLdsPlan is four words");
+_Static_assert(sizeof(MirtDenoiseParams) == 32, "MirtDenoiseParams is eight words");
 #endif
 
 #endif /* MIRT_H */

@@ -356,6 +356,23 @@ pub const MIRT_RADIANCE_POOL: u32 = 1 << 6;
 pub const MIRT_ADAPT_POOL: u32 = 1 << 1;
 /// `MirtAdaptParams.flags`: a step or run also accepts a scene that lives in LDS, where it stays (an HBM scene ignores it); bit 2 is unassigned.
 pub const MIRT_ADAPT_LDS: u32 = 1 << 3;
+/// The parameters of `mirt_ctx_denoise*`: the edge-avoiding a-trous filter over the accumulation or the adaptive records.  `_pad` is not read.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct MirtDenoiseParams {
+    pub source: u32,
+    pub levels: u32,
+    pub normal_log2: u32,
+    pub flags: u32,
+    pub sigma_colour: f32,
+    pub _pad: [u32; 3],
+}
+/// `MirtDenoiseParams.source`: the context's accumulation buffer, or its adaptive records.
+pub const MIRT_DENOISE_SRC_ACCUM: u32 = 0;
+pub const MIRT_DENOISE_SRC_ADAPT: u32 = 1;
+/// `MirtDenoiseParams.flags`: the output is `{r, g, b, 1.0}` as float32 (the linear mean), not RGBA8.
+pub const MIRT_DENOISE_OUT_F32: u32 = 1 << 0;
+
 /// The `flags` of `mirt_ctx_trace_rays*` and `mirt_ctx_render_features*`, and `MirtRadianceParams.flags`: the query also accepts a scene
 /// that lives in LDS, where it stays (the same records as on the same world held as an HBM scene, which ignores the flag).
 pub const MIRT_QUERY_LDS: u32 = 1 << 8;
@@ -492,6 +509,8 @@ extern "C" {
     pub fn mirt_ctx_adapt_run_device(ctx: *mut MirtContext, params: *const MirtParams, adapt: *const MirtAdaptParams, run: *const MirtAdaptRun, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_ctx_adapt_run_read(ctx: *mut MirtContext, out: *mut MirtAdaptRunStep, len: usize, n_steps: *mut u32) -> c_int;
     // adaptive steps on a scene that lives in LDS (MIRT_ADAPT_LDS): the launch's geometry and the device's rule for the sample groups, host only
+    pub fn mirt_ctx_denoise_device(ctx: *mut MirtContext, params: *const MirtParams, denoise: *const MirtDenoiseParams, d_guides: *const c_void, guides_len: usize, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ctx_denoise(ctx: *mut MirtContext, params: *const MirtParams, denoise: *const MirtDenoiseParams, guides: *const MirtFeaturePixel, guides_len: usize, out: *mut c_void, out_len: usize) -> c_int;
     pub fn mirt_adapt_lds_plan(n_spheres: u32, n_materials: u32, grid_bytes: u32, hosek: u32, lds_bytes_per_cu: u64, out: *mut MirtAdaptLdsPlan) -> c_int;
     pub fn mirt_adapt_lds_groups(count: u32, spp: u32, grid_waves: u32, out_log2: *mut u32) -> c_int;
     pub fn mirt_ctx_selftest_math(ctx: *mut MirtContext, out_mismatches: *mut u64) -> c_int;

@@ -58,6 +58,11 @@ MIRT_ADAPT_LDS = 1 << 3                 # MirtAdaptParams.flags: a step also run
 MIRT_QUERY_LDS = 1 << 8                 # the flags of mirt_ctx_trace_rays*, mirt_ctx_render_features* and MirtRadianceParams.flags: the query also runs on a scene that lives in LDS
 MIRT_ADAPT_RUN_MAX_STEPS = 256          # mirt_ctx_adapt_run_device: steps of one run, entries of its log
 
+# mirt_ctx_denoise*: MirtDenoiseParams.source and MirtDenoiseParams.flags
+MIRT_DENOISE_SRC_ACCUM = 0
+MIRT_DENOISE_SRC_ADAPT = 1
+MIRT_DENOISE_OUT_F32 = 1 << 0
+
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
 MIRT_NODE_RCCL = 1 << 0
@@ -241,6 +246,11 @@ class MirtAdaptLdsPlan(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MirtDenoiseParams(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("levels", C.c_uint32), ("normal_log2", C.c_uint32), ("flags", C.c_uint32), ("sigma_colour", C.c_float),
+                ("_pad", C.c_uint32 * 3)]
+
+
 class MirtAdaptStats(C.Structure):
     _fields_ = [("pixels", C.c_uint64), ("total_samples", C.c_uint64), ("active", C.c_uint32), ("steps", C.c_uint32), ("kernel_ms", C.c_double)]
 
@@ -327,6 +337,8 @@ SYMBOLS = {
     "mirt_ctx_adapt_list_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint32)]),
     "mirt_ctx_adapt_stats": (C.c_int, [C.c_void_p, _P(MirtAdaptStats)]),
     "mirt_adapt_run_spp": (C.c_int, [C.c_uint32, C.c_uint32, _P(MirtAdaptRun), _P(C.c_uint32)]),
+    "mirt_ctx_denoise_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtDenoiseParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mirt_ctx_denoise": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtDenoiseParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "mirt_adapt_lds_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P(MirtAdaptLdsPlan)]),
     "mirt_adapt_lds_groups": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
     "mirt_ctx_adapt_run_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtAdaptParams), _P(MirtAdaptRun), C.c_void_p]),

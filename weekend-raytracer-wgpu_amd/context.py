@@ -235,6 +235,32 @@ def _check_address(name, v) -> int:
 FEATURE_DTYPE = np.dtype([("albedo", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)), ("sphere", "<u4")])
 
 
+def make_denoise_params(source="accum", *, levels: int = 3, sigma_colour: float = 1.0, normal_log2: int = 5, f32: bool = False) -> _abi.MirtDenoiseParams:
+    """MirtDenoiseParams for Context.denoise*: source "accum" (the accumulation buffer) or "adapt" (the adaptive records); `levels`
+    a-trous levels (1..8), the colour weight's sigma (0: no colour weight), the normal weight's exponent as a power of two (0..8);
+    f32=True asks for the linear mean as float32 RGBA instead of RGBA8.  The types are checked here, the ranges by the library."""
+    if source not in ("accum", "adapt"):
+        raise ValueError(f'source must be "accum" or "adapt", not {source!r}')
+    for name, v in (("levels", levels), ("normal_log2", normal_log2)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 32:
+            raise ValueError(f"{name} must be an unsigned integer, not {v!r}")
+    if not isinstance(sigma_colour, (int, float, np.integer, np.floating)) or isinstance(sigma_colour, bool):
+        raise ValueError(f"sigma_colour must be a number, not {sigma_colour!r}")
+    if not isinstance(f32, (bool, np.bool_)):
+        raise ValueError(f"f32 must be a bool, not {f32!r}")
+    d = _abi.MirtDenoiseParams()
+    d.source = _abi.MIRT_DENOISE_SRC_ADAPT if source == "adapt" else _abi.MIRT_DENOISE_SRC_ACCUM
+    d.levels, d.normal_log2, d.flags = int(levels), int(normal_log2), _abi.MIRT_DENOISE_OUT_F32 if f32 else 0
+    d.sigma_colour = float(sigma_colour)
+    return d
+
+
+def _check_denoise(denoise) -> _abi.MirtDenoiseParams:
+    if not isinstance(denoise, _abi.MirtDenoiseParams):
+        raise ValueError(f"denoise must be a MirtDenoiseParams (make_denoise_params builds one), not {type(denoise).__name__}")
+    return denoise
+
+
 def _check_params(params) -> _abi.MirtParams:
     if not isinstance(params, _abi.MirtParams):
         raise ValueError(f"params must be a MirtParams (make_params builds one), not {type(params).__name__}")
@@ -609,6 +635,36 @@ class Context:
             raise ValueError(f"nbytes must be a byte count, not {nbytes!r}")
         check(lib().mirt_ctx_render_features_device(self._h, C.byref(params), (_abi.MIRT_FEATURES_FLAT if flat else 0) | lds_flag, C.c_void_p(d_ptr),
                                                     int(nbytes), _stream_arg(stream)))
+
+    # ---- the a-trous filter over the accumulation or the adaptive records (include/mirt.h) ----
+    def denoise(self, params: _abi.MirtParams, denoise: _abi.MirtDenoiseParams, guides: np.ndarray) -> np.ndarray:
+        """mirt_ctx_denoise: the filtered frame of the source `denoise` names, guided by `guides` -- a FEATURE_DTYPE array with one record
+        per pixel of the band, what render_features returned for the same width, height and rows -> uint8 [rows, width, 4], or float32
+        [rows, width, 4] (linear {r, g, b, 1}) with MIRT_DENOISE_OUT_F32.  Reads no scene; sums, records and guides stay as they are.
+        Blocking."""
+        params, denoise = _check_params(params), _check_denoise(denoise)
+        if not isinstance(guides, np.ndarray) or guides.dtype != FEATURE_DTYPE:
+            raise ValueError("guides must be a FEATURE_DTYPE array")
+        g = np.ascontiguousarray(guides).reshape(-1)
+        rows, width = max(params_out_rows(params), 0), int(params.width)
+        f32 = bool(denoise.flags & _abi.MIRT_DENOISE_OUT_F32)
+        out = np.zeros((max(rows, 1), max(width, 1), 4), np.float32 if f32 else np.uint8)
+        check(lib().mirt_ctx_denoise(self._h, C.byref(params), C.byref(denoise), C.c_void_p(g.ctypes.data) if len(g) else None, g.nbytes,
+                                     C.c_void_p(out.ctypes.data), rows * width * (16 if f32 else 4)))
+        return out[:rows, :width]
+
+    def denoise_device(self, params: _abi.MirtParams, denoise: _abi.MirtDenoiseParams, d_guides: int, guides_nbytes: int, d_out: int, nbytes: int,
+                       stream: Optional[int] = None) -> None:
+        """mirt_ctx_denoise_device: the same with the guides (`guides_nbytes` at `d_guides`) and the output (`nbytes` at `d_out`) in
+        device memory, both 4-byte aligned, queued on `stream` (see _stream_arg); no host synchronisation unless the context's scratch
+        must grow."""
+        params, denoise = _check_params(params), _check_denoise(denoise)
+        d_guides, d_out = _check_address("d_guides", d_guides), _check_address("d_out", d_out)
+        for name, v in (("guides_nbytes", guides_nbytes), ("nbytes", nbytes)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or int(v) < 0:
+                raise ValueError(f"{name} must be a byte count, not {v!r}")
+        check(lib().mirt_ctx_denoise_device(self._h, C.byref(params), C.byref(denoise), C.c_void_p(d_guides), int(guides_nbytes), C.c_void_p(d_out),
+                                            int(nbytes), _stream_arg(stream)))
 
     def bvh_refits(self) -> int:
         """mirt_ctx_bvh_refits: successful updates since the scene was set (0 after every set_scene)."""

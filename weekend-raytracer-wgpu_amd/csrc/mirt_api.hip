@@ -284,6 +284,7 @@ Tuning read_tuning()
     if (const char* e = std::getenv("MIRT_ADAPT_POOL_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_pool_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_ADAPT_LDS_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.adapt_lds_blocks = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_QUERY_LDS_BLOCKS")) { const int v = std::atoi(e); if (v >= 1) t.query_lds_blocks = (uint32_t)v; }
+    if (const char* e = std::getenv("MIRT_DENOISE_STAGED")) { const int v = std::atoi(e); if (v >= 0 && v <= 255) t.denoise_staged = v; }
     if (const char* e = std::getenv("MIRT_ADAPT_LDS_GROUPS")) { const int v = std::atoi(e); if (v >= 1 && v <= 3) t.adapt_lds_groups = (uint32_t)v; }
     if (const char* e = std::getenv("MIRT_GRID_BIG")) { const double v = std::atof(e); if (v >= 1.0 && v <= 1024.0) t.grid_big = v; }
     return t;
@@ -456,6 +457,10 @@ struct MirtContext {
     bool                adapt_pending = false;     // ev_adapt_end is recorded and nobody has waited for it yet
     bool                adapt_timed = false;
     double              adapt_ms = 0.0;
+
+    // mirt_ctx_denoise* (DESIGN.md 10.17): two colour planes and one guide plane, 16 bytes per pixel each; grows, never shrinks; shared by all denoise launches
+    unsigned char*      d_denoise = nullptr;
+    size_t              cap_denoise = 0;
 };
 
 extern "C" {
@@ -690,7 +695,7 @@ void mirt_ctx_destroy(MirtContext* c)
     if (!c->untimed_streams.empty()) (void)hipDeviceSynchronize();      // launches without an event may still read the tables freed below
     if (c->trace_pending) (void)hipEventSynchronize(c->ev_trace_end);    // a trace on a caller stream reads them too
     if (c->adapt_pending) (void)hipEventSynchronize(c->ev_adapt_end);    // ... and so does an adaptive step
-    (void)hipFree(c->d_adapt); (void)hipFree(c->d_adapt_sel);
+    (void)hipFree(c->d_adapt); (void)hipFree(c->d_adapt_sel); (void)hipFree(c->d_denoise);
     if (c->ev_adapt_begin) (void)hipEventDestroy(c->ev_adapt_begin);
     if (c->ev_adapt_end) (void)hipEventDestroy(c->ev_adapt_end);
     (void)hipFree(c->d_trace_counters); (void)hipFree(c->d_trace_rays); (void)hipFree(c->d_trace_hits); (void)hipFree(c->ray_sort.d);
@@ -2289,6 +2294,116 @@ int mirt_ctx_adapt_stats(MirtContext* c, MirtAdaptStats* out)
     out->active = (uint32_t)head[0];
     out->steps = c->adapt_steps;
     out->kernel_ms = c->adapt_ms;
+    return MIRT_OK;
+}
+
+// ---- the a-trous filter over the accumulation or the adaptive records (include/mirt.h) ----
+// What both entry points check, in the header's order; inv[i] = level i's 1 / sg^2 (all 1 for sigma_colour == 0, where nothing reads them).
+// Nothing is queued, and no scratch grown, before the last check has passed.
+static int check_denoise(const MirtContext* c, const MirtParams* p, const MirtDenoiseParams* d, const void* guides, size_t guides_len, const void* out,
+                         size_t out_len, float inv[8])
+{
+    if (!c || !p || !d || !guides || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/denoise/guides/out is null");
+    if (d->source > MIRT_DENOISE_SRC_ADAPT) return fail(MIRT_ERR_BAD_MODE, "unknown MirtDenoiseParams.source %u", d->source);
+    if (d->flags & ~(uint32_t)MIRT_DENOISE_OUT_F32) return fail(MIRT_ERR_BAD_MODE, "unknown MirtDenoiseParams.flags bits 0x%x", d->flags);
+    if (d->levels < 1u || d->levels > 8u) return fail(MIRT_ERR_BAD_MODE, "levels %u is outside 1..8", d->levels);
+    if (d->normal_log2 > 8u) return fail(MIRT_ERR_BAD_MODE, "normal_log2 %u is above 8", d->normal_log2);
+    if (!(d->sigma_colour >= 0.0f)) return fail(MIRT_ERR_BAD_MODE, "sigma_colour %g is negative or NaN", (double)d->sigma_colour);
+    for (uint32_t i = 0; i < 8u; ++i) inv[i] = 1.0f;
+    if (d->sigma_colour > 0.0f)
+        for (uint32_t i = 0; i < d->levels; ++i) {
+            const float sg = d->sigma_colour * std::ldexp(1.0f, -(int)i);      // float32, one operation each
+            inv[i] = 1.0f / (sg * sg);
+            if (!(inv[i] > 0.0f) || !std::isfinite(inv[i]))
+                return fail(MIRT_ERR_BAD_MODE, "sigma_colour %g: level %u's 1 / sg^2 is not finite and positive", (double)d->sigma_colour, i);
+        }
+    if (p->n_parts > 1u && p->tile_rows != 0u)
+        return fail(MIRT_ERR_BAD_ROWS, "a tile partition (part %u/%u, %u rows per tile): its compact rows are not neighbours in the image", p->part, p->n_parts, p->tile_rows);
+    const bool adapt = d->source == MIRT_DENOISE_SRC_ADAPT;
+    const uint64_t npix = adapt ? c->adapt_pixels : c->accum_pixels;
+    const uint32_t width = adapt ? c->adapt_width : c->accum_width, rows = adapt ? c->adapt_rows : c->accum_rows;
+    if (!(adapt ? (const void*)c->d_adapt : (const void*)c->d_accum) || npix == 0u)
+        return fail(MIRT_ERR_OUT_BUFFER, "no %s buffer: call %s first", adapt ? "adaptive" : "accumulation", adapt ? "mirt_ctx_adapt_reset" : "mirt_ctx_accum_reset");
+    if (p->width != width || out_rows(p) != rows) return fail(MIRT_ERR_OUT_BUFFER, "the %s buffer does not match these params: %u x %u at its reset",
+                                                              adapt ? "adaptive" : "accumulation", width, rows);
+    if (guides_len / sizeof(MirtFeaturePixel) < npix) return fail(MIRT_ERR_OUT_BUFFER, "the guides hold %zu bytes, %llu needed", guides_len,
+                                                                  (unsigned long long)npix * sizeof(MirtFeaturePixel));
+    const size_t px_bytes = (d->flags & MIRT_DENOISE_OUT_F32) ? 16u : 4u;
+    if (out_len / px_bytes < npix) return fail(MIRT_ERR_OUT_BUFFER, "output buffer holds %zu bytes, %llu needed", out_len, (unsigned long long)npix * px_bytes);
+    if (adapt ? c->adapt_steps == 0u : c->accum_samples == 0u)
+        return fail(MIRT_ERR_NO_SCENE, adapt ? "no adaptive step has run since the reset" : "nothing accumulated yet");
+    return MIRT_OK;
+}
+
+// The levels that run the staged shape, bit i = level i: by measurement at 1920 x 1080 staging wins up to step 8 (by 32,
+// 30, 21 and 8 us per level) and loses from step 16 on (by 12 and 35 us), where a class's staging loads are 256 bytes and more apart.
+constexpr uint32_t kDenoiseStagedLevels = 0x0fu;
+
+// Queue the prepare kernel and the levels on `st`.  No host synchronisation unless the scratch must grow.  An ACCUM denoise is a reading link
+// of the frame chain (launch_frame with spp == 0); the event pair and the pending flag are the ray queries' (mirt_ctx_trace_stats folds the time).
+static int launch_denoise(MirtContext* c, const MirtParams* p, const MirtDenoiseParams* d, const float inv[8], const void* d_guides, void* d_out, hipStream_t st)
+{
+    const bool adapt = d->source == MIRT_DENOISE_SRC_ADAPT;
+    const uint64_t npix = adapt ? c->adapt_pixels : c->accum_pixels;
+    const size_t need = (size_t)npix * 48u;                     // two colour planes and the guide plane
+    if (need > c->cap_denoise || !c->d_denoise) {
+        HIP_TRY(hipDeviceSynchronize());                        // an earlier denoise, on whatever stream, may still use the planes freed here
+        const int rc = ensure_capacity(&c->d_denoise, &c->cap_denoise, need);
+        if (rc != MIRT_OK) return rc;
+    }
+    if (!adapt) { const int rc = order_frame(c, st); if (rc != MIRT_OK) return rc; }
+    const bool timed = c->timing;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    const bool f32_out = (d->flags & MIRT_DENOISE_OUT_F32) != 0u;
+    const uint32_t staged = c->tuning.denoise_staged >= 0 ? (uint32_t)c->tuning.denoise_staged : kDenoiseStagedLevels;
+    HIP_TRY(kx::launch_denoise(d->source, adapt ? (const void*)c->d_adapt : (const void*)c->d_accum, c->accum_samples, d_guides,
+                               adapt ? c->adapt_width : c->accum_width, adapt ? c->adapt_rows : c->accum_rows, d->levels, d->normal_log2,
+                               d->sigma_colour != 0.0f, inv, f32_out, p->flags & (MIRT_FLAG_NO_TONEMAP | MIRT_FLAG_NO_SRGB), staged, c->d_denoise, d_out, st));
+    snprintf(c->last_kernel, sizeof c->last_kernel, "denoise_atrous_%skernel<%s>", ((staged >> (d->levels - 1u)) & 1u) ? "staged_" : "", f32_out ? "f32" : "rgba8");
+    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
+    c->trace_pending = true;
+    c->trace_timed = timed;
+    c->trace_counted = false;
+    c->trace_stats = MirtRayStats{};
+    if (!adapt) {
+        c->accum_stream = st;                               // the next frame, on whatever stream, is ordered after this read (order_frame)
+        if (st != c->stream) {                              // mirt_ctx_accum_reset / _resolve / _read must not overtake it (launch_frame)
+            HIP_TRY(hipEventRecord(c->ev_accum, st));
+            c->accum_pending = true;
+            if (std::find(c->untimed_streams.begin(), c->untimed_streams.end(), st) == c->untimed_streams.end()) c->untimed_streams.push_back(st);
+        }
+    }
+    return MIRT_OK;
+}
+
+int mirt_ctx_denoise_device(MirtContext* c, const MirtParams* p, const MirtDenoiseParams* d, const void* d_guides, size_t guides_len, void* d_out, size_t out_len,
+                            void* hip_stream)
+{
+    float inv[8];
+    const int rc = check_denoise(c, p, d, d_guides, guides_len, d_out, out_len, inv);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return launch_denoise(c, p, d, inv, d_guides, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int mirt_ctx_denoise(MirtContext* c, const MirtParams* p, const MirtDenoiseParams* d, const MirtFeaturePixel* guides, size_t guides_len, void* out, size_t out_len)
+{
+    float inv[8];
+    int rc = check_denoise(c, p, d, guides, guides_len, out, out_len, inv);
+    if (rc != MIRT_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool adapt = d->source == MIRT_DENOISE_SRC_ADAPT;
+    const size_t npix = (size_t)(adapt ? c->adapt_pixels : c->accum_pixels);
+    const size_t g_bytes = npix * sizeof(MirtFeaturePixel), o_bytes = npix * ((d->flags & MIRT_DENOISE_OUT_F32) ? 16u : 4u);
+    // the guides are staged where a host trace stages its hits, the result where it stages its rays
+    if ((rc = ensure_capacity(&c->d_trace_hits, &c->cap_trace_hits, g_bytes)) != MIRT_OK) return rc;
+    if ((rc = ensure_capacity(&c->d_trace_rays, &c->cap_trace_rays, o_bytes)) != MIRT_OK) return rc;
+    if (adapt && (rc = adapt_await(c)) != MIRT_OK) return rc;      // the HOST waits for a step on a caller stream (see mirt_ctx_adapt_resolve)
+    if (!adapt && c->accum_pending) { HIP_TRY(hipEventSynchronize(c->ev_accum)); c->accum_pending = false; }      // ... and for an add (see mirt_ctx_accum_resolve)
+    HIP_TRY(hipMemcpyAsync(c->d_trace_hits, guides, g_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_denoise(c, p, d, inv, c->d_trace_hits, c->d_trace_rays, c->stream)) != MIRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->d_trace_rays, o_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return MIRT_OK;
 }
 

@@ -286,6 +286,13 @@ hipError_t launch_adapt_select_run(const void* d_recs, uint32_t n, const MirtAda
                                    unsigned char* d_flags, uint32_t* d_block_counts, uint32_t* d_list, uint32_t* d_head, void* d_log_entry, hipStream_t stream);
 // adapt_resolve_kernel: n_pixels records -> RGBA8, every pixel over its own sample count
 hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pixels, uint32_t flags, hipStream_t stream);
+// mirt_ctx_denoise* (mirt_denoise_kernel.inc): denoise_prepare_kernel<source> and `levels` launches of denoise_atrous_kernel, the last
+// with its epilogue (RGBA8 per `flags`, or float32).  d_src: the accumulation sums (n_samples for every pixel) or the MirtAdaptPixel records;
+// d_guides: [width x rows] MirtFeaturePixel, 4-byte aligned; inv[levels]: every level's 1 / sg^2; d_scratch: three planes of 16 bytes per pixel;
+// bit i of staged_levels: level i runs denoise_atrous_staged_kernel.
+hipError_t launch_denoise(uint32_t source, const void* d_src, uint32_t n_samples, const void* d_guides, uint32_t width, uint32_t rows, uint32_t levels,
+                          uint32_t normal_log2, bool colour, const float* inv, bool f32_out, uint32_t flags, uint32_t staged_levels, void* d_scratch, void* d_out,
+                          hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);
 size_t     scene_lds_bytes(uint32_t n_spheres, uint32_t n_mats, bool pt, bool hosek);
 size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);

@@ -72,6 +72,7 @@ struct Tuning {
     uint32_t adapt_pool_blocks = 0;   // MIRT_ADAPT_POOL_BLOCKS=n (A/B runs, tests): a pooled adaptive step launches at most n blocks, whose waves stride over the units
     uint32_t adapt_lds_blocks = 0;    // MIRT_ADAPT_LDS_BLOCKS=n (A/B runs, tests): an MIRT_ADAPT_LDS step launches at most n blocks
     uint32_t query_lds_blocks = 0;    // MIRT_QUERY_LDS_BLOCKS=n (A/B runs, tests): an MIRT_QUERY_LDS launch (ray, feature or radiance query on a scene in LDS) launches at most n blocks
+    int32_t  denoise_staged = -1;     // MIRT_DENOISE_STAGED=mask (A/B runs, tests): bit i set: level i of mirt_ctx_denoise* runs the staged shape; -1: the measured choice
     uint32_t adapt_lds_groups = 0;    // MIRT_ADAPT_LDS_GROUPS=1/2/3 (A/B runs, tests): an MIRT_ADAPT_LDS step deals samples to 1 / 2 / 4 groups of lanes (capped by spp)
     bool     ext_events = true;       // MIRT_EXT_EVENTS=0: the event pair as two records in the stream instead of riding on the kernel dispatch (A/B runs)
 };

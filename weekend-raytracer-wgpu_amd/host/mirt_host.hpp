@@ -98,6 +98,31 @@ inline std::vector<MirtFeaturePixel> render_features(MirtContext* ctx, const Mir
     check(mirt_ctx_render_features(ctx, &params, flags, out.empty() ? &none : out.data(), out.size() * sizeof(MirtFeaturePixel)));
     return out;
 }
+// mirt_ctx_denoise: the edge-avoiding a-trous filter over the context's accumulation (denoise.source = MIRT_DENOISE_SRC_ACCUM) or its
+// adaptive records (MIRT_DENOISE_SRC_ADAPT), guided by `guides` -- what render_features returned for the same params' width, height and
+// rows -> the band's bytes: RGBA8, or {r, g, b, 1.0f} as float32 with MIRT_DENOISE_OUT_F32.  Reads no scene; blocking.
+static_assert(sizeof(MirtDenoiseParams) == 32 && MIRT_DENOISE_SRC_ADAPT == 1 && MIRT_DENOISE_OUT_F32 == 1u << 0, "MirtDenoiseParams");
+inline MirtDenoiseParams denoise_params(uint32_t source = MIRT_DENOISE_SRC_ACCUM, uint32_t levels = 3, float sigma_colour = 1.0f, uint32_t normal_log2 = 5, bool f32 = false)
+{
+    MirtDenoiseParams d{};
+    d.source = source; d.levels = levels; d.normal_log2 = normal_log2; d.flags = f32 ? (uint32_t)MIRT_DENOISE_OUT_F32 : 0u; d.sigma_colour = sigma_colour;
+    return d;
+}
+inline std::vector<uint8_t> denoise(MirtContext* ctx, const MirtParams& params, const MirtDenoiseParams& denoise, const std::vector<MirtFeaturePixel>& guides)
+{
+    const size_t px = (denoise.flags & MIRT_DENOISE_OUT_F32) ? 16u : 4u;
+    std::vector<uint8_t> out((size_t)mirt_params_out_rows(&params) * params.width * px);
+    uint8_t none[16] = {};
+    MirtFeaturePixel no_guide{};
+    check(mirt_ctx_denoise(ctx, &params, &denoise, guides.empty() ? &no_guide : guides.data(), guides.size() * sizeof(MirtFeaturePixel),
+                           out.empty() ? none : out.data(), out.size()));
+    return out;
+}
+inline void denoise_device(MirtContext* ctx, const MirtParams& params, const MirtDenoiseParams& denoise, const void* d_guides, size_t guides_len, void* d_out,
+                           size_t out_len, void* hip_stream = nullptr)
+{
+    check(mirt_ctx_denoise_device(ctx, &params, &denoise, d_guides, guides_len, d_out, out_len, hip_stream));
+}
 // the centre ray of pixel (x, y) exactly as the feature kernel traces it (mirt_camera_pixel_ray: float32 with fmaf, t_max = 1000)
 inline MirtRay camera_pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y)
 {

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import MirtError, check, lib
-from .context import Context, SceneData, make_params, make_rays, radiance_mean, set_scene_any_size
+from .context import Context, FEATURE_DTYPE, SceneData, make_params, make_rays, radiance_mean, set_scene_any_size
 from .node import Node
 
 f32 = np.float32
@@ -714,6 +714,7 @@ class Raytracer:
         self._accumulated = None        # RenderProgress (mod.rs:615-679): None = reset pending
         self.frame_number = 1           # mod.rs:284; advanced by every render_frame call (mod.rs:350), never reset
         self._frame_begin = 0           # frames rendered before the current accumulation started
+        self._last_seed = 0             # of the last progressive frame or adaptive call: denoised() takes its guides with it
 
     def scene_data(self) -> SceneData:
         return SceneData(self.camera.c, [s.to_c() for s in self.spheres], list(self.material_data),
@@ -735,6 +736,7 @@ class Raytracer:
         until `max_samples_per_pixel` is reached, then spp = 0 (show the mean, add nothing: mod.rs:350).  Clears the sums first
         after a reset."""
         smp = self.render_params.sampling
+        self._last_seed = seed
         if self._accumulated is None:                          # first frame after a reset: clear
             self._frame_begin = self.frame_number - 1          # this accumulation's frames are frame_number, frame_number + 1, ...
             self._ctx.accum_reset(self._params(smp.num_samples_per_pixel, seed, flags))
@@ -877,6 +879,7 @@ class Raytracer:
         compute units and the plan's resident waves and slots, times a small factor that nobody has tuned."""
         from .context import make_adapt_params
         adapt = make_adapt_params(min_spp, max_spp, tolerance, pool, lds)
+        self._last_seed = seed
         if run is not None and run is not True and not isinstance(run, _abi.MirtAdaptRun):
             raise ValueError(f"run must be None, True or a MirtAdaptRun (make_adapt_run builds one), not {run!r}")
         if not isinstance(step, (int, np.integer)) or isinstance(step, bool) or int(step) < 2 or int(step) % 2:
@@ -903,6 +906,30 @@ class Raytracer:
             if ctx.adapt_stats()["active"] == 0:
                 break
         return ctx.adapt_resolve(params), ctx.adapt_read()["samples"].reshape(h, w).copy()
+
+    def denoised(self, source: str = "accum", *, levels: int = 3, sigma_colour: float = 1.0, normal_log2: int = 5, f32: bool = False,
+                 seed: Optional[int] = None, flags: int = 0) -> np.ndarray:
+        """The frame accumulated so far (source "accum": what render_frame* has added since the last reset) or the records of the last
+        render_adaptive (source "adapt"), through the edge-avoiding a-trous filter of mirt_ctx_denoise -> RGBA8 [h][w][4], or with
+        f32=True the linear mean as float32 [h][w][4].  The guides are features() with the frame's `num_samples_per_pixel` and seed
+        (seed=None: that of the last frame or adaptive call), taken with lds=True when the scene lives in LDS, so it stays there.  The
+        sums, the records and the sample counts are not touched.  `flags`: MIRT_FLAG_NO_TONEMAP / MIRT_FLAG_NO_SRGB for the RGBA8 form.
+        A spatial filter, not a learned denoiser: it removes noise where neighbours of the same sphere, orientation and colour exist
+        (DESIGN.md 10.17 has what was measured).  Not available on a node: a member's tiles are not neighbours."""
+        from .context import make_denoise_params
+        if self._on_node:
+            raise ValueError("denoised needs a single context: a node member's tiles are not neighbours in the image")
+        if not isinstance(flags, (int, np.integer)) or isinstance(flags, bool) or int(flags) & ~(_abi.MIRT_FLAG_NO_TONEMAP | _abi.MIRT_FLAG_NO_SRGB):
+            raise ValueError(f"flags must be a combination of MIRT_FLAG_NO_TONEMAP and MIRT_FLAG_NO_SRGB, not {flags!r}")
+        d = make_denoise_params(source, levels=levels, sigma_colour=sigma_colour, normal_log2=normal_log2, f32=f32)
+        if seed is None:
+            seed = self._last_seed
+        w, h = (int(v) for v in self.render_params.viewport_size)
+        g = self.features(seed=seed, lds=not self._hbm)
+        guides = np.zeros((h, w), FEATURE_DTYPE)
+        for k in ("albedo", "normal", "t", "sphere"):
+            guides[k] = g[k]
+        return self._ctx.denoise(make_params(w, h, 0, mode=_abi.MIRT_MODE_PT, flags=int(flags)), d, guides)
 
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
         """All `max_samples_per_pixel` samples in one launch -> RGBA8 [h][w][4].
