@@ -965,6 +965,80 @@ int mirt_ctx_denoise_device(MirtContext* ctx, const MirtParams* params, const Mi
 int mirt_ctx_denoise(MirtContext* ctx, const MirtParams* params, const MirtDenoiseParams* denoise, const MirtFeaturePixel* guides, size_t guides_len,
                      void* out, size_t out_len);    /* host memory; blocking */
 
+/* ---- carry a denoised frame across camera motion: temporal reprojection by first-hit depth and id ----
+ * Takes the previous frame's result to this frame's pixels and blends it with this frame's colour.  No scene, no accumulation and no
+ * context state is read: the call works on HBM and LDS scenes alike and with no scene set at all.
+ *   params       read: width, height, the row fields, MIRT_FLAG_NO_TONEMAP and MIRT_FLAG_NO_SRGB of flags.  Nothing else.  Both frames
+ *                have this width, height and band; the host drops its history on a resize.
+ *   frames       all device pointers (the _device form) or all host pointers, 4-byte aligned, row-major over the compact band:
+ *                  colour        float32 x 4 per pixel: this frame, {r, g, b, ignored} -- what MIRT_DENOISE_OUT_F32 wrote
+ *                  guides        MirtFeaturePixel per pixel: this frame, taken with `current`
+ *                  prev_colour   float32 x 4: {r, g, b, history length} -- the `out` of the previous call, or a denoise output (length 1)
+ *                  prev_guides   MirtFeaturePixel: the previous frame, taken with `previous`
+ *                  out           float32 x 4: {r, g, b, new history length}
+ *                  out_rgba8     nullable: the same pixel through the 2^-20 fixed-point value and the resolve at one sample per
+ *                                params->flags, A = 255
+ *                  pixels        records every non-null buffer holds; >= rows * width
+ *   arithmetic   float32, every operation one IEEE operation in the order written, no contraction; the only fused operations are the
+ *                fmaf written out.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2.  For pixel (x, y) of the band (y the image row, compact row
+ *                y - row_begin, p its compact index):
+ *                  (o, d)  = the centre ray of (x, y) under `current`, exactly as mirt_camera_pixel_ray
+ *                  g       = guides[p]; hit = g.sphere != MIRT_RAY_MISS
+ *                  rel[k]  = hit ? fmaf(g.t, d[k], o[k]) - previous.eye[k] : d[k]           (a miss is a direction: rotation only)
+ *                  a[k]    = previous.lower_left_corner[k] - previous.eye[k];  H = previous.horizontal;  V = previous.vertical
+ *                  n       = (H1*V2 - H2*V1, H2*V0 - H0*V2, H0*V1 - H1*V0)
+ *                  s       = dot(rel, n) / dot(a, n)                                (the ray parameter of the point in the previous frame)
+ *                  q[k]    = rel[k] / s - a[k];  pu = dot(q, H) / dot(H, H);  pv = dot(q, V) / dot(V, V)
+ *                  fx      = pu * (float)width - 0.5f;  fy = (1.0f - pv) * (float)height - 0.5f
+ *                  ok      = s > 0 && s < +inf && fx > -1 && fx < (float)width && fy > -1 && fy < (float)height     (false on NaN)
+ *                  flx = floorf(fx), ix = (int32)flx, wx = fx - flx; likewise fly, iy, wy
+ *                  taps    dy = 0, 1 outer, dx = 0, 1 inner, q = (ix + dx, iy + dy); bw = (dx ? wx : 1.0f - wx) * (dy ? wy : 1.0f - wy)
+ *                          a tap counts iff ok, q lies in [0, width) x [row_begin, row_end), prev_guides[q].sphere == g.sphere
+ *                          (MISS == MISS included), prev_colour[q].w >= 1.0f, and for a hit
+ *                          fabsf(prev_guides[q].t - s) <= depth_tolerance * s;  a tap that does not count is SKIPPED
+ *                          wsum += bw; acc[k] += bw * prev_colour[q][k]; lacc += bw * prev_colour[q].w      (all from +0, in tap order)
+ *                  have    = wsum >= 0.015625f;  hist[k] = acc[k] / wsum;  hlen = lacc / wsum;  c[k] = colour[p][k]
+ *                  with MIRT_REPROJECT_CLAMP: lo = hi = c; for dy = -1..1 outer, dx = -1..1 inner, every in-band neighbour m of p in `colour`:
+ *                          lo[k] = (m[k] < lo[k]) ? m[k] : lo[k];  hi[k] = (m[k] > hi[k]) ? m[k] : hi[k]
+ *                          hist[k] = (hist[k] < lo[k]) ? lo[k] : hist[k];  then hist[k] = (hist[k] > hi[k]) ? hi[k] : hist[k]
+ *                  have:   nn = hlen + 1.0f; nn = (nn < max_history) ? nn : max_history; alpha = 1.0f / nn
+ *                          out = {hist[k] + alpha * (c[k] - hist[k]), nn}
+ *                  else:   out = {c[0], c[1], c[2], 1.0f}
+ *                Every bit pattern of every input is defined by these comparisons; the previous colours may be infinite or NaN, which
+ *                is why a tap that does not count is skipped and not weighted with zero.  The history is not divided by the albedo.
+ *   errors       in this order.  MIRT_ERR_NULL_POINTER: any pointer but out_rgba8.  MIRT_ERR_BAD_MODE: an unknown flag, a max_history
+ *                that is not finite and >= 1, a depth_tolerance that is not finite and >= 0.  MIRT_ERR_VIEWPORT_SIZE, MIRT_ERR_BAD_ROWS:
+ *                as mirt_ctx_render.  MIRT_ERR_BAD_ROWS: a tile partition (n_parts > 1 with tile_rows != 0), as for the denoiser.
+ *                MIRT_ERR_OUT_BUFFER: pixels < rows * width, or out / out_rgba8 overlapping any input or each other by their byte ranges
+ *                (pixels records each).  A refused call queues nothing and writes nothing.
+ *   state        as for every query: the launch ring, MirtStats, sums, records and sample counts are untouched;
+ *                mirt_ctx_trace_stats().kernel_ms spans the kernel, mirt_ctx_last_kernel names it, mirt_ctx_synchronize and
+ *                mirt_ctx_destroy wait for it.  There is no scratch: the _device form never synchronises.  The caller orders the call
+ *                against those that produce its inputs (the same stream in the normal pipeline).
+ *   mirt_camera_project   HOST ONLY, no device: the lines rel .. fy with rel = point - camera.eye and `camera` as `previous`; writes
+ *                {fx, fy, s}: the pixel coordinates (pixel centres at integers, row 0 on top) and the ray parameter of `point`; a point
+ *                is in front of the camera iff s > 0.  MIRT_ERR_NULL_POINTER for a null pointer, MIRT_ERR_VIEWPORT_SIZE for a zero size. */
+typedef struct MirtReprojectParams {            /* 208 B */
+    uint32_t flags;                             /* MIRT_REPROJECT_CLAMP */
+    float    max_history;                       /* finite, >= 1 */
+    float    depth_tolerance;                   /* finite, >= 0; relative */
+    uint32_t _pad;                              /* not read */
+    MirtGpuCamera previous, current;            /* the cameras the two guide frames were taken with */
+} MirtReprojectParams;
+typedef struct MirtReprojectFrames {            /* 56 B */
+    const void* colour;
+    const void* guides;
+    const void* prev_colour;
+    const void* prev_guides;
+    void*       out;
+    void*       out_rgba8;
+    uint64_t    pixels;
+} MirtReprojectFrames;
+enum { MIRT_REPROJECT_CLAMP = 1u << 0 };
+int mirt_ctx_reproject_device(MirtContext* ctx, const MirtParams* params, const MirtReprojectParams* reproject, const MirtReprojectFrames* frames, void* hip_stream);
+int mirt_ctx_reproject(MirtContext* ctx, const MirtParams* params, const MirtReprojectParams* reproject, const MirtReprojectFrames* frames);   /* host memory; blocking */
+int mirt_camera_project(const MirtGpuCamera* camera, uint32_t width, uint32_t height, const float point[3], float out_xy_s[3]);
+
 /* Device self-test of the arithmetic contract: the kernels' fast sqrt and reciprocal sequences
  * (hardware seed + one fma correction) are compared with the compiler's correctly rounded IEEE
  * expansions over ALL 2^32 binary32 bit patterns.  Writes the two mismatch counts (sqrt, 1/x);
@@ -1117,6 +1191,8 @@ static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
 static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
 static_assert(sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptLdsPlan is four words");
 static_assert(sizeof(MirtDenoiseParams) == 32, "MirtDenoiseParams is eight words");
+static_assert(sizeof(MirtReprojectParams) == 208, "MirtReprojectParams is four words and two cameras");
+static_assert(sizeof(MirtReprojectFrames) == 56, "MirtReprojectFrames is six pointers and a count");
 #else
 _Static_assert(sizeof(MirtSphere) == 32, "Sphere is 32 B (mod.rs:418-421)");
 _Static_assert(sizeof(MirtTextureDescriptor) == 12, "TextureDescriptor is 12 B (mod.rs:869-876)");
@@ -1138,6 +1214,8 @@ _Static_assert(sizeof(MirtAdaptRun) == 16, "MirtAdaptRun is four u32");
 _Static_assert(sizeof(MirtAdaptRunStep) == 8, "MirtAdaptRunStep is one 8-byte store");
 _Static_assert(sizeof(MirtAdaptLdsPlan) == 16, "MirtAdaptLdsPlan is four words");
 _Static_assert(sizeof(MirtDenoiseParams) == 32, "MirtDenoiseParams is eight words");
+_Static_assert(sizeof(MirtReprojectParams) == 208, "MirtReprojectParams is four words and two cameras");
+_Static_assert(sizeof(MirtReprojectFrames) == 56, "MirtReprojectFrames is six pointers and a count");
 #endif
 
 #endif /* MIRT_H */

@@ -372,6 +372,33 @@ pub const MIRT_DENOISE_SRC_ACCUM: u32 = 0;
 pub const MIRT_DENOISE_SRC_ADAPT: u32 = 1;
 /// `MirtDenoiseParams.flags`: the output is `{r, g, b, 1.0}` as float32 (the linear mean), not RGBA8.
 pub const MIRT_DENOISE_OUT_F32: u32 = 1 << 0;
+/// The parameters of `mirt_ctx_reproject*`: temporal reprojection by first-hit depth and id.  `previous` and `current` are the cameras the
+/// two guide frames were taken with; `_pad` is not read.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct MirtReprojectParams {
+    pub flags: u32,
+    pub max_history: f32,
+    pub depth_tolerance: f32,
+    pub _pad: u32,
+    pub previous: MirtGpuCamera,
+    pub current: MirtGpuCamera,
+}
+/// The planes of `mirt_ctx_reproject*`: all device pointers (the `_device` form) or all host pointers, 4-byte aligned, `pixels` records
+/// each; `out_rgba8` may be null.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct MirtReprojectFrames {
+    pub colour: *const c_void,
+    pub guides: *const c_void,
+    pub prev_colour: *const c_void,
+    pub prev_guides: *const c_void,
+    pub out: *mut c_void,
+    pub out_rgba8: *mut c_void,
+    pub pixels: u64,
+}
+/// `MirtReprojectParams.flags`: the history is clamped to the colours of the pixel's 3 x 3 neighbourhood in this frame.
+pub const MIRT_REPROJECT_CLAMP: u32 = 1 << 0;
 
 /// The `flags` of `mirt_ctx_trace_rays*` and `mirt_ctx_render_features*`, and `MirtRadianceParams.flags`: the query also accepts a scene
 /// that lives in LDS, where it stays (the same records as on the same world held as an HBM scene, which ignores the flag).
@@ -511,6 +538,9 @@ extern "C" {
     // adaptive steps on a scene that lives in LDS (MIRT_ADAPT_LDS): the launch's geometry and the device's rule for the sample groups, host only
     pub fn mirt_ctx_denoise_device(ctx: *mut MirtContext, params: *const MirtParams, denoise: *const MirtDenoiseParams, d_guides: *const c_void, guides_len: usize, d_out: *mut c_void, out_len: usize, hip_stream: *mut c_void) -> c_int;
     pub fn mirt_ctx_denoise(ctx: *mut MirtContext, params: *const MirtParams, denoise: *const MirtDenoiseParams, guides: *const MirtFeaturePixel, guides_len: usize, out: *mut c_void, out_len: usize) -> c_int;
+    pub fn mirt_ctx_reproject_device(ctx: *mut MirtContext, params: *const MirtParams, reproject: *const MirtReprojectParams, frames: *const MirtReprojectFrames, hip_stream: *mut c_void) -> c_int;
+    pub fn mirt_ctx_reproject(ctx: *mut MirtContext, params: *const MirtParams, reproject: *const MirtReprojectParams, frames: *const MirtReprojectFrames) -> c_int;
+    pub fn mirt_camera_project(camera: *const MirtGpuCamera, width: u32, height: u32, point: *const f32, out_xy_s: *mut f32) -> c_int;
     pub fn mirt_adapt_lds_plan(n_spheres: u32, n_materials: u32, grid_bytes: u32, hosek: u32, lds_bytes_per_cu: u64, out: *mut MirtAdaptLdsPlan) -> c_int;
     pub fn mirt_adapt_lds_groups(count: u32, spp: u32, grid_waves: u32, out_log2: *mut u32) -> c_int;
     pub fn mirt_ctx_selftest_math(ctx: *mut MirtContext, out_mismatches: *mut u64) -> c_int;

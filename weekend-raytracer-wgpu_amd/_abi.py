@@ -63,6 +63,9 @@ MIRT_DENOISE_SRC_ACCUM = 0
 MIRT_DENOISE_SRC_ADAPT = 1
 MIRT_DENOISE_OUT_F32 = 1 << 0
 
+# mirt_ctx_reproject*: MirtReprojectParams.flags
+MIRT_REPROJECT_CLAMP = 1 << 0
+
 # mirt_node_create: members at most, and its flags
 MIRT_NODE_MAX_MEMBERS = 16
 MIRT_NODE_RCCL = 1 << 0
@@ -251,6 +254,16 @@ class MirtDenoiseParams(C.Structure):
                 ("_pad", C.c_uint32 * 3)]
 
 
+class MirtReprojectParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("max_history", C.c_float), ("depth_tolerance", C.c_float), ("_pad", C.c_uint32),
+                ("previous", MirtGpuCamera), ("current", MirtGpuCamera)]
+
+
+class MirtReprojectFrames(C.Structure):
+    _fields_ = [("colour", C.c_void_p), ("guides", C.c_void_p), ("prev_colour", C.c_void_p), ("prev_guides", C.c_void_p), ("out", C.c_void_p),
+                ("out_rgba8", C.c_void_p), ("pixels", C.c_uint64)]
+
+
 class MirtAdaptStats(C.Structure):
     _fields_ = [("pixels", C.c_uint64), ("total_samples", C.c_uint64), ("active", C.c_uint32), ("steps", C.c_uint32), ("kernel_ms", C.c_double)]
 
@@ -339,6 +352,9 @@ SYMBOLS = {
     "mirt_adapt_run_spp": (C.c_int, [C.c_uint32, C.c_uint32, _P(MirtAdaptRun), _P(C.c_uint32)]),
     "mirt_ctx_denoise_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtDenoiseParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mirt_ctx_denoise": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtDenoiseParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "mirt_ctx_reproject_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtReprojectParams), _P(MirtReprojectFrames), C.c_void_p]),
+    "mirt_ctx_reproject": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtReprojectParams), _P(MirtReprojectFrames)]),
+    "mirt_camera_project": (C.c_int, [_P(MirtGpuCamera), C.c_uint32, C.c_uint32, _P(C.c_float), _P(C.c_float)]),
     "mirt_adapt_lds_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P(MirtAdaptLdsPlan)]),
     "mirt_adapt_lds_groups": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
     "mirt_ctx_adapt_run_device": (C.c_int, [C.c_void_p, _P(MirtParams), _P(MirtAdaptParams), _P(MirtAdaptRun), C.c_void_p]),

@@ -261,6 +261,55 @@ def _check_denoise(denoise) -> _abi.MirtDenoiseParams:
     return denoise
 
 
+def make_reproject_params(previous: _abi.MirtGpuCamera, current: _abi.MirtGpuCamera, *, max_history: float = 4.0, depth_tolerance: float = 0.05,
+                          clamp: bool = True) -> _abi.MirtReprojectParams:
+    """MirtReprojectParams for Context.reproject*: the cameras the previous and the current guide frame were taken with, the longest
+    history a pixel may carry (the blend weight of the new frame is 1 / min(length + 1, max_history)), the relative depth tolerance
+    of a tap, and whether the history is clamped to the colours of the pixel's 3 x 3 neighbourhood.  The types are checked here, the
+    ranges by the library."""
+    for name, v in (("previous", previous), ("current", current)):
+        if not isinstance(v, _abi.MirtGpuCamera):
+            raise ValueError(f"{name} must be a MirtGpuCamera, not {type(v).__name__}")
+    for name, v in (("max_history", max_history), ("depth_tolerance", depth_tolerance)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool):
+            raise ValueError(f"{name} must be a number, not {v!r}")
+    if not isinstance(clamp, (bool, np.bool_)):
+        raise ValueError(f"clamp must be a bool, not {clamp!r}")
+    r = _abi.MirtReprojectParams()
+    r.flags = _abi.MIRT_REPROJECT_CLAMP if clamp else 0
+    r.max_history, r.depth_tolerance = float(np.float32(max_history)), float(np.float32(depth_tolerance))
+    C.memmove(C.byref(r.previous), C.byref(previous), C.sizeof(_abi.MirtGpuCamera))
+    C.memmove(C.byref(r.current), C.byref(current), C.sizeof(_abi.MirtGpuCamera))
+    return r
+
+
+def _check_reproject(reproject) -> _abi.MirtReprojectParams:
+    if not isinstance(reproject, _abi.MirtReprojectParams):
+        raise ValueError(f"reproject must be a MirtReprojectParams (make_reproject_params builds one), not {type(reproject).__name__}")
+    return reproject
+
+
+def camera_project(camera: _abi.MirtGpuCamera, w: int, h: int, point) -> np.ndarray:
+    """mirt_camera_project: where `point` (three floats) falls in a w x h viewport of `camera` -> float32 [3] = {fx, fy, s}: pixel
+    coordinates with pixel centres at integers and row 0 on top, and the parameter of the point along the pixel's centre ray
+    (s > 0: in front of the camera).  The inverse of camera_pixel_ray up to rounding.  Needs no device."""
+    if not isinstance(camera, _abi.MirtGpuCamera):
+        raise ValueError(f"camera must be a MirtGpuCamera, not {type(camera).__name__}")
+    for name, v in (("w", w), ("h", h)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xffffffff:
+            raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+    try:
+        pt = np.array(point, np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"point must be three numbers, not {point!r}") from None
+    if pt.shape != (3,):
+        raise ValueError(f"point must be three numbers, not {point!r}")
+    out = np.zeros(3, np.float32)
+    fp = C.POINTER(C.c_float)
+    check(lib().mirt_camera_project(C.byref(camera), int(w), int(h), pt.ctypes.data_as(fp), out.ctypes.data_as(fp)))
+    return out
+
+
 def _check_params(params) -> _abi.MirtParams:
     if not isinstance(params, _abi.MirtParams):
         raise ValueError(f"params must be a MirtParams (make_params builds one), not {type(params).__name__}")
@@ -665,6 +714,55 @@ class Context:
                 raise ValueError(f"{name} must be a byte count, not {v!r}")
         check(lib().mirt_ctx_denoise_device(self._h, C.byref(params), C.byref(denoise), C.c_void_p(d_guides), int(guides_nbytes), C.c_void_p(d_out),
                                             int(nbytes), _stream_arg(stream)))
+
+    # ---- temporal reprojection of a denoised frame (include/mirt.h) ----
+    def reproject(self, params: _abi.MirtParams, reproject: _abi.MirtReprojectParams, colour: np.ndarray, guides: np.ndarray, prev_colour: np.ndarray,
+                  prev_guides: np.ndarray, *, rgba8: bool = False):
+        """mirt_ctx_reproject: this frame's `colour` (float32 [rows, width, 4], what denoise wrote with MIRT_DENOISE_OUT_F32) blended
+        with the previous frame's result `prev_colour` ({r, g, b, history length}: the result of the previous call, or a denoise
+        output) taken to this frame's pixels by the first-hit depth and id of `guides` / `prev_guides` (FEATURE_DTYPE [rows, width],
+        taken with reproject.current / reproject.previous) -> float32 [rows, width, 4] = {r, g, b, new history length}; with
+        rgba8=True a pair of that and uint8 [rows, width, 4] per params.flags.  Reads no scene and no state of the context.  Blocking."""
+        params, reproject = _check_params(params), _check_reproject(reproject)
+        if not isinstance(rgba8, (bool, np.bool_)):
+            raise ValueError(f"rgba8 must be a bool, not {rgba8!r}")
+        named = (("colour", colour, np.float32, (4,)), ("guides", guides, FEATURE_DTYPE, ()), ("prev_colour", prev_colour, np.float32, (4,)),
+                 ("prev_guides", prev_guides, FEATURE_DTYPE, ()))
+        for name, a, dt, tail in named:
+            if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim != 2 + len(tail):
+                raise ValueError(f"{name} must be a {'float32 [rows, width, 4]' if tail else 'FEATURE_DTYPE [rows, width]'} array")
+        rows, width = max(params_out_rows(params), 0), int(params.width)
+        planes = []
+        for name, a, dt, tail in named:
+            if a.shape != (rows, width) + tail:
+                raise ValueError(f"{name} has shape {a.shape}, the band is {(rows, width) + tail}")
+            planes.append(np.ascontiguousarray(a))
+        n = rows * width
+        out = np.zeros((max(rows, 1), max(width, 1), 4), np.float32)
+        rgba = np.zeros((max(rows, 1), max(width, 1), 4), np.uint8)
+        spare = [np.zeros(1, dt) for dt in (np.float32, FEATURE_DTYPE, np.float32, FEATURE_DTYPE)]       # a band without rows: the pointers stay non-null
+        f = _abi.MirtReprojectFrames()
+        f.colour, f.guides, f.prev_colour, f.prev_guides = (a.ctypes.data if n else s.ctypes.data for a, s in zip(planes, spare))
+        f.out, f.out_rgba8, f.pixels = out.ctypes.data, rgba.ctypes.data if rgba8 else None, n
+        check(lib().mirt_ctx_reproject(self._h, C.byref(params), C.byref(reproject), C.byref(f)))
+        out, rgba = out[:rows, :width], rgba[:rows, :width]
+        return (out, rgba) if rgba8 else out
+
+    def reproject_device(self, params: _abi.MirtParams, reproject: _abi.MirtReprojectParams, d_colour: int, d_guides: int, d_prev_colour: int, d_prev_guides: int,
+                         d_out: int, pixels: int, *, d_out_rgba8: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """mirt_ctx_reproject_device: the same with all planes in device memory (addresses, 4-byte aligned, `pixels` records each; 16
+        bytes per colour record, 32 per guide record, 4 per RGBA8 pixel), queued on `stream` (see _stream_arg).  d_out_rgba8=None: no
+        RGBA8 plane.  Never synchronises; the caller orders it against the calls that produce its inputs."""
+        params, reproject = _check_params(params), _check_reproject(reproject)
+        f = _abi.MirtReprojectFrames()
+        f.colour, f.guides = _check_address("d_colour", d_colour), _check_address("d_guides", d_guides)
+        f.prev_colour, f.prev_guides = _check_address("d_prev_colour", d_prev_colour), _check_address("d_prev_guides", d_prev_guides)
+        f.out = _check_address("d_out", d_out)
+        f.out_rgba8 = None if d_out_rgba8 is None else _check_address("d_out_rgba8", d_out_rgba8)
+        if not isinstance(pixels, (int, np.integer)) or isinstance(pixels, bool) or not 0 <= int(pixels) < 2 ** 64:
+            raise ValueError(f"pixels must be a record count, not {pixels!r}")
+        f.pixels = int(pixels)
+        check(lib().mirt_ctx_reproject_device(self._h, C.byref(params), C.byref(reproject), C.byref(f), _stream_arg(stream)))
 
     def bvh_refits(self) -> int:
         """mirt_ctx_bvh_refits: successful updates since the scene was set (0 after every set_scene)."""

@@ -2407,6 +2407,122 @@ int mirt_ctx_denoise(MirtContext* c, const MirtParams* p, const MirtDenoiseParam
     return MIRT_OK;
 }
 
+// ---- temporal reprojection of a denoised frame by first-hit depth and id (include/mirt.h) ----
+static bool ranges_overlap(const void* a, uint64_t a_len, const void* b, uint64_t b_len)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a_len != 0u && b_len != 0u && x < y + b_len && y < x + a_len;
+}
+
+// What both entry points check, in the header's order; *rb: the band's first image row, *rows: its rows (0: nothing to do).
+static int check_reproject(const MirtContext* c, const MirtParams* p, const MirtReprojectParams* r, const MirtReprojectFrames* f, uint32_t* rb, uint32_t* rows)
+{
+    if (!c || !p || !r || !f) return fail(MIRT_ERR_NULL_POINTER, "ctx/params/reproject/frames is null");
+    if (!f->colour || !f->guides || !f->prev_colour || !f->prev_guides || !f->out)
+        return fail(MIRT_ERR_NULL_POINTER, "colour/guides/prev_colour/prev_guides/out is null");
+    if (r->flags & ~(uint32_t)MIRT_REPROJECT_CLAMP) return fail(MIRT_ERR_BAD_MODE, "unknown MirtReprojectParams.flags bits 0x%x", r->flags);
+    if (!(r->max_history >= 1.0f) || !std::isfinite(r->max_history)) return fail(MIRT_ERR_BAD_MODE, "max_history %g is not finite and >= 1", (double)r->max_history);
+    if (!(r->depth_tolerance >= 0.0f) || !std::isfinite(r->depth_tolerance))
+        return fail(MIRT_ERR_BAD_MODE, "depth_tolerance %g is not finite and >= 0", (double)r->depth_tolerance);
+    if (p->width == 0 || p->height == 0)
+        return fail(MIRT_ERR_VIEWPORT_SIZE, "viewport_size elements cannot be zero: (%u, %u)", p->width, p->height);
+    uint32_t re;
+    if (!rows_valid(p, rb, &re)) return fail(MIRT_ERR_BAD_ROWS, "invalid row selection [%u,%u) of %u, part %u/%u", p->row_begin, p->row_end, p->height, p->part, p->n_parts);
+    if (p->n_parts > 1u && p->tile_rows != 0u)
+        return fail(MIRT_ERR_BAD_ROWS, "a tile partition (part %u/%u, %u rows per tile): its compact rows are not neighbours in the image", p->part, p->n_parts, p->tile_rows);
+    *rows = out_rows(p);
+    const uint64_t n = f->pixels;
+    if (n < (uint64_t)*rows * p->width) return fail(MIRT_ERR_OUT_BUFFER, "the frames hold %llu records, %llu needed", (unsigned long long)n, (unsigned long long)*rows * p->width);
+    const void* in[4] = { f->colour, f->guides, f->prev_colour, f->prev_guides };
+    const uint64_t in_len[4] = { n * 16u, n * sizeof(MirtFeaturePixel), n * 16u, n * sizeof(MirtFeaturePixel) };
+    for (int i = 0; i < 4; ++i)
+        if (ranges_overlap(f->out, n * 16u, in[i], in_len[i]) || (f->out_rgba8 && ranges_overlap(f->out_rgba8, n * 4u, in[i], in_len[i])))
+            return fail(MIRT_ERR_OUT_BUFFER, "out or out_rgba8 overlaps an input plane");
+    if (f->out_rgba8 && ranges_overlap(f->out, n * 16u, f->out_rgba8, n * 4u)) return fail(MIRT_ERR_OUT_BUFFER, "out and out_rgba8 overlap");
+    return MIRT_OK;
+}
+
+// Queue reproject_kernel on `st`: no scratch, no host synchronisation.  The event pair and the pending flag are the ray queries'
+// (mirt_ctx_trace_stats folds the time); the launch ring, MirtStats and the accumulation stay as they are.
+static int launch_reproject(MirtContext* c, const MirtParams* p, const MirtReprojectParams* r, uint32_t rb, uint32_t rows, const void* d_colour, const void* d_guides,
+                            const void* d_prev_colour, const void* d_prev_guides, void* d_out, void* d_rgba8, hipStream_t st)
+{
+    kx::ReprojectArgs a{};
+    a.previous = r->previous; a.current = r->current;
+    a.width = p->width; a.height = p->height; a.row_begin = rb; a.rows = rows;
+    a.flags = p->flags & (MIRT_FLAG_NO_TONEMAP | MIRT_FLAG_NO_SRGB);
+    a.max_history = r->max_history; a.depth_tolerance = r->depth_tolerance;
+    const bool clamp = (r->flags & MIRT_REPROJECT_CLAMP) != 0u;
+    const bool timed = c->timing;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_trace_begin, st));
+    HIP_TRY(kx::launch_reproject(a, clamp, d_colour, d_guides, d_prev_colour, d_prev_guides, d_out, d_rgba8, st));
+    snprintf(c->last_kernel, sizeof c->last_kernel, "reproject_kernel<%s,%s>", clamp ? "true" : "false", d_rgba8 ? "true" : "false");
+    HIP_TRY(hipEventRecord(c->ev_trace_end, st));
+    c->trace_pending = true;
+    c->trace_timed = timed;
+    c->trace_counted = false;
+    c->trace_stats = MirtRayStats{};
+    return MIRT_OK;
+}
+
+int mirt_ctx_reproject_device(MirtContext* c, const MirtParams* p, const MirtReprojectParams* r, const MirtReprojectFrames* f, void* hip_stream)
+{
+    uint32_t rb = 0, rows = 0;
+    const int rc = check_reproject(c, p, r, f, &rb, &rows);
+    if (rc != MIRT_OK || rows == 0u) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return launch_reproject(c, p, r, rb, rows, f->colour, f->guides, f->prev_colour, f->prev_guides, f->out, f->out_rgba8, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int mirt_ctx_reproject(MirtContext* c, const MirtParams* p, const MirtReprojectParams* r, const MirtReprojectFrames* f)
+{
+    uint32_t rb = 0, rows = 0;
+    int rc = check_reproject(c, p, r, f, &rb, &rows);
+    if (rc != MIRT_OK || rows == 0u) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the four input planes are staged where a host trace stages its hits, the two results where it stages its rays
+    const size_t n = (size_t)rows * p->width, c_bytes = n * 16u, g_bytes = n * sizeof(MirtFeaturePixel);
+    if ((rc = ensure_capacity(&c->d_trace_hits, &c->cap_trace_hits, 2u * (c_bytes + g_bytes))) != MIRT_OK) return rc;
+    if ((rc = ensure_capacity(&c->d_trace_rays, &c->cap_trace_rays, c_bytes + n * 4u)) != MIRT_OK) return rc;
+    unsigned char* in = reinterpret_cast<unsigned char*>(c->d_trace_hits);
+    unsigned char* out = reinterpret_cast<unsigned char*>(c->d_trace_rays);
+    unsigned char *d_colour = in, *d_guides = in + c_bytes, *d_prev_colour = d_guides + g_bytes, *d_prev_guides = d_prev_colour + c_bytes;
+    HIP_TRY(hipMemcpyAsync(d_colour, f->colour, c_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_guides, f->guides, g_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_prev_colour, f->prev_colour, c_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_prev_guides, f->prev_guides, g_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_reproject(c, p, r, rb, rows, d_colour, d_guides, d_prev_colour, d_prev_guides, out, f->out_rgba8 ? out + c_bytes : nullptr, c->stream)) != MIRT_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(f->out, out, c_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (f->out_rgba8) HIP_TRY(hipMemcpyAsync(f->out_rgba8, out + c_bytes, n * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MIRT_OK;
+}
+
+int mirt_camera_project(const MirtGpuCamera* cam, uint32_t width, uint32_t height, const float point[3], float out[3])
+{
+    if (!cam || !point || !out) return fail(MIRT_ERR_NULL_POINTER, "camera/point/out is null");
+    if (width == 0 || height == 0) return fail(MIRT_ERR_VIEWPORT_SIZE, "viewport_size elements cannot be zero: (%u, %u)", width, height);
+    // reproject_pixel's lines rel .. fy with `cam` as the previous camera, operation for operation (this file is compiled with
+    // -ffp-contract=off)
+    const float* H = cam->horizontal;
+    const float* V = cam->vertical;
+    float rel[3], a[3], q[3];
+    for (int k = 0; k < 3; ++k) {
+        rel[k] = point[k] - cam->eye[k];
+        a[k] = cam->lower_left_corner[k] - cam->eye[k];
+    }
+    const float n[3] = { H[1] * V[2] - H[2] * V[1], H[2] * V[0] - H[0] * V[2], H[0] * V[1] - H[1] * V[0] };
+    auto dot = [](const float* x, const float* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; };
+    const float s = dot(rel, n) / dot(a, n);
+    for (int k = 0; k < 3; ++k) q[k] = rel[k] / s - a[k];
+    const float pu = dot(q, H) / dot(H, H), pv = dot(q, V) / dot(V, V);
+    out[0] = pu * (float)width - 0.5f;
+    out[1] = (1.0f - pv) * (float)height - 0.5f;
+    out[2] = s;
+    return MIRT_OK;
+}
+
 int mirt_ctx_selftest_math(MirtContext* c, uint64_t out[2])
 {
     if (!c || !out) return fail(MIRT_ERR_NULL_POINTER, "ctx/out is null");

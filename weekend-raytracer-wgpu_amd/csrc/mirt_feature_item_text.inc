@@ -3,10 +3,7 @@
 //   MIRT_FEATURE_NEAREST   the nearest-hit expression over (ro, rd, alive, closest, work)
 //   MIRT_FEATURE_OF_HIT    the call that fills (hn, al) from (best, closest, ro, rd): feature_of_hit with the layout's tables
     // the centre ray
-    const float u = ((float)x + 0.5f) * C.inv_w;
-    const float v = 1.0f - ((float)y + 0.5f) * C.inv_h;
-    f3 ro = C.eye;
-    f3 rd = fma3(v, C.ver, fma3(u, C.hor, C.llc)) - C.eye;
+#include "mirt_centre_ray_text.inc"
     float closest;
     int best = MIRT_FEATURE_NEAREST;
     const uint32_t sphere = best >= 0 ? (uint32_t)best : kTraceMiss;

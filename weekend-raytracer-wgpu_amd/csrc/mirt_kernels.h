@@ -293,6 +293,18 @@ hipError_t launch_adapt_resolve(const void* d_recs, uint32_t* out, uint64_t n_pi
 hipError_t launch_denoise(uint32_t source, const void* d_src, uint32_t n_samples, const void* d_guides, uint32_t width, uint32_t rows, uint32_t levels,
                           uint32_t normal_log2, bool colour, const float* inv, bool f32_out, uint32_t flags, uint32_t staged_levels, void* d_scratch, void* d_out,
                           hipStream_t stream);
+// mirt_ctx_reproject* (mirt_reproject_kernel.inc): reproject_kernel<clamp, rgba8> over a band of width x rows pixels that starts at
+// image row row_begin.  All six planes hold the compact band, 4-byte aligned; d_rgba8 null: no RGBA8 plane.  `flags`: the two tone flags.
+struct ReprojectArgs {
+    MirtGpuCamera previous, current;
+    uint32_t width, height, row_begin, rows;
+    uint32_t flags;
+    float    max_history, depth_tolerance;
+    uint32_t tiles_x;              // ceil(width / 64); a tile is 64 x 4 pixels
+    uint64_t tiles;
+};
+hipError_t launch_reproject(ReprojectArgs a, bool clamp, const void* d_colour, const void* d_guides, const void* d_prev_colour, const void* d_prev_guides,
+                            void* d_out, void* d_rgba8, hipStream_t stream);
 hipError_t launch_assemble(const AssembleArgs& a, LaunchOn on);
 size_t     scene_lds_bytes(uint32_t n_spheres, uint32_t n_mats, bool pt, bool hosek);
 size_t     scene_lds_bytes_grid(uint32_t n_spheres, bool hosek);

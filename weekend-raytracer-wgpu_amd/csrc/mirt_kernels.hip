@@ -2260,6 +2260,7 @@ static QueryKernel kernel_handle(K kernel) { return reinterpret_cast<QueryKernel
 #include "mirt_feature_lds_kernel.inc"
 #include "mirt_radiance_lds_kernel.inc"
 #include "mirt_denoise_kernel.inc"
+#include "mirt_reproject_kernel.inc"
 
 // ------------------------------------------------------------------------------------------
 // self-test: the fast sqrt_/rcp_ against the IEEE expansions over ALL 2^32 binary32 patterns

@@ -4,6 +4,7 @@
 // FFI call.  Header-only; link with -lmirt.  No pixel is computed on the host.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <fstream>
@@ -122,6 +123,52 @@ inline void denoise_device(MirtContext* ctx, const MirtParams& params, const Mir
                            size_t out_len, void* hip_stream = nullptr)
 {
     check(mirt_ctx_denoise_device(ctx, &params, &denoise, d_guides, guides_len, d_out, out_len, hip_stream));
+}
+// mirt_ctx_reproject: this frame's `colour` ({r, g, b, ignored} as float32, what denoise wrote with MIRT_DENOISE_OUT_F32) blended with the
+// previous frame's result `prev_colour` ({r, g, b, history length}) taken to this frame's pixels by the first-hit depth and id of the two
+// guide frames -> {r, g, b, new history length} per pixel of the band; `rgba8` non-null: also the RGBA8 pixels per params.flags.  Reads no
+// scene; blocking.
+static_assert(sizeof(MirtReprojectParams) == 208 && sizeof(MirtReprojectFrames) == 56 && MIRT_REPROJECT_CLAMP == 1u << 0, "MirtReprojectParams");
+inline MirtReprojectParams reproject_params(const MirtGpuCamera& previous, const MirtGpuCamera& current, float max_history = 4.0f, float depth_tolerance = 0.05f,
+                                            bool clamp = true)
+{
+    MirtReprojectParams r{};
+    r.flags = clamp ? (uint32_t)MIRT_REPROJECT_CLAMP : 0u; r.max_history = max_history; r.depth_tolerance = depth_tolerance;
+    r.previous = previous; r.current = current;
+    return r;
+}
+inline std::vector<float> reproject(MirtContext* ctx, const MirtParams& params, const MirtReprojectParams& reproject, const std::vector<float>& colour,
+                                    const std::vector<MirtFeaturePixel>& guides, const std::vector<float>& prev_colour,
+                                    const std::vector<MirtFeaturePixel>& prev_guides, std::vector<uint8_t>* rgba8 = nullptr)
+{
+    const size_t n = (size_t)mirt_params_out_rows(&params) * params.width;
+    if (colour.size() < 4u * n || prev_colour.size() < 4u * n || guides.size() < n || prev_guides.size() < n)
+        throw std::invalid_argument("mirt_host::reproject: a plane holds fewer records than the band has pixels");
+    std::vector<float> out(4u * n);
+    if (rgba8) rgba8->assign(4u * n, 0u);
+    float none[4] = {};
+    uint8_t no_px[4] = {};
+    MirtFeaturePixel no_guide{};
+    MirtReprojectFrames f{};
+    f.colour = n ? (const void*)colour.data() : none; f.prev_colour = n ? (const void*)prev_colour.data() : none;
+    f.guides = n ? guides.data() : &no_guide; f.prev_guides = n ? prev_guides.data() : &no_guide;
+    f.out = n ? out.data() : none;
+    f.out_rgba8 = rgba8 ? (n ? rgba8->data() : no_px) : nullptr;
+    f.pixels = n;
+    check(mirt_ctx_reproject(ctx, &params, &reproject, &f));
+    return out;
+}
+inline void reproject_device(MirtContext* ctx, const MirtParams& params, const MirtReprojectParams& reproject, const MirtReprojectFrames& d_frames,
+                             void* hip_stream = nullptr)
+{
+    check(mirt_ctx_reproject_device(ctx, &params, &reproject, &d_frames, hip_stream));
+}
+// where `point` falls in the viewport: {fx, fy, s} (mirt_camera_project: pixel centres at integers, row 0 on top; s > 0 in front of the camera)
+inline std::array<float, 3> camera_project(const MirtGpuCamera& cam, uint32_t width, uint32_t height, const std::array<float, 3>& point)
+{
+    std::array<float, 3> out{};
+    check(mirt_camera_project(&cam, width, height, point.data(), out.data()));
+    return out;
 }
 // the centre ray of pixel (x, y) exactly as the feature kernel traces it (mirt_camera_pixel_ray: float32 with fmaf, t_max = 1000)
 inline MirtRay camera_pixel_ray(const MirtGpuCamera& cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y)

@@ -424,6 +424,16 @@ def pixel_ray(camera: _abi.MirtGpuCamera, width: int, height: int, x: int, y: in
     return eye, d.astype(f32)
 
 
+def pixel_project(camera: _abi.MirtGpuCamera, width: int, height: int, point) -> Tuple[float, float, float]:
+    """Where `point` falls in the viewport: (fx, fy, s) with pixel centres at integers and row 0 on top, and s the parameter of the
+    point along the centre ray of that position (s > 0: in front of the camera) -- mirt_camera_project, the rule mirt_ctx_reproject
+    takes a first hit to the previous frame with.  pixel_project(c, w, h, origin + t * direction) of pixel_ray(c, w, h, x, y) is
+    (x, y, t) up to float32 rounding."""
+    from .context import camera_project
+    fx, fy, s = camera_project(camera, width, height, point)
+    return float(fx), float(fy), float(s)
+
+
 def _query_target(owner, scene_data, lds):
     """The context a query of Layer / Raytracer runs on (member 0's on a node).  lds=False: the query needs the world in device memory,
     so a resident LDS scene -- or none yet -- is set again as a MIRT_SCENE_HBM scene first (owner._hbm is True afterwards).  lds=True
@@ -715,6 +725,8 @@ class Raytracer:
         self.frame_number = 1           # mod.rs:284; advanced by every render_frame call (mod.rs:350), never reset
         self._frame_begin = 0           # frames rendered before the current accumulation started
         self._last_seed = 0             # of the last progressive frame or adaptive call: denoised() takes its guides with it
+        self._temporal = None           # temporal_frame: the planes, the stream and the history it holds
+        self._temporal_calls = 0        # temporal_frame: calls so far (frame k draws under seed + k)
 
     def scene_data(self) -> SceneData:
         return SceneData(self.camera.c, [s.to_c() for s in self.spheres], list(self.material_data),
@@ -796,6 +808,7 @@ class Raytracer:
                                          self.global_texture_data, self.sky_state))
         self.spheres[first:first + len(moved)] = moved
         self._accumulated = None
+        self._drop_history()
 
     def set_world(self, spheres: Sequence[Sphere]) -> None:
         """The scene's spheres become `spheres` (any count; their material indices are taken).  A scene in device memory
@@ -808,6 +821,7 @@ class Raytracer:
                                               self.sky_state))
         self.spheres = new
         self._accumulated = None
+        self._drop_history()
 
     def _pick_target(self):
         return self._ctx
@@ -931,6 +945,85 @@ class Raytracer:
             guides[k] = g[k]
         return self._ctx.denoise(make_params(w, h, 0, mode=_abi.MIRT_MODE_PT, flags=int(flags)), d, guides)
 
+    def _drop_history(self) -> None:
+        """temporal_frame starts over: sphere ids may name other spheres now, or the planes have another size."""
+        held = getattr(self, "_temporal", None)
+        if held is not None:
+            held["have"] = False
+
+    def temporal_frame(self, *, seed: int = 0, levels: int = 3, sigma_colour: float = 1.0, normal_log2: int = 5, max_history: float = 4.0,
+                       depth_tolerance: float = 0.05, clamp: bool = True, flags: int = 0) -> np.ndarray:
+        """The frame of a MOVING camera -> RGBA8 [h][w][4]: `num_samples_per_pixel` fresh samples (every call resets the accumulation
+        and draws under seed + the number of calls so far, so frames are independent), the guides of those samples, the a-trous filter
+        of mirt_ctx_denoise to float32, and mirt_ctx_reproject against the history this object holds: the previous call's result,
+        guides and camera.  The whole frame is queued on one stream through the _device forms into planes this object owns (two
+        history planes and two guide planes, used alternately); the host waits once, for the RGBA8 copy.  The first call, and the
+        first after set_world, move_spheres or a changed viewport size, has no history and returns the denoised frame;
+        set_render_params with a new camera KEEPS the history.  Afterwards the accumulation is marked reset, so a progressive loop
+        starts over.  A scene held in LDS stays there.  `flags`: MIRT_FLAG_NO_TONEMAP / MIRT_FLAG_NO_SRGB.  The gain over
+        denoised() alone is modest (DESIGN.md 10.18 has what was measured); not available on a node."""
+        import torch
+        from .context import make_denoise_params, make_reproject_params
+        if self._on_node:
+            raise ValueError("temporal_frame needs a single context: a node member's tiles are not neighbours in the image")
+        if not isinstance(flags, (int, np.integer)) or isinstance(flags, bool) or int(flags) & ~(_abi.MIRT_FLAG_NO_TONEMAP | _abi.MIRT_FLAG_NO_SRGB):
+            raise ValueError(f"flags must be a combination of MIRT_FLAG_NO_TONEMAP and MIRT_FLAG_NO_SRGB, not {flags!r}")
+        if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or int(seed) < 0:
+            raise ValueError(f"seed must be an unsigned integer, not {seed!r}")
+        w, h = (int(v) for v in self.render_params.viewport_size)
+        cur_cam = _abi.MirtGpuCamera.from_buffer_copy(self.camera.c)
+        to_f32 = make_denoise_params("accum", levels=levels, sigma_colour=sigma_colour, normal_log2=normal_log2, f32=True)
+        to_rgba8 = make_denoise_params("accum", levels=levels, sigma_colour=sigma_colour, normal_log2=normal_log2)
+        lds = not self._hbm
+        ctx = _query_target(self, self.scene_data, lds)
+        n = w * h
+        T = self._temporal
+        if T is None or T["size"] != (w, h):
+            dev = f"cuda:{int(ctx.device)}"
+            plane = lambda nbytes: torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            T = self._temporal = {"size": (w, h), "have": False, "cur": 0, "camera": None, "stream": torch.cuda.Stream(device=dev),
+                                  "colour": plane(n * 16), "history": [plane(n * 16), plane(n * 16)], "guides": [plane(n * 32), plane(n * 32)],
+                                  "rgba8": plane(n * 4)}
+        repro = make_reproject_params(T["camera"] if T["have"] else cur_cam, cur_cam, max_history=max_history, depth_tolerance=depth_tolerance,
+                                      clamp=clamp)                # (checks its arguments before anything is queued)
+        st = int(T["stream"].cuda_stream)
+        frame_seed = int(seed) + self._temporal_calls
+        self._temporal_calls += 1
+        cur = T["cur"] ^ 1
+        guides, history, rgba8 = T["guides"][cur], T["history"][cur], T["rgba8"]
+
+        self._accumulated = None                                  # every call starts a fresh accumulation
+        params = self._next_frame(frame_seed, int(flags))
+        ctx.set_camera(cur_cam)
+        ctx.accum_frame_device(params, rgba8.data_ptr(), st)      # (its image is overwritten below)
+        self._frame_issued(params)
+        ctx.render_features_device(make_params(w, h, int(params.spp), mode=_abi.MIRT_MODE_PT, seed=frame_seed), guides.data_ptr(), n * 32, stream=st, lds=lds)
+        tone = make_params(w, h, 0, mode=_abi.MIRT_MODE_PT, flags=int(flags))
+        if T["have"]:
+            ctx.denoise_device(tone, to_f32, guides.data_ptr(), n * 32, T["colour"].data_ptr(), n * 16, st)
+            ctx.reproject_device(tone, repro, T["colour"].data_ptr(), guides.data_ptr(), T["history"][cur ^ 1].data_ptr(), T["guides"][cur ^ 1].data_ptr(),
+                                 history.data_ptr(), n, d_out_rgba8=rgba8.data_ptr(), stream=st)
+        else:                                                     # no history: the denoised frame is the history (its fourth channel is a length of 1)
+            ctx.denoise_device(tone, to_f32, guides.data_ptr(), n * 32, history.data_ptr(), n * 16, st)
+            ctx.denoise_device(tone, to_rgba8, guides.data_ptr(), n * 32, rgba8.data_ptr(), n * 4, st)
+        T["cur"], T["camera"], T["have"] = cur, cur_cam, True
+        self._accumulated = None                                  # a progressive loop restarts
+        with torch.cuda.stream(T["stream"]):
+            img = rgba8.cpu()                                     # ordered behind the frame on its stream; the one host wait
+        return img.numpy().reshape(h, w, 4).copy()
+
+    def temporal_history(self) -> Optional[np.ndarray]:
+        """The history temporal_frame holds -> float32 [h][w][4] = {r, g, b, history length} (linear, before the tone curves), or None
+        before the first frame and after the history was dropped."""
+        T = self._temporal
+        if T is None or not T["have"]:
+            return None
+        import torch
+        w, h = T["size"]
+        with torch.cuda.stream(T["stream"]):
+            a = T["history"][T["cur"]].cpu()
+        return a.numpy().view(np.float32).reshape(h, w, 4).copy()
+
     def render(self, *, seed: int = 0, flags: int = 0, frame_begin: int = 0) -> np.ndarray:
         """All `max_samples_per_pixel` samples in one launch -> RGBA8 [h][w][4].
 
@@ -945,10 +1038,11 @@ class Raytracer:
         return img
 
     def close(self) -> None:
-        self._ctx.close()
+        self._ctx.close()                                          # (mirt_ctx_destroy waits for what temporal_frame queued)
+        self._temporal = None
 
 
 __all__ = ["Angle", "Camera", "GpuCamera", "SamplingParams", "SkyParams", "RenderParams",
            "RenderParamsValidationError", "FlyCameraController", "Sphere", "Texture", "Material",
            "TextureDescriptor", "GpuMaterial", "Scene", "Layer", "Raytracer", "flatten_materials",
-           "asset_path", "MirtError", "decode_jpeg", "jpeg_info", "pixel_ray"]
+           "asset_path", "MirtError", "decode_jpeg", "jpeg_info", "pixel_ray", "pixel_project"]
